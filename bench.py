@@ -1,6 +1,6 @@
 """bench.py -- Mpixels/s forward+backward of the HIP rasterizer on BASELINE.json's metric configuration.
 
-    python bench.py --gpus N --steps K --warmup W [--config 2|4] [--scaling weak|strong]
+    python bench.py --gpus N --steps K --warmup W [--config 2|4] [--scaling weak|strong] [--full] [--dump-outputs DIR]
     (N > 1: one rank per GPU under torch.distributed.run -- started by the driver's launcher, or by bench.py itself when it is run as plain
     `python bench.py --gpus N`: it re-executes itself under `torch.distributed.run --nproc-per-node N` on 127.0.0.1)
 
@@ -14,9 +14,15 @@ multi-view fitter does on the host at deodr/mesh_fitter.py:518-527).  Views shar
 collective, per-GPU work is fixed as N grows ("weak"; `--scaling strong` deals `--views` views of the whole job to the ranks instead:
 BASELINE configs[3], one view per GPU at N = 8).  `--config 4` runs BASELINE configs[4] (2048^2, 100k triangles, 1024^2 texture): texture_b
 and uv_b -- per-scene arrays that every view of a rank adds into -- are part of the ONE all-reduced buffer (float32, 12.6 MB + the vertex sums).
-`--warmup W` is honoured to the step; `cold_start` / `steady_state` say what the same K steps read from an idle GPU and after 1 000 more.
+`--warmup W` is honoured to the step.
 
-The JSON line carries, besides the driver's contract:
+A plain run does only what the headline needs: it sets up, runs the fit step untimed for CLOCK_RAMP_S (the core clock of a running fit loop,
+which the auxiliary measurements give the headline under --full), the W warm-up steps, the K timed steps, writes the last timed step's
+outputs if `--dump-outputs DIR` is given, and prints the JSON line: metric, value, unit, n_gpus, steps, warmup, ms_per_step (one timed step),
+higher_is_better, dtype, config.  `--full` adds what follows, measured as before the plain run existed (`--no-*` switch parts of it off);
+`cold_start` / `steady_state` say what the same K steps read from an idle GPU and after 1 000 more.
+
+With --full the JSON line carries as well:
   roofline      dominant kernel group (largest average duration, from device time stamps of EVERY step of the timed region; "raster_fwd_kernel" = tile scan + forward raster -- which in a
                 fit step also back-propagates every tile and streams two thirds of the background fill --, "finalize_kernel" =
                 finalize + the last third of the fill): achieved = SURVEY.md 8d bytes that group moves (float32 buffers) / its
@@ -495,6 +501,43 @@ def single_view_latency(scenes_mod, DeviceScene, HipRasterizer, dev, S, sigma, o
     }  # fmt: skip
 
 
+DUMP_FILE_BYTES = 6 << 20  # --dump-outputs: bytes of one file at most (9 files at most: image, z, z_empty, 5 gradient arrays, the shared gradient)
+STRONG_SCALING_FLOOR = ("one view per GPU at N = 8: a step cannot be shorter than the single-view fit step (`single_view` of the N = 1 line: ~0.058 ms "
+                        "against ~0.117 ms for 8 views on one GPU, i.e. the strong-scaling curve of this batch tops out near 2 x)")
+CLOCK_RAMP_S = 0.25  # plain run: seconds of untimed fit steps in front of the warm-up (see main)
+
+
+def dump_outputs(out_dir, arrays, empty_inf=("z",)):
+    """--dump-outputs: {name: tensor} -> out_dir/<name>.npy, float32 / float64 as computed.  An array larger than DUMP_FILE_BYTES is
+    written as DUMP_FILE_BYTES worth of elements of its flattened form, in index order, chosen by a fixed seed from its size alone (the
+    same elements in every run with the same arguments).  Every value written is finite: the depth of a pixel no triangle covers is +inf
+    in the z buffer (as in the reference), so an array named in `empty_inf` is written with those pixels as 0 and, beside it,
+    <name>_empty.npy (float32, 1 where the pixel is empty); any other non-finite value is an error."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        if t is None:
+            continue
+        t = t.detach()
+        assert t.dtype in (torch.float32, torch.float64), (name, t.dtype)
+        flat = t.reshape(-1)
+        m = DUMP_FILE_BYTES // flat.element_size()
+        if flat.numel() > m:
+            idx = np.sort(np.random.default_rng(0).choice(flat.numel(), m, replace=False, shuffle=False))
+            a = flat[torch.as_tensor(idx, device=flat.device)].cpu().numpy()
+        else:
+            a = t.cpu().numpy()
+        files = {name: a}
+        if name in empty_inf:
+            empty = np.isposinf(a)
+            files = {name: np.where(empty, 0, a).astype(a.dtype), f"{name}_empty": empty.astype(np.float32)}
+        for fname, v in files.items():
+            assert np.isfinite(v).all(), f"--dump-outputs: {fname} holds {int(np.count_nonzero(~np.isfinite(v)))} non-finite values"
+            np.save(os.path.join(out_dir, f"{fname}.npy"), v)
+            total += v.nbytes
+    assert total <= 64_000_000, f"--dump-outputs wrote {total} bytes"
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -518,7 +561,17 @@ def main():
     ap.add_argument("--test-backend", choices=["nccl", "gloo"], default="nccl",
                     help="gloo: for the regression test of the multi-rank path on a ONE-GPU box (tests/test_hip_round3.py): the ranks share "
                          "the visible GPUs and all-reduce over gloo.  Never a measurement: the line says so in config.env_overrides")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: cold start, steady state, HBM probe, single view, frame / batch sweeps, per-kernel "
+                         "roofline, tile census, parity with the checker, the reduction check, other configurations, CPU baseline (--no-* "
+                         "switch parts of it off).  Without it the run sets up, warms up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (image, z, gradient arrays; rank 0) as DIR/<name>.npy "
+                         "(z: empty pixels, +inf in the z buffer, written as 0 and flagged in z_empty.npy); "
+                         f"an array over {DUMP_FILE_BYTES >> 20} MiB is written as a fixed, seeded sample of {DUMP_FILE_BYTES >> 20} MiB "
+                         "of its elements (flat, in index order)")
     args = ap.parse_args()
+    full = args.full
 
     # Nothing outside the command line may change what is timed: the library reads no environment variable, and a variable
     # that LOOKS like one of its former tuning knobs (or a library override used by tools/) is refused rather than ignored.
@@ -635,10 +688,7 @@ def main():
     it = [0]
     last_slot = [None]
 
-    def step():
-        it[0] += 1
-        slot = reduction.begin() if reduction is not None else None
-        g = slot.grads if slot is not None else grads
+    def fit_step(g, done_flag=None):
         if args.two_pass:
             g["ij_b"].zero_()
             g["colors_b"].zero_()
@@ -648,8 +698,13 @@ def main():
         else:
             # same outputs in one call: the forward raster back-propagates through the tiles without silhouette edges itself
             # (and zeroes the gradient arrays of the previous step on the way)
-            r.render_fit(ds, obs_views, args.sigma, grads=g, out=(image, z), check_overflow=False, clear_grads=True,
-                         done_flag=slot.done_flag if slot is not None else None)
+            r.render_fit(ds, obs_views, args.sigma, grads=g, out=(image, z), check_overflow=False, clear_grads=True, done_flag=done_flag)
+
+    def step():
+        it[0] += 1
+        slot = reduction.begin() if reduction is not None else None
+        g = slot.grads if slot is not None else grads
+        fit_step(g, slot.done_flag if slot is not None else None)
         if slot is not None:
             event = None
             if args.two_pass:  # (the two-call step stores no done flag: an event)
@@ -674,7 +729,7 @@ def main():
     # the headline `ms_per_step` -- W + K steps right after the line's other raster measurements (`single_view`, `batch_sweep`: the same
     # kernels, ~0.2 s of them, on every rank), i.e. at the clocks a fit loop runs at; `steady_state` -- K steps after 1 000 more untimed ones.
     cold_dt = None
-    if args.test_backend != "gloo":
+    if full and args.test_backend != "gloo":
         for _ in range(args.warmup):
             step()
         barrier()
@@ -683,13 +738,24 @@ def main():
             step()
         barrier()
         cold_dt = time.perf_counter() - t0
-    probe = hbm_probe(dev) if (rank == 0 and args.test_backend != "gloo") else None
+    probe = hbm_probe(dev) if (full and rank == 0 and args.test_backend != "gloo") else None
     single_view = sweep = frames = None
-    if not args.no_single_view and not textured and args.test_backend != "gloo":
+    if full and not args.no_single_view and not textured and args.test_backend != "gloo":
         single_view = single_view_latency(scenes, DeviceScene, HipRasterizer, dev, S, args.sigma, obs)
         # (the larger frames first: what runs right before the headline's warm-up is the same kernels on the same scene -- 16 and 32 views per launch)
         frames = batch_sweep(scenes, DeviceScene, HipRasterizer, dev, S, args.sigma, cases=[(1, 2 * S), (8, 2 * S), (1, 4 * S)]) if rank == 0 and S <= 1024 else None
         sweep = batch_sweep(scenes, DeviceScene, HipRasterizer, dev, S, args.sigma)
+    ramp_steps = 0
+    if not full and args.test_backend != "gloo":
+        # A plain run measures nothing but the headline, which is still timed at the clocks of a running fit loop (what the sweeps above
+        # give it under --full): CLOCK_RAMP_S of the same fit step on this rank's own gradient set, untimed, with no collective (the ranks
+        # may run different counts of it), then the W warm-up steps
+        t_end = time.perf_counter() + CLOCK_RAMP_S
+        while time.perf_counter() < t_end:
+            for _ in range(16):
+                fit_step(grads)
+            torch.cuda.synchronize()
+            ramp_steps += 16
     if dist is not None:
         dist.barrier()
     for _ in range(args.warmup):
@@ -700,7 +766,7 @@ def main():
     # between them).  EVERY step of the timed region is sampled and nothing is inserted between the launches -- a hipEvent pair per
     # kernel costs the step it brackets ~ 36 us: with 5 of 20 steps bracketed the same code read 0.1368 ms per step instead of 0.1277.
     # hipEvents are still used, AFTER the timed region, as a cross-check of the stamps (`avg_ms_events`).
-    stamps = torch.zeros((args.steps + 1, 4), dtype=torch.int64, device=dev) if args.time_every > 0 else None
+    stamps = torch.zeros((args.steps + 1, 4), dtype=torch.int64, device=dev) if (full and args.time_every > 0) else None
     barrier()
     if stamps is not None:
         hr.lib().deodr_hip_profile_stamps(stamps.data_ptr(), args.steps + 1)
@@ -711,6 +777,10 @@ def main():
         step()
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # what the last timed step returned, before any later step writes the same buffers again
+        last = last_slot[0].grads if last_slot[0] is not None else grads
+        dump_outputs(args.dump_outputs, dict(image=image, z=z, **last, shared_grad=last_slot[0].shared if last_slot[0] is not None else None))
     ms_sum = (C.c_double * 4)()
     launches = (C.c_ulonglong * 4)()
     stamp_ms = None
@@ -745,7 +815,7 @@ def main():
         hr.lib().deodr_hip_profile_read(ms_sum, launches)
     # the same K steps once more in the steady state (1 000 untimed steps in between): what --warmup is worth on this box
     steady_dt = None
-    if args.test_backend != "gloo":
+    if full and args.test_backend != "gloo":
         for _ in range(1000):
             step()
         barrier()
@@ -762,7 +832,7 @@ def main():
     # the shared gradient the pipeline all-reduced in the last timed step against the same reduction done again, step by step and
     # synchronously, from that step's gradient arrays (every rank takes part: it is a collective)
     reduction_check = None
-    if dist is not None:
+    if full and dist is not None:
         from deodr_amd import fronthalf
 
         from deodr_amd.distributed import SharedGradientBuffer
@@ -800,6 +870,27 @@ def main():
 
     if rank == 0:
         px = global_views * S * S * args.steps
+        step_s = dt / args.steps
+        ntiles = B * ((S + 7) // 8) ** 2
+        out = {
+            "metric": "Mpixels/s forward+backward, 1024^2 20k-tri scene" if not textured else "Mpixels/s forward+backward, 2048^2 100k-tri textured scene (BASELINE configs[4])",
+            "value": px / dt / 1e6, "unit": "Mpixels/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": step_s * 1e3,
+            "order": (f"{CLOCK_RAMP_S} s of the same fit step, untimed ({ramp_steps} steps: the core clock of a running fit loop), the W warm-up "
+                      "and the K timed steps (--full: the auxiliary measurements as well)") if not full else
+                     ("cold_start (W + K steps) first; then hbm_probe, single_view, frame_sweep (rank 0), batch_sweep (on every rank); then the W warm-up "
+                      "and K timed steps of the headline; steady_state, parity check, other configurations and the CPU baseline after it"),
+            "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "config": {"workload": (f"BASELINE configs[2]: {S}x{S}, {T}-triangle bumpy sphere, C={Cc} (RGB+depth), sigma=1, " if not textured else
+                                    f"BASELINE configs[4]: {S}x{S}, {T}-triangle bumpy sphere, textured Gouraud, {ds.texture.shape[1]}x{ds.texture.shape[0]} texture, C={Cc}, sigma=1, ")
+                                   + f"{B} views per GPU per step, float32 pixel buffers / float64 vertex arrays, all-double arithmetic",
+                       "step": "renderScene + renderScene_B (two calls)" if args.two_pass else "deodr_hip_render_scene_fit (forward + adjoint of sum (image - obs)^2, one call)",
+                       "views_per_gpu": B, "global_views": global_views, "env_overrides": overrides, "tiles": ntiles,
+                       "parallelism": f"views sharded {B}/GPU" + (", 1 RCCL all-reduce of the shared gradient per step" if world > 1 else "")
+                                      + (" (texture_b | vertices_b | colors_b | uv_b in one float32 buffer)" if textured and world > 1 else ""),
+                       **({"strong_scaling_floor": STRONG_SCALING_FLOOR} if args.scaling == "strong" else {})},
+        }  # fmt: skip
+    if rank == 0 and full:
         # which tiles held primitives / silhouette edges in this run (from the workspace: tile bitmap, saved edge counts)
         nonempty = edge_tiles = None
         try:
@@ -807,7 +898,6 @@ def main():
         except Exception as e:
             print(f"bench: tile census unavailable ({e!r})", file=sys.stderr)
         fused = not args.two_pass
-        ntiles = B * ((S + 7) // 8) ** 2
         alg_8d = algorithmic_bytes(S, S, Cc, T, V, B, fused)  # every frame byte of the step
         alg = algorithmic_bytes(S, S, Cc, T, V, B, fused, nonempty / ntiles if (fused and nonempty is not None) else None)
         if textured:
@@ -832,35 +922,18 @@ def main():
             # NOT measured in this run (PMC passes need rocprofv3 around the process): which profile the figure is from
             traffic_source = dict(tjson.get("_source") or {}, file="profiles/traffic_latest.json", measured_in_this_run=False)
         kernel_ms = sum(v["avg_ms"] for v in per_kernel.values())
-        step_s = dt / args.steps
         whole = sum(v for k, v in alg_8d.items() if k != "not_moved")
         moved = sum(v for k, v in alg.items() if k != "not_moved" and v is not None)
         if probe is None:  # (--test-backend gloo: a functional test, nothing is measured)
             probe = {"best_copy_GBps": GUIDE_COPY_GBS, "note": "not measured (--test-backend gloo)"}
         peak_meas = probe["best_copy_GBps"]
         dom_GBps = per_kernel[dom]["GBps"] if not textured else whole / step_s / 1e9  # (configs[4]: no per-group bytes -> the whole step)
-        single_floor = ("one view per GPU at N = 8: a step cannot be shorter than the single-view fit step (`single_view` of the N = 1 line: ~0.058 ms "
-                        "against ~0.117 ms for 8 views on one GPU, i.e. the strong-scaling curve of this batch tops out near 2 x)")
-        out = {
-            "metric": "Mpixels/s forward+backward, 1024^2 20k-tri scene" if not textured else "Mpixels/s forward+backward, 2048^2 100k-tri textured scene (BASELINE configs[4])",
-            "value": px / dt / 1e6, "unit": "Mpixels/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": step_s * 1e3,
+        out["config"].update(nonempty_tiles=nonempty, edge_tiles=edge_tiles)
+        out.update({
             # the same K steps timed again after 1 000 more untimed ones: what a longer --warmup would have read on this box
             "steady_state": None if steady_dt is None else {"ms_per_step": steady_dt / args.steps * 1e3, "value": px / steady_dt / 1e6, "untimed_steps_after_the_headline": 1000 + (7 if stamps is not None else 0)},
             # the same W + K steps as the first thing the process did (GPU idle before: the core clock has not ramped up yet)
             "cold_start": None if cold_dt is None else {"ms_per_step": cold_dt / args.steps * 1e3, "value": px / cold_dt / 1e6},
-            "order": "cold_start (W + K steps) first; then hbm_probe, single_view, frame_sweep (rank 0), batch_sweep (on every rank); then the W warm-up and K timed steps of the headline; "
-                     "steady_state, parity check, other configurations and the CPU baseline after it",
-            "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": (f"BASELINE configs[2]: {S}x{S}, {T}-triangle bumpy sphere, C={Cc} (RGB+depth), sigma=1, " if not textured else
-                                    f"BASELINE configs[4]: {S}x{S}, {T}-triangle bumpy sphere, textured Gouraud, {ds.texture.shape[1]}x{ds.texture.shape[0]} texture, C={Cc}, sigma=1, ")
-                                   + f"{B} views per GPU per step, float32 pixel buffers / float64 vertex arrays, all-double arithmetic",
-                       "step": "renderScene + renderScene_B (two calls)" if args.two_pass else "deodr_hip_render_scene_fit (forward + adjoint of sum (image - obs)^2, one call)",
-                       "views_per_gpu": B, "global_views": global_views, "env_overrides": overrides,
-                       "nonempty_tiles": nonempty, "edge_tiles": edge_tiles, "tiles": ntiles,
-                       "parallelism": f"views sharded {B}/GPU" + (", 1 RCCL all-reduce of the shared gradient per step" if world > 1 else "")
-                                      + (" (texture_b | vertices_b | colors_b | uv_b in one float32 buffer)" if textured and world > 1 else ""),
-                       **({"strong_scaling_floor": single_floor} if args.scaling == "strong" else {})},
             # dominant kernel group (largest hipEvent time).  achieved / frac: the SURVEY 8d bytes THIS group moves / its average
             # duration, against the 8 TB/s of the data sheet; frac_of_measured: against the copy bandwidth measured on this box.
             # whole_step: all of SURVEY 8d's bytes / the step time (the north star's 40 % is about this number); frac_moved_bytes:
@@ -883,16 +956,17 @@ def main():
                          "not_moved_bytes": alg.get("not_moved"),
                          "kernel_time_fraction_of_step": kernel_ms / (step_s * 1e3), "per_kernel": per_kernel},
             "hbm_probe": probe,
-        }  # fmt: skip
+        })  # fmt: skip
+    if rank == 0:
         if reduction_check is not None:
             out["reduction_check"] = reduction_check
-        if not args.no_parity_check:
+        if full and not args.no_parity_check:
             # the launch that was timed (its last step's outputs are still in image / z / the gradient set it wrote), views 0 and last
             last = last_slot[0].grads if last_slot[0] is not None else grads
             out["parity"] = parity_check(views, sorted({0, B - 1}), image, z, last, obs_views, sigma=args.sigma)
             out["parity_checked"] = out["parity"]["ok"]
             assert out["parity"]["ok"], f"bench: the timed launch does not match the checker: {out['parity']}"
-        if world == 1 and not args.no_other_configs and not textured:
+        if full and world == 1 and not args.no_other_configs and not textured:
             out["other_configs"] = other_configs(dev)
             out["other_configs"] += slow_family(dev, single_view["ms_eager"] if single_view is not None else None)
         if single_view is not None:
@@ -902,7 +976,7 @@ def main():
             if frames is not None:
                 # the same 20 000-triangle mesh on larger frames (views, size): where the pixel kernels take the step once the per-triangle work is amortised
                 out["frame_sweep"] = frames
-        if world == 1 and not args.no_cpu_baseline and not textured:
+        if full and world == 1 and not args.no_cpu_baseline and not textured:
             out["cpu_baseline"] = cpu_baseline(views[0], 2 * (image[0] - obs).cpu().numpy().astype(np.float64), poses, S)
         result_line = json.dumps(out)
     else:

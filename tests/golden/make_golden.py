@@ -18,6 +18,9 @@ Fixtures
                        the goldens of tests/test_triangle_soup_fitting.py:29-108.
   hand_mesh.npz        vertices / faces of deodr/data/hand.obj read with deodr/obj.py (input data for
                        BASELINE configs 2 and 4).
+  hand.obj             deodr/data/hand.obj itself (the mesh file the arrays of hand_mesh.npz were read from).
+  hand_adjacency.npz   TriMeshAdjacencies of the hand mesh (deodr/triangulated_mesh.py): face normals, vertex normals and the
+                       silhouette flags of the edges seen along z.
   depth_hand_fit.npz   deodr/examples/depth_image_hand_fitting.py `run(dl_library="none")`: the cropped depth image (float32 as
                        in deodr/data/depth.bin), the 50 energies of MeshDepthFitter.step (last one = the golden of the
                        reference's tests/test_depth_image_hand_fitting.py:36-42) and, for iteration 0, every intermediate of
@@ -143,6 +146,20 @@ def hand():
     faces, vertices = read_obj(os.path.join(deodr.data_path, "hand.obj"))
     np.savez_compressed(os.path.join(OUT, "hand_mesh.npz"), faces=np.asarray(faces, dtype=np.uint32), vertices=np.asarray(vertices, dtype=np.float64))
     print("hand mesh", np.shape(vertices), np.shape(faces))
+    shutil.copy(os.path.join(deodr.data_path, "hand.obj"), os.path.join(OUT, "hand.obj"))
+
+
+def hand_adjacency():
+    from deodr.triangulated_mesh import TriMeshAdjacencies
+
+    d = np.load(os.path.join(OUT, "hand_mesh.npz"))
+    adjacency = TriMeshAdjacencies(d["faces"].astype(np.int64))
+    face_normals = adjacency.compute_face_normals(d["vertices"])
+    np.savez_compressed(
+        os.path.join(OUT, "hand_adjacency.npz"), face_normals=face_normals, vertex_normals=adjacency.compute_vertex_normals(face_normals),
+        edge_on_silhouette=np.asarray(adjacency.edge_on_silhouette(d["vertices"][:, :2]), dtype=bool),
+    )  # fmt: skip
+    print("hand adjacency: edges on the silhouette", int(np.sum(adjacency.edge_on_silhouette(d["vertices"][:, :2]))))
 
 
 def depth_hand_fit():
@@ -433,6 +450,7 @@ if __name__ == "__main__":
             soup(True)
         if not only or "hand" in only:
             hand()
+            hand_adjacency()
         if not only or "fits" in only:
             depth_hand_fit()
             rgb_hand_fit()

@@ -743,7 +743,7 @@ def test_bench_two_ranks_on_one_gpu():
     JSON line from rank 0 -- with two ranks that share this box's GPU and all-reduce over gloo (`--test-backend gloo`: RCCL refuses two
     ranks on one device).  The line's own checks must hold: the timed launch against the unmodified reference, the all-reduced gradient
     against a synchronous reduction."""
-    out = _run_bench("--gpus", "2", "--steps", "6", "--warmup", "2", "--size", "256", "--views", "2", "--test-backend", "gloo")
+    out = _run_bench("--gpus", "2", "--steps", "6", "--warmup", "2", "--size", "256", "--views", "2", "--test-backend", "gloo", "--full")
     assert out["n_gpus"] == 2 and out["steps"] == 6 and out["warmup"] == 2 and out["scaling"] == "weak" and out["value"] > 0
     assert out["config"]["global_views"] == 4 and out["config"]["views_per_gpu"] == 2
     assert any("NOT a measurement" in o for o in out["config"]["env_overrides"])
@@ -757,7 +757,7 @@ def test_bench_two_ranks_textured_batch_strong_scaling():
     texture_b and uv_b are part of the ONE all-reduced buffer (float32, 12.6 MB + the vertex sums), checked against a synchronous
     reduction of the re-rendered step; the timed launch against the unmodified reference."""
     out = _run_bench("--gpus", "2", "--config", "4", "--scaling", "strong", "--steps", "3", "--warmup", "1", "--size", "256", "--views", "4",
-                     "--test-backend", "gloo", "--time-every", "0")  # fmt: skip
+                     "--test-backend", "gloo", "--time-every", "0", "--full")  # fmt: skip
     assert out["n_gpus"] == 2 and out["scaling"] == "strong" and out["config"]["global_views"] == 4 and out["config"]["views_per_gpu"] == 2
     assert "strong_scaling_floor" in out["config"] and "configs[4]" in out["config"]["workload"]
     rc = out["reduction_check"]

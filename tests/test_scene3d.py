@@ -114,7 +114,7 @@ def test_reference_duck_test_front_half_cpu(oracle_api):
 
 def test_read_and_save_obj_cpu(tmp_path):
     """deodr_amd.read_obj / save_obj (deodr/obj.py): v / f records, corners with texture and normal indices, relative indices,
-    a continued line; where the reference tree is at hand, its hand.obj gives the arrays of tests/golden/hand_mesh.npz"""
+    a continued line; the reference's hand.obj (tests/golden/hand.obj) gives the arrays of tests/golden/hand_mesh.npz"""
     import deodr_amd as deodr
 
     path = tmp_path / "m.obj"
@@ -125,10 +125,8 @@ def test_read_and_save_obj_cpu(tmp_path):
     deodr.save_obj(str(tmp_path / "hand.obj"), v, f)
     f2, v2 = deodr.read_obj(str(tmp_path / "hand.obj"))
     assert np.array_equal(f2, f) and np.array_equal(v2, v)
-    reference_hand = "/root/reference/deodr/data/hand.obj"
-    if os.path.exists(reference_hand):
-        f3, v3 = deodr.read_obj(reference_hand)
-        assert np.array_equal(f3, f) and np.array_equal(v3, v)
+    f3, v3 = deodr.read_obj(os.path.join(GOLDEN, "hand.obj"))
+    assert np.array_equal(f3, f) and np.array_equal(v3, v)
 
 
 def test_element_count_of_arrays_and_tensors_cpu():

@@ -5,7 +5,7 @@ TAG=${1:-r01}
 cd $GRAFT_REPO_ROOT
 OUT=$GRAFT_REPO_ROOT/gpurun_out/profile_$TAG
 mkdir -p $OUT
-python bench.py > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 tail -c 600 $OUT/bench.json; echo
 cd /tmp && export TMPDIR=/tmp
 timeout -k 5 240 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o k -- python $GRAFT_REPO_ROOT/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-single-view --no-other-configs --no-parity-check > $OUT/stats.log 2>&1
