@@ -899,11 +899,9 @@ __global__ __launch_bounds__(64, 6) void raster_bwd_fast_kernel(KParams p)
 	}
 }
 
-#ifndef DR_EDGE_OCC
-#define DR_EDGE_OCC 4 // waves per SIMD of the untextured edge kernel (3: no spills, 5: more) -- swept, 4 stays
-#endif
+constexpr int EDGE_OCC = 4; // waves per SIMD of the untextured edge kernel (3: no spills, 5: more) -- swept, 4 stays
 template <class PixT, bool TEX, int NC = 0>
-__global__ __launch_bounds__(64, TEX ? 2 : DR_EDGE_OCC) void raster_bwd_edge_kernel(KParams p)
+__global__ __launch_bounds__(64, TEX ? 2 : EDGE_OCC) void raster_bwd_edge_kernel(KParams p)
 {
 	if (NC)
 		p.C = NC, p.L.P = NC < 3 ? 3 : NC; // persistent waves over the lists of tiles that hold silhouette edges (built by tile_scan_kernel).  Grid (views, waves):
@@ -916,14 +914,11 @@ __global__ __launch_bounds__(64, TEX ? 2 : DR_EDGE_OCC) void raster_bwd_edge_ker
 	const ViewPtrs w = view_ptrs(p, view);
 	// the last workgroups of the grid stream the background of this kernel's share of the empty tiles (fill_share)
 	const int fill_n = fill_share(p.fill_mode, 0, p.L.nwords), fill_blocks = fill_share_blocks(fill_n);
-#ifndef DR_FILL_FIRST
-#define DR_FILL_FIRST 0 // measurement builds: 1 = the fill workgroups at the head of both grids instead of the tail
-#endif
 	const int walkers = (int)gridDim.y - fill_blocks;
-	const int by = DR_FILL_FIRST ? (int)blockIdx.y - fill_blocks : (int)blockIdx.y; // index among the walkers (< 0: a fill workgroup)
-	if (DR_FILL_FIRST ? by < 0 : by >= walkers)
+	const int by = (int)blockIdx.y; // index among the walkers (>= walkers: a fill workgroup)
+	if (by >= walkers)
 	{
-		for (int i = DR_FILL_FIRST ? (int)blockIdx.y : by - walkers; i < fill_n; i += fill_blocks)
+		for (int i = by - walkers; i < fill_n; i += fill_blocks)
 			fill_share_word(p, 0, view, i, lane);
 		return;
 	}

@@ -18,9 +18,6 @@ namespace
 // this one -- 38 us even when no two triangles share a vertex, because the table is flushed vertex-major: the lanes of one
 // instruction add to consecutive addresses).  Open addressing on the vertex index; a corner that finds no slot after VT_PROBES
 // steps falls back to the direct atomics.  Only KIND_INTERP triangles with nb_colors <= 4 (row: ij 2 + colours 4).
-#ifndef DR_FIN_MERGE
-#define DR_FIN_MERGE 1 // (measurement builds: 0 = every contribution straight to the gradient arrays, as in round 3)
-#endif
 constexpr int VT_SLOTS = 512, VT_ROW = 6, VT_PROBES = 8;
 struct VertexTable
 {
@@ -64,12 +61,10 @@ struct MergeSink // finalize_triangle's sink: corner i of the triangle adds into
 
 // DET: the deterministic mode (KParams::det): accumulators are read as int64 fixed point, contributions go to the int64 shadow arrays,
 // no vertex table (its LDS atomics are shared by four wavefronts: their order is not reproducible).
-// TABLE: the instance with the per-workgroup vertex table (launches of >= DR_PRIM_TABLES_MIN triangles: KParams::prim_tables); the one
+// TABLE: the instance with the per-workgroup vertex table (launches of >= PRIM_TABLES_MIN triangles: KParams::prim_tables); the one
 // without keeps round 3's registers and LDS -- a single 20 k-triangle view is a chain of round trips and lost 1.7 us to the table's mere presence.
+constexpr int FIN_WAVES = 4; // waves per SIMD finalize_kernel is compiled for (3: 144 registers with the vertex table, 21.4 -> 22.4 us)
 template <bool VTX64, int NC, bool DET = false, bool TABLE = false> // (the dtype of the vertex arrays and the channel count at compile time: see setup_bin_kernel)
-#ifndef DR_FIN_WAVES
-#define DR_FIN_WAVES 4 // waves per SIMD finalize_kernel is compiled for (3: 144 registers with the vertex table, 21.4 -> 22.4 us)
-#endif
 __device__ __forceinline__ void finalize_body(KParams &p)
 { // same split as setup_bin_kernel: triangle blocks, then edge-slot blocks compacted to the flagged slots.
   // (Lists of the front-facing triangles / drawn edges compacted by the set-up kernel were tried: a quarter as many wavefronts,
@@ -100,23 +95,20 @@ __device__ __forceinline__ void finalize_body(KParams &p)
 		}
 		return;
 	}
-	const int fill_n = fill_share(p.fill_mode, 1, p.L.nwords), fill_blocks = (p.n_views * fill_n + PRIM_BLOCK / 64 - 1) / (PRIM_BLOCK / 64);
+	const int fill_n = fill_share(p.fill_mode, 1, p.L.nwords);
 	const int bx = (int)blockIdx.x - loss_blocks;
 	// (small launches, KParams::setup_sparse: ONE edge slot per thread, as in the set-up kernel -- a soup's 600 flagged edges are three workgroups of one
 	// round each instead of one workgroup of three rounds)
 	const int edge_slots = p.setup_sparse > 1 ? 1 : EDGE_SLOTS, pblocks = prim_tri_blocks(p.T) + prim_edge_blocks(p.T, edge_slots);
-	const int fb = DR_FILL_FIRST ? bx : bx - p.n_views * pblocks; // index among the fill workgroups
-	if (DR_FILL_FIRST ? fb < fill_blocks : fb >= 0)
+	const int fb = bx - p.n_views * pblocks; // index among the fill workgroups (the tail of the grid)
+	if (fb >= 0)
 	{ // workgroups that stream the background of this kernel's share of the empty tiles (fill_share)
 		const int gw = fb * (PRIM_BLOCK / 64) + (int)(threadIdx.x >> 6);
 		if (fill_n > 0 && gw < p.n_views * fill_n)
 			fill_share_word(p, 1, gw / fill_n, gw % fill_n, threadIdx.x & 63);
 		return;
 	}
-#ifndef DR_FIN_EDGE_FIRST
-#define DR_FIN_EDGE_FIRST 1 // (triangle blocks first: finalize 37.5 -> 43.5 us)
-#endif
-	const PrimWork pw = prim_work(p, DR_FIN_EDGE_FIRST, (DR_FILL_FIRST ? fill_blocks : 0) + loss_blocks, -1, edge_slots);
+	const PrimWork pw = prim_work(p, true, loss_blocks, -1, edge_slots); // (edge-slot blocks first, as in the set-up kernel; triangle blocks first: finalize 37.5 -> 43.5 us)
 	const int view = pw.view;
 	const bool tri_block = pw.tri;
 	const SceneView s = scene_view(p, view);
@@ -185,7 +177,7 @@ __device__ __forceinline__ void finalize_body(KParams &p)
 		// (the table's 26 KB are only touched by a block that has a triangle for it: half the blocks of a closed mesh are all back-facing)
 		__shared__ __attribute__((aligned(16))) char s_vt_storage[TABLE ? sizeof(VertexTable) : 16]; // (no table, no LDS for it)
 		VertexTable &s_vt = *(VertexTable *)s_vt_storage;
-		const bool merge = TABLE && DR_FIN_MERGE && p.prim_tables && P <= 4 && __syncthreads_or(live && (flag & 3u) == KIND_INTERP);
+		const bool merge = TABLE && p.prim_tables && P <= 4 && __syncthreads_or(live && (flag & 3u) == KIND_INTERP);
 		if (merge)
 		{
 			for (int i = threadIdx.x; i < VT_SLOTS; i += PRIM_BLOCK)
@@ -325,7 +317,7 @@ __device__ __forceinline__ void step_done_signal(const KParams &p)
 }
 
 template <bool VTX64, int NC, bool DET = false, bool TABLE = false>
-__global__ __launch_bounds__(PRIM_BLOCK, DR_FIN_WAVES) void finalize_kernel(KParams p)
+__global__ __launch_bounds__(PRIM_BLOCK, FIN_WAVES) void finalize_kernel(KParams p)
 {
 	finalize_body<VTX64, NC, DET, TABLE>(p);
 	if (p.done_flag)

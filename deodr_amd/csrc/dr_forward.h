@@ -379,16 +379,7 @@ __device__ __forceinline__ void fill_background_tile(const KParams &p, int view,
 // Two tiles out of three receive nothing: this is what lets the forward launch one wavefront per tile that HAS work instead of
 // one per tile of the frame (the waves of the empty tiles used to take a third of its slot-time), and it takes the
 // many-primitive-tile flags and lists (two more dependent atomics per lane) out of the set-up kernel.
-#ifndef DR_WORK_CHUNK
-#define DR_WORK_CHUNK 64
-#endif
-constexpr int SCAN_BLOCK = SCAN_TILES, WORK_CHUNK = DR_WORK_CHUNK;
-#ifndef DR_DYN_WALKERS
-#define DR_DYN_WALKERS 0 // 1: persistent walkers with tickets on the others' list of a many-view fit step (KParams::dyn_groups)
-#endif
-#ifndef DR_PAIR_TILES
-#define DR_PAIR_TILES 1 // (measurement builds: 0 = one tile per wavefront everywhere, as in round 2)
-#endif
+constexpr int SCAN_BLOCK = SCAN_TILES, WORK_CHUNK = 64;
 constexpr uint32_t PAIR_FLAG = 0x80000000u; // in WorkEntry::tile of a pair of tiles (fwd_pair_tiles); then WorkEntry::ntri = nA | nB << 16
 static_assert(FIRST_PRIMS <= 8, "a paired tile carries at most eight triangle ids (two 16-byte pieces of its inline list)");
 // One tile workgroup in `heavy_share` walks the list of the many-primitive tiles (the head of the grid: dispatched first).  One in
@@ -396,13 +387,8 @@ static_assert(FIRST_PRIMS <= 8, "a paired tile carries at most eight triangle id
 // SIMD): with every slot of the first dispatch round on a 25 - 50 us tile the short tiles -- whose arithmetic hides those tiles'
 // round trips -- start late.  Measured on the 8-view benchmark step: 1/8 0.183 ms, 1/12 0.1775, 1/16 0.1767, 1/24 0.1784; on one
 // 2048^2 view (2 048 head workgroups at 1/8) 1/16 costs 4 %; on one 1024^2 view 1/2 0.0775, 1/4 0.0772, 1/8 0.0809, 1/16 0.090 ms.
-#ifndef DR_HEAVY_SHARE
-#define DR_HEAVY_SHARE 0 // measurement builds: a fixed share
-#endif
 __host__ inline int heavy_share_for(int n_views, int tile_blocks, bool fuse_edges)
 {
-	if (DR_HEAVY_SHARE)
-		return DR_HEAVY_SHARE;
 	// ~2 048 head workgroups over all views (40 % of the wave slots), the share a power of two between 1/4 and 1/16.  Twice as many
 	// when the head also holds every tile with silhouette edges and runs their adjoint (a fit step: ~1 000 head entries per view of
 	// the benchmark scene, 20 - 60 us each -- with 256 walkers per view the forward ended 14 us after its last short tile)
@@ -417,16 +403,10 @@ __host__ inline int heavy_share_for(int n_views, int tile_blocks, bool fuse_edge
 	return share;
 }
 
-#ifndef DR_SPLIT_EDGES
-#define DR_SPLIT_EDGES 1 // (measurement builds: 0 = a tile is one work item whatever its number of edges)
-#endif
 constexpr uint32_t SPLIT_FLAG = 0x80000000u; // in WorkEntry::nedge: bits 16 .. 19 = which part of the edges this copy of the tile back-propagates
-#ifndef DR_SPLIT_PART
-#define DR_SPLIT_PART 0 // (measurement builds: a fixed number of edges per part)
-#endif
 // Edges per part (KParams::split_part): 8 when the launch is about one dispatch round of walkers (one or two 1024^2 views: the longest
 // wavefront decides, 1 view 0.0607 -> 0.0585 ms), a whole batch of 16 otherwise (8 views: the repeated forward parts cost 1.5 us).
-__host__ inline int split_part_for(int n_views, int tile_blocks) { return DR_SPLIT_PART ? DR_SPLIT_PART : ((long long)n_views * tile_blocks <= 8192 ? 8 : 16); }
+__host__ inline int split_part_for(int n_views, int tile_blocks) { return (long long)n_views * tile_blocks <= 8192 ? 8 : 16; }
 
 __global__ __launch_bounds__(SCAN_BLOCK) void tile_scan_kernel(KParams p)
 {
@@ -481,9 +461,9 @@ __global__ __launch_bounds__(SCAN_BLOCK) void tile_scan_kernel(KParams p)
 	// adds its triangle ids to that entry.
 	bool pair_left = false, pair_right = false;
 	uint32_t ntri_right = 0;
-	// (textured scenes, round 6: below DR_TEX_TWO_KERNELS views per launch only -- KParams::pair_tex, the host's rule: from 8 views on the head walkers
+	// (textured scenes, round 6: below TEX_TWO_KERNELS views per launch only -- KParams::pair_tex, the host's rule: from 8 views on the head walkers
 	// are a kernel of their own and the critical path, pairs among the others bought nothing there and cost 11 %: profiles/r06tp_*)
-	if (DR_PAIR_TILES && p.fuse_edges && (!p.texture || p.pair_tex) && (p.L.tiles_x & 1) == 0 && p.tile_blocks % (8 * WORK_CHUNK) == 0)
+	if (p.fuse_edges && (!p.texture || p.pair_tex) && (p.L.tiles_x & 1) == 0 && p.tile_blocks % (8 * WORK_CHUNK) == 0)
 	{
 		const bool plain = work && !heavy && nedge == 0 && ntri > 0;
 		const uint32_t n_next = (uint32_t)__shfl_down((int)(plain ? ntri : 0u), 1, 64), n_prev = (uint32_t)__shfl_up((int)(plain ? ntri : 0u), 1, 64);
@@ -500,10 +480,10 @@ __global__ __launch_bounds__(SCAN_BLOCK) void tile_scan_kernel(KParams p)
 	// out for that many and no more: a soup of 20 000 slivers at sigma = 3 has more tiles of 17+ edges than empty ones, and its copies,
 	// unbounded, ran into the entries that come from the other end of the list (memory fault found by tests/fuzz_parity.py).
 	const unsigned long long below = (1ull << lane) - 1ull;
-	uint32_t extra = (DR_SPLIT_EDGES && heavy && p.fuse_edges && nedge > (uint32_t)TB && nedge <= (uint32_t)EMAX)
+	uint32_t extra = (heavy && p.fuse_edges && nedge > (uint32_t)TB && nedge <= (uint32_t)EMAX)
 						 ? (nedge + (uint32_t)p.split_part - 1) / (uint32_t)p.split_part - 1u
 						 : 0u; // 0 .. 15 copies asked for
-	if (p.fuse_edges && DR_SPLIT_EDGES)
+	if (p.fuse_edges)
 	{ // (a condition of the launch: every thread of the block takes the barrier)
 		const unsigned long long r0 = __ballot(extra & 1u), r1 = __ballot(extra & 2u), r2 = __ballot(extra & 4u), r3 = __ballot(extra & 8u);
 		if (lane == 0)
@@ -812,16 +792,8 @@ __global__ __launch_bounds__(64 * FILL_WAVES) void fill_kernel(KParams p, int ow
 // 110 MB of stores per 8-view step at the ~3 TB/s the store path sustains, i.e. ~37 us of bandwidth time wherever it goes: only the
 // forward raster (issue-bound, ~95 us, 0.6 TB/s of stores of its own) is long enough to hide most of it; finalize_kernel (bound by
 // the latency of its round trips) hides a part (all of it there: + 11 us).
-#ifndef DR_FILL_W_EDGE
-#define DR_FILL_W_EDGE 1
-#endif
-#ifndef DR_FILL_W_FIN
-#define DR_FILL_W_FIN 1
-#endif
-#ifndef DR_FILL_W_FWD
-#define DR_FILL_W_FWD 2
-#endif
-__host__ __device__ inline int fill_weight(int bit) { return bit == 0 ? DR_FILL_W_EDGE : (bit == 1 ? DR_FILL_W_FIN : DR_FILL_W_FWD); }
+constexpr int FILL_W_EDGE = 1, FILL_W_FIN = 1, FILL_W_FWD = 2;
+__host__ __device__ inline int fill_weight(int bit) { return bit == 0 ? FILL_W_EDGE : (bit == 1 ? FILL_W_FIN : FILL_W_FWD); }
 __host__ __device__ inline void fill_split(int fill_mode, int bit, int &den, int &off)
 { // of every `den` consecutive bitmap words, the fill_weight(bit) words starting at `off` are kernel `bit`'s
 	den = off = 0;
@@ -883,10 +855,7 @@ __host__ __device__ inline int fwd_tile_blocks(int ntiles, int n_views, bool dea
   // and longer walkers win there (same-box A/B, 8 views of the benchmark scene: /4 0.1242 - 0.1252, /5 0.1208 - 0.1214, /6 0.1211 - 0.1213,
   // /8 0.1271 - 0.1280 ms; 8 views of the hand 0.103 -> 0.096; 1 / 2 / 4 views lose 1 - 3 % at /6, 16 views are level: profiles/r04n)
 	const int unit = 8 * WORK_CHUNK;
-#ifndef DR_TILE_DIV
-#define DR_TILE_DIV 0 // (measurement builds: a fixed divisor)
-#endif
-	const int div = DR_TILE_DIV ? DR_TILE_DIV : ((dealt_fill && n_views >= 8) ? 6 : 4);
+	const int div = (dealt_fill && n_views >= 8) ? 6 : 4;
 	const int g = ((ntiles / div + unit - 1) / unit) * unit;
 	return g > 0 && g <= ntiles ? g : ntiles; // tiny frames: one workgroup per tile, plain order
 }
@@ -900,11 +869,9 @@ __host__ __device__ inline int fwd_tile_blocks(int ntiles, int n_views, bool dea
 // texture taps; at four waves it spills 414 registers.  configs[4], 1 / 8 views: four waves 0.176 / 0.886 - 0.930 ms, three 0.168 / 0.868 -
 // 0.893, two 0.167 / 1.02; the instances WITHOUT the edge adjoint lose 6 - 9 % at three: profiles/r05y_ab_fused_textured_edge_tiles.txt)
 // (tools/build_variants.sh builds the neighbours: -DDR_FWD_WAVES=n forces n for all).
-#ifndef DR_TEXE_HEAD_WAVES
-#define DR_TEXE_HEAD_WAVES 3 // waves per SIMD of the kernel of the head walkers alone (TEXE = 2)
-#endif
+constexpr int TEXE_HEAD_WAVES = 3; // waves per SIMD of the kernel of the head walkers alone (TEXE = 2)
 #ifndef DR_FWD_WAVES
-#define DR_FWD_WAVES (TEX ? (TEXE == 1 ? 3 : (TEXE == 2 ? DR_TEXE_HEAD_WAVES : 4)) : 5)
+#define DR_FWD_WAVES (TEX ? (TEXE == 1 ? 3 : (TEXE == 2 ? TEXE_HEAD_WAVES : 4)) : 5)
 #endif
 // Two horizontally adjacent tiles in one wavefront, two pixels per lane (lane = row * 8 + column: pixel `column` of the left tile A
 // and pixel `column` of the right tile B).  For the pairs the scan kernel forms -- both tiles non-empty, no silhouette edge, at
@@ -1278,9 +1245,6 @@ __device__ __forceinline__ void fwd_manyc_tile(const KParams &p, const ViewPtrs 
 // loop: the edge adjoint needs ~40 registers more than the rest, and as a branch of the common loop (or as a function called from
 // it) it cost EVERY tile spills on its path (forward 83 -> 90 us before the first edge tile was fused); as a disjoint path its
 // spills stay with the one workgroup in sixteen that walks the head.
-#ifndef DR_ONE_BATCH_BODY
-#define DR_ONE_BATCH_BODY 1 // (measurement builds: 0 = one body for every head tile, as until the end of round 5)
-#endif
 enum FwdMode
 {
 	FWD_PLAIN = 0,	  // forward only (or adjoint left to the two-call path): pass 2 saves its sweep for raster_bwd_edge_kernel
@@ -1318,9 +1282,6 @@ __device__ __forceinline__ void fwd_tiles(const KParams &p, WaveLds *s_lds, Edge
 	const bool persp = p.persp;
 	const PixT *texture = (const PixT *)p.texture;
 	WaveLds &S = s_lds[wave];
-	int grp = 0; // (persistent walkers) the ticket group of `view` this walker draws from: its own XCD's, until that one runs dry
-	for (int hop = 0;; hop++)
-	{ // (one pass, unless the walker is a persistent one that moves on to another group's entries: below)
 	const ViewPtrs w = view_ptrs(p, view);
 	// The first G / p.heavy_share workgroups of a view walk the many-primitive tiles (front of the list), the others the rest (from
 	// the back): the index of a workgroup's entry does not depend on the counts, so the counts, the entry header and the
@@ -1331,22 +1292,6 @@ __device__ __forceinline__ void fwd_tiles(const KParams &p, WaveLds *s_lds, Edge
 	const int qq = heavy_list ? q : q - Gh, stride = heavy_list ? Gh : G - Gh;
 	const bool chunk_here = chunked && stride % (8 * WORK_CHUNK) == 0;
 	uint32_t rank = chunk_here ? (uint32_t)((((qq >> 3) / WORK_CHUNK) * 8 + (qq & 7)) * WORK_CHUNK + (qq >> 3) % WORK_CHUNK) : (uint32_t)qq;
-	// Persistent walkers (KParams::dyn_groups, the others' list of a many-view fit step): far fewer workgroups than entries, all resident, each taking
-	// its entries by TICKET -- a wave slot then never waits for the dispatcher between two tiles (tools/wave_trace.py --slots: ~1 us from the end of a
-	// one-tile workgroup to the start of the next one on its SIMD, 27 000 times per 8-view step).  One counter per (view, XCD): ticket t of group g is
-	// entry (t / 8) * 64 + g * 8 + t % 8 -- runs of eight neighbouring entries stay on one XCD's L2.  The ticket of the entry after next is requested
-	// (one lane, returning atomic) when a tile starts, the next entry itself a tile ahead as before: no round trip is waited for between tiles.
-	const bool dyn = DR_DYN_WALKERS && MODE == FWD_NO_EDGES && p.dyn_groups > 0;
-	if (hop == 0)
-		grp = qq & (DYN_GROUPS - 1);
-	uint32_t *const tick = &w.edge_tile_cnt[(EDGE_LISTS + 1 + grp) * CNT_STRIDE];
-	auto ticket_rank = [&](uint32_t t) { return (t >> 3) * (8u * DYN_GROUPS) + (uint32_t)grp * 8u + (t & 7u); };
-	uint32_t tk = 0; // (lane 0) the ticket of the entry after the one whose header is in `head`
-	if (dyn)
-	{
-		if (lane0 == 0)
-			tk = atomicAdd(tick, 2u);
-	}
 	// The first entry of a walker (usually its only one) is requested TOGETHER with the count it is checked against -- the position of the
 	// entry does not depend on the count and lies inside the list whatever the count is (rank < stride <= tiles <= work_cap).  As the first
 	// statement of the loop body the load sat behind the branch on the count: a third dependent round trip (count, entry, records) in the
@@ -1355,12 +1300,6 @@ __device__ __forceinline__ void fwd_tiles(const KParams &p, WaveLds *s_lds, Edge
 	// (The compiler sinks loads that only the loop body uses below the branch on the count, whatever their place in the source: the empty
 	// asm statement takes the three results as read-write operands, so all three loads are issued, and waited for ONCE, in front of it.)
 	uint32_t n_work_v = w.hdr->work_count[heavy_list ? 0 : 1];
-	if (dyn)
-	{ // (the first two tickets in one request; the count travels with it)
-		const uint32_t t0 = (uint32_t)uniform((int)tk);
-		rank = ticket_rank(t0);
-		tk = t0 + 1u;
-	}
 	uint4 head = *(const uint4 *)entry_at(rank); // {tile, ntri, nedge, sweep_slot}
 	uint32_t ids_first = entry_at(rank)->ids[lane0 < ENTRY_IDS ? lane0 : 0];
 	asm volatile("" : "+v"(head.x), "+v"(head.y), "+v"(head.z), "+v"(head.w), "+v"(ids_first), "+v"(n_work_v));
@@ -1375,13 +1314,11 @@ __device__ __forceinline__ void fwd_tiles(const KParams &p, WaveLds *s_lds, Edge
 		// now, a whole tile ahead of its use: its position does not depend on anything this tile computes
 		const uint4 cur = head;
 		const uint32_t ids12 = ids_first;
-		rank = dyn ? ticket_rank((uint32_t)uniform((int)tk)) : rank + (uint32_t)stride;
+		rank += (uint32_t)stride;
 		if (rank < n_work)
 		{
 			head = *(const uint4 *)entry_at(rank);
 			ids_first = entry_at(rank)->ids[lane < ENTRY_IDS ? lane : 0];
-			if (dyn && lane == 0)
-				tk = atomicAdd(tick, 1u);
 		}
 		const uint32_t e_tile = (uint32_t)uniform((int)cur.x), e_ntri = (uint32_t)uniform((int)cur.y), e_nedge = (uint32_t)uniform((int)cur.z);
 		if (FUSED && (!TEX || TEXPAIR) && MODE == FWD_NO_EDGES && (e_tile & PAIR_FLAG))
@@ -1818,68 +1755,23 @@ __device__ __forceinline__ void fwd_tiles(const KParams &p, WaveLds *s_lds, Edge
 		}
 		}
 		};
-		if (MODE == FWD_EDGE_ADJ && DR_ONE_BATCH_BODY && !(e_nedge & SPLIT_FLAG) && e_nedge <= (uint32_t)TB)
+		if (MODE == FWD_EDGE_ADJ && !(e_nedge & SPLIT_FLAG) && e_nedge <= (uint32_t)TB)
 			tile_body(std::true_type{});
 		else
 			tile_body(std::false_type{});
 		lds_sync(); // the next tile of this wavefront reuses the staging area
 	}
-	if (q == 0 && hop == 0 && wave_lane() == 0)
+	if (q == 0 && wave_lane() == 0)
 		close_epoch(p, w, FUSED);
-#ifndef DR_DYN_HOPS
-#define DR_DYN_HOPS 6 // other groups a persistent walker may move on to
-#endif
-	if (!dyn || hop >= DR_DYN_HOPS)
-		break;
-	// This group's entries are all handed out.  Groups finish at different times (views differ in work, XCDs in the long tiles they hold): look at
-	// every group's counter against its number of entries -- lane = 8 * view + group, eight views per pass, ONE round trip -- and move on to one that
-	// has entries left: one of the own XCD's if there is any (its L2 holds that part of the scene), picked by the walker's index so that the
-	// walkers that run dry together do not all queue at one counter.
-	int best = -1;
-	for (int v0 = 0; v0 < p.n_views && best < 0; v0 += 8)
-	{
-		const int v = v0 + (lane0 >> 3), gg = lane0 & 7;
-		int remain = 0;
-		if (v < p.n_views)
-		{
-			const ViewPtrs wv = view_ptrs(p, v);
-			const uint32_t issued = __hip_atomic_load(&wv.edge_tile_cnt[(EDGE_LISTS + 1 + gg) * CNT_STRIDE], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-			const uint32_t nw = wv.hdr->work_count[1];
-			const int tail = (int)(nw & 63u) - gg * 8;
-			remain = (int)((nw >> 6) * 8u) + (tail < 0 ? 0 : (tail > 8 ? 8 : tail)) - (int)issued;
-		}
-		const unsigned long long any = __ballot(remain > 1), same = any & (0x0101010101010101ull << grp);
-		unsigned long long pick = same ? same : any;
-		if (pick)
-		{
-			uint32_t k = ((b * 2654435761u) >> 16) % (uint32_t)__popcll(pick);
-			for (; k > 0; k--)
-				pick &= pick - 1ull;
-			best = v0 * 8 + (int)__builtin_ctzll(pick);
-		}
-	}
-	if (best < 0)
-		break;
-	view = best >> 3;
-	grp = best & 7;
-	}
 }
 
-#ifndef DR_FUSE_TEX_EDGES
-#define DR_FUSE_TEX_EDGES 1 // (measurement builds: 0 = the tiles with silhouette edges of a TEXTURED fit step wait for raster_bwd_edge_kernel, as until round 4)
-#endif
-// The forward raster of a textured fit step of DR_TEX_TWO_KERNELS views or more as TWO kernels on two streams -- the head walkers (edge adjoint: 168
+// The forward raster of a textured fit step of TEX_TWO_KERNELS views or more as TWO kernels on two streams -- the head walkers (edge adjoint: 168
 // registers, three waves per SIMD) on the library's side stream, everybody else (128 registers, four waves again) on the caller's, both behind the scan
 // kernel, joined in front of finalize.  As one kernel the 95 % of the tiles that hold no edge run at the occupancy the edge adjoint dictates.
 // configs[4]: 8 views 0.839 - 0.841 -> 0.800 - 0.810 ms; 4 views level (0.436 / 0.434); 2 views 0.235 -> 0.275, one view 0.166 -> 0.21 (the fork and the
 // join cost more than the occupancy returns), hence the threshold; head walkers at two waves: worse everywhere (profiles/r05z6_ab_two_kernels.txt).
-// 0: never.  Not while the stream is being captured (the single kernel then).
-#ifndef DR_TEX_TWO_KERNELS
-#define DR_TEX_TWO_KERNELS 8
-#endif
-#ifndef DR_FUSE_EDGES
-#define DR_FUSE_EDGES 1 // (measurement builds: 0 = the tiles with silhouette edges of a fit step wait for raster_bwd_edge_kernel, as in round 2)
-#endif
+// Not while the stream is being captured (the single kernel then).
+constexpr int TEX_TWO_KERNELS = 8;
 // CLAMP: residual of sum (clamp(image) - obs)^2 (KParams::clamp).  NC: the channel count at compile time (0: whatever the scene says).
 // Every per-channel statement of the walkers is guarded by `cc < C`; with C known the guards and the code behind the false ones go:
 // the 8-view benchmark step (C = 4) 0.160 -> 0.150 ms.  The host picks the instance (3 and 4 channels, the fit step's kernels).
@@ -1912,30 +1804,10 @@ __global__ __launch_bounds__(64, DR_FWD_WAVES) void raster_fwd_fast_kernel(KPara
 	// stores per 8-view step: same-box A/B 0.1279 / 0.1274 -> 0.1238 / 0.1232 ms, profiles/r04l).  (Round 3 measured "spread evenly:
 	// nothing" -- with the heavy tiles still deciding when the kernel ends.)
 	const uint32_t n_walk = (uint32_t)p.n_views * p.fwd_walkers, n_fill = p.fwd_n_fill; // (= n_views * fill_share(fill_mode, 2, nwords), from the host)
-#ifndef DR_FILL_DEAL
-#define DR_FILL_DEAL 1 // (measurement builds: 0 = the fill workgroups behind the walkers, as in round 3)
-#endif
-	const uint32_t dealt = (DR_FILL_DEAL && FUSED && !TEX) ? p.fwd_dealt : 0; // groups of 64 walkers + 8 fill workgroups (the host: fuse_edges && n_walk >= 8 n_fill ? n_fill / 8 : 0)
+	const uint32_t dealt = (FUSED && !TEX) ? p.fwd_dealt : 0; // groups of 64 walkers + 8 fill workgroups (the host: fuse_edges && n_walk >= 8 n_fill ? n_fill / 8 : 0)
 	uint32_t b = blockIdx.x + p.block_base; // (32-bit throughout: see fwd_tiles)
 	int fi = -1;
-	if (DR_DYN_WALKERS && p.dyn_groups > 0)
-	{ // (persistent walkers: half as many workgroups for the same fill -- sixteen fill workgroups behind every 64 walkers)
-		if (b < dealt * 80)
-		{
-			const uint32_t grp = b / 80, r = b - grp * 80;
-			if (r < 64)
-				b = grp * 64 + r;
-			else
-				fi = (int)(grp * 16 + (r - 64));
-		}
-		else
-		{
-			b -= dealt * 16;
-			if (b >= n_walk)
-				fi = (int)(dealt * 16 + (b - n_walk));
-		}
-	}
-	else if (b < dealt * 72)
+	if (b < dealt * 72)
 	{
 		const uint32_t grp = b / 72, r = b - grp * 72;
 		if (r < 64)
@@ -1961,7 +1833,7 @@ __global__ __launch_bounds__(64, DR_FWD_WAVES) void raster_fwd_fast_kernel(KPara
 		fwd_tiles<PixT, FUSED, TEX, FWD_EDGE_ADJ, CLAMP>(p, s_lds, s_es, b); // (this launch: the head walkers, nobody else)
 	else if constexpr (TEXE == 3)
 		fwd_tiles<PixT, FUSED, TEX, FWD_NO_EDGES, CLAMP>(p, s_lds, s_es, b); // (this launch: everybody else)
-	else if (FUSED && DR_FUSE_EDGES && (!TEX || TEXE))
+	else if (FUSED && (!TEX || TEXE))
 	{ // (p.fuse_edges is set: the host and the scan kernel follow the same rule -- fit step of an untextured scene)
 		const int G = p.tile_blocks;
 		const bool chunked = G % (8 * WORK_CHUNK) == 0;

@@ -168,10 +168,8 @@ int fill_params(const DeodrHipScene *sc, double sigma, void *workspace, size_t w
 	p.ws = (char *)workspace;
 	p.row_group = ROW_GROUP;
 	// (see KParams::prim_tables; measured on the 20 k-triangle benchmark scene: 1 view loses 1.7 us to the tables, 8 views gain 6)
-#ifndef DR_PRIM_TABLES_MIN
-#define DR_PRIM_TABLES_MIN 40000
-#endif
-	p.prim_tables = (long long)sc->n_views * sc->nb_triangles >= DR_PRIM_TABLES_MIN;
+	constexpr long long PRIM_TABLES_MIN = 40000;
+	p.prim_tables = (long long)sc->n_views * sc->nb_triangles >= PRIM_TABLES_MIN;
 	return 0;
 }
 
@@ -273,10 +271,7 @@ void det_convert(const KParams &p, int n_views, hipStream_t st)
 }
 // Tuning constants (measured in round 1, profiles/README.md); deliberately NOT read from the environment: nothing outside the
 // arguments of a call may change what the call launches.
-#ifndef DR_EDGE_WAVES
-#define DR_EDGE_WAVES 1024
-#endif
-constexpr int EDGE_WAVES = DR_EDGE_WAVES; // persistent waves per view of the adjoint's edge kernel
+constexpr int EDGE_WAVES = 1024; // persistent waves per view of the adjoint's edge kernel
 
 // The channel count (and the "usual frame" flag) as compile-time constants of the raster kernels -- for float32 pixel buffers, the storage of the
 // fit loops; with float64 buffers (the 1e-9 parity path, the NumPy drop-ins of the reference's entry points) every call takes the run-time-C
@@ -402,42 +397,21 @@ int side_stream(SideStream &out)
 	return 0;
 }
 
-// KParams::fwd_* / views_magic: what every workgroup of the staged forward (and of raster_bwd_fast_kernel, which walks the same list) would otherwise
-// derive for itself (tile_blocks, heavy_share, fill_mode, n_views are set)
+// KParams::fwd_* / views_magic: what every workgroup of the staged forward would otherwise derive for itself (tile_blocks, heavy_share, fill_mode,
+// n_views are set).  Only the staged forward reads them: the adjoint's launches do not call this.
 void forward_launch_constants(KParams &q)
 {
 	const bool chunked = q.tile_blocks % (8 * WORK_CHUNK) == 0;
 	q.fwd_heads = chunked ? (uint32_t)(q.tile_blocks / q.heavy_share) : 0u;
 	q.fwd_walkers = (uint32_t)q.tile_blocks;
-	q.dyn_groups = 0;
-#ifndef DR_DYN_MIN
-#define DR_DYN_MIN 20000 // walkers (all views) from which the others' list of a fit step is walked by persistent walkers with tickets
-#endif
-#ifndef DR_DYN_TOTAL
-#define DR_DYN_TOTAL 4608 // persistent walkers of all views together (the chip holds 5 120 wavefronts of the forward raster)
-#endif
-	if (DR_DYN_WALKERS && chunked && q.fuse_edges && q.texture == nullptr && (long long)q.n_views * q.tile_blocks >= DR_DYN_MIN)
-	{
-		const uint32_t others = ((uint32_t)DR_DYN_TOTAL / (uint32_t)q.n_views) & ~7u;
-		if (others >= 8 && q.fwd_heads + others < (uint32_t)q.tile_blocks)
-		{
-			q.fwd_walkers = q.fwd_heads + others;
-			q.dyn_groups = DYN_GROUPS;
-		}
-	}
 	const uint32_t n_walk = (uint32_t)q.n_views * q.fwd_walkers;
 	q.fwd_n_fill = (uint32_t)q.n_views * (uint32_t)fill_share(q.fill_mode, 2, q.L.nwords);
-	if (q.dyn_groups)
-		q.fwd_dealt = q.fwd_n_fill / 16 < n_walk / 64 ? q.fwd_n_fill / 16 : n_walk / 64; // sixteen fill workgroups behind every 64 walkers
-	else
-		q.fwd_dealt = (q.fuse_edges && n_walk >= 8 * q.fwd_n_fill) ? q.fwd_n_fill / 8 : 0u;
+	q.fwd_dealt = (q.fuse_edges && n_walk >= 8 * q.fwd_n_fill) ? q.fwd_n_fill / 8 : 0u;
 	q.views_magic = q.n_views == 1 ? 0xffffffffu : (uint32_t)(0x100000000ull / (unsigned long long)q.n_views) + 1u; // (see div_views)
 }
 
-#ifndef DR_SPARSE_MAX
-#define DR_SPARSE_MAX 16384 // triangles (all views) up to which the per-primitive kernels spread their work over more wavefronts (KParams::setup_sparse)
-#endif
-bool small_launch(int T, int n_views) { return (long long)T * n_views <= DR_SPARSE_MAX; }
+constexpr long long SPARSE_MAX = 16384; // triangles (all views) up to which the per-primitive kernels spread their work over more wavefronts (KParams::setup_sparse)
+bool small_launch(int T, int n_views) { return (long long)T * n_views <= SPARSE_MAX; }
 
 // Staged forward: counters -> work list + tile bitmap (scan), then the raster on the caller's stream and, forked from it, the
 // background fill on the side stream.  *join receives the event the caller's stream has to wait for before the call returns
@@ -449,10 +423,7 @@ int launch_forward_staged(const KParams &p, bool fused, hipStream_t stream, hipE
 	q.tile_blocks = fwd_tile_blocks(p.L.ntiles, p.n_views, fused && p.fuse_edges);
 	q.heavy_share = heavy_share_for(p.n_views, q.tile_blocks, fused && p.fuse_edges);
 	q.split_part = split_part_for(p.n_views, q.tile_blocks);
-#ifndef DR_PAIR_TEX
-#define DR_PAIR_TEX 1 // (measurement builds: 0 = textured scenes do not pair their tiles, as until round 6)
-#endif
-	q.pair_tex = DR_PAIR_TEX && p.texture != nullptr && (!DR_TEX_TWO_KERNELS || p.n_views < DR_TEX_TWO_KERNELS);
+	q.pair_tex = p.texture != nullptr && p.n_views < TEX_TWO_KERNELS;
 	forward_launch_constants(q);
 	hipLaunchKernelGGL(tile_scan_kernel, dim3((p.L.ntiles + SCAN_BLOCK - 1) / SCAN_BLOCK, p.n_views), dim3(SCAN_BLOCK), 0, stream, q);
 	if (p.fill_mode == 0)
@@ -472,11 +443,11 @@ int launch_forward_staged(const KParams &p, bool fused, hipStream_t stream, hipE
 	const bool tex = p.texture != nullptr; // (see launch_adjoint_raster)
 	const bool common = p.strict && p.W % TILE == 0 && p.H % TILE == 0;
 	hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-	if (DR_TEX_TWO_KERNELS && fused && tex && p.fuse_edges)
+	if (fused && tex && p.fuse_edges)
 		(void)hipStreamIsCapturing(stream, &capturing);
 	// (the split point must fall between two groups of eight workgroups -- a walker's list and XCD follow from its index in the one-kernel grid
-	// (KParams::block_base) --: true for the shares heavy_share_for returns, checked here for measurement builds with another DR_HEAVY_SHARE)
-	if (DR_TEX_TWO_KERNELS && fused && tex && p.fuse_edges && !p.clamp && p.n_views >= DR_TEX_TWO_KERNELS && q.tile_blocks % (8 * WORK_CHUNK) == 0 &&
+	// (KParams::block_base) --: true for the shares heavy_share_for returns, checked here all the same)
+	if (fused && tex && p.fuse_edges && !p.clamp && p.n_views >= TEX_TWO_KERNELS && q.tile_blocks % (8 * WORK_CHUNK) == 0 &&
 		q.tile_blocks % q.heavy_share == 0 && (q.tile_blocks / q.heavy_share) % 8 == 0 && capturing == hipStreamCaptureStatusNone)
 	{ // the head walkers (edge adjoint: many registers) on the side stream, everybody else (+ the fill workgroups) on the caller's, both behind the scan
 		const unsigned head = (unsigned)p.n_views * (unsigned)(q.tile_blocks / q.heavy_share);
@@ -893,16 +864,13 @@ static int render_scene_fit_impl(const DeodrHipScene *sc, void *image, void *z_b
 	if (opt && opt->clamp)
 		p.clamp = 1, p.clamp_lo = opt->clamp_lo, p.clamp_hi = opt->clamp_hi;
 	// the background of the empty tiles rides on the adjoint's kernels (fill_share); without any of them: the side stream
-#ifndef DR_FILL_MASK
-#define DR_FILL_MASK 7 // measurement builds: 0 side stream, 1 edge kernel only, 2 finalize only, 4 forward raster only
-#endif
 	// The forward raster also back-propagates the tiles with silhouette edges (no edge-tile kernel, no saved sweeps) and streams a share
 	// of the background.  Textured scenes too since round 5 (round 2 measured 0.264 -> 0.407 ms for one 2048^2 view of 100 k triangles:
 	// 400 spilled registers on the edge path at four waves per SIMD; with the instances of their own at three waves, the many-edge tiles
 	// split into parts and the quadrant windows of the texture gradient it is 0.195 -> 0.168 ms, 2 / 4 / 8 views 0.257 -> 0.243 /
 	// 0.448 -> 0.451 / 0.890 -> 0.893: profiles/r05y_ab_fused_textured_edge_tiles.txt).  (sigma = 0: no edge anywhere, the lighter instances)
-	p.fuse_edges = DR_FUSE_EDGES && fused && (!p.texture || (DR_FUSE_TEX_EDGES && sigma > 0));
-	p.fill_mode = fused ? ((((sigma > 0 && !p.fuse_edges) ? 1 : 0) | (p.T > 0 ? 2 : 0) | ((p.T > 0 && p.fuse_edges) ? 4 : 0)) & DR_FILL_MASK) : 0;
+	p.fuse_edges = fused && (!p.texture || sigma > 0);
+	p.fill_mode = fused ? (((sigma > 0 && !p.fuse_edges) ? 1 : 0) | (p.T > 0 ? 2 : 0) | ((p.T > 0 && p.fuse_edges) ? 4 : 0)) : 0;
 	note_forward(workspace, fused);
 	hipEvent_t join = nullptr;
 	if (launch_forward(sc, p, st, &join, fused))

@@ -88,30 +88,19 @@ __device__ __forceinline__ bool tile_outside_halfplanes(const double *eq, int tx
 // (Workgroups of one wavefront -- 64 triangles, or a span of 256 edge slots compacted by each of four single-wave blocks -- were
 // measured: every wave starts within 10 us instead of 23, and the kernels take 38 / 35 us instead of 35 / 33: they are bound by
 // the memory-side atomics and the arithmetic of the long waves, not by wave slots.)
-#ifndef DR_PRIM_BLOCK
-#define DR_PRIM_BLOCK 256
-#endif
-constexpr int PRIM_BLOCK = DR_PRIM_BLOCK;
-#ifndef DR_PRIM_WAVES
-#define DR_PRIM_WAVES 3 // waves per SIMD the per-primitive kernels are compiled for (4: spills, same time)
-#endif
+constexpr int PRIM_BLOCK = 256;
+constexpr int PRIM_WAVES = 3; // waves per SIMD the per-primitive kernels are compiled for (4: spills, same time)
 
 __host__ __device__ inline int prim_tri_blocks(int T) { return (T + PRIM_BLOCK - 1) / PRIM_BLOCK; }
 // An edge-slot block looks at EDGE_SLOTS consecutive slots per thread (a few per cent of the slots are flagged as silhouette edges:
 // with one slot per thread three quarters of both kernels' wavefronts did nothing but look at 64 flags)
-#ifndef DR_EDGE_SLOTS
-#define DR_EDGE_SLOTS 4
-#endif
-constexpr int EDGE_SLOTS = DR_EDGE_SLOTS, EDGE_BLOCK_SLOTS = PRIM_BLOCK * EDGE_SLOTS;
+constexpr int EDGE_SLOTS = 4, EDGE_BLOCK_SLOTS = PRIM_BLOCK * EDGE_SLOTS;
 __host__ __device__ inline int prim_blocks(int T) { return prim_tri_blocks(T) + (3 * T + EDGE_BLOCK_SLOTS - 1) / EDGE_BLOCK_SLOTS; }
 
 // Grid of the per-primitive kernels: 1-D, n_views * prim_blocks(T) workgroups.  The edge-slot blocks of every view come first,
 // then the triangle blocks (views fastest inside each class): the wavefront that works on flagged edges is the longest
 // dependent chain of both kernels (13 - 20 us against 3 us for a triangle wavefront, tools/wave_trace.py), and dispatched after
 // the triangle blocks it was the 15 us tail of the kernel.
-#ifndef DR_EDGE_FIRST
-#define DR_EDGE_FIRST 1
-#endif
 struct PrimWork
 {
 	int view, index; // index of the block inside its class
@@ -121,7 +110,7 @@ struct PrimWork
 // tri_slots: triangle slots of a view (p.T, or p.T * KParams::setup_sparse in the set-up kernel of a small scene: see setup_bin_kernel)
 __host__ __device__ inline int prim_edge_blocks(int T, int slots_per_thread) { return (3 * T + PRIM_BLOCK * slots_per_thread - 1) / (PRIM_BLOCK * slots_per_thread); }
 // edge_slots: edge slots an edge-slot block looks at per thread (EDGE_SLOTS, or 1 in the set-up kernel of a small scene)
-__device__ __forceinline__ PrimWork prim_work(const KParams &p, bool edge_first = DR_EDGE_FIRST, int skip = 0, int tri_slots = -1, int edge_slots = EDGE_SLOTS)
+__device__ __forceinline__ PrimWork prim_work(const KParams &p, bool edge_first, int skip = 0, int tri_slots = -1, int edge_slots = EDGE_SLOTS)
 {
 	const int TBk = prim_tri_blocks(tri_slots < 0 ? p.T : tri_slots), EB = prim_edge_blocks(p.T, edge_slots), nv = p.n_views;
 	int b = (int)blockIdx.x - skip;
@@ -130,12 +119,8 @@ __device__ __forceinline__ PrimWork prim_work(const KParams &p, bool edge_first 
 	const bool in_first = b < first;
 	if (!in_first)
 		b -= first;
-#ifndef DR_VIEW_MAJOR
-#define DR_VIEW_MAJOR 0 // measurement builds: 1 = all blocks of a view, then the next view (instead of views fastest)
-#endif
-	const int per_view = in_first == edge_first ? EB : TBk; // blocks per view of this block's class
-	w.view = DR_VIEW_MAJOR ? b / per_view : b % nv;
-	w.index = DR_VIEW_MAJOR ? b % per_view : b / nv;
+	w.view = b % nv;
+	w.index = b / nv;
 	w.tri = edge_first ? !in_first : in_first;
 	w.view_block = w.tri ? w.index : TBk + w.index;
 	return w;
@@ -247,7 +232,7 @@ struct WaveTrace
 // the inputs of one triangle.
 // NC: the channel count at compile time (0: whatever the scene says), as for raster_fwd_fast_kernel.
 template <bool VTX64, int NC>
-__global__ __launch_bounds__(PRIM_BLOCK, DR_PRIM_WAVES) void setup_bin_kernel(KParams p)
+__global__ __launch_bounds__(PRIM_BLOCK, PRIM_WAVES) void setup_bin_kernel(KParams p)
 {
 	p.vtx_f64 = VTX64 ? 1 : 0; // (what the host passed: now known to the compiler; scene_view() copies it)
 	if (NC)
@@ -257,11 +242,11 @@ __global__ __launch_bounds__(PRIM_BLOCK, DR_PRIM_WAVES) void setup_bin_kernel(KP
 	// Small scenes (round 6): a triangle every `sparse` lanes.  A mesh of a thousand large triangles (the hand at 1024^2: 33 tiles per triangle) is 17
 	// wavefronts on 256 CUs, each with 64 triangles' worth of 3 x 3-tile blocks to bin -- two or three rounds of dependent slot requests (bin_rest), a
 	// soup of 200 triangles nine; the lanes in between take part in that dealing and have nothing else to do, so spread over four times the wavefronts
-	// (on a chip that is empty anyway) a wavefront's share fits one round.  The host sets it for launches of at most DR_SPARSE_MAX triangles.
+	// (on a chip that is empty anyway) a wavefront's share fits one round.  The host sets it for launches of at most SPARSE_MAX triangles.
 	// The same for the edge-slot blocks: ONE slot per thread instead of EDGE_SLOTS (a soup flags every edge: 600 slots were one workgroup working
 	// through three rounds of 256 edges, each with its own rounds of slot requests).
 	const int sparse = p.setup_sparse > 1 ? p.setup_sparse : 1, edge_slots = p.setup_sparse > 1 ? 1 : EDGE_SLOTS;
-	const PrimWork pw = prim_work(p, DR_EDGE_FIRST, 0, p.T * sparse, edge_slots);
+	const PrimWork pw = prim_work(p, true, 0, p.T * sparse, edge_slots);
 	const int view = pw.view;
 	const int item = pw.view_block * PRIM_BLOCK + threadIdx.x; // only an id for the housekeeping below
 	const int n_items = (prim_tri_blocks(p.T * sparse) + prim_edge_blocks(p.T, edge_slots)) * PRIM_BLOCK;
@@ -277,7 +262,7 @@ __global__ __launch_bounds__(PRIM_BLOCK, DR_PRIM_WAVES) void setup_bin_kernel(KP
 		w.hdr->snap_count[1 - cur] = 0;
 		w.hdr->work_count[0] = w.hdr->work_count[1] = 0; // filled by tile_scan_kernel, read by the forward raster
 	}
-	if (item <= EDGE_LISTS + DYN_GROUPS) // appended to by tile_scan_kernel, the next kernel on the stream (+ the ticket counters of the forward raster's persistent walkers)
+	if (item <= EDGE_LISTS) // appended to by tile_scan_kernel, the next kernel on the stream
 		w.edge_tile_cnt[item * CNT_STRIDE] = 0;
 	if (p.loss_wave) // (one partial per tile walker of the forward raster, two kernels later)
 		for (int v = item; v < LOSS_SLOTS; v += n_items)

@@ -26,7 +26,9 @@
 #   fwdN       -DDR_FWD_WAVES=N the staged forward compiled for N waves / SIMD  (tools/step_time.py --lib)
 #   (tools/variants/lean_many_walkers.patch: a round-5 walker experiment as a `git diff` against the sources of commit 824e91e -- apply from the root of a
 #    checkout of that commit with `patch -p1`; measured and not adopted, profiles/r05y_ab_lean_and_many_edge_walkers.txt.  Its sibling, the tile body
-#    compiled twice, is in the product since commit 3de053c: -DDR_ONE_BATCH_BODY=0 builds the neighbour)
+#    compiled twice, is in the product since commit 3de053c)
+#   (tools/variants/span_rcp.patch, dyn_walkers_view_interleaved.patch, head_tickets.patch: round-6 experiments, measured and not adopted, against code
+#    that has since been removed -- they fit the sources of commit 8cd22f9: `git worktree add /tmp/r6 8cd22f9` and apply them there)
 #   <name>     EXTRA="-D..."    anything else: the product sources with the flags of $EXTRA
 ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 OUT=$ROOT/tools/variants

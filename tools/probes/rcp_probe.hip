@@ -1,11 +1,29 @@
-// round 6: (1) accuracy of v_rcp_f64 (what dr_math.h's quick_floor_quotient assumes: relative error <= 2^-20), (2) quick_floor_quotient against
+// round 6: (1) accuracy of v_rcp_f64 (what quick_floor_quotient below assumes: relative error <= 2^-20), (2) quick_floor_quotient against
 // floor(a / b) / ceil(a / b) on random and on adversarial operands (integer quotients, quotients one ulp either side of an integer, tiny / huge
 // divisors).  Tools only; not part of the library.   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -o rcp_probe rcp_probe.hip
+// (The scanline spans by reciprocal were measured and not adopted: tools/variants/span_rcp.patch, profiles/r06a_*.)
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include "../../deodr_amd/csrc/dr_math.h"
+
+// floor(a / b) WITHOUT the IEEE division, for the usual quotient: branch-free, and `ok` is cleared when the result is not PROVEN equal to
+// floor(fl(a / b)) (and the result + 1 to ceil(fl(a / b))).
+// q~ = a * r with r = 1 / b from the hardware reciprocal (v_rcp_f64: 2^-20 relative error is assumed here) and ONE Newton step, so r is good
+// to 2^-39 and, as |a / b| < 2^15 behind the reference's own guard, |q~ - a / b| < 2^-23.  fl(a / b) is within half an ulp (< 2^-38) of a / b.
+// When q~ lies at least 2^-20 away from both neighbouring integers, a / b and fl(a / b) lie strictly between the same two integers:
+// floor(fl(a / b)) = floor(q~) and ceil(fl(a / b)) = floor(q~) + 1, bit for bit.  Otherwise (integer vertex coordinates do that: the quotient
+// IS an integer, and fl() of a quotient just below one may round up to it), or when the guard fails (the reference's slow walk), or with a
+// NaN / infinite intermediate (both comparisons fail): ok = false.
+__device__ double quick_floor_quotient(double a, double b, bool &ok)
+{
+	double r = __builtin_amdgcn_rcp(b); // v_rcp_f64
+	r = __builtin_fma(__builtin_fma(-b, r, 1.0), r, r);
+	const double q = a * r, fl = floor(q), d = q - fl; // (d: exact)
+	ok = ok & (fabs(b) * DR_SHRT_MAX > fabs(a) + fabs(b)) & (d > 0x1p-20) & (d < 1.0 - 0x1p-20);
+	return fl;
+}
 
 __device__ uint64_t rng(uint64_t &s)
 {
@@ -56,8 +74,9 @@ __global__ void quotient_check(unsigned long long *counts, int iters, int kind)
 		if (!(fabs(b) * DR_SHRT_MAX > fabs(a) + fabs(b)))
 			continue;
 		tested++;
-		double fl;
-		if (dr::quick_floor_quotient(a, b, fl))
+		bool ok = true;
+		const double fl = quick_floor_quotient(a, b, ok);
+		if (ok)
 		{
 			quick++;
 			const double q = a / b;
