@@ -693,7 +693,7 @@ __device__ __forceinline__ void bwd_fast_tile(const KParams &p, const ViewPtrs &
 	{ // more than EMAX edges in one tile (or pool overflow): the un-staged code, right here (pathological and slow, but no
 	  // queue and no extra launch for the tiles that never exist in a real scene)
 		lds_sync();
-		bwd_tile_generic_impl<PixT, true, TEX>(p, view, tx, ty, lane, (volatile uint32_t *)es->sorted);
+		bwd_tile_generic_impl<PixT, true, TEX, false>(p, view, tx, ty, lane, (volatile uint32_t *)es->sorted);
 		lds_sync();
 		return;
 	}
@@ -721,6 +721,7 @@ __device__ __forceinline__ void bwd_fast_tile(const KParams &p, const ViewPtrs &
 		}
 		else
 		{ // residual mode: dL/dimage of L = sum (image - obs)^2 formed on the fly from the rendered image and the observation
+		  // (deodr_hip_render_scene_b: no per-pixel weights on this entry -- a weighted fit step runs this adjoint inside its forward raster)
 			const PixT *im = (const PixT *)p.image_in + vpix * C, *ob = (const PixT *)p.obs + vpix * C;
 #pragma unroll
 			for (int cc = 0; cc < CH; cc++)

@@ -44,7 +44,8 @@ __device__ __forceinline__ void texture_scatter(PixT *texture_b, const Tap &tap,
 // adjoint of one tile, any channel count / edge count / mode; `order` is a per-wave LDS array of MAX_SORTED entries.
 // LEAN: the instance inlined into raster_bwd_edge_kernel for the (pathological) tiles with more than EMAX edges: at most CH
 // channels and no antialiase_error, which the compiler can then drop.
-template <class PixT, bool LEAN, bool TEX = true>
+// WGT: residual mode with per-pixel weights (KParams::weights != NULL, fit_weight): instances of their own, the others are compiled without.
+template <class PixT, bool LEAN, bool TEX = true, bool WGT = false>
 __device__ __forceinline__ void bwd_tile_generic_impl(const KParams &p, int view, int tx, int ty, int lane, volatile uint32_t *order)
 {
 	const ViewPtrs w = view_ptrs(p, view);
@@ -144,6 +145,7 @@ __device__ __forceinline__ void bwd_tile_generic_impl(const KParams &p, int view
 
 	// ---- antialiase_error mode: the edges blended the squared residual err_buffer, not the image (H.h:2200-2368, 2481-2618)
 	double eb = 0; // running adjoint of err_buffer at this pixel
+	const PixT wt = fit_weight<WGT, PixT>(p, vpix, inb);
 	if (aa_err)
 	{
 		const PixT *obs = (const PixT *)p.obs + vpix * C;
@@ -255,7 +257,7 @@ __device__ __forceinline__ void bwd_tile_generic_impl(const KParams &p, int view
 						g[j] = -2 * ((double)((const PixT *)p.obs)[vpix * C + c0 + j] - base_channel(c0 + j)) * eb;
 					else
 						g[j] = p.image_b ? (double)((const PixT *)p.image_b)[vpix * C + c0 + j]
-										 : fit_residual<true>(p, (double)((const PixT *)p.image_in)[vpix * C + c0 + j], (double)((const PixT *)p.obs)[vpix * C + c0 + j]);
+										 : fit_weighted<WGT>(fit_residual<true>(p, (double)((const PixT *)p.image_in)[vpix * C + c0 + j], (double)((const PixT *)p.obs)[vpix * C + c0 + j]), wt);
 				}
 			}
 			if (nedge > 0 && !aa_err)
@@ -453,9 +455,15 @@ __device__ __noinline__ void bwd_tile_generic(const KParams &p, int view, int tx
 {
 	bwd_tile_generic_impl<PixT, false>(p, view, tx, ty, lane, order);
 }
-
 template <class PixT>
-__global__ __launch_bounds__(256) void raster_bwd_kernel(KParams p)
+__device__ __noinline__ void bwd_tile_generic_weighted(const KParams &p, int view, int tx, int ty, int lane, volatile uint32_t *order)
+{
+	bwd_tile_generic_impl<PixT, false, true, true>(p, view, tx, ty, lane, order);
+}
+
+// four tiles (wavefronts) per workgroup; WGT: a fit step with per-pixel weights (KParams::weights != NULL)
+template <class PixT, bool WGT>
+__device__ __forceinline__ void raster_bwd_body(const KParams &p)
 {
 	__shared__ volatile uint32_t s_order[4][MAX_SORTED];
 	const int wave = uniform(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -463,7 +471,23 @@ __global__ __launch_bounds__(256) void raster_bwd_kernel(KParams p)
 	const int b = xcd_band(blockIdx.x, gridDim.x);
 	const int ty = xcd_strip_row(b / strips_x, p.L.tiles_y, p.row_group), tx = (b % strips_x) * 4 + wave;
 	if (tx < p.L.tiles_x)
-		bwd_tile_generic<PixT>(p, blockIdx.y, tx, ty, lane, s_order[wave]);
+	{
+		if constexpr (WGT)
+			bwd_tile_generic_weighted<PixT>(p, blockIdx.y, tx, ty, lane, s_order[wave]);
+		else
+			bwd_tile_generic<PixT>(p, blockIdx.y, tx, ty, lane, s_order[wave]);
+	}
+}
+template <class PixT>
+__global__ __launch_bounds__(256) void raster_bwd_kernel(KParams p)
+{
+	raster_bwd_body<PixT, false>(p);
+}
+// (a kernel of its own name rather than a template flag: the names of the kernels that existed before the weights are what they were)
+template <class PixT>
+__global__ __launch_bounds__(256) void raster_bwd_weighted_kernel(KParams p)
+{
+	raster_bwd_body<PixT, true>(p);
 }
 
 } // namespace

@@ -601,6 +601,56 @@ __global__ __launch_bounds__(FH_BLOCK) void l2_loss_kernel(const PixT *image, co
 		out[0] = total[0];
 }
 
+// The same sum with one weight per pixel of C channels, sum_p w[p] sum_c (clamp(image) - obs)^2 (DeodrHipFitOptions::weights): the one-pass fallback of a
+// weighted fit step the staged kernels do not take.  A copy of l2_loss_kernel, which stays what it was: the same traversal and the same order of
+// additions, every squared residual times its pixel's weight -- weights of 1 give the unweighted sum bit for bit.
+// (A copy on purpose: with one body templated on the weights and two thin kernels around it -- as background_loss_tile below, tried twice -- the
+// compiler allocates l2_loss_kernel's scalar registers differently, 54 / 58 -> 56, and the kernels that existed before are to be what they were.
+// A change to the traversal or to the tail has to be made in both.)
+template <class PixT>
+__global__ __launch_bounds__(FH_BLOCK) void l2_loss_weighted_kernel(const PixT *image, const PixT *obs, const PixT *weights, int C, size_t count, double *out, double *partials, unsigned *counter,
+																	 int clamp, double clamp_lo, double clamp_hi)
+{
+	auto value = [&](PixT v) {
+		const double x = (double)v;
+		return clamp ? (x < clamp_lo ? clamp_lo : (x > clamp_hi ? clamp_hi : x)) : x;
+	};
+	constexpr int W = 32 / sizeof(PixT);
+	struct alignas(32) Chunk
+	{
+		PixT v[W];
+	};
+	double s[1] = {0};
+	const size_t chunks = count / W, stride = (size_t)gridDim.x * FH_BLOCK;
+	for (size_t i = (size_t)blockIdx.x * FH_BLOCK + threadIdx.x; i < chunks; i += L2_ROUND * stride)
+	{
+		Chunk a[L2_ROUND], b[L2_ROUND];
+#pragma unroll
+		for (int u = 0; u < L2_ROUND; u++)
+		{
+			const size_t at = i + u * stride < chunks ? i + u * stride : i;
+			a[u] = ((const Chunk *)image)[at], b[u] = ((const Chunk *)obs)[at];
+		}
+#pragma unroll
+		for (int u = 0; u < L2_ROUND; u++)
+			if (i + u * stride < chunks)
+#pragma unroll
+				for (int j = 0; j < W; j++)
+				{
+					const double r = value(a[u].v[j]) - (double)b[u].v[j];
+					s[0] += (r * r) * (double)weights[((i + u * stride) * W + j) / (size_t)C];
+				}
+	}
+	if (blockIdx.x == 0 && threadIdx.x < count - chunks * W)
+	{
+		const double r = value(image[chunks * W + threadIdx.x]) - (double)obs[chunks * W + threadIdx.x];
+		s[0] += (r * r) * (double)weights[(chunks * W + threadIdx.x) / (size_t)C];
+	}
+	double total[1];
+	if (grid_sum<1>(s, partials, counter, total) && threadIdx.x == 0)
+		out[0] = total[0];
+}
+
 // ---- the data term of the depth fitter (deodr/mesh_fitter.py:108-123): depth = clamp(image, 0, max_depth), diff = (depth - obs)^2,
 // loss = sum diff, image_b = d loss / d image = 2 (depth - obs) where the clamp passes (0 <= image <= max_depth), else 0
 template <class PixT>
@@ -626,9 +676,9 @@ __global__ __launch_bounds__(FH_BLOCK) void depth_residual_kernel(const PixT *im
 // ---- the loss of a fit step without a pass over the frame (deodr_hip_render_scene_fit_loss): the caller's table holds, per tile and in
 // total, the loss sum (background - obs)^2 of a frame that is all background -- computed ONCE per observation by the two kernels
 // below --; the forward raster only adds, per non-empty tile, (loss of the tile as rendered - its background loss).
-template <class PixT>
-__global__ __launch_bounds__(64) void background_loss_kernel(KParams p, double *table)
-{ // one wavefront per tile: table[1 + view * ntiles + tile]
+template <class PixT, bool WGT>
+__device__ __forceinline__ void background_loss_tile(const KParams &p, double *table)
+{ // one wavefront per tile: table[1 + view * ntiles + tile]; WGT: every pixel's share times its weight (KParams::weights != NULL)
 	const int tile = blockIdx.x, view = blockIdx.y, lane = threadIdx.x;
 	const int px = (tile % p.L.tiles_x) * TILE + (lane & 7), py = (tile / p.L.tiles_x) * TILE + (lane >> 3);
 	double r2 = 0;
@@ -641,10 +691,21 @@ __global__ __launch_bounds__(64) void background_loss_kernel(KParams p, double *
 			const double d = fit_value<true>(p, (double)(PixT)background_channel<PixT>(p, view, pix, c)) - (double)o[c]; // (the frame holds the background rounded to PixT)
 			r2 += d * d;
 		}
+		r2 = fit_weighted<WGT>(r2, fit_weight<WGT, PixT>(p, (size_t)view * p.H * p.W + pix, true));
 	}
 	r2 = wave_sum(r2);
 	if (lane == 0)
 		table[1 + (size_t)view * p.L.ntiles + tile] = r2;
+}
+template <class PixT>
+__global__ __launch_bounds__(64) void background_loss_kernel(KParams p, double *table)
+{
+	background_loss_tile<PixT, false>(p, table);
+}
+template <class PixT>
+__global__ __launch_bounds__(64) void background_loss_weighted_kernel(KParams p, double *table)
+{
+	background_loss_tile<PixT, true>(p, table);
 }
 __global__ __launch_bounds__(FH_BLOCK) void background_loss_total_kernel(double *table, size_t count)
 { // table[0] = sum of the others, by one workgroup in a fixed order

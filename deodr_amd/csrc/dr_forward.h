@@ -325,7 +325,7 @@ template <class PixT, bool TEX, int NBATCH, class Lds, class BaseFn> // (NBATCH:
 __device__ __forceinline__ void edge_reverse_sweep(const KParams &p, const ViewPtrs &w, Lds &S, const EdgeSort *es, int lane, double x, double y, int n_edges,
 												   int b_hi, int b_lo, bool top_staged, const uint32_t (&tm)[NBATCH], double (&cur)[CH], double (&g)[CH],
 												   double (&base)[CH], bool &have_base, BaseFn pixel_base, int r_lo = 0, int r_hi = TB - 1);
-template <class PixT, bool LEAN, bool TEX>
+template <class PixT, bool LEAN, bool TEX, bool WGT>
 __device__ __forceinline__ void bwd_tile_generic_impl(const KParams &p, int view, int tx, int ty, int lane, volatile uint32_t *order);
 
 // Background of one tile that received no primitive: colour, depth = +inf, no owner (H.h:2728-2744).
@@ -885,7 +885,7 @@ constexpr int TEXE_HEAD_WAVES = 3; // waves per SIMD of the kernel of the head w
 // TEX (round 6): textured scenes pair up too -- configs[4]'s tiles hold 5.9 triangles on average (median 4), and of an edge-free textured tile's 20 k
 // cycles 7.3 k are the prologue and pass 1 that a pair pays once; the winner's texels are fetched per pixel, and the adjoint of pass 1 runs twice
 // (owner_adjoint with the texture-gradient window, tile A then tile B).
-template <class PixT, bool CLAMP, bool TEX = false>
+template <class PixT, bool CLAMP, bool TEX = false, bool WGT = false>
 __device__ __forceinline__ void fwd_pair_tiles(const KParams &p, const ViewPtrs &w, WaveLds &S, int view, int lane, int tile, int nA, int nB, uint32_t my_id,
 											   double *loss_at)
 { // loss_at (or NULL): this walker's partial of the loss, see tile_loss
@@ -918,6 +918,7 @@ __device__ __forceinline__ void fwd_pair_tiles(const KParams &p, const ViewPtrs 
 			if (cc < C)
 				obB[cc] = o[cc];
 	}
+	const PixT wtA = fit_weight<WGT, PixT>(p, vbase + pixA, inbA), wtB = fit_weight<WGT, PixT>(p, vbase + pixB, inbB); // (WGT: the pixels' weights)
 	if (lane < nb)
 		S.ids[lane] = my_id;
 	lds_sync();
@@ -1059,7 +1060,10 @@ __device__ __forceinline__ void fwd_pair_tiles(const KParams &p, const ViewPtrs 
 			{
 				const double dA = inbA ? fit_value<CLAMP>(p, (double)(PixT)colA[cc]) - (double)obA[cc] : 0.0,
 							 dB = inbB ? fit_value<CLAMP>(p, (double)(PixT)colB[cc]) - (double)obB[cc] : 0.0;
-				r2 += dA * dA + dB * dB;
+				if constexpr (WGT)
+					r2 += (double)wtA * (dA * dA) + (double)wtB * (dB * dB);
+				else
+					r2 += dA * dA + dB * dB;
 			}
 		r2 = wave_sum(r2);
 		if (lane == 0)
@@ -1075,8 +1079,8 @@ __device__ __forceinline__ void fwd_pair_tiles(const KParams &p, const ViewPtrs 
 #pragma unroll
 			for (int cc = 0; cc < CH; cc++)
 			{
-				gs[0][cc] = (cc < C && inbA && jA >= 0) ? fit_residual_f32<CLAMP>(p, (float)colA[cc], (float)obA[cc]) : 0.0f;
-				gs[1][cc] = (cc < C && inbB && jB >= 0) ? fit_residual_f32<CLAMP>(p, (float)colB[cc], (float)obB[cc]) : 0.0f;
+				gs[0][cc] = (cc < C && inbA && jA >= 0) ? fit_weighted<WGT>(fit_residual_f32<CLAMP>(p, (float)colA[cc], (float)obA[cc]), wtA) : 0.0f;
+				gs[1][cc] = (cc < C && inbB && jB >= 0) ? fit_weighted<WGT>(fit_residual_f32<CLAMP>(p, (float)colB[cc], (float)obB[cc]), wtB) : 0.0f;
 			}
 			owner_adjoint_slots<2>(p, w, lane, x0, y0, slot, gs, my_id, nb, (float *)&S.rec[0]);
 		}
@@ -1089,7 +1093,7 @@ __device__ __forceinline__ void fwd_pair_tiles(const KParams &p, const ViewPtrs 
 	{
 #pragma unroll
 		for (int cc = 0; cc < CH; cc++)
-			g[cc] = (cc < C && inbA) ? fit_residual<CLAMP>(p, (double)(PixT)colA[cc], (double)obA[cc]) : 0.0;
+			g[cc] = (cc < C && inbA) ? fit_weighted<WGT>(fit_residual<CLAMP>(p, (double)(PixT)colA[cc], (double)obA[cc]), wtA) : 0.0;
 		lds_sync();
 		owner_adjoint<PixT, TEX>(p, w, lane, xA, y, kA, kA >= 0 ? kindA : (int)KIND_NONE, g, tapA, LA, (double *)&S.rec[0], (uint32_t *)&S.cover[0][0], WIN);
 	}
@@ -1097,7 +1101,7 @@ __device__ __forceinline__ void fwd_pair_tiles(const KParams &p, const ViewPtrs 
 	{
 #pragma unroll
 		for (int cc = 0; cc < CH; cc++)
-			g[cc] = (cc < C && inbB) ? fit_residual<CLAMP>(p, (double)(PixT)colB[cc], (double)obB[cc]) : 0.0;
+			g[cc] = (cc < C && inbB) ? fit_weighted<WGT>(fit_residual<CLAMP>(p, (double)(PixT)colB[cc], (double)obB[cc]), wtB) : 0.0;
 		lds_sync();
 		owner_adjoint<PixT, TEX>(p, w, lane, xB, y, kB, kB >= 0 ? kindB : (int)KIND_NONE, g, tapB, LB, (double *)&S.rec[0], (uint32_t *)&S.cover[0][0], WIN);
 	}
@@ -1255,7 +1259,7 @@ enum FwdMode
 // (rasterize_edge_*_error, H.h:2067-2197, 2371-2478).  Forward-only instances (FUSED = false: the adjoint of this mode is the two-call path's).
 // TEXPAIR: (TEX) the instance also walks PAIRS of textured tiles (fwd_pair_tiles<…, true>): the one-kernel form of a textured fit step only -- compiled into
 // the two kernels of the 8-view form as well (where the scan kernel forms no textured pair) the code alone cost them 13 % (128 registers + spills instead of 101)
-template <class PixT, bool FUSED, bool TEX, int MODE, bool CLAMP, bool AA = false, bool MANYC = false, bool TEXPAIR = false>
+template <class PixT, bool FUSED, bool TEX, int MODE, bool CLAMP, bool AA = false, bool MANYC = false, bool TEXPAIR = false, bool WGT = false>
 __device__ __forceinline__ void fwd_tiles(const KParams &p, WaveLds *s_lds, EdgeSort *s_es, const uint32_t b)
 { // b: index of this walker among the walkers of the grid (the workgroup index, unless fill workgroups are dealt among them).
   // (32-bit: a grid has fewer than 2^31 workgroups, and every wavefront pays for this arithmetic on the scalar unit before its first load --
@@ -1323,7 +1327,7 @@ __device__ __forceinline__ void fwd_tiles(const KParams &p, WaveLds *s_lds, Edge
 		const uint32_t e_tile = (uint32_t)uniform((int)cur.x), e_ntri = (uint32_t)uniform((int)cur.y), e_nedge = (uint32_t)uniform((int)cur.z);
 		if (FUSED && (!TEX || TEXPAIR) && MODE == FWD_NO_EDGES && (e_tile & PAIR_FLAG))
 		{ // two adjacent tiles, two pixels per lane (the scan kernel pairs them up: fwd_pair_tiles)
-			fwd_pair_tiles<PixT, CLAMP, TEX>(p, w, S, view, lane, (int)(e_tile & ~PAIR_FLAG), (int)(e_ntri & 0xffffu), (int)(e_ntri >> 16), ids12,
+			fwd_pair_tiles<PixT, CLAMP, TEX, WGT>(p, w, S, view, lane, (int)(e_tile & ~PAIR_FLAG), (int)(e_ntri & 0xffffu), (int)(e_ntri >> 16), ids12,
 								 p.loss_wave ? p.loss_wave + (size_t)view * LOSS_SLOTS + q % LOSS_SLOTS : nullptr);
 			lds_sync();
 			continue;
@@ -1363,6 +1367,7 @@ __device__ __forceinline__ void fwd_tiles(const KParams &p, WaveLds *s_lds, Edge
 		{
 		{
 		PixT ob[CH] = {0, 0, 0, 0};
+		PixT wt = 0; // (WGT: the pixel's weight, loaded below with its observation; a tile that skips the load forms no residual and no loss)
 		constexpr bool fuse_edges = MODE == FWD_EDGE_ADJ; // tiles with silhouette edges are back-propagated right here as well
 		if ((AA && inb) || (FUSED && inb && ((nedge == 0 ? ntri > 0 : fuse_edges) || p.loss_wave)))
 		{ // requested now, used after the last triangle
@@ -1371,6 +1376,7 @@ __device__ __forceinline__ void fwd_tiles(const KParams &p, WaveLds *s_lds, Edge
 			for (int cc = 0; cc < CH; cc++)
 				if (cc < C)
 					ob[cc] = o[cc];
+			wt = fit_weight<WGT, PixT>(p, vpix, true);
 		}
 		PixState st;
 		st.zbest = INFINITY;
@@ -1678,7 +1684,7 @@ __device__ __forceinline__ void fwd_tiles(const KParams &p, WaveLds *s_lds, Edge
 					const double d = fit_value<CLAMP>(p, (double)(PixT)col[cc]) - (double)ob[cc];
 					r2 += d * d;
 				}
-			r2 = wave_sum(r2);
+			r2 = wave_sum(fit_weighted<WGT>(r2, wt));
 			if (lane == 0)
 				atomic_add_f64(p.loss_wave + (size_t)view * LOSS_SLOTS + q % LOSS_SLOTS, r2 - p.loss_tile_bg[1 + (size_t)view * p.L.ntiles + tile]);
 		}
@@ -1689,7 +1695,7 @@ __device__ __forceinline__ void fwd_tiles(const KParams &p, WaveLds *s_lds, Edge
 			double g[CH], base[CH] = {0, 0, 0, 0};
 #pragma unroll
 			for (int cc = 0; cc < CH; cc++)
-				g[cc] = (cc < C && inb) ? fit_residual<CLAMP>(p, (double)(PixT)col[cc], (double)ob[cc]) : 0.0;
+				g[cc] = (cc < C && inb) ? fit_weighted<WGT>(fit_residual<CLAMP>(p, (double)(PixT)col[cc], (double)ob[cc]), wt) : 0.0;
 			if (n_edges > 0)
 			{
 				bool have_base = false;
@@ -1731,7 +1737,7 @@ __device__ __forceinline__ void fwd_tiles(const KParams &p, WaveLds *s_lds, Edge
 				__builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
 				__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
 				lds_sync();
-				bwd_tile_generic_impl<PixT, true, TEX>(p, view, tx, ty, lane, (volatile uint32_t *)s_es[wave].sorted);
+				bwd_tile_generic_impl<PixT, true, TEX, WGT>(p, view, tx, ty, lane, (volatile uint32_t *)s_es[wave].sorted);
 			}
 		}
 		if (FUSED && nedge == 0 && __ballot(st.kbest >= 0) != 0)
@@ -1743,7 +1749,7 @@ __device__ __forceinline__ void fwd_tiles(const KParams &p, WaveLds *s_lds, Edge
 												 // after its load, it was spilled (four doubles per lane) through the whole of pass 1
 #pragma unroll
 			for (int cc = 0; cc < CH; cc++)
-				g[cc] = (cc < C && inb) ? fit_residual<CLAMP>(p, (double)(PixT)col[cc], (double)ob[cc]) : 0.0;
+				g[cc] = (cc < C && inb) ? fit_weighted<WGT>(fit_residual<CLAMP>(p, (double)(PixT)col[cc], (double)ob[cc]), wt) : 0.0;
 			lds_sync();
 			// (round 5: owner_adjoint_slots for the unpaired tiles -- and for the tiles with edges above -- was built and measured: with both
 			// adjoints in the walker the headline instance spills 123 registers instead of 98 and the step is 0.1140 - 0.1160 ms against
@@ -1780,6 +1786,9 @@ constexpr int TEX_TWO_KERNELS = 8;
 // TEXE: (FUSED && TEX) 1: the instance for KParams::fuse_edges -- its head walkers run the adjoint of the tiles with silhouette edges too;
 // 2 / 3: the same grid as TWO kernels for two streams, the head walkers (2) and everybody else (3: four waves per SIMD again) -- KParams::block_base.
 // VAR (round 6, forward-only instances): 1 = antialiase_error (the edges blend the error buffer), 2 = more than CH channels (fwd_manyc_tile).
+// VAR = 3 (FUSED && CLAMP, TEXE 0 or 1): the fit step with per-pixel weights (KParams::weights != NULL, fit_weight): instances of their own, as for the
+// clamp and for the same reason, and the clamp-capable ones (the depth fitter needs both at once; weights x clamp does not double the instances).
+// A value of VAR rather than one more flag: the names of the instances that existed before it are what they were.
 template <class PixT, bool FUSED, bool TEX, bool CLAMP = false, int NC = 0, bool COMMON = false, int TEXE = 0, int VAR = 0>
 __global__ __launch_bounds__(64, DR_FWD_WAVES) void raster_fwd_fast_kernel(KParams p)
 {
@@ -1803,6 +1812,8 @@ __global__ __launch_bounds__(64, DR_FWD_WAVES) void raster_fwd_fast_kernel(KPara
 	// dispatched behind the last walker they START when the last walker has a slot, and the kernel then ends a fill later (73 MB of
 	// stores per 8-view step: same-box A/B 0.1279 / 0.1274 -> 0.1238 / 0.1232 ms, profiles/r04l).  (Round 3 measured "spread evenly:
 	// nothing" -- with the heavy tiles still deciding when the kernel ends.)
+	constexpr bool WGT = VAR == 3;
+	static_assert(!WGT || (FUSED && CLAMP && TEXE < 2), "weighted instances: fused, clamp-capable, one kernel");
 	const uint32_t n_walk = (uint32_t)p.n_views * p.fwd_walkers, n_fill = p.fwd_n_fill; // (= n_views * fill_share(fill_mode, 2, nwords), from the host)
 	const uint32_t dealt = (FUSED && !TEX) ? p.fwd_dealt : 0; // groups of 64 walkers + 8 fill workgroups (the host: fuse_edges && n_walk >= 8 n_fill ? n_fill / 8 : 0)
 	uint32_t b = blockIdx.x + p.block_base; // (32-bit throughout: see fwd_tiles)
@@ -1839,12 +1850,12 @@ __global__ __launch_bounds__(64, DR_FWD_WAVES) void raster_fwd_fast_kernel(KPara
 		const bool chunked = G % (8 * WORK_CHUNK) == 0;
 		const int q = chunked ? (int)div_views(p, b >> 3) * 8 + (int)(b & 7) : 0;
 		if (chunked && q >= (int)p.fwd_heads)
-			fwd_tiles<PixT, FUSED, TEX, FWD_NO_EDGES, CLAMP, false, false, TEXE == 1>(p, s_lds, s_es, b); // the rest of the list: no tile with edges
+			fwd_tiles<PixT, FUSED, TEX, FWD_NO_EDGES, CLAMP, false, false, TEXE == 1, WGT>(p, s_lds, s_es, b); // the rest of the list: no tile with edges
 		else
-			fwd_tiles<PixT, FUSED, TEX, FWD_EDGE_ADJ, CLAMP>(p, s_lds, s_es, b); // the head (tiny frames: the whole list)
+			fwd_tiles<PixT, FUSED, TEX, FWD_EDGE_ADJ, CLAMP, false, false, false, WGT>(p, s_lds, s_es, b); // the head (tiny frames: the whole list)
 	}
 	else
-		fwd_tiles<PixT, FUSED, TEX, FWD_PLAIN, CLAMP, VAR == 1, VAR == 2>(p, s_lds, s_es, b);
+		fwd_tiles<PixT, FUSED, TEX, FWD_PLAIN, CLAMP, VAR == 1, VAR == 2, false, WGT>(p, s_lds, s_es, b);
 }
 
 } // namespace

@@ -286,7 +286,10 @@ void launch_adjoint_raster(const KParams &p, bool fast, bool owner_tiles, dim3 g
 {
 	if (!fast)
 	{
-		hipLaunchKernelGGL(raster_bwd_kernel<PixT>, grid4, dim3(256), 0, st, p);
+		if (fit_weights(p)) // (a weighted fit step on the un-staged kernels: more than CH channels, the deterministic mode)
+			hipLaunchKernelGGL(raster_bwd_weighted_kernel<PixT>, grid4, dim3(256), 0, st, p);
+		else
+			hipLaunchKernelGGL(raster_bwd_kernel<PixT>, grid4, dim3(256), 0, st, p);
 		return;
 	}
 	// the kernels are compiled twice: a scene without texture (no KIND_TEXTURED primitive can exist: the set-up kernel drops
@@ -447,7 +450,7 @@ int launch_forward_staged(const KParams &p, bool fused, hipStream_t stream, hipE
 		(void)hipStreamIsCapturing(stream, &capturing);
 	// (the split point must fall between two groups of eight workgroups -- a walker's list and XCD follow from its index in the one-kernel grid
 	// (KParams::block_base) --: true for the shares heavy_share_for returns, checked here all the same)
-	if (fused && tex && p.fuse_edges && !p.clamp && p.n_views >= TEX_TWO_KERNELS && q.tile_blocks % (8 * WORK_CHUNK) == 0 &&
+	if (fused && tex && p.fuse_edges && !p.clamp && !fit_weights(p) && p.n_views >= TEX_TWO_KERNELS && q.tile_blocks % (8 * WORK_CHUNK) == 0 &&
 		q.tile_blocks % q.heavy_share == 0 && (q.tile_blocks / q.heavy_share) % 8 == 0 && capturing == hipStreamCaptureStatusNone)
 	{ // the head walkers (edge adjoint: many registers) on the side stream, everybody else (+ the fill workgroups) on the caller's, both behind the scan
 		const unsigned head = (unsigned)p.n_views * (unsigned)(q.tile_blocks / q.heavy_share);
@@ -477,6 +480,16 @@ int launch_forward_staged(const KParams &p, bool fused, hipStream_t stream, hipE
 		hipLaunchKernelGGL((raster_fwd_fast_kernel<PixT, false, true, false, 0, false, 0, 1>), grid, dim3(64), 0, stream, q);
 	else if (p.aa_err && !fused)
 		hipLaunchKernelGGL((raster_fwd_fast_kernel<PixT, false, false, false, 0, false, 0, 1>), grid, dim3(64), 0, stream, q);
+	// (per-pixel weights: instances of their own again, VAR = 3, which are the clamp-capable ones -- p.clamp decides at run time as in the
+	// clamped instances below; a weighted textured step takes the one-kernel form at any number of views, as the clamped one does)
+	else if (fused && fit_weights(p) && tex && p.fuse_edges)
+		hipLaunchKernelGGL((raster_fwd_fast_kernel<PixT, true, true, true, 0, false, 1, 3>), grid, dim3(64), 0, stream, q);
+	else if (fused && fit_weights(p) && tex)
+		hipLaunchKernelGGL((raster_fwd_fast_kernel<PixT, true, true, true, 0, false, 0, 3>), grid, dim3(64), 0, stream, q);
+	else if (fused && fit_weights(p) && p.C == 1) // (a depth image with holes)
+		hipLaunchKernelGGL((raster_fwd_fast_kernel<PixT, true, false, true, nc_for<PixT, 1>, false, 0, 3>), grid, dim3(64), 0, stream, q);
+	else if (fused && fit_weights(p))
+		hipLaunchKernelGGL((raster_fwd_fast_kernel<PixT, true, false, true, 0, false, 0, 3>), grid, dim3(64), 0, stream, q);
 	else if (fused && p.clamp && tex && p.fuse_edges) // (the clamped residual of the depth fitter: its own instances of the fused kernel)
 		hipLaunchKernelGGL((raster_fwd_fast_kernel<PixT, true, true, true, 0, false, 1>), grid, dim3(64), 0, stream, q);
 	else if (fused && tex && p.fuse_edges && p.C == 3) // (textured fit step, sigma > 0: the instances with the edge adjoint)
@@ -823,13 +836,13 @@ int deodr_hip_render_scene_b(const DeodrHipScene *sc, const void *image, const v
 	p.image_b = image_b;
 	p.image_in = image;
 	p.obs = obs;
-	p.err_b = err_buffer_b;
+	p.err_b = antialiase_error ? err_buffer_b : nullptr; // (ignored without antialiase_error, as ever; the slot is KParams::weights then: never a caller's pointer)
 	p.aa_err = antialiase_error != 0;
 	return launch_adjoint(sc, p, st, true);
 }
 
 static int l2_loss_impl(const void *image, const void *obs, int pixel_dtype, size_t count, double *out, void *scratch, size_t scratch_bytes, void *stream,
-					   int clamp, double clamp_lo, double clamp_hi);
+					   int clamp, double clamp_lo, double clamp_hi, const void *weights = nullptr, int nb_colors = 1);
 
 static int render_scene_fit_impl(const DeodrHipScene *sc, void *image, void *z_buffer, double sigma, const void *obs, int clear_gradients,
 								 const DeodrHipFitOptions *opt, void *workspace, size_t workspace_bytes, void *stream)
@@ -863,6 +876,7 @@ static int render_scene_fit_impl(const DeodrHipScene *sc, void *image, void *z_b
 		p.loss_tile_bg = tile_loss, p.loss_wave = loss_scratch, p.loss_out = loss_out;
 	if (opt && opt->clamp)
 		p.clamp = 1, p.clamp_lo = opt->clamp_lo, p.clamp_hi = opt->clamp_hi;
+	p.weights = opt ? opt->weights : nullptr;
 	// the background of the empty tiles rides on the adjoint's kernels (fill_share); without any of them: the side stream
 	// The forward raster also back-propagates the tiles with silhouette edges (no edge-tile kernel, no saved sweeps) and streams a share
 	// of the background.  Textured scenes too since round 5 (round 2 measured 0.264 -> 0.407 ms for one 2048^2 view of 100 k triangles:
@@ -890,7 +904,7 @@ static int render_scene_fit_impl(const DeodrHipScene *sc, void *image, void *z_b
 		if (check_hip(hipMemsetAsync(loss_scratch, 0, 64 + 8 * (size_t)L2_BLOCKS, st), "loss scratch"))
 			return 1;
 		if (l2_loss_impl(image, obs, sc->pixel_dtype, (size_t)sc->n_views * sc->height * sc->width * sc->nb_colors, loss_out, loss_scratch,
-						 64 + 8 * (size_t)L2_BLOCKS, stream, p.clamp, p.clamp_lo, p.clamp_hi))
+						 64 + 8 * (size_t)L2_BLOCKS, stream, p.clamp, p.clamp_lo, p.clamp_hi, fit_weights(p), sc->nb_colors))
 			return 1;
 	}
 	if (done_flag && !fin_signals)
@@ -938,11 +952,16 @@ int deodr_hip_background_loss(const DeodrHipScene *sc, const void *obs, const De
 		return fail("background_loss needs obs and the table");
 	if (options && options->clamp)
 		p.clamp = 1, p.clamp_lo = options->clamp_lo, p.clamp_hi = options->clamp_hi;
+	p.weights = options ? options->weights : nullptr;
 	p.obs = obs;
 	p.n_views = sc->n_views;
 	hipStream_t st = (hipStream_t)stream;
 	const dim3 grid((unsigned)p.L.ntiles, (unsigned)sc->n_views);
-	if (sc->pixel_dtype == DEODR_HIP_F64)
+	if (fit_weights(p) && sc->pixel_dtype == DEODR_HIP_F64)
+		hipLaunchKernelGGL(background_loss_weighted_kernel<double>, grid, dim3(64), 0, st, p, tile_loss);
+	else if (fit_weights(p))
+		hipLaunchKernelGGL(background_loss_weighted_kernel<float>, grid, dim3(64), 0, st, p, tile_loss);
+	else if (sc->pixel_dtype == DEODR_HIP_F64)
 		hipLaunchKernelGGL(background_loss_kernel<double>, grid, dim3(64), 0, st, p, tile_loss);
 	else
 		hipLaunchKernelGGL(background_loss_kernel<float>, grid, dim3(64), 0, st, p, tile_loss);
@@ -1231,8 +1250,8 @@ int deodr_hip_fit_front(const double *ij, const uint32_t *faces, const uint32_t 
 }
 
 static int l2_loss_impl(const void *image, const void *obs, int pixel_dtype, size_t count, double *out, void *scratch, size_t scratch_bytes, void *stream,
-					   int clamp, double clamp_lo, double clamp_hi)
-{
+					   int clamp, double clamp_lo, double clamp_hi, const void *weights, int nb_colors)
+{ // weights != NULL: one weight per pixel of nb_colors channels (count = pixels * nb_colors)
 	if (!image || !obs || !out || count == 0 || (pixel_dtype != DEODR_HIP_F32 && pixel_dtype != DEODR_HIP_F64))
 		return fail("l2_loss: bad arguments");
 	if (!scratch || scratch_bytes < fit_scratch_need_l2())
@@ -1243,7 +1262,13 @@ static int l2_loss_impl(const void *image, const void *obs, int pixel_dtype, siz
 	const dim3 grid((unsigned)(want < (size_t)L2_BLOCKS ? want : (size_t)L2_BLOCKS));
 	double *partials = (double *)((char *)scratch + 64);
 	unsigned *counter = (unsigned *)scratch + FC_L2;
-	if (pixel_dtype == DEODR_HIP_F64)
+	if (weights && pixel_dtype == DEODR_HIP_F64)
+		hipLaunchKernelGGL(l2_loss_weighted_kernel<double>, grid, dim3(FH_BLOCK), 0, (hipStream_t)stream, (const double *)image, (const double *)obs,
+						   (const double *)weights, nb_colors, count, out, partials, counter, clamp, clamp_lo, clamp_hi);
+	else if (weights)
+		hipLaunchKernelGGL(l2_loss_weighted_kernel<float>, grid, dim3(FH_BLOCK), 0, (hipStream_t)stream, (const float *)image, (const float *)obs,
+						   (const float *)weights, nb_colors, count, out, partials, counter, clamp, clamp_lo, clamp_hi);
+	else if (pixel_dtype == DEODR_HIP_F64)
 		hipLaunchKernelGGL(l2_loss_kernel<double>, grid, dim3(FH_BLOCK), 0, (hipStream_t)stream, (const double *)image, (const double *)obs, count, out, partials,
 						   counter, clamp, clamp_lo, clamp_hi);
 	else

@@ -176,7 +176,18 @@ struct KParams
 	double offset, sigma;
 	// pixel buffers of this call
 	void *image, *zbuf, *err;
-	const void *image_b, *obs, *err_b, *image_in;
+	const void *image_b, *obs;
+	union
+	{
+		const void *err_b; // antialiase_error (aa_err != 0): the adjoint of the error buffer
+		// Fit step (aa_err == 0): per-pixel weights (DeodrHipFitOptions::weights), [n_views][H][W] in the pixel type, NULL: none.
+		// L = sum_p w[p] sum_c (f(image) - obs)^2, residual w[p] * fit_residual.  Read only by the instances compiled for it (WGT: fit_weight
+		// below).  The two never meet -- a fit step has no error buffer, antialiase_error takes no weights -- and sharing the slot keeps
+		// sizeof(KParams) and the kernel-argument layout of every other instance what they were measured with (see kparams_pad; the un-staged
+		// kernels also keep a copy of KParams in scratch).  Host code asks fit_weights(p), never p.weights alone.
+		const void *weights;
+	};
+	const void *image_in;
 	int aa_err;
 	int n_views;
 	int heavy_share; // staged forward: one workgroup in heavy_share walks the many-primitive tiles (heavy_share_for)
@@ -242,6 +253,8 @@ struct KParams
 	char *ws;
 	Layout L;
 };
+// the weights of a fit step, or NULL (KParams::weights shares its slot with the error-buffer adjoint of antialiase_error)
+inline const void *fit_weights(const KParams &p) { return p.aa_err ? nullptr : p.weights; }
 
 struct ViewPtrs
 {
@@ -286,6 +299,27 @@ __device__ __forceinline__ float fit_residual_f32(const KParams &p, float v, flo
 	if (CLAMP && p.clamp && ((double)v < p.clamp_lo || (double)v > p.clamp_hi))
 		return 0.0f;
 	return 2.0f * (v - o);
+}
+
+// Per-pixel weight of a fit step (KParams::weights), one per pixel and view: loaded ONCE per pixel where the walker loads the observation, in the
+// pixel type.  WGT false: compiled without it (the instances of an unweighted step are not to pay a register for it); WGT true: the host
+// launches these instances only with weights != NULL, so there is no run-time test.  fit_weighted scales a residual (or a pixel's squared
+// distance) by it: the weight is >= 0 by contract and never checked -- everything is linear in it.
+template <bool WGT, class PixT>
+__device__ __forceinline__ PixT fit_weight(const KParams &p, size_t vpix, bool inb)
+{
+	if constexpr (WGT)
+		return inb ? ((const PixT *)p.weights)[vpix] : (PixT)0;
+	else
+		return (PixT)1;
+}
+template <bool WGT, class T, class PixT>
+__device__ __forceinline__ T fit_weighted(T r, PixT wt)
+{
+	if constexpr (WGT)
+		return r * (T)wt;
+	else
+		return r;
 }
 
 __device__ __forceinline__ ViewPtrs view_ptrs(const KParams &p, int view)

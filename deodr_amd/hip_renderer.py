@@ -20,7 +20,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libdeodr_hip.so")
-ABI_VERSION = 12
+ABI_VERSION = 13
 ERR_FACES, ERR_FACES_UV, ERR_NO_TEXTURE, ERR_INTERNAL, ERR_DET_RANGE = 1, 2, 4, 8, 16  # include/deodr_hip.h DEODR_HIP_ERR_*
 _STATUS_NEEDED, _STATUS_ERRORS = 11, 12  # words of the 64-byte status block at the start of the workspace
 
@@ -43,7 +43,7 @@ class _FitOptionsC(C.Structure):
     """include/deodr_hip.h::DeodrHipFitOptions"""
 
     _fields_ = [("tile_loss", C.c_void_p), ("loss", C.c_void_p), ("loss_scratch", C.c_void_p), ("clamp", C.c_int), ("clamp_lo", C.c_double),
-                ("clamp_hi", C.c_double), ("done_flag", C.c_void_p), ("done_value", C.c_uint32)]  # fmt: skip
+                ("clamp_hi", C.c_double), ("done_flag", C.c_void_p), ("done_value", C.c_uint32), ("weights", C.c_void_p)]  # fmt: skip
 
 
 def lib():
@@ -451,11 +451,11 @@ class HipRasterizer:
         self._last = (ds, float(sigma), bool(antialiase_error), obs_t, image, err, self.generation, False)
         return (image, z, err) if antialiase_error else (image, z)
 
-    def _loss_table(self, ds, sc, obs_t, options):
-        """the background-loss table of (obs, background, clamp) for the loss of a fit step, computed once (deodr_hip_background_loss)"""
+    def _loss_table(self, ds, sc, obs_t, options, weights_t=None):
+        """the background-loss table of (obs, background, clamp, weights) for the loss of a fit step, computed once (deodr_hip_background_loss)"""
         key = (obs_t.data_ptr(), obs_t._version, tuple(obs_t.shape), None if ds.background_color is None else (ds.background_color.data_ptr(), ds.background_color._version),
                None if ds.background_image is None else (ds.background_image.data_ptr(), ds.background_image._version),
-               (options.clamp, options.clamp_lo, options.clamp_hi))  # fmt: skip
+               (options.clamp, options.clamp_lo, options.clamp_hi), None if weights_t is None else (weights_t.data_ptr(), weights_t._version))  # fmt: skip
         cache = getattr(self, "_loss_cache", None)
         if cache is None or cache[0] != key:
             L = lib()
@@ -464,10 +464,28 @@ class HipRasterizer:
             _check(L.deodr_hip_background_loss(C.byref(sc), _ptr(obs_t), C.byref(options), _ptr(table), _ptr(self.workspace), self.nbytes,
                                                _stream(self.device)))  # fmt: skip
             # (every tensor whose address is part of the key is kept alive by the cache: a new tensor cannot land on a keyed address)
-            self._loss_cache = cache = (key, table, scratch, (obs_t, ds.background_color, ds.background_image))
+            self._loss_cache = cache = (key, table, scratch, (obs_t, ds.background_color, ds.background_image, weights_t))
         return cache[1], cache[2]
 
-    def render_fit(self, ds, obs, sigma=1.0, grads=None, out=None, check_overflow=None, clear_grads=False, loss_out=None, clamp=None, done_flag=None):
+    def _fit_weights(self, ds, weights):
+        """per-pixel weights of a fit step as the library wants them: [n_views, H, W], the scene's device and pixel dtype, contiguous (a tensor
+        that already is all that is passed through untouched, so that the loss-table cache recognises it); [H, W] is expanded over the views"""
+        n, H, W = ds.n_views, ds.height, ds.width
+        w = weights if torch.is_tensor(weights) else torch.as_tensor(np.asarray(weights))
+        if tuple(w.shape) not in ((n, H, W), (H, W)):
+            raise ValueError(f"weights must have shape [{n}, {H}, {W}] (one value per view and pixel) or [{H}, {W}], not {list(w.shape)}")
+        if w.dim() == 3 and w.device == ds.device and w.dtype == ds.pixel_dtype and w.is_contiguous():
+            return w
+        cached = getattr(self, "_weights_cache", None)  # (source tensor, its version, converted): the same tensor again, unchanged, is not converted again
+        if torch.is_tensor(weights) and cached is not None and cached[0] is weights and cached[1] == weights._version:
+            return cached[2]
+        w_t = w.to(device=ds.device, dtype=ds.pixel_dtype).expand(n, H, W).contiguous()
+        if torch.is_tensor(weights):  # (an array can change without a trace: converted at every call)
+            self._weights_cache = (weights, weights._version, w_t)
+        return w_t
+
+    def render_fit(self, ds, obs, sigma=1.0, grads=None, out=None, check_overflow=None, clear_grads=False, loss_out=None, clamp=None, done_flag=None,
+                   weights=None):  # fmt: skip
         """One fit step in one call: render ``ds`` and back-propagate ``sum((image - obs)**2)``; -> (image, z_buffer, grads).
 
         Same results as :meth:`render` followed by ``render_backward(residual_obs=obs)`` (what the reference's
@@ -479,10 +497,15 @@ class HipRasterizer:
         (lo, hi): the loss is ``sum((image.clamp(lo, hi) - obs)**2)``, the depth fitter's data term (deodr/mesh_fitter.py:108-123);
         the returned image is the un-clamped rendering.  ``done_flag`` = (int32 / uint32 device tensor of one element, value): the step
         stores ``value`` there when its gradients are complete -- what a consumer on another stream waits for with :func:`wait_flag`
-        instead of an event (``DeodrHipFitOptions::done_flag``)."""
+        instead of an event (``DeodrHipFitOptions::done_flag``).  ``weights``: one value per view and pixel, ``[n_views, H, W]`` (or
+        ``[H, W]`` for all views): the loss is ``sum(weights[..., None] * (image - obs)**2)`` (of the clamped image with ``clamp``) and
+        the residual is scaled alike -- masks, sensor holes, per-camera confidence.  Meant to be ``>= 0`` and not checked; pixels of weight
+        0 are still rendered, only their residual vanishes.  Pass a contiguous tensor in the scene's pixel dtype on its device to avoid a
+        conversion.  Any other shape raises ``ValueError``."""
         self._check_scene(ds)
         n, H, W, Cc = ds.n_views, ds.height, ds.width, ds.nb_colors
         pd = ds.pixel_dtype
+        weights_t = None if weights is None else self._fit_weights(ds, weights)
         with torch.cuda.device(self.device):
             image, z = self._frame(ds, out)
             obs_t = obs if torch.is_tensor(obs) else torch.as_tensor(np.asarray(obs))
@@ -497,11 +520,13 @@ class HipRasterizer:
             self._inspect_poll(sc)
             if done_flag is not None and (done_flag[0].element_size() != 4 or done_flag[0].numel() != 1 or done_flag[0].device != ds.device):
                 raise ValueError("done_flag must be (a 4-byte integer tensor of one element on the scene's device, value)")
-            if loss_out is None and clamp is None and done_flag is None:
+            if loss_out is None and clamp is None and done_flag is None and weights_t is None:
                 _check(lib().deodr_hip_render_scene_fit(C.byref(sc), _ptr(image), _ptr(z), float(sigma), _ptr(obs_t), int(bool(clear_grads)),
                                                         _ptr(self.workspace), self.nbytes, _stream(self.device)))  # fmt: skip
             else:
                 options = _FitOptionsC()
+                if weights_t is not None:
+                    options.weights = weights_t.data_ptr()
                 if done_flag is not None:
                     options.done_flag, options.done_value = done_flag[0].data_ptr(), int(done_flag[1]) & 0xFFFFFFFF
                 if clamp is not None:
@@ -509,13 +534,14 @@ class HipRasterizer:
                 if loss_out is not None:
                     if loss_out.dtype != torch.float64 or loss_out.device != ds.device or loss_out.numel() != 1:
                         raise ValueError("loss_out must be a float64 tensor of one element on the scene's device")
-                    table, scratch = self._loss_table(ds, sc, obs_t, options)
+                    table, scratch = self._loss_table(ds, sc, obs_t, options, weights_t)
                     options.tile_loss, options.loss, options.loss_scratch = table.data_ptr(), loss_out.data_ptr(), scratch.data_ptr()
                 _check(lib().deodr_hip_render_scene_fit_ex(C.byref(sc), _ptr(image), _ptr(z), float(sigma), _ptr(obs_t), int(bool(clear_grads)),
                                                            C.byref(options), _ptr(self.workspace), self.nbytes, _stream(self.device)))  # fmt: skip
             self._poll()
         self.generation += 1
         self._last = (ds, float(sigma), False, obs_t, image, None, self.generation, True)
+        self._last_weights = weights_t  # (kept alive like the observation: the launches above may still be queued)
         return image, z, grads
 
     def render_backward(self, ds, image_b=None, err_buffer_b=None, grads=None, have_forward_state=True, residual_obs=None,

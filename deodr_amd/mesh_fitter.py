@@ -314,6 +314,27 @@ class _PoseFitter:
     def _allreduce_shared(self, shared):
         pass  # single process, every view local
 
+    weights = None  # per-pixel weights of the data term [n,H,W] (float64, this fitter's device), or None: set_image(s)(..., weights=...)
+
+    def _set_weights(self, weights, n, height, width):
+        """``weights`` of ``set_image`` / ``set_images``: [H,W] (all views) or [n,H,W], ``>= 0``, not checked for sign; None: an unweighted fit"""
+        self._weights_key = None
+        if weights is None:
+            self.weights = None
+            return
+        w = np.asarray(weights.detach().cpu() if torch.is_tensor(weights) else weights, dtype=np.float64)
+        if w.shape not in ((height, width), (n, height, width)):
+            raise ValueError(f"weights must have shape [{height}, {width}] or [{n}, {height}, {width}] (one value per pixel), not {list(w.shape)}")
+        self.weights = torch.as_tensor(np.array(np.broadcast_to(w, (n, height, width))), device=self.device)
+
+    def _fit_weights(self):
+        """the weights as the rasterizer's fit step takes them: [n,H,W] in its pixel dtype, converted once (None: no weights)"""
+        if self.weights is None:
+            return None
+        if getattr(self, "_weights_key", None) is not self.weights:
+            self._weights_key, self._weights_pix = self.weights, self.weights.to(self.scene.pixel_dtype).contiguous()
+        return self._weights_pix
+
 
 class MeshDepthFitter(_PoseFitter):
     """Fit a deformable mesh to a depth image (reference deodr/mesh_fitter.py:20-196)."""
@@ -329,8 +350,12 @@ class MeshDepthFitter(_PoseFitter):
     def set_depth_scale(self, depth_scale):
         self.depthScale = depth_scale
 
-    def set_image(self, mesh_image, focal=None, distortion=None):
+    def set_image(self, mesh_image, focal=None, distortion=None, weights=None):
+        """``weights`` [H,W], ``>= 0`` (or None): the data term becomes ``sum(weights * (clip(depth) - mesh_image)**2)`` -- 0 where the sensor
+        returned no depth (a hole), so that whatever ``mesh_image`` holds there does not pull on the mesh.  Both the direct path (hence
+        ``GraphedStep``) and the autograd path use them; the difference image a step returns for display stays un-weighted."""
         assert np.ndim(mesh_image) == 2
+        self._set_weights(weights, 1, *np.shape(mesh_image))
         self.height, self.width = mesh_image.shape
         self.mesh_image = torch.as_tensor(np.asarray(mesh_image, dtype=np.float64), device=self.device)
         self.camera = self._camera(self.height, self.width, focal, distortion, self.camera_center)
@@ -343,7 +368,8 @@ class MeshDepthFitter(_PoseFitter):
         depth = depth.clamp(0, self.max_depth).to(torch.float64)
         diff_image = ((depth - self.mesh_image[:, :, None]) ** 2).sum(dim=2)
         e_rigid, g_rigid = self.rigid_energy.evaluate(self.vertices_leaf.detach())
-        return diff_image.sum(), e_rigid, g_rigid, depth[:, :, 0], diff_image
+        e_data = diff_image.sum() if self.weights is None else (self.weights[0] * diff_image).sum()
+        return e_data, e_rigid, g_rigid, depth[:, :, 0], diff_image
 
     def _observation(self):
         """the target depth image as the rasterizer's fit step takes it: [1,H,W,1] in its pixel dtype, converted once"""
@@ -358,7 +384,7 @@ class MeshDepthFitter(_PoseFitter):
         # the data term sum (clip(depth image, 0, max_depth) - target)^2, its gradients and its value from the rasterizer's one-call fit
         # step (four launches; render + residual + render_backward were nine)
         image, _z, _g = d.rasterizer.render_fit(d.ds, self._observation(), self.scene.sigma, grads=d.grads, out=(d.image, d.z), clear_grads=True,
-                                                loss_out=d.e_data, clamp=(0.0, self.max_depth))  # fmt: skip
+                                                loss_out=d.e_data, clamp=(0.0, self.max_depth), weights=self._fit_weights())  # fmt: skip
         if d.depth is None:
             d.depth, d.diff, d.image_b = torch.empty_like(self.mesh_image), torch.empty_like(self.mesh_image), torch.empty_like(image)
             d.display_loss = torch.zeros(1, dtype=torch.float64, device=self.device)
@@ -421,8 +447,8 @@ class MeshDepthFitterPytorchOptim:
         self.energy = MeshDepthFitterEnergy(vertices, faces, euler_init, translation_init, cregu, device=device, pixel_dtype=pixel_dtype)
         self.optimizer = torch.optim.LBFGS(self.energy.parameters(), lr=lr, max_iter=1)
 
-    def set_image(self, depth_image, focal=None, distortion=None):
-        self.energy.set_image(depth_image, focal=focal, distortion=distortion)
+    def set_image(self, depth_image, focal=None, distortion=None, weights=None):
+        self.energy.set_image(depth_image, focal=focal, distortion=distortion, weights=weights)
 
     def set_max_depth(self, max_depth):
         self.energy.set_max_depth(max_depth)
@@ -463,8 +489,11 @@ class MeshRGBFitterWithPose(_PoseFitter):
     def set_background_color(self, background_color):
         self.scene.set_background_color(background_color)
 
-    def set_image(self, mesh_image, focal=None, distortion=None):
+    def set_image(self, mesh_image, focal=None, distortion=None, weights=None):
+        """``weights`` [H,W], ``>= 0`` (or None): the data term becomes ``sum(weights[..., None] * (image - mesh_image)**2)`` -- a foreground
+        mask, an occluder to ignore, a confidence map.  Used by the direct path (hence ``GraphedStep``) and by the autograd path alike."""
         assert np.ndim(mesh_image) == 3
+        self._set_weights(weights, 1, *np.shape(mesh_image)[:2])
         self.height, self.width = mesh_image.shape[:2]
         self.mesh_image = torch.as_tensor(np.asarray(mesh_image, dtype=np.float64), device=self.device)[None]
         self.camera = self._camera(self.height, self.width, focal, distortion, self.camera_center)
@@ -499,7 +528,7 @@ class MeshRGBFitterWithPose(_PoseFitter):
         """-> (data energy, image [n,H,W,C]).  The data term of the colour fitters is exactly sum (image - obs)^2
         (mesh_fitter.py:296-318): rendered AND back-propagated by the one-call fit step (Scene3DDevice.render_l2)."""
         self._pose_scene()
-        loss, image = self.scene.render_l2(self.camera, self._observation())
+        loss, image = self.scene.render_l2(self.camera, self._observation(), weights=self._fit_weights())
         return self.data_weight * loss, image
 
     def diff_image(self, image):
@@ -517,7 +546,8 @@ class MeshRGBFitterWithPose(_PoseFitter):
         obs = self._observation()
         # image, gradients AND the data energy from the rasterizer's four launches (the residual of every pixel is in the tile walkers'
         # registers; a separate pass over the 8-view frame was 73 us of a 350 us iteration)
-        image, _z, _g = d.rasterizer.render_fit(d.ds, obs, self.scene.sigma, grads=d.grads, out=(d.image, d.z), clear_grads=True, loss_out=d.e_data)
+        image, _z, _g = d.rasterizer.render_fit(d.ds, obs, self.scene.sigma, grads=d.grads, out=(d.image, d.z), clear_grads=True, loss_out=d.e_data,
+                                                weights=self._fit_weights())  # fmt: skip
         fronthalf.vertex_shade_b(d.posed, topo, self.light_directional, self.light_ambient, self.mesh_color, None, d.grads["colors_b"], d.posed_b, d.shade_out,
                                  d.scratch)  # fmt: skip
         extra = []
@@ -604,9 +634,17 @@ class MeshRGBFitterWithPoseMultiFrame(MeshRGBFitterWithPose):
     # and is followed as repaired, see tests/golden/make_golden.py::rgb_multiview_fit)
     data_weight = property(lambda self: self.cdata / self.n_views_total)
 
-    def set_images(self, mesh_images, focal=None, distortion=None):
-        """``mesh_images``: the images of ALL views (every rank keeps only its own)"""
+    def set_images(self, mesh_images, focal=None, distortion=None, weights=None):
+        """``mesh_images``: the images of ALL views (every rank keeps only its own).  ``weights``: [H,W] for every view or [n_views_total,H,W],
+        of ALL views as well -- sharded with the images (``distributed.shard_views``) --, ``>= 0``: the data term of view v becomes
+        ``sum(weights[v][..., None] * (image_v - mesh_images[v])**2)``; a view of weight 0 everywhere does not pull on the shared parameters."""
         imgs = np.stack([np.asarray(mesh_images[i], dtype=np.float64) for i in self.my_views])
+        if weights is not None:
+            w = np.asarray(weights.detach().cpu() if torch.is_tensor(weights) else weights, dtype=np.float64)
+            if w.shape not in (imgs.shape[1:3], (self.n_views_total,) + imgs.shape[1:3]):
+                raise ValueError(f"weights must have shape {list(imgs.shape[1:3])} or {[self.n_views_total] + list(imgs.shape[1:3])}, not {list(w.shape)}")
+            weights = w if w.ndim == 2 else w[self.my_views]
+        self._set_weights(weights, len(self.my_views), *imgs.shape[1:3])
         self.height, self.width = imgs.shape[1:3]
         self.mesh_image = torch.as_tensor(imgs, device=self.device)
         cam = self._camera(self.height, self.width, focal, distortion, self.camera_center)

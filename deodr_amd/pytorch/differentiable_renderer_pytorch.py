@@ -150,24 +150,28 @@ class TorchRenderViewsL2LossFunc(torch.autograd.Function):
     (deodr/pytorch/mesh_fitter_pytorch.py, dr.py:701-740): here the forward is one ``deodr_hip_render_scene_fit`` call that
     renders AND back-propagates the residual (the gradient of the loss w.r.t. the image is known as soon as a pixel is
     resolved), so ``backward`` only scales the stored gradients.  ``image`` and ``z_buffer`` of the last call are kept on
-    the context owner (``rasterizer.last_fit``) for display."""
+    the context owner (``rasterizer.last_fit``) for display.  ``weights`` ([n,H,W] or [H,W], or None): the loss is
+    ``sum(weights[..., None] * (image - obs)**2)``, see :meth:`HipRasterizer.render_fit` (no gradient with respect to them)."""
 
     @staticmethod
-    def forward(ctx, ij, colors, obs, device_scene, rasterizer, sigma):
+    def forward(ctx, ij, colors, obs, device_scene, rasterizer, sigma, weights=None):
         device_scene.set_views(ij=ij.detach(), colors=colors.detach())
-        image, z, g = rasterizer.render_fit(device_scene, obs, sigma, clear_grads=False)
+        image, z, g = rasterizer.render_fit(device_scene, obs, sigma, clear_grads=False, weights=weights)
         rasterizer.last_fit = (image, z)
         ctx.save_for_backward(g["ij_b"].to(ij.dtype), g["colors_b"].to(colors.dtype))
-        return ((image.double() - obs.to(image.device).double()) ** 2).sum()
+        r2 = (image.double() - obs.to(image.device).double()) ** 2
+        if weights is not None:
+            r2 = r2 * torch.as_tensor(weights).to(image.device).double()[..., None]
+        return r2.sum()
 
     @staticmethod
     def backward(ctx, loss_b):
         ij_b, colors_b = ctx.saved_tensors
-        return loss_b.to(ij_b.dtype) * ij_b, loss_b.to(colors_b.dtype) * colors_b, None, None, None, None
+        return loss_b.to(ij_b.dtype) * ij_b, loss_b.to(colors_b.dtype) * colors_b, None, None, None, None, None
 
 
-def TorchRenderViewsL2Loss(ij, colors, obs, device_scene, rasterizer, sigma=1.0):
-    return TorchRenderViewsL2LossFunc.apply(ij, colors, obs, device_scene, rasterizer, sigma)
+def TorchRenderViewsL2Loss(ij, colors, obs, device_scene, rasterizer, sigma=1.0, weights=None):
+    return TorchRenderViewsL2LossFunc.apply(ij, colors, obs, device_scene, rasterizer, sigma, weights)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

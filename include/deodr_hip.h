@@ -143,7 +143,20 @@ int deodr_hip_render_scene_fit(const DeodrHipScene *scene, void *image, void *z_
  *
  * clamp: the residual is that of L = sum (clamp(image, clamp_lo, clamp_hi) - obs)^2 -- the data term of the reference's depth fitter
  * (deodr/mesh_fitter.py:108-123: the rendered depth image is clipped to [0, max_depth] before it is compared) --, its gradient
- * passing on the closed interval as NumPy's / torch's clip does.  The stored image is the un-clamped rendering. */
+ * passing on the closed interval as NumPy's / torch's clip does.  The stored image is the un-clamped rendering.
+ *
+ * weights (ABI 13): one value per pixel and view, [n_views][height][width] in the scene's pixel dtype, contiguous device memory, or NULL.
+ * With v the rendered value as stored (rounded to the pixel type), o the observation and f the identity or the clamp above:
+ *     loss      L = sum over views and pixels p of  w[p] * sum over channels of (f(v) - o)^2
+ *     residual  dL/dv = w[p] * 2 (f(v) - o)   (0 outside a clamp interval, as without weights)
+ * -- the usual way to ignore the holes of a depth sensor or everything outside a foreground mask (w = 0), or to trust one camera less than
+ * another.  Weights are meant to be >= 0; their values are NOT checked (the step is linear in them).  A pixel of weight 0 is still
+ * rendered: image and z_buffer are those of the unweighted step, only its residual and its share of the loss vanish.  NULL: the unweighted
+ * step, bit for bit, on the kernel instances it always ran.  A weighted step runs instances of the fused forward raster of its own (which are
+ * also the clamp-capable ones: weights and clamp combine freely) and, for a textured scene, the ONE-kernel form at any number of views, as the
+ * clamped step does -- nothing goes through the side stream.  The table of deodr_hip_background_loss depends on the weights: it is a function
+ * of (observation, background, clamp, weights), to be made with the same `weights` as the steps that use it.  The step-done flag and
+ * clear_gradients work as without weights.  deodr_hip_render_scene_fit / _render_scene / _render_scene_b take no weights. */
 typedef struct DeodrHipFitOptions
 {
 	const double *tile_loss; /* table of deodr_hip_background_loss (made with the same clamp), or NULL: no loss wanted */
@@ -162,6 +175,7 @@ typedef struct DeodrHipFitOptions
 	 * itself behind the step's stream (an event, or stream order), as before. */
 	uint32_t *done_flag;
 	uint32_t done_value;
+	const void *weights; /* per-pixel weights [n_views][height][width], pixel dtype, device; NULL: none (appended with ABI 13: a zero-initialised struct of an older caller means "none") */
 } DeodrHipFitOptions;
 size_t deodr_hip_fit_loss_bytes(int height, int width, int n_views);
 int deodr_hip_background_loss(const DeodrHipScene *scene, const void *obs, const DeodrHipFitOptions *options, double *tile_loss, void *workspace,
@@ -357,7 +371,7 @@ const char *deodr_hip_last_error(void);
 
 /* ABI version of this header; bumped on any incompatible change. */
 int deodr_hip_abi_version(void);
-#define DEODR_HIP_ABI_VERSION 12
+#define DEODR_HIP_ABI_VERSION 13
 
 #ifdef __cplusplus
 }
