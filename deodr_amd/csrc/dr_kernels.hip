@@ -30,7 +30,8 @@
 //   dr_fronthalf.h, dr_fititer.h   the O(V) kernels either side of the rasterizer in a fit iteration (pose + projection, shading,
 //                           silhouette flags, their adjoints, rigid energy, data terms, momentum update): deterministic sums
 //
-// Where: dr_workspace.h (layout, KParams, wave primitives) . dr_setup.h (setup_bin_kernel) . dr_forward.h (tile_scan_kernel, fill,
+// Where: dr_dispatch.h (host only: which template instance of a kernel a call runs, the tables of the instances) . dr_workspace.h (layout, KParams,
+// wave primitives) . dr_setup.h (setup_bin_kernel) . dr_forward.h (tile_scan_kernel, fill,
 // raster_fwd_fast_kernel) . dr_backward.h (raster_bwd_fast_kernel, raster_bwd_edge_kernel) . dr_finalize.h (finalize_kernel) .
 // dr_forward_generic.h / dr_backward_generic.h (the un-staged family, edge ordering) . dr_math.h / dr_prims.h (per-primitive math) .
 // dr_fronthalf.h / dr_fititer.h (fit iteration).
@@ -55,9 +56,11 @@
 #include <vector>
 
 #include "../../include/deodr_hip.h"
+#include "dr_dispatch.h"
 #include "dr_fititer.h" // <- dr_finalize.h <- dr_backward.h <- dr_backward_generic.h <- dr_forward.h <- dr_forward_generic.h <- dr_setup.h <- dr_workspace.h <- dr_prims.h
 
 using namespace dr;
+using namespace dr::dispatch;
 
 namespace
 {
@@ -273,16 +276,26 @@ void det_convert(const KParams &p, int n_views, hipStream_t st)
 // arguments of a call may change what the call launches.
 constexpr int EDGE_WAVES = 1024; // persistent waves per view of the adjoint's edge kernel
 
-// The channel count (and the "usual frame" flag) as compile-time constants of the raster kernels -- for float32 pixel buffers, the storage of the
-// fit loops; with float64 buffers (the 1e-9 parity path, the NumPy drop-ins of the reference's entry points) every call takes the run-time-C
-// instance: 28 raster instances fewer to compile (the library builds in ~3.5 minutes instead of ~4.7; their step is a few per cent longer).
-template <class PixT, int NC>
-constexpr int nc_for = sizeof(PixT) == 4 ? NC : 0;
-template <class PixT>
-constexpr bool common_for = sizeof(PixT) == 4;
+// ---- which instance of a kernel a call runs: the rule and the tables of dr_dispatch.h; here the tables become kernels
+static_assert(STAGED_CHANNELS == CH && TWO_KERNEL_VIEWS == TEX_TWO_KERNELS && WALKER_UNIT == 8 * WORK_CHUNK, "dr_dispatch.h restates the kernels' constants");
+
+// Runs launch(std::integral_constant<size_t, i>{}) for the entry i of `table` that equals `want`.  The tables are the only place that names an
+// instance: a generic lambda turns entry i into template arguments (and so instantiates every entry).  An instance the table does not hold (or that
+// launch refuses: returns false) is the error `no_instance`, never a fall into some default.
+template <size_t I = 0, class Inst, size_t N, class Launch>
+int launch_from(const char *no_instance, const Inst (&table)[N], const Inst &want, Launch launch)
+{
+	if constexpr (I < N)
+		return table[I] == want && launch(std::integral_constant<size_t, I>{}) ? 0 : launch_from<I + 1>(no_instance, table, want, launch);
+	return fail(no_instance);
+}
+
+// The pixel-dtype tag as a type: f(double{}) or f(float{}) for a generic lambda.
+template <class F>
+auto with_pixel_type(bool f64, F f) { return f64 ? f(double{}) : f(float{}); }
 
 template <class PixT>
-void launch_adjoint_raster(const KParams &p, bool fast, bool owner_tiles, dim3 grid4, dim3 edge_grid, hipStream_t st)
+int launch_adjoint_raster(const KParams &p, bool fast, bool owner_tiles, dim3 grid4, dim3 edge_grid, hipStream_t st)
 {
 	if (!fast)
 	{
@@ -290,48 +303,41 @@ void launch_adjoint_raster(const KParams &p, bool fast, bool owner_tiles, dim3 g
 			hipLaunchKernelGGL(raster_bwd_weighted_kernel<PixT>, grid4, dim3(256), 0, st, p);
 		else
 			hipLaunchKernelGGL(raster_bwd_kernel<PixT>, grid4, dim3(256), 0, st, p);
-		return;
+		return 0;
 	}
-	// the kernels are compiled twice: a scene without texture (no KIND_TEXTURED primitive can exist: the set-up kernel drops
-	// textured triangles of such a scene and raises DEODR_HIP_ERR_NO_TEXTURE) runs the instances without any texture code
-	const bool tex = p.texture != nullptr;
+	constexpr bool f64 = sizeof(PixT) == 8;
+	// raster_bwd_edge_kernel (edge: std::true_type) or raster_bwd_fast_kernel, the instance for this scene
+	auto launch = [&](auto edge, dim3 grid, const KParams &args) {
+		return launch_from("internal: no instance of the adjoint raster kernels for this call", BWD_INSTANCES, select_adjoint_raster(f64, p.texture != nullptr, p.C), [&](auto i) {
+			constexpr BwdInst k = BWD_INSTANCES[decltype(i)::value];
+			if constexpr (bwd_exists(k, f64) && decltype(edge)::value)
+				hipLaunchKernelGGL((raster_bwd_edge_kernel<PixT, k.tex, k.nc>), grid, dim3(64), 0, st, args);
+			else if constexpr (bwd_exists(k, f64))
+				hipLaunchKernelGGL((raster_bwd_fast_kernel<PixT, k.tex, k.nc>), grid, dim3(64), 0, st, args);
+			return bwd_exists(k, f64);
+		});
+	};
 	if (owner_tiles) // (after a fused forward the tiles without edges have already been back-propagated)
 	{
 		KParams q = p;
 		q.tile_blocks = fwd_tile_blocks(p.L.ntiles, p.n_views, false); // the grid of the forward that built the work list (never a fused one)
 		q.heavy_share = heavy_share_for(p.n_views, q.tile_blocks, false);
 		q.split_part = 16; // (no fit step here: nothing is split)
-		const dim3 grid((unsigned)p.n_views * (unsigned)q.tile_blocks);
-		// (instances for the channel counts that occur: RGB, RGB + depth -- see raster_fwd_fast_kernel)
-#define DR_LAUNCH_NC(kernel, tex_, grid_, q_)                                                        \
-	do                                                                                               \
-	{                                                                                                \
-		if (tex_ && (q_).C == 3)                                                                     \
-			hipLaunchKernelGGL((kernel<PixT, true, nc_for<PixT, 3>>), grid_, dim3(64), 0, st, q_);                 \
-		else if (tex_)                                                                               \
-			hipLaunchKernelGGL((kernel<PixT, true, 0>), grid_, dim3(64), 0, st, q_);                 \
-		else if ((q_).C == 4)                                                                        \
-			hipLaunchKernelGGL((kernel<PixT, false, nc_for<PixT, 4>>), grid_, dim3(64), 0, st, q_);                \
-		else if ((q_).C == 3)                                                                        \
-			hipLaunchKernelGGL((kernel<PixT, false, nc_for<PixT, 3>>), grid_, dim3(64), 0, st, q_);                \
-		else                                                                                         \
-			hipLaunchKernelGGL((kernel<PixT, false, 0>), grid_, dim3(64), 0, st, q_);                \
-	} while (0)
-		DR_LAUNCH_NC(raster_bwd_fast_kernel, tex, grid, q);
+		if (launch(std::false_type{}, dim3((unsigned)p.n_views * (unsigned)q.tile_blocks), q))
+			return 1;
 	}
 	// (running the two kernels side by side on a forked stream was measured: no gain, the edge kernel just stretches)
 	if (p.sigma > 0 && p.aa_err)
 	{ // antialiase_error: the sweep ran over the error buffer, and so does its adjoint (bwd_err_tile, dr_backward.h)
 		const dim3 grid(edge_grid.x, edge_grid.y);
-		if (tex)
+		if (p.texture != nullptr)
 			hipLaunchKernelGGL((raster_bwd_edge_err_kernel<PixT, true>), grid, dim3(64), 0, st, p);
 		else
 			hipLaunchKernelGGL((raster_bwd_edge_err_kernel<PixT, false>), grid, dim3(64), 0, st, p);
 	}
 	else if (p.sigma > 0 && !p.fuse_edges) // (a fit step back-propagates the tiles with edges inside its forward raster)
-	{
-		DR_LAUNCH_NC(raster_bwd_edge_kernel, tex, edge_grid, p);
-	}
+		return launch(std::true_type{}, edge_grid, p);
+	return 0;
 }
 
 std::vector<ProfEvent> g_prof_events;
@@ -414,7 +420,24 @@ void forward_launch_constants(KParams &q)
 }
 
 constexpr long long SPARSE_MAX = 16384; // triangles (all views) up to which the per-primitive kernels spread their work over more wavefronts (KParams::setup_sparse)
-bool small_launch(int T, int n_views) { return (long long)T * n_views <= SPARSE_MAX; }
+// KParams::setup_sparse and the workgroups of a per-primitive kernel over all views: the edge blocks (one edge slot per thread in a small launch) + the
+// triangle blocks (set-up: `spread_triangles`, a small launch gives every triangle setup_sparse threads; finalize: one thread per triangle)
+unsigned prim_grid(KParams &p, int n_views, bool spread_triangles)
+{
+	p.setup_sparse = (long long)p.T * n_views <= SPARSE_MAX ? 4 : 1;
+	return (unsigned)(prim_tri_blocks(spread_triangles ? p.T * p.setup_sparse : p.T) + prim_edge_blocks(p.T, p.setup_sparse > 1 ? 1 : EDGE_SLOTS)) * (unsigned)n_views;
+}
+
+// Which family of kernels a call runs.  The staged one (LDS staging, work lists) for up to CH channels, unless the un-staged one is forced or the
+// deterministic mode is on: this is the test of the adjoint and of the fused fit step ...
+bool staged_adjoint(const DeodrHipScene *sc, const KParams &p) { return p.C <= CH && !g_force_generic && !det_mode(sc); }
+// ... and a forward on its own is also staged with more than CH channels (the second operand of ||) when the frame has no silhouette edge and no texture
+// and nothing is fused -- Scene3D.render_deferred's frame, sigma = 0 -- through fwd_manyc_tile (the adjoint has no such path).  antialiase_error: staged
+// since round 6, the AA instances of the forward raster.
+bool staged_forward(const DeodrHipScene *sc, const KParams &p, bool fused)
+{
+	return (p.C <= CH || (!(p.sigma > 0) && !p.aa_err && !p.texture && !fused)) && !g_force_generic && !det_mode(sc);
+}
 
 // Staged forward: counters -> work list + tile bitmap (scan), then the raster on the caller's stream and, forked from it, the
 // background fill on the side stream.  *join receives the event the caller's stream has to wait for before the call returns
@@ -443,90 +466,37 @@ int launch_forward_staged(const KParams &p, bool fused, hipStream_t stream, hipE
 	}
 	// (+ the workgroups that stream this kernel's share of the background of the empty tiles, one bitmap word each)
 	const dim3 grid((unsigned)p.n_views * (unsigned)q.fwd_walkers + (unsigned)p.n_views * (unsigned)fill_share(p.fill_mode, 2, p.L.nwords));
-	const bool tex = p.texture != nullptr; // (see launch_adjoint_raster)
-	const bool common = p.strict && p.W % TILE == 0 && p.H % TILE == 0;
+	const bool tex = p.texture != nullptr;
 	hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
 	if (fused && tex && p.fuse_edges)
 		(void)hipStreamIsCapturing(stream, &capturing);
-	// (the split point must fall between two groups of eight workgroups -- a walker's list and XCD follow from its index in the one-kernel grid
-	// (KParams::block_base) --: true for the shares heavy_share_for returns, checked here all the same)
-	if (fused && tex && p.fuse_edges && !p.clamp && !fit_weights(p) && p.n_views >= TEX_TWO_KERNELS && q.tile_blocks % (8 * WORK_CHUNK) == 0 &&
-		q.tile_blocks % q.heavy_share == 0 && (q.tile_blocks / q.heavy_share) % 8 == 0 && capturing == hipStreamCaptureStatusNone)
-	{ // the head walkers (edge adjoint: many registers) on the side stream, everybody else (+ the fill workgroups) on the caller's, both behind the scan
-		const unsigned head = (unsigned)p.n_views * (unsigned)(q.tile_blocks / q.heavy_share);
-		std::lock_guard<std::mutex> lock(g_side_mutex);
-		SideStream ss;
-		if (side_stream(ss) || check_hip(hipEventRecord(ss.fork, stream), "fork") || check_hip(hipStreamWaitEvent(ss.stream, ss.fork, 0), "fork"))
-			return 1;
-		KParams rest = q;
-		rest.block_base = head;
-		if (p.C == 3)
-		{
-			hipLaunchKernelGGL((raster_fwd_fast_kernel<PixT, true, true, false, nc_for<PixT, 3>, false, 2>), dim3(head), dim3(64), 0, ss.stream, q);
-			hipLaunchKernelGGL((raster_fwd_fast_kernel<PixT, true, true, false, nc_for<PixT, 3>, false, 3>), dim3(grid.x - head), dim3(64), 0, stream, rest);
-		}
-		else
-		{
-			hipLaunchKernelGGL((raster_fwd_fast_kernel<PixT, true, true, false, 0, false, 2>), dim3(head), dim3(64), 0, ss.stream, q);
-			hipLaunchKernelGGL((raster_fwd_fast_kernel<PixT, true, true, false, 0, false, 3>), dim3(grid.x - head), dim3(64), 0, stream, rest);
-		}
-		if (check_hip(hipEventRecord(ss.join, ss.stream), "join") || check_hip(hipStreamWaitEvent(stream, ss.join, 0), "join"))
-			return 1;
-		return 0;
-	}
-	if (p.C > CH) // (more than CH channels: launch_forward sends only forward-only calls without edges and without texture here)
-		hipLaunchKernelGGL((raster_fwd_fast_kernel<PixT, false, false, false, 0, false, 0, 2>), grid, dim3(64), 0, stream, q);
-	else if (p.aa_err && !fused && tex) // (antialiase_error: the edges blend the error buffer, the image stays un-antialiased)
-		hipLaunchKernelGGL((raster_fwd_fast_kernel<PixT, false, true, false, 0, false, 0, 1>), grid, dim3(64), 0, stream, q);
-	else if (p.aa_err && !fused)
-		hipLaunchKernelGGL((raster_fwd_fast_kernel<PixT, false, false, false, 0, false, 0, 1>), grid, dim3(64), 0, stream, q);
-	// (per-pixel weights: instances of their own again, VAR = 3, which are the clamp-capable ones -- p.clamp decides at run time as in the
-	// clamped instances below; a weighted textured step takes the one-kernel form at any number of views, as the clamped one does)
-	else if (fused && fit_weights(p) && tex && p.fuse_edges)
-		hipLaunchKernelGGL((raster_fwd_fast_kernel<PixT, true, true, true, 0, false, 1, 3>), grid, dim3(64), 0, stream, q);
-	else if (fused && fit_weights(p) && tex)
-		hipLaunchKernelGGL((raster_fwd_fast_kernel<PixT, true, true, true, 0, false, 0, 3>), grid, dim3(64), 0, stream, q);
-	else if (fused && fit_weights(p) && p.C == 1) // (a depth image with holes)
-		hipLaunchKernelGGL((raster_fwd_fast_kernel<PixT, true, false, true, nc_for<PixT, 1>, false, 0, 3>), grid, dim3(64), 0, stream, q);
-	else if (fused && fit_weights(p))
-		hipLaunchKernelGGL((raster_fwd_fast_kernel<PixT, true, false, true, 0, false, 0, 3>), grid, dim3(64), 0, stream, q);
-	else if (fused && p.clamp && tex && p.fuse_edges) // (the clamped residual of the depth fitter: its own instances of the fused kernel)
-		hipLaunchKernelGGL((raster_fwd_fast_kernel<PixT, true, true, true, 0, false, 1>), grid, dim3(64), 0, stream, q);
-	else if (fused && tex && p.fuse_edges && p.C == 3) // (textured fit step, sigma > 0: the instances with the edge adjoint)
-		hipLaunchKernelGGL((raster_fwd_fast_kernel<PixT, true, true, false, nc_for<PixT, 3>, false, 1>), grid, dim3(64), 0, stream, q);
-	else if (fused && tex && p.fuse_edges)
-		hipLaunchKernelGGL((raster_fwd_fast_kernel<PixT, true, true, false, 0, false, 1>), grid, dim3(64), 0, stream, q);
-	else if (fused && p.clamp && tex)
-		hipLaunchKernelGGL((raster_fwd_fast_kernel<PixT, true, true, true>), grid, dim3(64), 0, stream, q);
-	else if (fused && p.clamp && p.C == 1) // (a depth image)
-		hipLaunchKernelGGL((raster_fwd_fast_kernel<PixT, true, false, true, nc_for<PixT, 1>>), grid, dim3(64), 0, stream, q);
-	else if (fused && p.clamp)
-		hipLaunchKernelGGL((raster_fwd_fast_kernel<PixT, true, false, true>), grid, dim3(64), 0, stream, q);
-	else if (fused && tex && p.C == 3) // (the channel counts that occur: RGB, RGB + depth; others take the run-time instance)
-		hipLaunchKernelGGL((raster_fwd_fast_kernel<PixT, true, true, false, nc_for<PixT, 3>>), grid, dim3(64), 0, stream, q);
-	else if (fused && tex)
-		hipLaunchKernelGGL((raster_fwd_fast_kernel<PixT, true, true>), grid, dim3(64), 0, stream, q);
-	else if (fused && p.C == 4 && common)
-		hipLaunchKernelGGL((raster_fwd_fast_kernel<PixT, true, false, false, nc_for<PixT, 4>, common_for<PixT>>), grid, dim3(64), 0, stream, q);
-	else if (fused && p.C == 3 && common)
-		hipLaunchKernelGGL((raster_fwd_fast_kernel<PixT, true, false, false, nc_for<PixT, 3>, common_for<PixT>>), grid, dim3(64), 0, stream, q);
-	else if (fused && p.C == 4)
-		hipLaunchKernelGGL((raster_fwd_fast_kernel<PixT, true, false, false, nc_for<PixT, 4>>), grid, dim3(64), 0, stream, q);
-	else if (fused && p.C == 3)
-		hipLaunchKernelGGL((raster_fwd_fast_kernel<PixT, true, false, false, nc_for<PixT, 3>>), grid, dim3(64), 0, stream, q);
-	else if (fused)
-		hipLaunchKernelGGL((raster_fwd_fast_kernel<PixT, true, false>), grid, dim3(64), 0, stream, q);
-	else if (tex && p.C == 3)
-		hipLaunchKernelGGL((raster_fwd_fast_kernel<PixT, false, true, false, nc_for<PixT, 3>>), grid, dim3(64), 0, stream, q);
-	else if (tex)
-		hipLaunchKernelGGL((raster_fwd_fast_kernel<PixT, false, true>), grid, dim3(64), 0, stream, q);
-	else if (p.C == 4)
-		hipLaunchKernelGGL((raster_fwd_fast_kernel<PixT, false, false, false, nc_for<PixT, 4>>), grid, dim3(64), 0, stream, q);
-	else if (p.C == 3)
-		hipLaunchKernelGGL((raster_fwd_fast_kernel<PixT, false, false, false, nc_for<PixT, 3>>), grid, dim3(64), 0, stream, q);
-	else
-		hipLaunchKernelGGL((raster_fwd_fast_kernel<PixT, false, false>), grid, dim3(64), 0, stream, q);
-	return 0;
+	constexpr bool f64 = sizeof(PixT) == 8;
+	const FwdInst inst = select_forward(FwdCall{f64, fused, tex, p.fuse_edges != 0, p.clamp != 0, fit_weights(p) != nullptr, p.aa_err != 0,
+												p.strict && p.W % TILE == 0 && p.H % TILE == 0, capturing != hipStreamCaptureStatusNone, p.C, p.n_views,
+												q.tile_blocks, q.heavy_share});
+	auto launch = [&](const FwdInst &want, dim3 g, hipStream_t on, const KParams &args) {
+		return launch_from("internal: no instance of raster_fwd_fast_kernel for this call", FWD_INSTANCES, want, [&](auto i) {
+			constexpr FwdInst k = FWD_INSTANCES[decltype(i)::value];
+			if constexpr (fwd_exists(k, f64))
+				hipLaunchKernelGGL((raster_fwd_fast_kernel<PixT, k.fused, k.tex, k.clamp, k.nc, k.common, k.texe, k.var>), g, dim3(64), 0, on, args);
+			return fwd_exists(k, f64);
+		});
+	};
+	if (inst.texe != 2)
+		return launch(inst, grid, stream, q);
+	// the two-kernel form: the head walkers (edge adjoint: many registers) on the side stream, everybody else (+ the fill workgroups) on the caller's,
+	// both behind the scan
+	const unsigned head = (unsigned)p.n_views * (unsigned)(q.tile_blocks / q.heavy_share);
+	std::lock_guard<std::mutex> lock(g_side_mutex);
+	SideStream ss;
+	if (side_stream(ss) || check_hip(hipEventRecord(ss.fork, stream), "fork") || check_hip(hipStreamWaitEvent(ss.stream, ss.fork, 0), "fork"))
+		return 1;
+	KParams rest = q;
+	FwdInst others = inst;
+	rest.block_base = head, others.texe = 3;
+	if (launch(inst, dim3(head), ss.stream, q) || launch(others, dim3(grid.x - head), stream, rest))
+		return 1;
+	return check_hip(hipEventRecord(ss.join, ss.stream), "join") || check_hip(hipStreamWaitEvent(stream, ss.join, 0), "join");
 }
 
 // grid of the un-staged kernels: four tiles (wavefronts) per workgroup
@@ -541,46 +511,24 @@ int launch_forward(const DeodrHipScene *sc, KParams &p, hipStream_t stream, hipE
 	g_profile = g_profile_every > 0 && (g_profile_calls++ % (unsigned)g_profile_every) == 0;
 	p.stamp = (g_stamps && g_stamp_calls < (unsigned)g_stamp_rows) ? g_stamps + 4 * (size_t)g_stamp_calls++ : nullptr;
 	p.n_views = n_views;
-	// (antialiase_error: staged since round 6, the AA instances of the forward raster; more than CH channels: staged when the frame has no silhouette
-	// edge and no texture and nothing is fused -- Scene3D.render_deferred's frame, sigma = 0 -- through fwd_manyc_tile)
-	const bool many_channels = p.C > CH && !(p.sigma > 0) && !p.aa_err && !p.texture && !fused;
-	const bool fast = (p.C <= CH || many_channels) && !g_force_generic && !det_mode(sc);
+	const bool f64 = sc->pixel_dtype == DEODR_HIP_F64;
 	if (p.T > 0)
 	{
-		p.setup_sparse = small_launch(p.T, n_views) ? 4 : 1;
-		dim3 grid((unsigned)(prim_tri_blocks(p.T * p.setup_sparse) + prim_edge_blocks(p.T, p.setup_sparse > 1 ? 1 : EDGE_SLOTS)) * (unsigned)n_views);
+		const dim3 grid(prim_grid(p, n_views, true));
 		ScopedKernelTimer t(KID_SETUP, stream);
-		// (instances for the vertex dtype and for the channel counts that occur -- RGB, RGB + depth --; other counts: the run-time one)
-#define DR_LAUNCH_PRIM(kernel, grid_, stream_)                                                                              \
-	do                                                                                                                      \
-	{                                                                                                                       \
-		if (p.vtx_f64 && p.C == 4)                                                                                          \
-			hipLaunchKernelGGL((kernel<true, 4>), grid_, dim3(PRIM_BLOCK), 0, stream_, p);                                  \
-		else if (p.vtx_f64 && p.C == 3)                                                                                     \
-			hipLaunchKernelGGL((kernel<true, 3>), grid_, dim3(PRIM_BLOCK), 0, stream_, p);                                  \
-		else if (p.vtx_f64)                                                                                                 \
-			hipLaunchKernelGGL((kernel<true, 0>), grid_, dim3(PRIM_BLOCK), 0, stream_, p);                                  \
-		else if (p.C == 4)                                                                                                  \
-			hipLaunchKernelGGL((kernel<false, 4>), grid_, dim3(PRIM_BLOCK), 0, stream_, p);                                 \
-		else if (p.C == 3)                                                                                                  \
-			hipLaunchKernelGGL((kernel<false, 3>), grid_, dim3(PRIM_BLOCK), 0, stream_, p);                                 \
-		else                                                                                                                \
-			hipLaunchKernelGGL((kernel<false, 0>), grid_, dim3(PRIM_BLOCK), 0, stream_, p);                                 \
-	} while (0)
-		DR_LAUNCH_PRIM(setup_bin_kernel, grid, stream);
+		if (launch_from("internal: no instance of setup_bin_kernel for this call", SETUP_INSTANCES, select_setup(p.vtx_f64 != 0, p.C), [&](auto i) {
+				constexpr PrimInst k = SETUP_INSTANCES[decltype(i)::value];
+				hipLaunchKernelGGL((setup_bin_kernel<k.vtx_f64, k.nc>), grid, dim3(PRIM_BLOCK), 0, stream, p);
+				return true;
+			}))
+			return 1;
 	}
 	{
 		ScopedKernelTimer t(KID_RASTER_FWD, stream);
-		const bool f64 = sc->pixel_dtype == DEODR_HIP_F64;
-		if (fast)
-		{
-			if (f64 ? launch_forward_staged<double>(p, fused, stream, join) : launch_forward_staged<float>(p, fused, stream, join))
-				return 1;
-		}
-		else if (f64)
-			hipLaunchKernelGGL(raster_fwd_kernel<double>, generic_grid(p, n_views), dim3(256), 0, stream, p);
-		else
-			hipLaunchKernelGGL(raster_fwd_kernel<float>, generic_grid(p, n_views), dim3(256), 0, stream, p);
+		if (!staged_forward(sc, p, fused))
+			with_pixel_type(f64, [&](auto pix) { hipLaunchKernelGGL(raster_fwd_kernel<decltype(pix)>, generic_grid(p, n_views), dim3(256), 0, stream, p); });
+		else if (with_pixel_type(f64, [&](auto pix) { return launch_forward_staged<decltype(pix)>(p, fused, stream, join); }))
+			return 1;
 	}
 	return check_hip(hipGetLastError(), "forward launch");
 }
@@ -588,18 +536,12 @@ int launch_forward(const DeodrHipScene *sc, KParams &p, hipStream_t stream, hipE
 // the caller's stream waits for the side stream's work of this call
 int join_side(hipStream_t stream, hipEvent_t join) { return join ? check_hip(hipStreamWaitEvent(stream, join, 0), "join") : 0; }
 
-template <class Kernel>
-void launch_finalize(Kernel kernel, dim3 grid, hipStream_t st, const KParams &p)
-{
-	hipLaunchKernelGGL(kernel, grid, dim3(PRIM_BLOCK), 0, st, p);
-}
-
 // adjoint raster and the per-primitive finalize; owner_tiles = false after a fused forward
 int launch_adjoint(const DeodrHipScene *sc, KParams &p, hipStream_t st, bool owner_tiles)
 {
 	// (antialiase_error, round 6: the tiles without silhouette edges through raster_bwd_fast_kernel -- their gradient is -2 (obs - image) err_buffer_b,
 	// H.h:3054-3060 --, the tiles with edges through the un-staged tile code, called tile by tile from raster_bwd_edge_kernel's work lists)
-	const bool fast = p.C <= CH && !g_force_generic && !det_mode(sc);
+	const bool fast = staged_adjoint(sc, p);
 	p.n_views = sc->n_views;
 	if (det_mode(sc) && det_shadows(p, sc->n_views, st))
 		return 1;
@@ -610,40 +552,22 @@ int launch_adjoint(const DeodrHipScene *sc, KParams &p, hipStream_t st, bool own
 	if (!fast || owner_tiles || (p.sigma > 0 && !p.fuse_edges)) // (a fit step with fused edge tiles launches nothing here)
 	{
 		ScopedKernelTimer t(KID_RASTER_BWD, st);
-		if (sc->pixel_dtype == DEODR_HIP_F64)
-			launch_adjoint_raster<double>(p, fast, owner_tiles, generic_grid(p, sc->n_views), edge_grid, st);
-		else
-			launch_adjoint_raster<float>(p, fast, owner_tiles, generic_grid(p, sc->n_views), edge_grid, st);
+		auto raster = [&](auto pix) { return launch_adjoint_raster<decltype(pix)>(p, fast, owner_tiles, generic_grid(p, sc->n_views), edge_grid, st); };
+		if (with_pixel_type(sc->pixel_dtype == DEODR_HIP_F64, raster))
+			return 1;
 	}
 	if (p.T > 0)
 	{
 		const int fill_words = fast ? sc->n_views * fill_share(p.fill_mode, 1, p.L.nwords) : 0;
-		p.setup_sparse = small_launch(p.T, sc->n_views) ? 4 : 1; // (finalize_kernel: one edge slot per thread then)
-		dim3 g2((unsigned)(prim_tri_blocks(p.T) + prim_edge_blocks(p.T, p.setup_sparse > 1 ? 1 : EDGE_SLOTS)) * (unsigned)sc->n_views +
-				(unsigned)((fill_words + PRIM_BLOCK / 64 - 1) / (PRIM_BLOCK / 64)) +
+		dim3 g2(prim_grid(p, sc->n_views, false) + (unsigned)((fill_words + PRIM_BLOCK / 64 - 1) / (PRIM_BLOCK / 64)) +
 				(p.loss_out ? 1u : 0u)); // (+ the workgroup that adds up the loss)
 		ScopedKernelTimer t(KID_FINALIZE, st);
-		if (p.det && p.vtx_f64)
-			launch_finalize(finalize_kernel<true, 0, true>, g2, st, p);
-		else if (p.det)
-			launch_finalize(finalize_kernel<false, 0, true>, g2, st, p);
-		else if (p.prim_tables && p.C <= CH)
-		{ // (the instances with the per-workgroup vertex table, for the channel counts that occur)
-			if (p.vtx_f64 && p.C == 4)
-				launch_finalize(finalize_kernel<true, 4, false, true>, g2, st, p);
-			else if (p.vtx_f64 && p.C == 3)
-				launch_finalize(finalize_kernel<true, 3, false, true>, g2, st, p);
-			else if (p.vtx_f64)
-				launch_finalize(finalize_kernel<true, 0, false, true>, g2, st, p);
-			else if (p.C == 4)
-				launch_finalize(finalize_kernel<false, 4, false, true>, g2, st, p);
-			else if (p.C == 3)
-				launch_finalize(finalize_kernel<false, 3, false, true>, g2, st, p);
-			else
-				launch_finalize(finalize_kernel<false, 0, false, true>, g2, st, p);
-		}
-		else
-			DR_LAUNCH_PRIM(finalize_kernel, g2, st);
+		if (launch_from("internal: no instance of finalize_kernel for this call", FINALIZE_INSTANCES, select_finalize(p.vtx_f64 != 0, p.C, p.det != 0, p.prim_tables != 0), [&](auto i) {
+				constexpr PrimInst k = FINALIZE_INSTANCES[decltype(i)::value];
+				hipLaunchKernelGGL((finalize_kernel<k.vtx_f64, k.nc, k.det, k.table>), g2, dim3(PRIM_BLOCK), 0, st, p);
+				return true;
+			}))
+			return 1;
 	}
 	if (p.det)
 		det_convert(p, sc->n_views, st);
@@ -671,6 +595,7 @@ bool last_forward_was_fused(const void *workspace)
 // Streaming copy / fill / read with 16-byte non-temporal accesses, the access pattern of the rasterizer's own frame stores and
 // background fill (deodr_hip_copy_probe: the copy ceiling of the box a roofline fraction may also be quoted against).
 typedef uint32_t probe_u4 __attribute__((ext_vector_type(4)));
+constexpr int PROBE_MODES[] = {0, 1, 2}; // copy, fill, read
 template <int MODE>
 __global__ __launch_bounds__(256) void copy_probe_kernel(probe_u4 *dst, const probe_u4 *src, size_t n16)
 {
@@ -765,12 +690,10 @@ int deodr_hip_copy_probe(void *dst, const void *src, size_t bytes, int mode, int
 		blocks = 256 * 32; // 32 workgroups per CU, grid-stride beyond
 	for (int r = 0; r < reps; r++)
 	{
-		if (mode == 0)
-			hipLaunchKernelGGL(copy_probe_kernel<0>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (probe_u4 *)dst, (const probe_u4 *)src, n16);
-		else if (mode == 1)
-			hipLaunchKernelGGL(copy_probe_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (probe_u4 *)dst, (const probe_u4 *)src, n16);
-		else
-			hipLaunchKernelGGL(copy_probe_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (probe_u4 *)dst, (const probe_u4 *)src, n16);
+		(void)launch_from("internal: no instance of copy_probe_kernel for this mode", PROBE_MODES, mode, [&](auto i) { // (mode was checked above)
+			hipLaunchKernelGGL(copy_probe_kernel<PROBE_MODES[decltype(i)::value]>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (probe_u4 *)dst, (const probe_u4 *)src, n16);
+			return true;
+		});
 	}
 	return check_hip(hipGetLastError(), "copy_probe launch");
 }
@@ -870,7 +793,7 @@ static int render_scene_fit_impl(const DeodrHipScene *sc, void *image, void *z_b
 		if (p.texture_b && check_hip(hipMemsetAsync(p.texture_b, 0, (size_t)p.tex_h * p.tex_w * p.C * ps, st), "clear texture_b"))
 			return 1;
 	}
-	const bool fused = p.C <= CH && !g_force_generic && !det_mode(sc);
+	const bool fused = staged_adjoint(sc, p);
 	const bool loss_in_kernels = loss_out && fused && p.T > 0; // (the tile walkers of the staged forward + finalize's last workgroup)
 	if (loss_in_kernels)
 		p.loss_tile_bg = tile_loss, p.loss_wave = loss_scratch, p.loss_out = loss_out;
@@ -957,14 +880,12 @@ int deodr_hip_background_loss(const DeodrHipScene *sc, const void *obs, const De
 	p.n_views = sc->n_views;
 	hipStream_t st = (hipStream_t)stream;
 	const dim3 grid((unsigned)p.L.ntiles, (unsigned)sc->n_views);
-	if (fit_weights(p) && sc->pixel_dtype == DEODR_HIP_F64)
-		hipLaunchKernelGGL(background_loss_weighted_kernel<double>, grid, dim3(64), 0, st, p, tile_loss);
-	else if (fit_weights(p))
-		hipLaunchKernelGGL(background_loss_weighted_kernel<float>, grid, dim3(64), 0, st, p, tile_loss);
-	else if (sc->pixel_dtype == DEODR_HIP_F64)
-		hipLaunchKernelGGL(background_loss_kernel<double>, grid, dim3(64), 0, st, p, tile_loss);
-	else
-		hipLaunchKernelGGL(background_loss_kernel<float>, grid, dim3(64), 0, st, p, tile_loss);
+	with_pixel_type(sc->pixel_dtype == DEODR_HIP_F64, [&](auto pix) {
+		if (fit_weights(p))
+			hipLaunchKernelGGL(background_loss_weighted_kernel<decltype(pix)>, grid, dim3(64), 0, st, p, tile_loss);
+		else
+			hipLaunchKernelGGL(background_loss_kernel<decltype(pix)>, grid, dim3(64), 0, st, p, tile_loss);
+	});
 	hipLaunchKernelGGL(background_loss_total_kernel, dim3(1), dim3(FH_BLOCK), 0, st, tile_loss, (size_t)sc->n_views * p.L.ntiles);
 	return check_hip(hipGetLastError(), "background_loss launch");
 }
@@ -1262,18 +1183,15 @@ static int l2_loss_impl(const void *image, const void *obs, int pixel_dtype, siz
 	const dim3 grid((unsigned)(want < (size_t)L2_BLOCKS ? want : (size_t)L2_BLOCKS));
 	double *partials = (double *)((char *)scratch + 64);
 	unsigned *counter = (unsigned *)scratch + FC_L2;
-	if (weights && pixel_dtype == DEODR_HIP_F64)
-		hipLaunchKernelGGL(l2_loss_weighted_kernel<double>, grid, dim3(FH_BLOCK), 0, (hipStream_t)stream, (const double *)image, (const double *)obs,
-						   (const double *)weights, nb_colors, count, out, partials, counter, clamp, clamp_lo, clamp_hi);
-	else if (weights)
-		hipLaunchKernelGGL(l2_loss_weighted_kernel<float>, grid, dim3(FH_BLOCK), 0, (hipStream_t)stream, (const float *)image, (const float *)obs,
-						   (const float *)weights, nb_colors, count, out, partials, counter, clamp, clamp_lo, clamp_hi);
-	else if (pixel_dtype == DEODR_HIP_F64)
-		hipLaunchKernelGGL(l2_loss_kernel<double>, grid, dim3(FH_BLOCK), 0, (hipStream_t)stream, (const double *)image, (const double *)obs, count, out, partials,
-						   counter, clamp, clamp_lo, clamp_hi);
-	else
-		hipLaunchKernelGGL(l2_loss_kernel<float>, grid, dim3(FH_BLOCK), 0, (hipStream_t)stream, (const float *)image, (const float *)obs, count, out, partials,
-						   counter, clamp, clamp_lo, clamp_hi);
+	with_pixel_type(pixel_dtype == DEODR_HIP_F64, [&](auto pix) {
+		using PixT = decltype(pix);
+		if (weights)
+			hipLaunchKernelGGL(l2_loss_weighted_kernel<PixT>, grid, dim3(FH_BLOCK), 0, (hipStream_t)stream, (const PixT *)image, (const PixT *)obs,
+							   (const PixT *)weights, nb_colors, count, out, partials, counter, clamp, clamp_lo, clamp_hi);
+		else
+			hipLaunchKernelGGL(l2_loss_kernel<PixT>, grid, dim3(FH_BLOCK), 0, (hipStream_t)stream, (const PixT *)image, (const PixT *)obs, count, out, partials,
+							   counter, clamp, clamp_lo, clamp_hi);
+	});
 	return check_hip(hipGetLastError(), "l2_loss launch");
 }
 
@@ -1293,12 +1211,11 @@ int deodr_hip_depth_residual(const void *image, int pixel_dtype, const double *o
 	const dim3 grid((unsigned)(want < (size_t)L2_BLOCKS ? want : (size_t)L2_BLOCKS));
 	double *partials = (double *)((char *)scratch + 64);
 	unsigned *counter = (unsigned *)scratch + FC_L2;
-	if (pixel_dtype == DEODR_HIP_F64)
-		hipLaunchKernelGGL(depth_residual_kernel<double>, grid, dim3(FH_BLOCK), 0, (hipStream_t)stream, (const double *)image, obs, max_depth, count, depth, diff,
-						   (double *)image_b, loss, partials, counter);
-	else
-		hipLaunchKernelGGL(depth_residual_kernel<float>, grid, dim3(FH_BLOCK), 0, (hipStream_t)stream, (const float *)image, obs, max_depth, count, depth, diff,
-						   (float *)image_b, loss, partials, counter);
+	with_pixel_type(pixel_dtype == DEODR_HIP_F64, [&](auto pix) {
+		using PixT = decltype(pix);
+		hipLaunchKernelGGL(depth_residual_kernel<PixT>, grid, dim3(FH_BLOCK), 0, (hipStream_t)stream, (const PixT *)image, obs, max_depth, count, depth, diff,
+						   (PixT *)image_b, loss, partials, counter);
+	});
 	return check_hip(hipGetLastError(), "depth_residual launch");
 }
 

@@ -1,4 +1,4 @@
-"""ctypes front-end of tests/sim/libtile_sim.so (host instantiation of the kernels' per-primitive code; tests only)."""
+"""ctypes front-end of tests/sim/libtile_sim.so (host instantiation of the kernels' per-primitive code) and libdispatch_sim.so; tests only."""
 
 import ctypes as C
 import os
@@ -19,15 +19,24 @@ class SimScene(C.Structure):
     )
 
 
+def _built(src, out, headers):
+    deps = [src] + [os.path.join(HERE, "..", "deodr_amd", "csrc", h) for h in headers]
+    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
+        subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", out, src], check=True)
+    return C.CDLL(out)
+
+
 def lib():
-    deps = [SRC] + [os.path.join(HERE, "..", "deodr_amd", "csrc", h) for h in ("dr_math.h", "dr_prims.h")]
-    if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", LIB, SRC], check=True)
-    L = C.CDLL(LIB)
+    L = _built(SRC, LIB, ("dr_math.h", "dr_prims.h"))
     L.sim_bin_counts.argtypes = [C.POINTER(SimScene), C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.sim_tri_coverage.argtypes = [C.POINTER(SimScene), C.c_int, C.c_void_p]
     L.sim_edge_coverage.argtypes = [C.POINTER(SimScene), C.c_int, C.c_int, C.c_void_p]
     return L
+
+
+def dispatch_lib():
+    """tests/sim/libdispatch_sim.so: the instance rules and tables of deodr_amd/csrc/dr_dispatch.h (tests/sim/dispatch_sim.cpp)."""
+    return _built(os.path.join(HERE, "sim", "dispatch_sim.cpp"), os.path.join(HERE, "sim", "libdispatch_sim.so"), ("dr_dispatch.h",))
 
 
 def sim_scene(s, sigma=1.0):
