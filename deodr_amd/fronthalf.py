@@ -7,47 +7,18 @@ import ctypes as C
 
 import torch
 
-from .hip_renderer import _check, _stream, lib
+from .hip_renderer import _check, _ptr, _stream, lib
+
+
+def _launch(function, device, *args):
+    """one call of the library on the current stream of `device` (every function here takes the stream last)"""
+    with torch.cuda.device(device):
+        _check(function(*args, _stream(device)))
 
 
 def usable(*tensors):
     """the kernels take contiguous float64 tensors on a ROCm device"""
     return all(t is not None and t.is_cuda and t.dtype == torch.float64 for t in tensors)
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-_bound = False
-
-
-def _lib():
-    global _bound
-    L = lib()
-    if not _bound:
-        vp, i, d = C.c_void_p, C.c_int, C.c_double
-        L.deodr_hip_rigid_transform.argtypes = [vp, vp, vp, vp, i, i, vp]
-        L.deodr_hip_rigid_transform_b.argtypes = [vp, vp, vp, vp, vp, i, i, vp]
-        L.deodr_hip_project_points.argtypes = [vp] * 6 + [i, i, vp]
-        L.deodr_hip_project_points_b.argtypes = [vp] * 7 + [i, i, vp]
-        L.deodr_hip_silhouette_flags.argtypes = [vp, vp, vp, vp, i, i, i, i, vp]
-        L.deodr_hip_momentum_update.argtypes = [i, vp, vp, vp, vp, vp, vp, vp, vp, d, d, vp, vp, vp, vp, vp, d, vp, C.c_size_t, vp]
-        L.deodr_hip_fit_front.argtypes = [vp] * 4 + [i] + [vp] * 6 + [i] + [vp] * 7 + [d, vp, vp, vp, C.c_size_t, i, i, i, vp]
-        L.deodr_hip_fit_scratch_bytes.argtypes, L.deodr_hip_fit_scratch_bytes.restype = [i, i], C.c_size_t
-        L.deodr_hip_fit_pose_project.argtypes = [vp] * 11 + [d, i, i, vp]
-        L.deodr_hip_fit_pose_project_b.argtypes = [vp] * 9 + [d, vp, vp, vp, C.c_size_t, i, i, vp, i, vp, vp]
-        L.deodr_hip_views_gradient_sum.argtypes = [vp] * 6 + [d, vp, i, i, vp, i, vp, vp]
-        L.deodr_hip_vertex_shade.argtypes = [vp] * 7 + [i, vp, vp, i, i, i, vp]
-        L.deodr_hip_vertex_shade_b.argtypes = [vp] * 7 + [i, vp, vp, vp, vp, vp, C.c_size_t, i, i, i, vp]
-        L.deodr_hip_rigid_energy.argtypes = [vp] * 5 + [d, vp, vp, vp, d, vp, C.c_size_t, i, vp]
-        L.deodr_hip_l2_loss.argtypes = [vp, vp, i, C.c_size_t, vp, vp, C.c_size_t, vp]
-        L.deodr_hip_depth_residual.argtypes = [vp, i, vp, d, C.c_size_t, vp, vp, vp, vp, vp, C.c_size_t, vp]
-        for f in ("rigid_transform", "rigid_transform_b", "project_points", "project_points_b", "silhouette_flags", "momentum_update", "fit_pose_project",
-                  "fit_pose_project_b", "views_gradient_sum", "vertex_shade", "vertex_shade_b", "rigid_energy", "l2_loss", "depth_residual", "fit_front"):  # fmt: skip
-            getattr(L, "deodr_hip_" + f).restype = i
-        _bound = True
-    return L
 
 
 class RigidTransformFunc(torch.autograd.Function):
@@ -58,8 +29,7 @@ class RigidTransformFunc(torch.autograd.Function):
         v, q, t = vertices.contiguous(), quaternions.contiguous(), translations.contiguous()
         n, V = q.shape[0], v.shape[0]
         out = torch.empty((n, V, 3), dtype=torch.float64, device=v.device)
-        with torch.cuda.device(v.device):
-            _check(_lib().deodr_hip_rigid_transform(_p(v), _p(q), _p(t), _p(out), V, n, _stream(v.device)))
+        _launch(lib().deodr_hip_rigid_transform, v.device, _ptr(v), _ptr(q), _ptr(t), _ptr(out), V, n)
         ctx.save_for_backward(v, q)
         return out
 
@@ -70,8 +40,7 @@ class RigidTransformFunc(torch.autograd.Function):
         out_b = out_b.contiguous()
         v_b = torch.empty_like(v)
         pose_b = torch.empty(7 * n, dtype=torch.float64, device=v.device)
-        with torch.cuda.device(v.device):
-            _check(_lib().deodr_hip_rigid_transform_b(_p(v), _p(q), _p(out_b), _p(v_b), _p(pose_b), V, n, _stream(v.device)))
+        _launch(lib().deodr_hip_rigid_transform_b, v.device, _ptr(v), _ptr(q), _ptr(out_b), _ptr(v_b), _ptr(pose_b), V, n)
         return v_b, pose_b[: 4 * n].view(n, 4), pose_b[4 * n :].view(n, 3)
 
 
@@ -96,8 +65,8 @@ class ProjectPointsFunc(torch.autograd.Function):
         _check_cameras(n, extrinsic, intrinsic, distortion)
         ij = torch.empty((n, V, 2), dtype=torch.float64, device=pts.device)
         depths = torch.empty((n, V), dtype=torch.float64, device=pts.device)
-        with torch.cuda.device(pts.device):
-            _check(_lib().deodr_hip_project_points(_p(pts), _p(extrinsic), _p(intrinsic), _p(distortion), _p(ij), _p(depths), V, n, _stream(pts.device)))
+        _launch(lib().deodr_hip_project_points, pts.device, _ptr(pts), _ptr(extrinsic), _ptr(intrinsic), _ptr(distortion), _ptr(ij),
+                _ptr(depths), V, n)  # fmt: skip
         ctx.save_for_backward(pts, extrinsic, intrinsic)
         ctx.distortion = distortion
         return ij, depths
@@ -109,9 +78,8 @@ class ProjectPointsFunc(torch.autograd.Function):
         ij_b = ij_b.contiguous()
         depths_b = None if depths_b is None else depths_b.contiguous()
         pts_b = torch.empty_like(pts)
-        with torch.cuda.device(pts.device):
-            _check(_lib().deodr_hip_project_points_b(_p(pts), _p(extrinsic), _p(intrinsic), _p(ctx.distortion), _p(ij_b), _p(depths_b), _p(pts_b), V, n,
-                                                     _stream(pts.device)))  # fmt: skip
+        _launch(lib().deodr_hip_project_points_b, pts.device, _ptr(pts), _ptr(extrinsic), _ptr(intrinsic), _ptr(ctx.distortion), _ptr(ij_b),
+                _ptr(depths_b), _ptr(pts_b), V, n)  # fmt: skip
         return pts_b, None, None, None
 
 
@@ -120,8 +88,7 @@ def silhouette_flags(ij, faces_u32, edge_faces_u32, clockwise, out=None):
     ij = ij.detach().contiguous()
     n, V, T = ij.shape[0], ij.shape[1], faces_u32.shape[0]
     flags = torch.empty((n, T, 3), dtype=torch.uint8, device=ij.device) if out is None else out
-    with torch.cuda.device(ij.device):
-        _check(_lib().deodr_hip_silhouette_flags(_p(ij), _p(faces_u32), _p(edge_faces_u32), _p(flags), T, V, n, int(bool(clockwise)), _stream(ij.device)))
+    _launch(lib().deodr_hip_silhouette_flags, ij.device, _ptr(ij), _ptr(faces_u32), _ptr(edge_faces_u32), _ptr(flags), T, V, n, int(bool(clockwise)))
     return flags
 
 
@@ -139,13 +106,11 @@ def momentum_update(entries, inertia, damping, scratch=None, energy=None, data_e
     count = (C.c_int * k)(*[int(e[0].numel()) for e in entries])
     rows = (C.c_int * k)(*[int(e[6]) for e in entries])
     scale = (C.c_double * k)(*[float(e[7]) for e in entries])
-    dev = entries[0][0].device
     for e in entries:
         assert e[0].is_contiguous() and e[1].is_contiguous() and e[2].is_contiguous() and (e[3] is None or e[3].is_contiguous())
-    with torch.cuda.device(dev):
-        _check(_lib().deodr_hip_momentum_update(k, ptrs(0), ptrs(1), ptrs(2), ptrs(3), factor, step_max, count, rows, float(inertia), float(damping), scale,
-                                                ptrs(8), ptrs(9), _p(energy), _p(data_energy), float(data_weight), _p(scratch),
-                                                0 if scratch is None else scratch.numel(), _stream(dev)))  # fmt: skip
+    _launch(lib().deodr_hip_momentum_update, entries[0][0].device, k, ptrs(0), ptrs(1), ptrs(2), ptrs(3), factor, step_max, count, rows, float(inertia),
+            float(damping), scale, ptrs(8), ptrs(9), _ptr(energy), _ptr(data_energy), float(data_weight), _ptr(scratch),
+            0 if scratch is None else scratch.numel())  # fmt: skip
 
 
 # ---- one fit iteration without an autograd graph (deodr_amd/csrc/dr_fititer.h) ----------------------------------------------------
@@ -153,7 +118,7 @@ def momentum_update(entries, inertia, damping, scratch=None, energy=None, data_e
 
 def fit_scratch(V, n, device):
     """zero-filled scratch of the kernels below (their counter words stay zero between launches)"""
-    return torch.zeros(int(_lib().deodr_hip_fit_scratch_bytes(int(V), int(n))), dtype=torch.uint8, device=device)
+    return torch.zeros(int(lib().deodr_hip_fit_scratch_bytes(int(V), int(n))), dtype=torch.uint8, device=device)
 
 
 def _topology_scratch(topology, n):
@@ -169,9 +134,9 @@ def fit_pose_project(vertices, vertices_mean, quaternions, translations, camera,
     translation, project them with every view's camera -> posed [n,V,3], ij [n,V,2], depths [n,V] (all written)"""
     n, V = posed.shape[0], posed.shape[1]
     _check_cameras(n, camera.extrinsic, camera.intrinsic, camera.distortion)
-    with torch.cuda.device(posed.device):
-        _check(_lib().deodr_hip_fit_pose_project(_p(vertices), _p(vertices_mean), _p(quaternions), _p(translations), _p(camera.extrinsic), _p(camera.intrinsic),
-                                                 _p(camera.distortion), _p(posed), _p(ij), _p(depths), _p(depth_colors), float(depth_scale), V, n, _stream(posed.device)))  # fmt: skip
+    _launch(lib().deodr_hip_fit_pose_project, posed.device, _ptr(vertices), _ptr(vertices_mean), _ptr(quaternions), _ptr(translations),
+            _ptr(camera.extrinsic), _ptr(camera.intrinsic), _ptr(camera.distortion), _ptr(posed), _ptr(ij), _ptr(depths), _ptr(depth_colors),
+            float(depth_scale), V, n)  # fmt: skip
 
 
 def fit_pose_project_b(vertices, quaternions, posed, camera, posed_b, ij_b, depths_b, vertices_b, out, scratch, depths_b_scale=1.0, colors_b=None,
@@ -180,10 +145,9 @@ def fit_pose_project_b(vertices, quaternions, posed, camera, posed_b, ij_b, dept
     [n,4] (raw quaternions), translation adjoints [n,3]; colors_sum [V,C] (optional) = colors_b [n,V,C] summed over the views"""
     n, V = posed.shape[0], posed.shape[1]
     _check_cameras(n, camera.extrinsic, camera.intrinsic, camera.distortion)
-    with torch.cuda.device(posed.device):
-        _check(_lib().deodr_hip_fit_pose_project_b(_p(vertices), _p(quaternions), _p(posed), _p(camera.extrinsic), _p(camera.intrinsic), _p(camera.distortion),
-                                                   _p(posed_b), _p(ij_b), _p(depths_b), float(depths_b_scale), _p(vertices_b), _p(out), _p(scratch), scratch.numel(), V, n,
-                                                   _p(colors_b), 0 if colors_b is None else int(colors_b.shape[-1]), _p(colors_sum), _stream(posed.device)))  # fmt: skip
+    _launch(lib().deodr_hip_fit_pose_project_b, posed.device, _ptr(vertices), _ptr(quaternions), _ptr(posed), _ptr(camera.extrinsic),
+            _ptr(camera.intrinsic), _ptr(camera.distortion), _ptr(posed_b), _ptr(ij_b), _ptr(depths_b), float(depths_b_scale), _ptr(vertices_b),
+            _ptr(out), _ptr(scratch), scratch.numel(), V, n, _ptr(colors_b), 0 if colors_b is None else int(colors_b.shape[-1]), _ptr(colors_sum))  # fmt: skip
 
 
 def views_gradient_sum(posed, camera, ij_b, vertices_b, depths_b=None, depths_b_scale=1.0, colors_b=None, colors_sum=None, validate=True):
@@ -193,10 +157,9 @@ def views_gradient_sum(posed, camera, ij_b, vertices_b, depths_b=None, depths_b_
     n, V = posed.shape[0], posed.shape[1]
     if validate:  # (validate=False: a caller that launches the same, already validated, tensors every step -- OverlappedViewsReduction)
         _validate_views_gradient_sum(posed, camera, ij_b, vertices_b, depths_b, colors_b, colors_sum)
-    with torch.cuda.device(posed.device):
-        _check(_lib().deodr_hip_views_gradient_sum(_p(posed), _p(camera.extrinsic), _p(camera.intrinsic), _p(camera.distortion), _p(ij_b), _p(depths_b),
-                                                   float(depths_b_scale), _p(vertices_b), V, n, _p(colors_b), 0 if colors_b is None else int(colors_b.shape[-1]),
-                                                   _p(colors_sum), _stream(posed.device)))  # fmt: skip
+    _launch(lib().deodr_hip_views_gradient_sum, posed.device, _ptr(posed), _ptr(camera.extrinsic), _ptr(camera.intrinsic), _ptr(camera.distortion),
+            _ptr(ij_b), _ptr(depths_b), float(depths_b_scale), _ptr(vertices_b), V, n, _ptr(colors_b),
+            0 if colors_b is None else int(colors_b.shape[-1]), _ptr(colors_sum))  # fmt: skip
 
 
 def _validate_views_gradient_sum(posed, camera, ij_b, vertices_b, depths_b, colors_b, colors_sum):
@@ -220,10 +183,9 @@ def _validate_views_gradient_sum(posed, camera, ij_b, vertices_b, depths_b, colo
 def vertex_shade(posed, topology, light, ambient, color=None, luminosity=None, colors=None):
     """luminosity [n,V] = max(0, -normal . light) + ambient and / or colors [n,V,C] = color [C] * luminosity (written)"""
     n, V = posed.shape[0], posed.shape[1]
-    with torch.cuda.device(posed.device):
-        _check(_lib().deodr_hip_vertex_shade(_p(posed), _p(topology._faces_u32), _p(topology._vf_offsets), _p(topology._vf_corners), _p(light), _p(ambient),
-                                             _p(color), 0 if color is None else color.numel(), _p(luminosity), _p(colors), V, n, int(topology.clockwise),
-                                             _stream(posed.device)))  # fmt: skip
+    _launch(lib().deodr_hip_vertex_shade, posed.device, _ptr(posed), _ptr(topology._faces_u32), _ptr(topology._vf_offsets),
+            _ptr(topology._vf_corners), _ptr(light), _ptr(ambient), _ptr(color), 0 if color is None else color.numel(), _ptr(luminosity),
+            _ptr(colors), V, n, int(topology.clockwise))  # fmt: skip
 
 
 def fit_front(topology, n, scratch, ij=None, flags=None, posed=None, light=None, ambient=None, color=None, luminosity=None, colors=None, vertices=None,
@@ -231,38 +193,34 @@ def fit_front(topology, n, scratch, ij=None, flags=None, posed=None, light=None,
     """:func:`silhouette_flags` (``flags`` given), :func:`vertex_shade` (``luminosity`` or ``colors`` given) and :func:`rigid_energy`
     (``gradient`` given; energy[0] only) in ONE launch -- the three do not depend on one another.  Same results bit for bit."""
     off, cols, vals = topology._m_csr if gradient is not None else (None, None, None)
-    dev = scratch.device
-    with torch.cuda.device(dev):
-        _check(_lib().deodr_hip_fit_front(_p(ij), _p(topology._faces_u32), _p(topology._edge_faces), _p(flags), topology.nb_faces, _p(posed), _p(topology._vf_offsets),
-                                          _p(topology._vf_corners), _p(light), _p(ambient), _p(color), 0 if color is None else color.numel(), _p(luminosity), _p(colors),
-                                          _p(vertices), _p(vertices_ref), _p(off), _p(cols), _p(vals), float(cregu), _p(gradient), _p(energy), _p(scratch),
-                                          scratch.numel(), topology.nb_vertices, int(n), int(topology.clockwise), _stream(dev)))  # fmt: skip
+    _launch(lib().deodr_hip_fit_front, scratch.device, _ptr(ij), _ptr(topology._faces_u32), _ptr(topology._edge_faces), _ptr(flags), topology.nb_faces,
+            _ptr(posed), _ptr(topology._vf_offsets), _ptr(topology._vf_corners), _ptr(light), _ptr(ambient), _ptr(color),
+            0 if color is None else color.numel(), _ptr(luminosity), _ptr(colors), _ptr(vertices), _ptr(vertices_ref), _ptr(off), _ptr(cols),
+            _ptr(vals), float(cregu), _ptr(gradient), _ptr(energy), _ptr(scratch), scratch.numel(), topology.nb_vertices, int(n),
+            int(topology.clockwise))  # fmt: skip
 
 
 def vertex_shade_b(posed, topology, light, ambient, color, luminosity_b, colors_b, posed_b, out, scratch):
     """adjoint of :func:`vertex_shade`: -> posed_b [n,V,3] (written), out [4 + C] = light_b, ambient_b, color_b"""
     n, V = posed.shape[0], posed.shape[1]
-    with torch.cuda.device(posed.device):
-        _check(_lib().deodr_hip_vertex_shade_b(_p(posed), _p(topology._faces_u32), _p(topology._vf_offsets), _p(topology._vf_corners), _p(light), _p(ambient),
-                                               _p(color), 0 if color is None else color.numel(), _p(luminosity_b), _p(colors_b), _p(posed_b), _p(out), _p(scratch),
-                                               scratch.numel(), V, n, int(topology.clockwise), _stream(posed.device)))  # fmt: skip
+    _launch(lib().deodr_hip_vertex_shade_b, posed.device, _ptr(posed), _ptr(topology._faces_u32), _ptr(topology._vf_offsets),
+            _ptr(topology._vf_corners), _ptr(light), _ptr(ambient), _ptr(color), 0 if color is None else color.numel(), _ptr(luminosity_b),
+            _ptr(colors_b), _ptr(posed_b), _ptr(out), _ptr(scratch), scratch.numel(), V, n, int(topology.clockwise))  # fmt: skip
 
 
 def rigid_energy(vertices, vertices_ref, topology, cregu, gradient, energy, scratch, data_energy=None, data_weight=1.0):
     """energy[0] = 0.5 c d^T (L^T L) d, gradient [V,3] = c (L^T L) d, d = vertices - vertices_ref (both written); with ``data_energy`` [1]
     also energy[1] = data_weight * data_energy[0] + energy[0]"""
     off, cols, vals = topology._m_csr
-    with torch.cuda.device(vertices.device):
-        _check(_lib().deodr_hip_rigid_energy(_p(vertices), _p(vertices_ref), _p(off), _p(cols), _p(vals), float(cregu), _p(gradient), _p(energy), _p(data_energy),
-                                             float(data_weight), _p(scratch), scratch.numel(), vertices.shape[0], _stream(vertices.device)))  # fmt: skip
+    _launch(lib().deodr_hip_rigid_energy, vertices.device, _ptr(vertices), _ptr(vertices_ref), _ptr(off), _ptr(cols), _ptr(vals), float(cregu),
+            _ptr(gradient), _ptr(energy), _ptr(data_energy), float(data_weight), _ptr(scratch), scratch.numel(), vertices.shape[0])  # fmt: skip
 
 
 def l2_loss(image, obs, out, scratch):
     """out[0] = sum (image - obs)^2, image and obs contiguous tensors of one pixel dtype (float32 / float64) and one shape"""
     assert image.dtype == obs.dtype and image.shape == obs.shape and image.is_contiguous() and obs.is_contiguous()
-    with torch.cuda.device(image.device):
-        _check(_lib().deodr_hip_l2_loss(_p(image), _p(obs), 1 if image.dtype == torch.float64 else 0, image.numel(), _p(out), _p(scratch), scratch.numel(),
-                                        _stream(image.device)))  # fmt: skip
+    _launch(lib().deodr_hip_l2_loss, image.device, _ptr(image), _ptr(obs), 1 if image.dtype == torch.float64 else 0, image.numel(), _ptr(out),
+            _ptr(scratch), scratch.numel())  # fmt: skip
 
 
 def depth_residual(image, obs, max_depth, depth, diff, image_b, loss, scratch):
@@ -270,9 +228,8 @@ def depth_residual(image, obs, max_depth, depth, diff, image_b, loss, scratch):
     image_b = d sum(diff) / d image in the pixel dtype, loss[0] = sum diff (deodr/mesh_fitter.py:108-123)"""
     assert obs.dtype == torch.float64 and depth.dtype == torch.float64 and diff.dtype == torch.float64 and image_b.dtype == image.dtype
     assert all(t.is_contiguous() and t.numel() == image.numel() for t in (image, obs, depth, diff, image_b))
-    with torch.cuda.device(image.device):
-        _check(_lib().deodr_hip_depth_residual(_p(image), 1 if image.dtype == torch.float64 else 0, _p(obs), float(max_depth), image.numel(), _p(depth), _p(diff),
-                                               _p(image_b), _p(loss), _p(scratch), scratch.numel(), _stream(image.device)))  # fmt: skip
+    _launch(lib().deodr_hip_depth_residual, image.device, _ptr(image), 1 if image.dtype == torch.float64 else 0, _ptr(obs), float(max_depth),
+            image.numel(), _ptr(depth), _ptr(diff), _ptr(image_b), _ptr(loss), _ptr(scratch), scratch.numel())  # fmt: skip
 
 
 class VertexLuminosityFunc(torch.autograd.Function):

@@ -14,40 +14,26 @@ torch is used for device memory and streams only.
 
 import ctypes as C
 import os
+from collections import namedtuple
 
 import numpy as np
 import torch
 
+from . import _abi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libdeodr_hip.so")
-ABI_VERSION = 13
-ERR_FACES, ERR_FACES_UV, ERR_NO_TEXTURE, ERR_INTERNAL, ERR_DET_RANGE = 1, 2, 4, 8, 16  # include/deodr_hip.h DEODR_HIP_ERR_*
-_STATUS_NEEDED, _STATUS_ERRORS = 11, 12  # words of the 64-byte status block at the start of the workspace
-
-
-class _SceneC(C.Structure):
-    _fields_ = (
-        [(n, C.c_void_p) for n in ("faces", "faces_uv", "textured", "shaded", "depths", "ij", "shade", "colors", "edgeflags", "uv")]
-        + [(n, C.c_void_p) for n in ("texture", "background_image", "background_color")]
-        + [(n, C.c_void_p) for n in ("uv_b", "ij_b", "shade_b", "colors_b", "texture_b")]
-        + [(n, C.c_int) for n in ("nb_triangles", "nb_vertices", "nb_uv", "height", "width", "nb_colors", "texture_height", "texture_width")]
-        + [(n, C.c_int) for n in ("clockwise", "backface_culling", "strict_edge", "perspective_correct", "integer_pixel_centers")]
-        + [(n, C.c_int) for n in ("n_views", "vertex_dtype", "pixel_dtype", "deterministic")]
-    )
-
+_H = _abi.HEADER  # the structs, the constants and (in lib()) the signatures are read from include/deodr_hip.h: deodr_amd/_abi.py
+_SceneC, _FitOptionsC, ABI_VERSION = _H.structs["DeodrHipScene"], _H.structs["DeodrHipFitOptions"], _H.defines["DEODR_HIP_ABI_VERSION"]
+ERR_FACES, ERR_FACES_UV, ERR_NO_TEXTURE, ERR_INTERNAL, ERR_DET_RANGE = (_H.defines["DEODR_HIP_ERR_" + n] for n in "FACES FACES_UV NO_TEXTURE INTERNAL DET_RANGE".split())
+# words of the 64-byte status block at the start of the workspace
+_STATUS_NEEDED, _STATUS_ERRORS = _H.defines["DEODR_HIP_STATUS_WORD_NEEDED_PAIRS"], _H.defines["DEODR_HIP_STATUS_WORD_SCENE_ERRORS"]
 
 _lib = None
 
 
-class _FitOptionsC(C.Structure):
-    """include/deodr_hip.h::DeodrHipFitOptions"""
-
-    _fields_ = [("tile_loss", C.c_void_p), ("loss", C.c_void_p), ("loss_scratch", C.c_void_p), ("clamp", C.c_int), ("clamp_lo", C.c_double),
-                ("clamp_hi", C.c_double), ("done_flag", C.c_void_p), ("done_value", C.c_uint32), ("weights", C.c_void_p)]  # fmt: skip
-
-
 def lib():
-    """The HIP library; raises (never falls back) when it has not been built."""
+    """The HIP library, every function of the header bound; raises (never falls back) when it has not been built."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
@@ -56,41 +42,9 @@ def lib():
                 "(hipcc --offload-arch=gfx950). deodr_amd has no CPU fallback."
             )
         L = C.CDLL(LIB_PATH)
-        L.deodr_hip_abi_version.restype = C.c_int
         if L.deodr_hip_abi_version() != ABI_VERSION:
             raise ImportError("libdeodr_hip.so ABI version mismatch; rebuild it")
-        L.deodr_hip_last_error.restype = C.c_char_p
-        L.deodr_hip_workspace_bytes.restype = C.c_size_t
-        L.deodr_hip_workspace_bytes.argtypes = [C.c_int] * 5 + [C.c_size_t]
-        L.deodr_hip_render_scene.restype = C.c_int
-        L.deodr_hip_render_scene.argtypes = [C.POINTER(_SceneC), C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_void_p,
-                                             C.c_void_p, C.c_size_t, C.c_void_p]  # fmt: skip
-        L.deodr_hip_render_scene_b.restype = C.c_int
-        L.deodr_hip_render_scene_b.argtypes = [C.POINTER(_SceneC), C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_void_p,
-                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]  # fmt: skip
-        L.deodr_hip_render_scene_fit.restype = C.c_int
-        L.deodr_hip_render_scene_fit.argtypes = [C.POINTER(_SceneC), C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int, C.c_void_p,
-                                                 C.c_size_t, C.c_void_p]  # fmt: skip
-        L.deodr_hip_fit_loss_bytes.restype, L.deodr_hip_fit_loss_bytes.argtypes = C.c_size_t, [C.c_int] * 3
-        L.deodr_hip_background_loss.restype = C.c_int
-        L.deodr_hip_background_loss.argtypes = [C.POINTER(_SceneC), C.c_void_p, C.POINTER(_FitOptionsC), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.deodr_hip_render_scene_fit_ex.restype = C.c_int
-        L.deodr_hip_render_scene_fit_ex.argtypes = [C.POINTER(_SceneC), C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int, C.POINTER(_FitOptionsC),
-                                                    C.c_void_p, C.c_size_t, C.c_void_p]  # fmt: skip
-        L.deodr_hip_wait_flag.restype = C.c_int
-        L.deodr_hip_wait_flag.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_double, C.c_void_p]
-        L.deodr_hip_workspace_status.restype = C.c_int
-        L.deodr_hip_workspace_status.argtypes = [C.POINTER(_SceneC), C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_int),
-                                                 C.POINTER(C.c_ulonglong), C.POINTER(C.c_int)]  # fmt: skip
-        L.deodr_hip_workspace_census.restype = C.c_int
-        L.deodr_hip_workspace_census.argtypes = [C.POINTER(_SceneC), C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_ulonglong),
-                                                 C.POINTER(C.c_ulonglong)]  # fmt: skip
-        L.deodr_hip_workspace_pool_pairs.restype = C.c_int
-        L.deodr_hip_workspace_pool_pairs.argtypes = [C.POINTER(_SceneC), C.c_size_t, C.POINTER(C.c_ulonglong)]
-        L.deodr_hip_profile_stamps.restype, L.deodr_hip_profile_stamps.argtypes = C.c_int, [C.c_void_p, C.c_int]
-        L.deodr_hip_copy_probe.restype = C.c_int
-        L.deodr_hip_copy_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p]
-        _lib = L
+        _lib = _abi.bind(L)
     return _lib
 
 
@@ -117,10 +71,9 @@ def force_generic(on):
 
 def tile_census(rasterizer, ds):
     """(tiles with a primitive, tiles with silhouette edges) of the last forward on `rasterizer`, over all views (synchronises)."""
-    sc = ds.c_struct()
     a, b = C.c_ulonglong(0), C.c_ulonglong(0)
     with torch.cuda.device(rasterizer.device):
-        _check(lib().deodr_hip_workspace_census(C.byref(sc), _ptr(rasterizer.workspace), rasterizer.nbytes, _stream(rasterizer.device),
+        _check(lib().deodr_hip_workspace_census(C.byref(ds.c_struct()), _ptr(rasterizer.workspace), rasterizer.nbytes, _stream(rasterizer.device),
                                                 C.byref(a), C.byref(b)))  # fmt: skip
     return int(a.value), int(b.value)
 
@@ -170,16 +123,31 @@ def _count(a):
     return 0 if a is None else int(a.numel()) if torch.is_tensor(a) else int(np.size(a))
 
 
+def _as_tensor(a):
+    return a if torch.is_tensor(a) else torch.as_tensor(np.asarray(a))
+
+
+def _tensor(a, device, dtype):
+    """an array or a tensor as a contiguous tensor of `dtype` on `device` (the tensor itself when it already is one)"""
+    return _as_tensor(a).to(device=device, dtype=dtype).contiguous()
+
+
 def _on(t, device, dtype, shape, what):
     """`t` as a contiguous tensor of `dtype` on `device` with `shape` (no copy when it already is one)."""
-    if not torch.is_tensor(t):
-        t = torch.as_tensor(np.asarray(t))
-    t = t.to(device=device, dtype=dtype)
+    t = _tensor(t, device, dtype)
     if tuple(t.shape) != tuple(shape):
         if t.numel() != int(np.prod(shape)):
             raise ValueError(f"{what}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
         t = t.reshape(shape)
-    return t.contiguous()
+    return t
+
+
+def _pixels(t, ds):
+    """an observation or residual target as [n,H,W,C] in the pixel dtype on the scene's device; a tensor that already is that passes
+    through untouched (the loss-table cache keys on its identity)"""
+    shape = (ds.n_views, ds.height, ds.width, ds.nb_colors)
+    t = _tensor(t, ds.device, ds.pixel_dtype)
+    return t if tuple(t.shape) == shape else t.expand(shape).contiguous()  # pass [n,H,W,C] to avoid this copy
 
 
 class DeviceScene:
@@ -199,20 +167,17 @@ class DeviceScene:
         # integer accumulation for the calls on THIS scene (DeodrHipScene::deterministic): gradients bit-identical from run to run, several times
         # slower; may be switched at any time (it is read when a call is made).  set_deterministic() is the process-wide switch.
         self.deterministic = bool(deterministic)
-        as_t = lambda a, dt: torch.as_tensor(np.asarray(a) if not torch.is_tensor(a) else a).to(device=dev, dtype=dt).contiguous()
-        self.faces = as_t(np.asarray(faces).astype(np.int64) if not torch.is_tensor(faces) else faces, torch.int32)
-        self.faces_uv = as_t(np.asarray(faces_uv).astype(np.int64) if not torch.is_tensor(faces_uv) else faces_uv, torch.int32)
-        self.textured = as_t(textured, torch.uint8)
-        self.shaded = as_t(shaded, torch.uint8)
-        self.uv = as_t(uv, vertex_dtype).reshape(-1, 2)
+        self.faces = _tensor(np.asarray(faces).astype(np.int64) if not torch.is_tensor(faces) else faces, dev, torch.int32)
+        self.faces_uv = _tensor(np.asarray(faces_uv).astype(np.int64) if not torch.is_tensor(faces_uv) else faces_uv, dev, torch.int32)
+        self.textured = _tensor(textured, dev, torch.uint8)
+        self.shaded = _tensor(shaded, dev, torch.uint8)
+        self.uv = _tensor(uv, dev, vertex_dtype).reshape(-1, 2)
         self.height, self.width = int(height), int(width)
         self.flags = dict(clockwise=bool(clockwise), backface_culling=bool(backface_culling), strict_edge=bool(strict_edge),
                           perspective_correct=bool(perspective_correct), integer_pixel_centers=bool(integer_pixel_centers))  # fmt: skip
-        self.texture = None
-        if _count(texture) > 0:
-            self.texture = as_t(texture, pixel_dtype)
-        self.background_color = None if background_color is None else as_t(background_color, pixel_dtype).reshape(-1)
-        self.background_image = None if background_image is None else as_t(background_image, pixel_dtype)
+        self.texture = _tensor(texture, dev, pixel_dtype) if _count(texture) > 0 else None
+        self.background_color = None if background_color is None else _tensor(background_color, dev, pixel_dtype).reshape(-1)
+        self.background_image = None if background_image is None else _tensor(background_image, dev, pixel_dtype)
         self.set_views(ij, depths, colors, shade, edgeflags)
         if self.background_image is not None:
             self.background_image = self.background_image.reshape(self.n_views, self.height, self.width, self.nb_colors).contiguous()
@@ -235,20 +200,19 @@ class DeviceScene:
     def set_views(self, ij=None, depths=None, colors=None, shade=None, edgeflags=None):
         """Replace per-view arrays (tensors are used as they are when already contiguous on the device)."""
         dev, vd = self.device, self.vertex_dtype
-        conv = lambda a, dt: (a if torch.is_tensor(a) else torch.as_tensor(np.asarray(a))).to(device=dev, dtype=dt).contiguous()
         if depths is not None:
-            d = conv(depths, vd)
+            d = _tensor(depths, dev, vd)
             self.depths = d.reshape(1, -1) if d.dim() == 1 else d
         n, V = self.depths.shape
         self.n_views = n
         if ij is not None:
-            self.ij = conv(ij, vd).reshape(n, V, 2)
+            self.ij = _tensor(ij, dev, vd).reshape(n, V, 2)
         if colors is not None:
-            self.colors = conv(colors, vd).reshape(n, V, -1)
+            self.colors = _tensor(colors, dev, vd).reshape(n, V, -1)
         if shade is not None:
-            self.shade = conv(shade, vd).reshape(n, V)
+            self.shade = _tensor(shade, dev, vd).reshape(n, V)
         if edgeflags is not None:
-            self.edgeflags = conv(edgeflags, torch.uint8).reshape(n, -1, 3)
+            self.edgeflags = _tensor(edgeflags, dev, torch.uint8).reshape(n, -1, 3)
         self.nb_colors = int(self.colors.shape[2])
 
     @property
@@ -256,12 +220,10 @@ class DeviceScene:
         return int(self.faces.shape[0])
 
     def zero_grads(self):
-        vd, pd, dev = self.vertex_dtype, self.pixel_dtype, self.device
-        g = dict(
+        return dict(
             ij_b=torch.zeros_like(self.ij), colors_b=torch.zeros_like(self.colors), shade_b=torch.zeros_like(self.shade),
             uv_b=torch.zeros_like(self.uv), texture_b=None if self.texture is None else torch.zeros_like(self.texture),
         )  # fmt: skip
-        return g
 
     def c_struct(self, grads=None):
         s = _SceneC()
@@ -284,6 +246,11 @@ class DeviceScene:
         return s
 
 
+# What the workspace of a HipRasterizer holds the forward state of; the tensors are kept alive with it (the launches that read them may
+# still be queued).  fused: a fit step -- its forward raster has already back-propagated through the tiles without edges and kept no owner ids.
+_Forward = namedtuple("_Forward", "scene sigma antialiase_error obs image err_buffer generation fused weights")
+
+
 class HipRasterizer:
     """Owns the device workspace of one scene shape and runs renderScene / renderScene_B on it.
 
@@ -303,6 +270,9 @@ class HipRasterizer:
         self.device = _resolve_device(device)
         self.poll_every = int(poll_every)
         self.generation = 0
+        self.alloc_count = 0  # a captured HIP graph holds the OLD workspace address: see GraphedStep
+        self._polls = 0  # calls of poll_status
+        self._weights_cache = None  # (source tensor, its version, converted): the same tensor again, unchanged, is not converted again
         self._alloc(pool_pairs)
 
     def _alloc(self, pool_pairs):
@@ -319,22 +289,15 @@ class HipRasterizer:
         self._forwards = 0
         self._checked = False
         self._pool_cap = None
-        self._last = None
+        self._last = None  # the _Forward whose state the workspace holds
         self._loss_cache = None  # (the background-loss table belongs to one (observation, background, clamp) of one workspace)
-        self.alloc_count = getattr(self, "alloc_count", 0) + 1  # a captured HIP graph holds the OLD workspace address: see GraphedStep
+        self.alloc_count += 1
 
     @classmethod
     def for_scene(cls, ds, pool_pairs=0):
         return cls(ds.nb_triangles, ds.height, ds.width, ds.nb_colors, ds.n_views, ds.device, pool_pairs)
 
     # ---- status ------------------------------------------------------------------------------------------------------
-
-    def _capacity(self, sc):
-        if self._pool_cap is None:
-            cap = C.c_ulonglong(0)
-            _check(lib().deodr_hip_workspace_pool_pairs(C.byref(sc), self.nbytes, C.byref(cap)))
-            self._pool_cap = int(cap.value)
-        return self._pool_cap
 
     def _inspect_poll(self, sc):
         """Look at the last completed asynchronous copy of the status block (never waits)."""
@@ -345,22 +308,31 @@ class HipRasterizer:
         needed, errors = int(self._status_host[_STATUS_NEEDED]) & 0xFFFFFFFF, int(self._status_host[_STATUS_ERRORS])
         if errors:
             raise RuntimeError("deodr_hip: " + scene_error_message(errors))
-        if needed > self._capacity(sc):
+        if self._pool_cap is None:
+            cap = C.c_ulonglong(0)
+            _check(lib().deodr_hip_workspace_pool_pairs(C.byref(sc), self.nbytes, C.byref(cap)))
+            self._pool_cap = int(cap.value)
+        if needed > self._pool_cap:
             self._alloc(max(2 * needed, 1024))
             raise RuntimeError(
                 f"deodr_hip: the spill pool of the workspace overflowed ({needed} pairs needed): frames rendered since the last "
                 "check were incomplete; the workspace has been regrown, render again"
             )
 
+    def _copy_status(self, due):
+        """Queue an asynchronous copy of the status block, and the event that tells when it has landed, behind what was just launched --
+        when one is `due`, none is in flight and the stream is not being captured.  -> whether a copy was queued"""
+        if not due or self._status_event is not None or torch.cuda.is_current_stream_capturing():
+            return False
+        self._status_host.copy_(self._status_words, non_blocking=True)
+        self._status_event = torch.cuda.Event()
+        self._status_event.record()
+        return True
+
     def _poll(self):
-        """Queue an asynchronous copy of the status block behind the forward that was just launched."""
+        """A forward was just launched: copy the status block after each of the first two, then after every ``poll_every``-th."""
         self._forwards += 1
-        if torch.cuda.is_current_stream_capturing():
-            return
-        if self._status_event is None and (self._forwards <= 2 or self._forwards % self.poll_every == 0):
-            self._status_host.copy_(self._status_words, non_blocking=True)
-            self._status_event = torch.cuda.Event()
-            self._status_event.record()
+        self._copy_status(self._forwards <= 2 or self._forwards % self.poll_every == 0)
 
     def poll_status(self):
         """For callers that launch this workspace's kernels without going through :meth:`render` & co (a captured HIP graph being
@@ -368,26 +340,21 @@ class HipRasterizer:
         forward since the previous look overflowed the spill pool (the workspace is regrown: capture again) or met invalid indices."""
         if self._last is None:
             return
-        self._inspect_poll(self._last[0].c_struct())
-        self._polls = getattr(self, "_polls", 0) + 1
-        if self._status_event is None and (self._polls - 1) % max(self.poll_every, 1) == 0:  # (a copy + event per replay is ~13 us of a ~200 us iteration)
-            self._forwards = max(self._forwards, 2)
-            self._status_host.copy_(self._status_words, non_blocking=True)
-            self._status_event = torch.cuda.Event()
-            self._status_event.record()
+        self._inspect_poll(self._last.scene.c_struct())
+        self._polls += 1
+        if self._copy_status((self._polls - 1) % max(self.poll_every, 1) == 0):  # (a copy + event per replay is ~13 us of a ~200 us iteration)
+            self._forwards = max(self._forwards, 2)  # (the forwards of a replayed graph: past "each of the first two")
 
     def status(self, ds):
         """Synchronous check: -> (overflowed, needed_pairs, scene_error_bits)."""
-        sc = ds.c_struct()
         over, need, errs = C.c_int(0), C.c_ulonglong(0), C.c_int(0)
         with torch.cuda.device(self.device):
-            _check(lib().deodr_hip_workspace_status(C.byref(sc), _ptr(self.workspace), self.nbytes, _stream(self.device), C.byref(over),
+            _check(lib().deodr_hip_workspace_status(C.byref(ds.c_struct()), _ptr(self.workspace), self.nbytes, _stream(self.device), C.byref(over),
                                                     C.byref(need), C.byref(errs)))  # fmt: skip
         return bool(over.value), int(need.value), int(errs.value)
 
     def _check_scene(self, ds):
-        n, H, W, Cc = ds.n_views, ds.height, ds.width, ds.nb_colors
-        if (ds.nb_triangles, H, W, Cc, n) != self.dims:
+        if (ds.nb_triangles, ds.height, ds.width, ds.nb_colors, ds.n_views) != self.dims:
             raise ValueError("scene shape differs from the workspace shape")
         if ds.device != self.device:
             raise ValueError(f"scene lives on {ds.device}, the workspace on {self.device}")
@@ -403,25 +370,25 @@ class HipRasterizer:
                 raise ValueError("out= buffers must be contiguous pixel-dtype tensors [n,H,W,C] / [n,H,W] on the scene's device")
         return image, z
 
-    def _run_checked(self, ds, launch, check_overflow):
-        """Launch a forward; with a synchronous check, regrow the workspace and repeat until nothing spills."""
-        sync = check_overflow is True or (check_overflow is None and not self._checked)
+    def _until_it_fits(self, ds, launch):
+        """`launch()` something that runs a forward, check synchronously, regrow the workspace and repeat until nothing spills;
+        -> what the last `launch()` returned"""
         for _attempt in range(16):
-            launch()
-            if not sync:
-                self._poll()
-                return
+            result = launch()
             over, need, errs = self.status(ds)
             self._checked = True
             if errs:
                 raise RuntimeError("deodr_hip: " + scene_error_message(errs))
             if not over:
-                self._forwards += 1
-                return
-            self._alloc(max(2 * need, 1024))  # regrow (zero-filled) and render again
-            self._checked = True
+                return result
+            self._alloc(max(2 * need, 1024))  # regrow (zero-filled) and launch again
         # the pool doubles every time: this is not a scene that needs more room, something is wrong
         raise RuntimeError("deodr_hip: the spill pool still overflows after 16 regrows")
+
+    def _stamp(self, ds, sigma, antialiase_error, obs, image, err_buffer=None, fused=False, weights=None):
+        """The workspace now holds the forward state of these: a new generation."""
+        self.generation += 1
+        self._last = _Forward(ds, float(sigma), bool(antialiase_error), obs, image, err_buffer, self.generation, fused, weights)
 
     # ---- calls -------------------------------------------------------------------------------------------------------
 
@@ -446,9 +413,13 @@ class HipRasterizer:
                 _check(lib().deodr_hip_render_scene(C.byref(sc), _ptr(image), _ptr(z), float(sigma), int(antialiase_error), _ptr(obs_t),
                                                     _ptr(err), _ptr(self.workspace), self.nbytes, _stream(self.device)))  # fmt: skip
 
-            self._run_checked(ds, launch, check_overflow)
-        self.generation += 1
-        self._last = (ds, float(sigma), bool(antialiase_error), obs_t, image, err, self.generation, False)
+            if check_overflow is True or (check_overflow is None and not self._checked):
+                self._until_it_fits(ds, launch)
+                self._forwards += 1
+            else:
+                launch()
+                self._poll()
+        self._stamp(ds, sigma, antialiase_error, obs_t, image, err)
         return (image, z, err) if antialiase_error else (image, z)
 
     def _loss_table(self, ds, sc, obs_t, options, weights_t=None):
@@ -456,7 +427,7 @@ class HipRasterizer:
         key = (obs_t.data_ptr(), obs_t._version, tuple(obs_t.shape), None if ds.background_color is None else (ds.background_color.data_ptr(), ds.background_color._version),
                None if ds.background_image is None else (ds.background_image.data_ptr(), ds.background_image._version),
                (options.clamp, options.clamp_lo, options.clamp_hi), None if weights_t is None else (weights_t.data_ptr(), weights_t._version))  # fmt: skip
-        cache = getattr(self, "_loss_cache", None)
+        cache = self._loss_cache
         if cache is None or cache[0] != key:
             L = lib()
             n = int(L.deodr_hip_fit_loss_bytes(ds.height, ds.width, ds.n_views)) // 8
@@ -471,12 +442,12 @@ class HipRasterizer:
         """per-pixel weights of a fit step as the library wants them: [n_views, H, W], the scene's device and pixel dtype, contiguous (a tensor
         that already is all that is passed through untouched, so that the loss-table cache recognises it); [H, W] is expanded over the views"""
         n, H, W = ds.n_views, ds.height, ds.width
-        w = weights if torch.is_tensor(weights) else torch.as_tensor(np.asarray(weights))
+        w = _as_tensor(weights)
         if tuple(w.shape) not in ((n, H, W), (H, W)):
             raise ValueError(f"weights must have shape [{n}, {H}, {W}] (one value per view and pixel) or [{H}, {W}], not {list(w.shape)}")
         if w.dim() == 3 and w.device == ds.device and w.dtype == ds.pixel_dtype and w.is_contiguous():
             return w
-        cached = getattr(self, "_weights_cache", None)  # (source tensor, its version, converted): the same tensor again, unchanged, is not converted again
+        cached = self._weights_cache
         if torch.is_tensor(weights) and cached is not None and cached[0] is weights and cached[1] == weights._version:
             return cached[2]
         w_t = w.to(device=ds.device, dtype=ds.pixel_dtype).expand(n, H, W).contiguous()
@@ -503,15 +474,10 @@ class HipRasterizer:
         0 are still rendered, only their residual vanishes.  Pass a contiguous tensor in the scene's pixel dtype on its device to avoid a
         conversion.  Any other shape raises ``ValueError``."""
         self._check_scene(ds)
-        n, H, W, Cc = ds.n_views, ds.height, ds.width, ds.nb_colors
-        pd = ds.pixel_dtype
         weights_t = None if weights is None else self._fit_weights(ds, weights)
         with torch.cuda.device(self.device):
             image, z = self._frame(ds, out)
-            obs_t = obs if torch.is_tensor(obs) else torch.as_tensor(np.asarray(obs))
-            obs_t = obs_t.to(device=ds.device, dtype=pd)
-            if tuple(obs_t.shape) != (n, H, W, Cc) or not obs_t.is_contiguous():  # pass [n,H,W,C] to avoid this copy
-                obs_t = obs_t.expand(n, H, W, Cc).contiguous()
+            obs_t = _pixels(obs, ds)
             if check_overflow or (check_overflow is None and not self._checked):
                 self.render(ds, sigma, out=(image, z), check_overflow=True)  # sizes the spill pool once (synchronises)
             if grads is None:
@@ -539,9 +505,7 @@ class HipRasterizer:
                 _check(lib().deodr_hip_render_scene_fit_ex(C.byref(sc), _ptr(image), _ptr(z), float(sigma), _ptr(obs_t), int(bool(clear_grads)),
                                                            C.byref(options), _ptr(self.workspace), self.nbytes, _stream(self.device)))  # fmt: skip
             self._poll()
-        self.generation += 1
-        self._last = (ds, float(sigma), False, obs_t, image, None, self.generation, True)
-        self._last_weights = weights_t  # (kept alive like the observation: the launches above may still be queued)
+        self._stamp(ds, sigma, False, obs_t, image, fused=True, weights=weights_t)
         return image, z, grads
 
     def render_backward(self, ds, image_b=None, err_buffer_b=None, grads=None, have_forward_state=True, residual_obs=None,
@@ -557,8 +521,9 @@ class HipRasterizer:
         self._check_scene(ds)
         if self._last is None:
             raise RuntimeError("deodr_hip: render_backward called before any render on this workspace")
-        last_ds, last_sigma, aa, obs_t, image, _err, gen, fused = self._last
-        sigma = last_sigma if sigma is None else float(sigma)
+        last = self._last
+        aa, obs_t, image = last.antialiase_error, last.obs, last.image
+        sigma = last.sigma if sigma is None else float(sigma)
         n, H, W, Cc = ds.n_views, ds.height, ds.width, ds.nb_colors
         pd = ds.pixel_dtype
         with torch.cuda.device(self.device):
@@ -569,13 +534,10 @@ class HipRasterizer:
             if aa:
                 eb = _on(err_buffer_b, ds.device, pd, (n, H, W), "err_buffer_b")
             elif residual_obs is not None:
-                obs_t = residual_obs if torch.is_tensor(residual_obs) else torch.as_tensor(np.asarray(residual_obs))
-                obs_t = obs_t.to(device=ds.device, dtype=pd)
-                if tuple(obs_t.shape) != (n, H, W, Cc) or not obs_t.is_contiguous():  # pass [n,H,W,C] to avoid this copy
-                    obs_t = obs_t.expand(n, H, W, Cc).contiguous()
+                obs_t = _pixels(residual_obs, ds)
             else:
                 ib = _on(image_b, ds.device, pd, (n, H, W, Cc), "image_b")
-            state = have_forward_state and last_ds is ds and not fused and (generation is None or generation == gen)
+            state = have_forward_state and last.scene is ds and not last.fused and (generation is None or generation == last.generation)
             if not state and not aa and residual_obs is not None:
                 # residual mode forms 2 (image - obs) inside the kernels from the frame of THIS forward; the frame at hand belongs to
                 # another one (a later forward used the workspace, or the last call was a fit step): render again, then the state --
@@ -588,9 +550,19 @@ class HipRasterizer:
                 # a forward ran inside the call: the workspace now holds the state of THIS (ds, sigma), stamped anew so that
                 # any other pending adjoint sees that its own forward state is gone
                 self._poll()
-                self.generation += 1
-                self._last = (ds, sigma, aa, obs_t, image, _err, self.generation, False)
+                self._stamp(ds, sigma, aa, obs_t, image, last.err_buffer)
         return grads
+
+    def render_backward_of(self, ds, sigma, image, antialiase_error=False, obs=None, image_b=None, err_buffer_b=None):
+        """Adjoint of a frame the CALLER hands in (``image`` [n,H,W,C], of ``ds`` at ``sigma``; ``obs`` with ``antialiase_error``) without
+        a forward on this workspace before: the forward state is recomputed inside the call, which synchronises and makes sure that
+        nothing spilled (regrow + repeat otherwise).  -> fresh gradient tensors."""
+
+        def launch():
+            self._stamp(ds, sigma, antialiase_error, obs, image)
+            return self.render_backward(ds, image_b=image_b, err_buffer_b=err_buffer_b, have_forward_state=False)
+
+        return self._until_it_fits(ds, launch)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -601,6 +573,11 @@ def _np(a, dtype=None):
     if torch.is_tensor(a):
         a = a.detach().cpu().numpy()
     return np.ascontiguousarray(a, dtype=dtype)
+
+
+def _f64(a):
+    """an array of the caller as a float64 CPU tensor (None stays None)"""
+    return None if a is None else torch.as_tensor(_np(a, np.float64))
 
 
 _ctx_cache = {}
@@ -639,11 +616,9 @@ def renderSceneCpp(scene, sigma, image, z_buffer, antialiase_error=False, obs=No
         check_scene(scene, image, z_buffer, False, None, antialiase_error, obs, err_buffer)
     ds = _device_scene(scene, image.shape[2])
     r = _rasterizer_for(ds)
-    out = r.render(ds, sigma, bool(antialiase_error), None if obs is None else torch.as_tensor(_np(obs, np.float64)), check_overflow=True)
-    image[...] = out[0][0].cpu().numpy()
-    z_buffer[...] = out[1][0].cpu().numpy()
-    if antialiase_error:
-        err_buffer[...] = out[2][0].cpu().numpy()
+    out = r.render(ds, sigma, bool(antialiase_error), _f64(obs), check_overflow=True)
+    for buffer, rendered in zip((image, z_buffer, err_buffer), out):  # (out has the error buffer with antialiase_error only)
+        buffer[...] = rendered[0].cpu().numpy()
 
 
 def renderSceneBCpp(scene, sigma, image, z_buffer, image_b=None, antialiase_error=False, obs=None, err_buffer=None, err_buffer_b=None,
@@ -657,30 +632,11 @@ def renderSceneBCpp(scene, sigma, image, z_buffer, image_b=None, antialiase_erro
         check_scene(scene, image, z_buffer, True, image_b, antialiase_error, obs, err_buffer)
     if scene.perspective_correct:
         raise RuntimeError("backward gradient propagation not supported yet with perspective_correct=True")
-    nb_colors = image.shape[2]
-    ds = _device_scene(scene, nb_colors)
-    r = _rasterizer_for(ds)
-    dev = ds.device
-    img_t = torch.as_tensor(_np(image, np.float64)).to(dev)[None]
-    obs_t = None if obs is None else torch.as_tensor(_np(obs, np.float64)).to(dev)[None].contiguous()
-    for _attempt in range(16):
-        r.generation += 1
-        r._last = (ds, float(sigma), bool(antialiase_error), obs_t, img_t, None, r.generation, False)
-        if antialiase_error:
-            g = r.render_backward(ds, err_buffer_b=torch.as_tensor(_np(err_buffer_b, np.float64)), have_forward_state=False)
-        else:
-            g = r.render_backward(ds, image_b=torch.as_tensor(_np(image_b, np.float64)), have_forward_state=False)
-        over, need, errs = r.status(ds)  # the call is synchronous anyway: the stateless forward must not have spilled
-        if errs:
-            raise RuntimeError("deodr_hip: " + scene_error_message(errs))
-        if not over:
-            break
-        r._alloc(max(2 * need, 1024))
-    else:
-        raise RuntimeError("deodr_hip: the spill pool still overflows after 16 regrows")
+    ds = _device_scene(scene, image.shape[2])
+    obs_t = None if obs is None else _f64(obs).to(ds.device)[None].contiguous()
+    # stateless: the forward state is recomputed inside (the seed that does not belong to the mode is ignored); synchronous anyway
+    g = _rasterizer_for(ds).render_backward_of(ds, sigma, _f64(image).to(ds.device)[None], bool(antialiase_error), obs_t, _f64(image_b), _f64(err_buffer_b))
     for name in ("uv_b", "ij_b", "shade_b", "colors_b", "texture_b"):
-        new = g[name]
-        old = getattr(scene, name, None)
-        if new is None or old is None or _count(old) == 0:
-            continue
-        setattr(scene, name, _np(old, np.float64) + new.cpu().numpy().reshape(np.shape(old)))
+        new, old = g[name], getattr(scene, name, None)
+        if new is not None and old is not None and _count(old):
+            setattr(scene, name, _np(old, np.float64) + new.cpu().numpy().reshape(np.shape(old)))

@@ -14,7 +14,7 @@ import types
 import numpy as np
 import torch
 
-from deodr_amd import Scene2D, hip_renderer
+from deodr_amd import Scene2D, _abi, hip_renderer
 
 
 def _view(ptr, shape, dtype):
@@ -37,6 +37,21 @@ class FakeLib:
         self.error = b""
         self.calls = dict(render_scene=0, render_scene_b=0, render_scene_fit=0)
         self.generic = 0
+
+    def __getattribute__(self, name):
+        """every entry point is called as through ctypes: as many arguments as the header declares, each one convertible to its type"""
+        f = object.__getattribute__(self, name)
+        if not name.startswith("deodr_hip_"):
+            return f
+        argtypes = _abi.HEADER.functions[name][1]
+
+        def checked(*args):
+            assert len(args) == len(argtypes), name
+            for argtype, arg in zip(argtypes, args):
+                argtype.from_param(arg)  # (raises what the real call would)
+            return f(*args)
+
+        return checked
 
     # ---- the small entry points ------------------------------------------------------------------------------------------------
     def deodr_hip_abi_version(self):

@@ -2,7 +2,9 @@
 
 import ctypes as C
 import os
+import re
 import subprocess
+import tempfile
 
 import numpy as np
 
@@ -37,6 +39,38 @@ def lib():
 def dispatch_lib():
     """tests/sim/libdispatch_sim.so: the instance rules and tables of deodr_amd/csrc/dr_dispatch.h (tests/sim/dispatch_sim.cpp)."""
     return _built(os.path.join(HERE, "sim", "dispatch_sim.cpp"), os.path.join(HERE, "sim", "libdispatch_sim.so"), ("dr_dispatch.h",))
+
+
+def declared_symbols():
+    """the deodr_hip_* names include/deodr_hip.h declares, found with one regular expression (not with deodr_amd/_abi.py)"""
+    text = open(os.path.join(HERE, "..", "include", "deodr_hip.h")).read()
+    return sorted(set(re.findall(r"\b(deodr_hip_\w+)\s*\(", re.sub(r"/\*.*?\*/", "", text, flags=re.S))))
+
+
+def struct_layout(struct, fields):
+    """(sizeof, [(offsetof, sizeof) of every field]) of a struct of include/deodr_hip.h as the host C compiler lays it out: a few
+    generated lines of C that include the header -- the judge of the ctypes mirrors that does not go through deodr_amd/_abi.py"""
+    lines = "".join(f'\tprintf("%zu %zu\\n", offsetof({struct}, {f}), sizeof((({struct} *)0)->{f}));\n' for f in fields)
+    source = f'#include <stdio.h>\n#include "deodr_hip.h"\nint main(void)\n{{\n\tprintf("%zu\\n", sizeof({struct}));\n{lines}\treturn 0;\n}}\n'
+    with tempfile.TemporaryDirectory() as tmp:
+        with open(os.path.join(tmp, "layout.c"), "w") as f:
+            f.write(source)
+        subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(HERE, "..", "include"), "-o", os.path.join(tmp, "layout"),
+                        os.path.join(tmp, "layout.c")], check=True)  # fmt: skip
+        out = subprocess.run([os.path.join(tmp, "layout")], check=True, capture_output=True, text=True).stdout.split("\n")
+    return int(out[0]), [tuple(map(int, line.split())) for line in out[1 : 1 + len(fields)]]
+
+
+def assert_layout_is_the_compilers(mirror, struct, fields):
+    """`mirror` (a ctypes.Structure that deodr_amd/_abi.py derived from the header) has the fields `fields` = [(name, ctypes type)], and
+    its size and every field's offset and size are those the C compiler gives `struct` -- the reader that does not share _abi's parser"""
+    assert [n for n, _ in fields] == [f[0] for f in mirror._fields_]
+    size, layout = struct_layout(struct, [n for n, _ in fields])
+    assert size == C.sizeof(mirror)
+    for (name, expected), (offset, field_size) in zip(fields, layout):
+        field = getattr(mirror, name)
+        assert (field.offset, field.size) == (offset, field_size), name
+        assert C.sizeof(expected) == field_size, name
 
 
 def sim_scene(s, sigma=1.0):

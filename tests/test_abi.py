@@ -1,28 +1,32 @@
 """CPU-only checks of the drop-in boundary: the C-ABI library builds, loads and exports what include/*.h declares."""
 
 import ctypes
-import os
-import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# DeodrHipScene of include/deodr_hip.h, written out (DeodrHipFitOptions: tests/test_fit_weights_host.py): the ctypes mirror derived from the
+# header (deodr_amd/_abi.py) and the layout the C compiler gives the struct (tests/sim_util.py) must both agree with it
+SCENE_FIELDS = (
+    [(n, ctypes.c_void_p) for n in ("faces", "faces_uv", "textured", "shaded", "depths", "ij", "shade", "colors", "edgeflags", "uv")]
+    + [(n, ctypes.c_void_p) for n in ("texture", "background_image", "background_color")]
+    + [(n, ctypes.c_void_p) for n in ("uv_b", "ij_b", "shade_b", "colors_b", "texture_b")]
+    + [(n, ctypes.c_int) for n in ("nb_triangles", "nb_vertices", "nb_uv", "height", "width", "nb_colors", "texture_height", "texture_width")]
+    + [(n, ctypes.c_int) for n in ("clockwise", "backface_culling", "strict_edge", "perspective_correct", "integer_pixel_centers")]
+    + [(n, ctypes.c_int) for n in ("n_views", "vertex_dtype", "pixel_dtype", "deterministic")]
+)
 
 
 @pytest.fixture(scope="module")
 def hip_lib():
     import __graft_entry__ as g
+    from deodr_amd import _abi
 
-    return ctypes.CDLL(g.build_hip())
-
-
-def declared_symbols():
-    text = open(os.path.join(ROOT, "include", "deodr_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(deodr_hip_\w+)\s*\(", text)))
+    return _abi.bind(ctypes.CDLL(g.build_hip()))
 
 
 def test_every_declared_symbol_is_exported(hip_lib):
+    from sim_util import declared_symbols
+
     names = declared_symbols()
     assert {"deodr_hip_render_scene", "deodr_hip_render_scene_b", "deodr_hip_workspace_bytes"} <= set(names)
     for n in names:
@@ -33,8 +37,6 @@ def test_abi_version_and_workspace_query(hip_lib):
     from deodr_amd import hip_renderer as hr
 
     assert hip_lib.deodr_hip_abi_version() == hr.ABI_VERSION
-    hip_lib.deodr_hip_workspace_bytes.restype = ctypes.c_size_t
-    hip_lib.deodr_hip_workspace_bytes.argtypes = [ctypes.c_int] * 5 + [ctypes.c_size_t]
     one = hip_lib.deodr_hip_workspace_bytes(20000, 1024, 1024, 4, 1, 0)
     assert 20e6 < one < 200e6  # tens of MB per 1024^2 / 20k-triangle view
     assert hip_lib.deodr_hip_workspace_bytes(20000, 1024, 1024, 4, 8, 0) == 8 * one
@@ -46,17 +48,15 @@ def test_python_struct_matches_header():
     """Field order of the ctypes mirror == field order of DeodrHipScene in the header."""
     from deodr_amd.hip_renderer import _SceneC
 
-    text = open(os.path.join(ROOT, "include", "deodr_hip.h")).read()
-    body = text[text.index("typedef struct DeodrHipScene") : text.index("} DeodrHipScene;")]
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = []
-    for decl in body.split("{", 1)[1].split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        names = re.sub(r"^(const\s+)?(void|uint32_t|uint8_t|int)\s*", "", decl)
-        fields += [n.strip().lstrip("*").strip() for n in names.split(",")]
-    assert fields == [f[0] for f in _SceneC._fields_]
+    assert [n for n, _ in SCENE_FIELDS] == [f[0] for f in _SceneC._fields_]
+    assert [t for _, t in SCENE_FIELDS] == [f[1] for f in _SceneC._fields_]
+
+
+def test_scene_struct_agrees_with_the_c_compiler():
+    from deodr_amd.hip_renderer import _SceneC
+    from sim_util import assert_layout_is_the_compilers
+
+    assert_layout_is_the_compilers(_SceneC, "DeodrHipScene", SCENE_FIELDS)
 
 
 def test_no_cpu_fallback_without_gpu():
@@ -74,6 +74,7 @@ def test_no_cpu_fallback_without_gpu():
 def test_scene_checks_of_the_boundary_reject_before_any_launch():
     """The host-side part of checkSceneValid (H.h:2664-2715, 2924, 810) at the C ABI: every bad argument is refused with a message,
     before any HIP call -- the pointers below are never dereferenced, no GPU is needed."""
+    from deodr_amd import _abi as abi
     from deodr_amd import hip_renderer as hr
 
     L = hr.lib()
@@ -99,8 +100,7 @@ def test_scene_checks_of_the_boundary_reject_before_any_launch():
         rc = L.deodr_hip_render_scene_b(ctypes.byref(sc), fake, fake, image_b, 1.0, 0, None, None, None, fake, 1 << 30, 1, None)
         return rc, L.deodr_hip_last_error().decode()
 
-    text = open(os.path.join(ROOT, "include", "deodr_hip.h")).read()
-    assert re.search(r"DEODR_HIP_F32\s*=?\s*0", text) and re.search(r"DEODR_HIP_F64\s*=?\s*1", text)
+    assert (abi.HEADER.defines["DEODR_HIP_F32"], abi.HEADER.defines["DEODR_HIP_F64"]) == (0, 1)
     assert forward(None) == (1, "scene == NULL")
     for n in arrays:
         assert forward(scene(**{n: None})) == (1, "scene array == NULL"), n

@@ -3,7 +3,6 @@ ABI version, and the shape checks of the Python layers -- which must refuse a wr
 
 import ctypes
 import os
-import re
 import types
 
 import numpy as np
@@ -13,35 +12,19 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
-C_TYPES = {
-    "const double *": ctypes.c_void_p, "double *": ctypes.c_void_p, "void *": ctypes.c_void_p, "const void *": ctypes.c_void_p,
-    "uint32_t *": ctypes.c_void_p, "int": ctypes.c_int, "double": ctypes.c_double, "uint32_t": ctypes.c_uint32,
-}  # fmt: skip
-
-
-def header_fit_options():
-    """[(field name, ctypes type)] of DeodrHipFitOptions as include/deodr_hip.h declares it"""
-    text = open(os.path.join(ROOT, "include", "deodr_hip.h")).read()
-    body = text[text.index("typedef struct DeodrHipFitOptions") : text.index("} DeodrHipFitOptions;")]
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S).split("{", 1)[1]
-    fields = []
-    for decl in body.split(";"):
-        decl = " ".join(decl.split())
-        if not decl:
-            continue
-        m = re.match(r"^((?:const )?\w+ ?\*?)\s*(.*)$", decl)
-        base = m.group(1).strip()
-        for name in m.group(2).split(","):
-            name = name.strip()
-            typ = base + " *" if name.startswith("*") and not base.endswith("*") else base
-            fields.append((name.lstrip("* "), C_TYPES[typ]))
-    return fields
+# DeodrHipFitOptions of include/deodr_hip.h, written out
+FIT_OPTIONS_FIELDS = [("tile_loss", ctypes.c_void_p), ("loss", ctypes.c_void_p), ("loss_scratch", ctypes.c_void_p), ("clamp", ctypes.c_int),
+                      ("clamp_lo", ctypes.c_double), ("clamp_hi", ctypes.c_double), ("done_flag", ctypes.c_void_p), ("done_value", ctypes.c_uint32),
+                      ("weights", ctypes.c_void_p)]  # fmt: skip
 
 
 def test_fit_options_struct_matches_header():
+    """names, order, types, offsets and size of the ctypes mirror (derived from the header by deodr_amd/_abi.py) == the list above and == what
+    the C compiler makes of the header"""
     from deodr_amd.hip_renderer import _FitOptionsC
+    from sim_util import assert_layout_is_the_compilers
 
-    fields = header_fit_options()
+    fields = FIT_OPTIONS_FIELDS
     assert [n for n, _ in fields] == [n for n, _ in _FitOptionsC._fields_]
     assert [t for _, t in fields] == [t for _, t in _FitOptionsC._fields_]
     assert fields[-1] == ("weights", ctypes.c_void_p)  # appended: a zero-initialised struct of an older caller means "no weights"
@@ -50,14 +33,15 @@ def test_fit_options_struct_matches_header():
     for name, _ in fields:
         assert getattr(mirror, name).offset == getattr(_FitOptionsC, name).offset, name
     assert _FitOptionsC().weights is None
+    assert_layout_is_the_compilers(_FitOptionsC, "DeodrHipFitOptions", fields)
 
 
 def test_abi_version_13_on_both_sides():
     import __graft_entry__ as g
+    from deodr_amd import _abi
     from deodr_amd import hip_renderer as hr
 
-    text = open(os.path.join(ROOT, "include", "deodr_hip.h")).read()
-    assert int(re.search(r"#define DEODR_HIP_ABI_VERSION (\d+)", text).group(1)) == 13 == hr.ABI_VERSION
+    assert _abi.HEADER.defines["DEODR_HIP_ABI_VERSION"] == 13 == hr.ABI_VERSION
     assert ctypes.CDLL(g.build_hip()).deodr_hip_abi_version() == 13
 
 
@@ -71,7 +55,7 @@ def test_render_fit_refuses_a_wrong_weights_shape_before_the_library(monkeypatch
     cpu = torch.device("cpu")
     ds = types.SimpleNamespace(n_views=2, height=24, width=40, nb_colors=3, nb_triangles=5, device=cpu, pixel_dtype=torch.float32)
     r = hr.HipRasterizer.__new__(hr.HipRasterizer)
-    r.dims, r.device = (5, 24, 40, 3, 2), cpu
+    r.dims, r.device, r._weights_cache = (5, 24, 40, 3, 2), cpu, None  # (all the shape checks and the conversion touch)
     obs = torch.zeros(2, 24, 40, 3)
     for shape in [(2, 24, 40, 3), (2, 24, 40, 1), (3, 24, 40), (40, 24), (2, 40, 24), (24,), ()]:
         with pytest.raises(ValueError, match="weights"):

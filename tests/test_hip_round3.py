@@ -613,7 +613,7 @@ def test_examples_run(capsys):
 
 
 def test_fit_step_loss_from_the_rasterizer_kernels():
-    """deodr_hip_render_scene_fit_loss: sum (image - obs)^2 from the tile walkers + the background table, against the sum over the
+    """deodr_hip_render_scene_fit_ex with a loss: sum (image - obs)^2 from the tile walkers + the background table, against the sum over the
     frame the same call stored -- every tile class (pairs, tiles with edges fused or left to the edge kernel, more than 16 edges, tiny
     frames, frames that are no multiple of the tile), both pixel types, background colour and image, several views, a second step with
     the same table, and the two fall-backs (more than 4 channels, no triangle at all)"""
