@@ -9,7 +9,9 @@ import os
 import re
 import types
 
-HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "deodr_hip.h")
+_INCLUDE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
+HEADER_PATH = os.path.join(_INCLUDE, "deodr_hip.h")
+TEXTURE_HEADER_PATH = os.path.join(_INCLUDE, "deodr_hip_texture.h")  # the companion header (texture estimation), versioned on its own
 
 # C type (without `const`, without spaces around the stars) -> ctypes.  Data pointers are c_void_p: callers pass device addresses (Python
 # ints, c_void_p), None, byref(...) and small ctypes arrays, and c_void_p takes all of them.  int and unsigned long long are only ever
@@ -22,8 +24,11 @@ _CTYPES = {
 }  # fmt: skip
 
 
+_parsing = "include/deodr_hip.h"  # the header parse() is working on, for its error texts
+
+
 def _refuse(what, declaration):
-    raise ImportError(f"include/deodr_hip.h: {what}: `{' '.join(declaration.split())}`")
+    raise ImportError(f"{_parsing}: {what}: `{' '.join(declaration.split())}`")
 
 
 def _ctype(c_type, ctypes_of, declaration):
@@ -39,8 +44,11 @@ def _typed_name(text, ctypes_of, declaration):
     return _ctype(c_type + ("*" if array else ""), ctypes_of, declaration), name
 
 
-def parse(text):
-    """-> namespace(defines {name: int}, structs {name: ctypes.Structure}, functions {name: (restype, [argtypes])}) of a header text"""
+def parse(text, name="include/deodr_hip.h"):
+    """-> namespace(name, defines {name: int}, structs {name: ctypes.Structure}, functions {name: (restype, [argtypes])}) of a header text;
+    ``name``: what the header is called in error texts"""
+    global _parsing
+    _parsing = name
     text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
     text = re.sub(r"#ifdef __cplusplus.*?#endif", " ", text, flags=re.S)  # (the extern "C" braces)
     defines = {name: int(value) for name, value in re.findall(r"^[ \t]*#define[ \t]+(\w+)[ \t]+(-?\d+)[ \t]*$", text, flags=re.M)}
@@ -55,7 +63,7 @@ def parse(text):
             if not all(re.fullmatch(r"\s*\w+\s*", other) for other in others):
                 _refuse("cannot parse", decl)
             fields += [(n.strip(), c_type) for n in [name] + others]
-        structs[m.group(1)] = type(m.group(1), (C.Structure,), {"_fields_": fields, "__doc__": f"include/deodr_hip.h::{m.group(1)}"})
+        structs[m.group(1)] = type(m.group(1), (C.Structure,), {"_fields_": fields, "__doc__": f"{name}::{m.group(1)}"})
         ctypes_of[m.group(1) + "*"] = C.POINTER(structs[m.group(1)])
         return " "
 
@@ -67,14 +75,15 @@ def parse(text):
         restype = None if m.group(1).split() == ["void"] else _ctype(m.group(1), ctypes_of, decl)
         params = [] if m.group(3).split() == ["void"] else m.group(3).split(",")
         functions[m.group(2)] = (restype, [_typed_name(p, ctypes_of, decl)[0] for p in params])
-    return types.SimpleNamespace(defines=defines, structs=structs, functions=functions)
+    return types.SimpleNamespace(name=name, defines=defines, structs=structs, functions=functions)
 
 
 def bind(library, header=None):
     """Set restype / argtypes of every function the header declares on a loaded ``ctypes.CDLL``; -> the library."""
-    for name, (restype, argtypes) in (header or HEADER).functions.items():
+    header = header or HEADER
+    for name, (restype, argtypes) in header.functions.items():
         if not hasattr(library, name):
-            raise ImportError(f"{library._name} does not export {name}, which include/deodr_hip.h declares; rebuild it")
+            raise ImportError(f"{library._name} does not export {name}, which {getattr(header, 'name', 'include/deodr_hip.h')} declares; rebuild it")
         function = getattr(library, name)
         function.restype, function.argtypes = restype, argtypes
     return library
@@ -82,3 +91,5 @@ def bind(library, header=None):
 
 with open(HEADER_PATH) as _f:
     HEADER = parse(_f.read())
+with open(TEXTURE_HEADER_PATH) as _f:
+    TEXTURE_HEADER = parse(_f.read(), "include/deodr_hip_texture.h")

@@ -57,7 +57,9 @@
 
 #include "../../include/deodr_hip.h"
 #include "dr_dispatch.h"
+#include "../../include/deodr_hip_texture.h"
 #include "dr_fititer.h" // <- dr_finalize.h <- dr_backward.h <- dr_backward_generic.h <- dr_forward.h <- dr_forward_generic.h <- dr_setup.h <- dr_workspace.h <- dr_prims.h
+#include "dr_texfit.h"  // texture smoothness + step (include/deodr_hip_texture.h); uses grid_sum of dr_fronthalf.h
 
 using namespace dr;
 using namespace dr::dispatch;
@@ -1217,6 +1219,107 @@ int deodr_hip_depth_residual(const void *image, int pixel_dtype, const double *o
 						   (PixT *)image_b, loss, partials, counter);
 	});
 	return check_hip(hipGetLastError(), "depth_residual launch");
+}
+
+// ---- texture estimation (include/deodr_hip_texture.h, kernels in dr_texfit.h)
+
+int deodr_hip_texture_abi_version(void) { return DEODR_HIP_TEXTURE_ABI_VERSION; }
+
+static int texture_dims(const char *&why, int Ht, int Wt, int C, int pixel_dtype)
+{ // -> number of elements, or 0 with the reason
+	if (Ht < 2 || Wt < 2)
+		why = "texture must be at least 2 x 2";
+	else if (C < 1 || C > DEODR_HIP_MAX_COLORS)
+		why = "nb_colors out of range";
+	else if (pixel_dtype != DEODR_HIP_F32 && pixel_dtype != DEODR_HIP_F64)
+		why = "unknown dtype tag";
+	else if ((unsigned long long)Ht * (unsigned long long)Wt * (unsigned long long)C > (1ull << 30))
+		why = "texture larger than 2^30 elements";
+	else
+		return Ht * Wt * C;
+	return 0;
+}
+
+static bool texture_overlap(const void *a, const void *b, size_t bytes)
+{
+	const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+	return x < y + bytes && y < x + bytes;
+}
+
+size_t deodr_hip_texture_scratch_bytes(int Ht, int Wt, int C)
+{
+	const char *why;
+	return texture_dims(why, Ht, Wt, C, DEODR_HIP_F32) ? 64 + sizeof(double) * TEX_SMOOTH_BLOCKS : 0;
+}
+
+int deodr_hip_texture_smoothness(const void *texture, int Ht, int Wt, int C, int pixel_dtype, double weight, void *gradient, double *energy, void *scratch,
+								 size_t scratch_bytes, void *stream)
+{
+	if (!texture || !gradient || !energy)
+		return fail("texture_smoothness: texture, gradient or energy == NULL");
+	const char *why = "";
+	const int N = texture_dims(why, Ht, Wt, C, pixel_dtype);
+	if (!N)
+		return fail(why);
+	if (!scratch || scratch_bytes < deodr_hip_texture_scratch_bytes(Ht, Wt, C))
+		return fail("texture_smoothness: scratch too small (deodr_hip_texture_scratch_bytes)");
+	const size_t elem = pixel_dtype == DEODR_HIP_F64 ? 8 : 4;
+	if (texture_overlap(texture, gradient, (size_t)N * elem))
+		return fail("texture_smoothness: gradient must not overlap texture");
+	if ((((uintptr_t)texture | (uintptr_t)gradient) & (elem - 1)) || ((uintptr_t)scratch & 7))
+		return fail("texture_smoothness: misaligned pointer");
+	TexSmoothArgs a;
+	a.texture = texture, a.gradient = gradient, a.energy = energy;
+	a.counter = (unsigned *)scratch, a.partials = (double *)((char *)scratch + 64);
+	a.weight = weight, a.Ht = Ht, a.R = Wt * C, a.C = C, a.N = N;
+	const int pieces = N / (int)(16 / elem), want = (pieces + FH_BLOCK - 1) / FH_BLOCK;
+	const dim3 grid((unsigned)(want < 1 ? 1 : (want < TEX_SMOOTH_BLOCKS ? want : TEX_SMOOTH_BLOCKS)));
+	switch (pixel_dtype)
+	{
+	case DEODR_HIP_F32:
+		hipLaunchKernelGGL(texture_smoothness_kernel<float>, grid, dim3(FH_BLOCK), 0, (hipStream_t)stream, a);
+		break;
+	case DEODR_HIP_F64:
+		hipLaunchKernelGGL(texture_smoothness_kernel<double>, grid, dim3(FH_BLOCK), 0, (hipStream_t)stream, a);
+		break;
+	}
+	return check_hip(hipGetLastError(), "texture_smoothness launch");
+}
+
+int deodr_hip_texture_step(void *texture, void *speed, const void *gradient, int Ht, int Wt, int C, int pixel_dtype, double factor, double step_max,
+						   double inertia, double damping, int clamp, double clamp_lo, double clamp_hi, void *stream)
+{
+	if (!texture || !speed || !gradient)
+		return fail("texture_step: texture, speed or gradient == NULL");
+	const char *why = "";
+	const int N = texture_dims(why, Ht, Wt, C, pixel_dtype);
+	if (!N)
+		return fail(why);
+	const size_t elem = pixel_dtype == DEODR_HIP_F64 ? 8 : 4;
+	if (texture_overlap(texture, gradient, (size_t)N * elem))
+		return fail("texture_step: gradient must not overlap texture");
+	if (texture_overlap(texture, speed, (size_t)N * elem) || texture_overlap(speed, gradient, (size_t)N * elem))
+		return fail("texture_step: speed must not overlap texture or gradient");
+	if (((uintptr_t)texture | (uintptr_t)speed | (uintptr_t)gradient) & (elem - 1))
+		return fail("texture_step: misaligned pointer");
+	if (clamp && !(clamp_lo <= clamp_hi))
+		return fail("texture_step: clamp_lo > clamp_hi");
+	TexStepArgs a;
+	a.texture = texture, a.speed = speed, a.gradient = gradient;
+	a.factor = factor, a.step_max = step_max, a.inertia = inertia, a.damping = damping, a.clamp_lo = clamp_lo, a.clamp_hi = clamp_hi;
+	a.clamp = clamp != 0, a.N = N;
+	const int pieces = N / (int)(16 / elem), want = (pieces + FH_BLOCK - 1) / FH_BLOCK;
+	const dim3 grid((unsigned)(want < 1 ? 1 : (want < TEX_STEP_BLOCKS ? want : TEX_STEP_BLOCKS)));
+	switch (pixel_dtype)
+	{
+	case DEODR_HIP_F32:
+		hipLaunchKernelGGL(texture_step_kernel<float>, grid, dim3(FH_BLOCK), 0, (hipStream_t)stream, a);
+		break;
+	case DEODR_HIP_F64:
+		hipLaunchKernelGGL(texture_step_kernel<double>, grid, dim3(FH_BLOCK), 0, (hipStream_t)stream, a);
+		break;
+	}
+	return check_hip(hipGetLastError(), "texture_step launch");
 }
 
 #ifdef DR_WAVE_TRACE

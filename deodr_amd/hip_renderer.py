@@ -26,6 +26,8 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libdeodr_hip.so")
 _H = _abi.HEADER  # the structs, the constants and (in lib()) the signatures are read from include/deodr_hip.h: deodr_amd/_abi.py
 _SceneC, _FitOptionsC, ABI_VERSION = _H.structs["DeodrHipScene"], _H.structs["DeodrHipFitOptions"], _H.defines["DEODR_HIP_ABI_VERSION"]
 ERR_FACES, ERR_FACES_UV, ERR_NO_TEXTURE, ERR_INTERNAL, ERR_DET_RANGE = (_H.defines["DEODR_HIP_ERR_" + n] for n in "FACES FACES_UV NO_TEXTURE INTERNAL DET_RANGE".split())
+_HT = _abi.TEXTURE_HEADER  # the companion header include/deodr_hip_texture.h (texture estimation), bound onto the same library
+TEXTURE_ABI_VERSION, MAX_COLORS = _HT.defines["DEODR_HIP_TEXTURE_ABI_VERSION"], _H.defines["DEODR_HIP_MAX_COLORS"]
 # words of the 64-byte status block at the start of the workspace
 _STATUS_NEEDED, _STATUS_ERRORS = _H.defines["DEODR_HIP_STATUS_WORD_NEEDED_PAIRS"], _H.defines["DEODR_HIP_STATUS_WORD_SCENE_ERRORS"]
 
@@ -44,6 +46,9 @@ def lib():
         L = C.CDLL(LIB_PATH)
         if L.deodr_hip_abi_version() != ABI_VERSION:
             raise ImportError("libdeodr_hip.so ABI version mismatch; rebuild it")
+        _abi.bind(L, _HT)  # (a library that lacks one of its symbols is refused by name)
+        if L.deodr_hip_texture_abi_version() != TEXTURE_ABI_VERSION:
+            raise ImportError("libdeodr_hip.so texture ABI version mismatch (include/deodr_hip_texture.h); rebuild it")
         _lib = _abi.bind(L)
     return _lib
 
@@ -150,6 +155,79 @@ def _pixels(t, ds):
     return t if tuple(t.shape) == shape else t.expand(shape).contiguous()  # pass [n,H,W,C] to avoid this copy
 
 
+# ---- texture estimation (include/deodr_hip_texture.h) ---------------------------------------------------------------------------------
+
+_texture_scratch_cache = {}  # (device, stream) -> the zero-filled scratch of deodr_hip_texture_smoothness
+
+
+def _texture_args(what, texture, others):
+    """checks before the library is called: a [Ht,Wt,C] float32 / float64 contiguous ROCm tensor, `others` {name: tensor} of its shape, dtype and device"""
+    if not torch.is_tensor(texture) or not texture.is_cuda:
+        raise ValueError(f"{what}: texture must be a ROCm tensor (deodr_amd has no CPU path)")
+    if texture.dim() != 3 or texture.shape[0] < 2 or texture.shape[1] < 2 or not 1 <= texture.shape[2] <= MAX_COLORS:
+        raise ValueError(f"{what}: texture must have shape [Ht >= 2, Wt >= 2, 1 <= C <= {MAX_COLORS}], not {list(texture.shape)}")
+    if texture.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"{what}: texture must be float32 or float64, not {texture.dtype}")
+    for name, t in [("texture", texture)] + list(others.items()):
+        if not torch.is_tensor(t) or t.device != texture.device or t.dtype != texture.dtype or tuple(t.shape) != tuple(texture.shape):
+            raise ValueError(f"{what}: {name} must be a tensor of the texture's shape, dtype and device")
+        if not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be contiguous")
+    return (int(texture.shape[0]), int(texture.shape[1]), int(texture.shape[2]), 1 if texture.dtype == torch.float64 else 0)
+
+
+def texture_scratch(device):
+    """the scratch of :func:`texture_smoothness`, zero-filled as the library wants it once; for a caller that keeps its own (one per stream in use)"""
+    with torch.cuda.device(device):
+        return torch.zeros(int(lib().deodr_hip_texture_scratch_bytes(2, 2, 1)), dtype=torch.uint8, device=device)  # (the size does not depend on the texture)
+
+
+def texture_smoothness(texture, gradient, weight, energy_out=None, scratch=None):
+    """``deodr_hip_texture_smoothness``: ``E = 0.5 weight (sum of the squared differences of x- and y-neighbours)`` of ``texture`` [Ht,Wt,C], free
+    boundary; ``dE/dtexture`` is ACCUMULATED into ``gradient`` (same shape and dtype -- typically the rasterizer's ``texture_b``); -> ``energy_out``
+    (a float64 device tensor of one element, allocated when None) holding E.  Deterministic; asynchronous on the current stream.  ``scratch``: a
+    :func:`texture_scratch` of the caller's (a fitter whose step is captured in a graph keeps one); None: one per device and stream, made at the first call."""
+    dims = _texture_args("texture_smoothness", texture, {"gradient": gradient})
+    dev = texture.device
+    with torch.cuda.device(dev):
+        if energy_out is None:
+            energy_out = torch.empty(1, dtype=torch.float64, device=dev)
+        if energy_out.dtype != torch.float64 or energy_out.device != dev or energy_out.numel() != 1:
+            raise ValueError("texture_smoothness: energy_out must be a float64 tensor of one element on the texture's device")
+        key = (dev, torch.cuda.current_stream(dev).cuda_stream)
+        if scratch is None:
+            scratch = _texture_scratch_cache.get(key)
+        elif scratch.device != dev or scratch.dtype != torch.uint8 or not scratch.is_contiguous():
+            raise ValueError("texture_smoothness: scratch must be a texture_scratch() of the texture's device")
+        if scratch is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("texture_smoothness: pass scratch= (texture_scratch) when capturing a graph: none exists for this stream yet")
+            scratch = _texture_scratch_cache[key] = texture_scratch(dev)
+        _check(lib().deodr_hip_texture_smoothness(_ptr(texture), *dims, float(weight), _ptr(gradient), _ptr(energy_out), _ptr(scratch), scratch.numel(),
+                                                  _stream(dev)))  # fmt: skip
+    return energy_out
+
+
+def _touched(t):
+    """a kernel of the library has written `t` in place: tell torch (version counters are how conversions of `t` are recognised as stale)"""
+    bump = getattr(torch.autograd.graph, "increment_version", None)
+    if bump is not None:
+        bump(t)
+
+
+def texture_step(texture, speed, gradient, factor, step_max=None, inertia=0.0, damping=0.0, clamp=None):
+    """``deodr_hip_texture_step``: ``speed = (1 - damping) (inertia speed + (1 - inertia) clip(-factor gradient, +-step_max))``, ``texture += speed``,
+    IN PLACE on ``texture`` and ``speed`` (``_Momentum.update`` for a pixel-typed array); ``clamp`` = (lo, hi): the texture is clipped to it and the
+    speed set to 0 where it clipped.  ``gradient`` is only read.  Asynchronous on the current stream."""
+    dims = _texture_args("texture_step", texture, {"speed": speed, "gradient": gradient})
+    dev = texture.device
+    lo, hi = (0.0, 0.0) if clamp is None else (float(clamp[0]), float(clamp[1]))
+    with torch.cuda.device(dev):
+        _check(lib().deodr_hip_texture_step(_ptr(texture), _ptr(speed), _ptr(gradient), *dims, float(factor), 0.0 if step_max is None else float(step_max),
+                                            float(inertia), float(damping), int(clamp is not None), lo, hi, _stream(dev)))  # fmt: skip
+    _touched(texture), _touched(speed)
+
+
 class DeviceScene:
     """The arrays of ``struct Scene`` (reference H.h:56-90) as contiguous ROCm tensors, for ``n_views`` views of one mesh.
 
@@ -171,11 +249,13 @@ class DeviceScene:
         self.faces_uv = _tensor(np.asarray(faces_uv).astype(np.int64) if not torch.is_tensor(faces_uv) else faces_uv, dev, torch.int32)
         self.textured = _tensor(textured, dev, torch.uint8)
         self.shaded = _tensor(shaded, dev, torch.uint8)
-        self.uv = _tensor(uv, dev, vertex_dtype).reshape(-1, 2)
+        self.uv = _tensor(uv, dev, vertex_dtype).reshape(-1, 2).detach()
         self.height, self.width = int(height), int(width)
         self.flags = dict(clockwise=bool(clockwise), backface_culling=bool(backface_culling), strict_edge=bool(strict_edge),
                           perspective_correct=bool(perspective_correct), integer_pixel_centers=bool(integer_pixel_centers))  # fmt: skip
-        self.texture = _tensor(texture, dev, pixel_dtype) if _count(texture) > 0 else None
+        self.texture = _tensor(texture, dev, pixel_dtype).detach() if _count(texture) > 0 else None
+        self._texture_given = self._uv_given = None  # (tensor last handed to set_texture / set_uv, its version): see there
+        self._texture_buffer = self._uv_buffer = None
         self.background_color = None if background_color is None else _tensor(background_color, dev, pixel_dtype).reshape(-1)
         self.background_image = None if background_image is None else _tensor(background_image, dev, pixel_dtype)
         self.set_views(ij, depths, colors, shade, edgeflags)
@@ -214,6 +294,35 @@ class DeviceScene:
         if edgeflags is not None:
             self.edgeflags = _tensor(edgeflags, dev, torch.uint8).reshape(n, -1, 3)
         self.nb_colors = int(self.colors.shape[2])
+
+    def _set_shared(self, name, t, dtype, shape):
+        given = getattr(self, f"_{name}_given")
+        if torch.is_tensor(t) and given is not None and given[0] is t and given[1] == t._version:
+            return  # the same tensor, unchanged since: what the scene holds is its value
+        source, t = t, _as_tensor(t).detach()
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"set_{name}: expected shape {list(shape)}, got {list(t.shape)} (a new shape needs a new DeviceScene)")
+        if t.device == self.device and t.dtype == dtype and t.is_contiguous():
+            setattr(self, name, t)
+        else:
+            if getattr(self, f"_{name}_buffer") is None:
+                setattr(self, f"_{name}_buffer", torch.empty(shape, dtype=dtype, device=self.device))
+            getattr(self, f"_{name}_buffer").copy_(t)
+            setattr(self, name, getattr(self, f"_{name}_buffer"))
+        setattr(self, f"_{name}_given", (source, t._version))
+
+    def set_texture(self, t):
+        """The next calls read the value ``t`` [Ht,Wt,C] has NOW: the tensor itself when it is contiguous, on the scene's device and in the pixel dtype
+        (later in-place updates -- an optimiser's, :func:`texture_step`'s -- are then seen without another call); anything else is converted, once per
+        call, into a buffer the scene keeps for that purpose (the same tensor again, unchanged by torch's count, is not converted again).  The shape
+        cannot change, and a scene built without a texture cannot get one."""
+        if self.texture is None:
+            raise ValueError("set_texture: the scene was built without a texture")
+        self._set_shared("texture", t, self.pixel_dtype, self.texture.shape)
+
+    def set_uv(self, uv):
+        """The same for the texture coordinates [Vuv,2] (vertex dtype)."""
+        self._set_shared("uv", uv, self.vertex_dtype, self.uv.shape)
 
     @property
     def nb_triangles(self):

@@ -671,3 +671,189 @@ class MeshRGBFitterWithPoseMultiFrame(MeshRGBFitterWithPose):
     def step(self):
         energy, image = self.step_device()
         return float(energy.detach()), image.to(torch.float64).cpu().numpy(), self.diff_image(image).cpu().numpy()
+
+
+# ---- texture estimation -----------------------------------------------------------------------------------------------------------------
+
+
+def texture_smoothness_torch(texture, gradient, weight):
+    """``deodr_hip_texture_smoothness`` as torch ops, for tensors the library does not take (CPU tensors: the CPU suite): -> the energy
+    ``0.5 weight (sum of the squared differences of x- and y-neighbours)`` of ``texture`` [Ht,Wt,C] (float64 scalar tensor); its gradient
+    ``weight (deg t - sum of the neighbours)`` is accumulated into ``gradient`` in place.  Arithmetic in float64, one rounding to the storage type."""
+    t = texture.detach().to(torch.float64)
+    dx, dy = t[:, 1:] - t[:, :-1], t[1:] - t[:-1]
+    g = torch.zeros_like(t)
+    g[:, 1:] += dx
+    g[:, :-1] -= dx
+    g[1:] += dy
+    g[:-1] -= dy
+    gradient.copy_((gradient.to(torch.float64) + weight * g).to(gradient.dtype))
+    return 0.5 * weight * ((dx * dx).sum() + (dy * dy).sum())
+
+
+def texture_step_torch(texture, speed, gradient, factor, step_max=None, inertia=0.0, damping=0.0, clamp=None):
+    """``deodr_hip_texture_step`` as torch ops (:meth:`_Momentum.update` plus the clamp), in place on ``texture`` and ``speed``; float64 arithmetic"""
+    step = -factor * gradient.to(torch.float64)
+    if step_max is not None and step_max > 0:
+        step = step.clamp(-step_max, step_max)
+    s = (1 - damping) * (inertia * speed.to(torch.float64) + (1 - inertia) * step)
+    t = texture.detach().to(torch.float64) + s
+    if clamp is not None:
+        clipped = (t < clamp[0]) | (t > clamp[1])
+        t, s = t.clamp(clamp[0], clamp[1]), torch.where(clipped, torch.zeros_like(s), s)  # (the momentum does not keep pushing into the wall)
+    texture.detach().copy_(t.to(texture.dtype))
+    speed.copy_(s.to(speed.dtype))
+
+
+class MeshTextureFitterMultiFrame:
+    """Fit the TEXTURE of a mesh of known shape to ``n`` calibrated views: geometry, poses / cameras and light are given (for example by a
+    :class:`MeshRGBFitterWithPoseMultiFrame` run), the unknown is ``texture`` [Ht,Wt,C].  With the geometry fixed the image is linear in the texels:
+    the energy ``sum(weights * (image - observation)**2) + 0.5 smoothness (squared differences of neighbouring texels)`` is a linear least-squares
+    problem, minimised by the momentum descent of the other fitters; texels no view sees are in-painted by the smoothness term.
+
+    ``poses`` = (euler angles [n,3], translations [n,3]) of the mesh in front of the fitters' camera (the convention of
+    :class:`MeshRGBFitterWithPoseMultiFrame`: the vertices are centred, rotated and moved), or ``cameras`` = a :class:`DeviceCamera` of ``n`` views (or a
+    list of cameras) looking at the vertices as they are.
+
+    Projection, silhouette flags and luminosity are computed ONCE, in :meth:`set_images`.  An iteration on the device is then a fixed sequence: the
+    rasterizer's one-call fit step (image, data energy, ``texture_b``), ``deodr_hip_texture_smoothness`` into the same ``texture_b``,
+    ``deodr_hip_texture_step`` in place -- no autograd graph, no tensor rebound, so ``GraphedStep(fitter)`` replays it as it is.  On CPU tensors the same
+    two formulas run as torch ops around ``Scene3DDevice._rasterize_l2`` under autograd (which has no CPU implementation in the product: tests put a
+    checker-backed stand-in there)."""
+
+    step_factor_texture = 0.5
+
+    def __init__(self, vertices, faces, uv, faces_uv, texture_init, light_directional, light_ambient, poses=None, cameras=None, smoothness=0.1,
+                 inertia=0.9, damping=0.05, clamp=(0.0, 1.0), step_max=None, clockwise=False, sigma=1.0, device="cuda", pixel_dtype=torch.float32):  # fmt: skip
+        if (poses is None) == (cameras is None):
+            raise ValueError("MeshTextureFitterMultiFrame: give either poses = (euler [n,3], translations [n,3]) or cameras")
+        self.device, self.pixel_dtype = torch.device(device), pixel_dtype
+        self.smoothness, self.inertia, self.damping, self.clamp, self.step_max = float(smoothness), inertia, damping, clamp, step_max
+        v0 = np.asarray(vertices, dtype=np.float64)
+        self.texture_init = torch.as_tensor(np.asarray(texture_init, dtype=np.float64), device=self.device).to(pixel_dtype).contiguous()
+        if self.texture_init.dim() != 3:
+            raise ValueError("texture_init must have shape [Ht, Wt, C]")
+        self.mesh = DeviceMesh(np.asarray(faces), v0, clockwise=clockwise, uv=uv, faces_uv=faces_uv, texture=None, device=self.device)
+        self.scene = Scene3DDevice(sigma=sigma, pixel_dtype=pixel_dtype)
+        self.scene.set_mesh(self.mesh)
+        self.scene.set_light(light_directional, light_ambient)
+        self.poses, self.cameras = poses, cameras
+        self.object_center, self.object_radius = v0.mean(axis=0), float(np.max(np.std(v0, axis=0)))
+        self.camera_center = self.object_center + np.array([0, 0, 6]) * self.object_radius  # (MeshRGBFitterWithPoseMultiFrame's)
+        self.weights = self._views = None
+        self.reset()
+
+    def reset(self):
+        self.texture = self.texture_init.clone()
+        self.mesh.texture = self.texture  # (the scene renders the value this tensor has at every call; it is updated in place)
+        self.momentum = _Momentum(self.inertia, self.damping)
+        self.momentum.speed["texture"] = torch.zeros_like(self.texture)
+        self.iter = 0
+
+    def set_background_color(self, background_color):
+        self.scene.set_background_color(background_color)
+
+    def set_images(self, images, focal=None, distortion=None, weights=None):
+        """``images`` [n,H,W,C]: one photograph per view.  ``weights`` [H,W] or [n,H,W], ``>= 0`` (or None): per-pixel weights of the squared residual --
+        a mask on what is not the object, a view to leave out (0 everywhere)."""
+        from . import hip_renderer
+
+        imgs = np.stack([np.asarray(im, dtype=np.float64) for im in images])
+        n, height, width, nb_colors = imgs.shape
+        if nb_colors != int(self.texture.shape[2]):
+            raise ValueError(f"the images have {nb_colors} channels, the texture {int(self.texture.shape[2])}")
+        dev, mesh = self.device, self.mesh
+        if self.cameras is not None:
+            cam = self.cameras if isinstance(self.cameras, DeviceCamera) else DeviceCamera.stack(list(self.cameras), dev)
+            posed = mesh.vertices
+        else:
+            euler, translation = (np.atleast_2d(np.asarray(a, dtype=np.float64)) for a in self.poses)
+            focal = 2 * width if focal is None else focal
+            rot = np.diag([1.0, -1.0, -1.0])
+            intrinsic = np.array([[focal, 0, width / 2], [0, focal, height / 2], [0, 0, 1.0]])
+            extrinsic = np.column_stack((rot, -rot.T.dot(self.camera_center)))
+            cam = DeviceCamera(np.broadcast_to(extrinsic, (n, 3, 4)).copy(), np.broadcast_to(intrinsic, (n, 3, 3)).copy(), height, width, distortion, dev)
+            q = torch.as_tensor(np.broadcast_to(np.asarray([_quat_from_euler_zyx(e) for e in euler]), (n, 4)).copy(), device=dev)
+            t = torch.as_tensor(np.broadcast_to(translation, (n, 3)).copy(), device=dev)
+            centred = mesh.vertices - mesh.vertices.mean(dim=0, keepdim=True)
+            posed = qrot(q / q.norm(dim=-1, keepdim=True), centred[None].expand(n, -1, -1)) + t[:, None, :]
+        if cam.n_views != n or (cam.height, cam.width) != (height, width):
+            raise ValueError(f"{n} images of {height} x {width} for {cam.n_views} cameras of {cam.height} x {cam.width}")
+        with torch.no_grad():  # the front half of an iteration, once: nothing in it depends on the texture
+            ij, depths = cam.project_points(posed)
+            lum = self.scene.vertices_luminosity(posed)
+            lum = lum[None].expand(n, -1) if lum.dim() == 1 else lum
+            flags = mesh.topology.edge_on_silhouette(ij) if self.scene.sigma > 0 else torch.zeros((n, mesh.nb_faces, 3), dtype=torch.uint8, device=dev)
+        colors = torch.zeros((n, mesh.nb_vertices, nb_colors), dtype=torch.float64, device=dev)
+        self.camera = cam
+        self._views = dict(ij=ij.contiguous(), depths=depths.contiguous(), colors=colors, shade=lum.contiguous(), edgeflags=flags.contiguous())
+        self.mesh_image = torch.as_tensor(imgs, device=dev)
+        self._obs = self.mesh_image.to(self.pixel_dtype).contiguous()
+        if weights is not None:
+            w = np.asarray(weights.detach().cpu() if torch.is_tensor(weights) else weights, dtype=np.float64)
+            if w.shape not in ((height, width), (n, height, width)):
+                raise ValueError(f"weights must have shape [{height}, {width}] or [{n}, {height}, {width}] (one value per pixel), not {list(w.shape)}")
+            weights = torch.as_tensor(np.array(np.broadcast_to(w, (n, height, width))), device=dev).to(self.pixel_dtype).contiguous()
+        self.weights = weights
+        z = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=dev)
+        self.e_data, self.e_smooth, self._energy = z(1), z(1), z(1)
+        self._direct = None
+        if self.device.type == "cuda":
+            if (self.scene.background_image is None) == (self.scene.background_color is None):
+                raise BaseException("You need to provide either a background image or background color")
+            ds, r = self.scene._rasterizer(n, height, width, nb_colors, True, True)
+            pd = self.pixel_dtype
+            out = (torch.empty((n, height, width, nb_colors), dtype=pd, device=dev), torch.empty((n, height, width), dtype=pd, device=dev))
+            ds.set_views(**self._views)
+            ds.set_texture(self.texture)
+            self._direct = (ds, r, ds.zero_grads(), out)
+            self._scratch = hip_renderer.texture_scratch(dev)  # (its own: a captured step replays on the addresses it was captured with)
+        self.iter = 0
+
+    def _gradient(self):
+        """-> (texture_b = d (data + smoothness) / d texture, image [n,H,W,C]); the two energies land in ``self.e_data`` / ``self.e_smooth``"""
+        from . import hip_renderer
+
+        v = self._views
+        if self._direct is not None:
+            ds, r, grads, out = self._direct
+            ds.set_views(**v)  # (no copies: the tensors are used as they are; another render of the scene may have rebound them)
+            ds.set_texture(self.texture)
+            image, _z, _g = r.render_fit(ds, self._obs, self.scene.sigma, grads=grads, out=out, clear_grads=True, loss_out=self.e_data, weights=self.weights)
+            texture_b = grads["texture_b"]
+            hip_renderer.texture_smoothness(self.texture, texture_b, self.smoothness, self.e_smooth, scratch=self._scratch)
+            return texture_b, image
+        leaf = self.texture.detach().requires_grad_(True)
+        extra = {} if self.weights is None else {"weights": self.weights}
+        loss, image = self.scene._rasterize_l2(self.camera, v["ij"], v["depths"], v["colors"], v["shade"], True, True, self._obs, texture=leaf, **extra)
+        (texture_b,) = torch.autograd.grad(loss, leaf)
+        texture_b = texture_b.to(self.texture.dtype).contiguous()
+        self.e_data.copy_(loss.detach().reshape(1))
+        self.e_smooth.copy_(texture_smoothness_torch(self.texture, texture_b, self.smoothness).reshape(1))
+        return texture_b, image.detach()
+
+    def energy(self):
+        """-> data energy + smoothness energy of the current texture (a device tensor of one element); nothing is updated"""
+        assert self._views is not None, "call set_images first"
+        self._gradient()
+        return self.e_data + self.e_smooth
+
+    def step_device(self):
+        """One iteration on the device -> (energy BEFORE the update [1], image [n,H,W,C]).  ``self.texture`` and the momentum speed are updated in place,
+        and the returned tensors are the same storage every step (clone what is to be kept); :meth:`step` converts at once."""
+        from . import hip_renderer
+
+        assert self._views is not None, "call set_images first"
+        texture_b, image = self._gradient()
+        speed = self.momentum.speed["texture"]
+        update = hip_renderer.texture_step if self._direct is not None else texture_step_torch
+        update(self.texture, speed, texture_b, self.step_factor_texture, self.step_max, self.inertia, self.damping, self.clamp)
+        torch.add(self.e_data, self.e_smooth, out=self._energy)
+        self.iter += 1
+        return self._energy, image
+
+    def step(self):
+        """-> (energy, images [n,H,W,C], squared difference per pixel [n,H,W]) as a float and NumPy arrays (synchronises)"""
+        energy, image = self.step_device()
+        image = image.to(torch.float64)
+        return float(energy[0]), image.cpu().numpy(), ((image - self.mesh_image) ** 2).sum(dim=-1).cpu().numpy()

@@ -11,6 +11,7 @@ from ..mesh_fitter import (  # noqa: F401
     MeshDepthFitterPytorchOptim,
     MeshRGBFitterWithPose,
     MeshRGBFitterWithPoseMultiFrame,
+    MeshTextureFitterMultiFrame,
 )
 from ..mesh_fitter import qrot  # noqa: F401  (deodr/pytorch/mesh_fitter_pytorch.py:26-31)
 from ..scene3d import DeviceCamera, DeviceMesh, LaplacianRigidEnergyDevice, MeshTopology, Scene3DDevice  # noqa: F401  (the batched classes, n views per call)

@@ -17,6 +17,14 @@ import torch
 from ..hip_renderer import DeviceScene, HipRasterizer, _count, _resolve_device
 
 
+def _set_shared(device_scene, texture, uv):
+    """the texture / texture coordinates a render is to read (None: what the scene holds)"""
+    if texture is not None:
+        device_scene.set_texture(texture)
+    if uv is not None:
+        device_scene.set_uv(uv)
+
+
 def _to_np(a):
     return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
 
@@ -120,45 +128,59 @@ TorchDifferentiableRender2D = TorchDifferentiableRenderer2DFunc.apply
 
 
 class TorchDifferentiableRenderViewsFunc(torch.autograd.Function):
-    """n_views views in one launch: (ij [n,V,2], colors [n,V,C]) -> image [n,H,W,C] on ``device_scene``'s GPU."""
+    """n_views views in one launch: (ij [n,V,2], colors [n,V,C][, texture [Ht,Wt,C], uv [Vuv,2]]) -> image [n,H,W,C] on ``device_scene``'s GPU.
+    ``texture`` / ``uv`` (optional): rendered with these values (``DeviceScene.set_texture`` / ``set_uv``) and differentiated, their gradients summed
+    over the views; not given: the scene's own, no gradient, the launches of always."""
 
     @staticmethod
-    def forward(ctx, ij, colors, device_scene, rasterizer, sigma):
+    def forward(ctx, ij, colors, device_scene, rasterizer, sigma, texture=None, uv=None):
         device_scene.set_views(ij=ij.detach(), colors=colors.detach())
+        _set_shared(device_scene, texture, uv)
         image, _ = rasterizer.render(device_scene, sigma)
         ctx.ds, ctx.r, ctx.in_dtypes, ctx.generation, ctx.sigma = device_scene, rasterizer, (ij.dtype, colors.dtype), rasterizer.generation, sigma
-        ctx.save_for_backward(ij, colors)
+        held = lambda given: None if given is None else given[0]  # (what the scene read them from when they are not inputs: restored in backward)
+        ctx.held = (held(device_scene._texture_given) if texture is None else None, held(device_scene._uv_given) if uv is None else None)
+        ctx.given = (texture is not None, uv is not None)
+        ctx.save_for_backward(ij, colors, *[t for t in (texture, uv) if t is not None])
         return image
 
     @staticmethod
     def backward(ctx, image_b):
+        ij, colors, *rest = ctx.saved_tensors
+        texture, uv = (rest.pop(0) if given else None for given in ctx.given)
         if ctx.r.generation != ctx.generation:  # another forward has used the scene / workspace since: restore the inputs
-            ij, colors = ctx.saved_tensors
             ctx.ds.set_views(ij=ij.detach(), colors=colors.detach())
+            _set_shared(ctx.ds, ctx.held[0] if texture is None else texture, ctx.held[1] if uv is None else uv)
         g = ctx.r.render_backward(ctx.ds, image_b=image_b, generation=ctx.generation, sigma=ctx.sigma)
-        return g["ij_b"].to(ctx.in_dtypes[0]), g["colors_b"].to(ctx.in_dtypes[1]), None, None, None
+        shared_b = (None if texture is None else g["texture_b"].to(texture.dtype), None if uv is None else g["uv_b"].to(uv.dtype))
+        return (g["ij_b"].to(ctx.in_dtypes[0]), g["colors_b"].to(ctx.in_dtypes[1]), None, None, None) + shared_b
 
 
-def TorchDifferentiableRenderViews(ij, colors, device_scene, rasterizer, sigma=1.0):
-    return TorchDifferentiableRenderViewsFunc.apply(ij, colors, device_scene, rasterizer, sigma)
+def TorchDifferentiableRenderViews(ij, colors, device_scene, rasterizer, sigma=1.0, texture=None, uv=None):
+    shared = () if texture is None and uv is None else (texture, uv)
+    return TorchDifferentiableRenderViewsFunc.apply(ij, colors, device_scene, rasterizer, sigma, *shared)
 
 
 class TorchRenderViewsL2LossFunc(torch.autograd.Function):
-    """sum((render(ij, colors) - obs)**2) over ``n_views`` views as ONE op: (ij [n,V,2], colors [n,V,C]) -> scalar loss.
+    """sum((render(ij, colors) - obs)**2) over ``n_views`` views as ONE op: (ij [n,V,2], colors [n,V,C][, texture, uv]) -> scalar loss.
 
     What the reference's fitters write as ``image = render(...); loss = ((image - obs) ** 2).sum(); loss.backward()``
     (deodr/pytorch/mesh_fitter_pytorch.py, dr.py:701-740): here the forward is one ``deodr_hip_render_scene_fit`` call that
     renders AND back-propagates the residual (the gradient of the loss w.r.t. the image is known as soon as a pixel is
     resolved), so ``backward`` only scales the stored gradients.  ``image`` and ``z_buffer`` of the last call are kept on
     the context owner (``rasterizer.last_fit``) for display.  ``weights`` ([n,H,W] or [H,W], or None): the loss is
-    ``sum(weights[..., None] * (image - obs)**2)``, see :meth:`HipRasterizer.render_fit` (no gradient with respect to them)."""
+    ``sum(weights[..., None] * (image - obs)**2)``, see :meth:`HipRasterizer.render_fit` (no gradient with respect to them).
+    ``texture`` / ``uv`` (optional): as in :class:`TorchDifferentiableRenderViewsFunc`."""
 
     @staticmethod
-    def forward(ctx, ij, colors, obs, device_scene, rasterizer, sigma, weights=None):
+    def forward(ctx, ij, colors, obs, device_scene, rasterizer, sigma, weights=None, texture=None, uv=None):
         device_scene.set_views(ij=ij.detach(), colors=colors.detach())
+        _set_shared(device_scene, texture, uv)
         image, z, g = rasterizer.render_fit(device_scene, obs, sigma, clear_grads=False, weights=weights)
         rasterizer.last_fit = (image, z)
-        ctx.save_for_backward(g["ij_b"].to(ij.dtype), g["colors_b"].to(colors.dtype))
+        ctx.given = (texture is not None, uv is not None)
+        shared_b = [g[k].to(t.dtype) for k, t in (("texture_b", texture), ("uv_b", uv)) if t is not None]
+        ctx.save_for_backward(g["ij_b"].to(ij.dtype), g["colors_b"].to(colors.dtype), *shared_b)
         r2 = (image.double() - obs.to(image.device).double()) ** 2
         if weights is not None:
             r2 = r2 * torch.as_tensor(weights).to(image.device).double()[..., None]
@@ -166,12 +188,14 @@ class TorchRenderViewsL2LossFunc(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, loss_b):
-        ij_b, colors_b = ctx.saved_tensors
-        return loss_b.to(ij_b.dtype) * ij_b, loss_b.to(colors_b.dtype) * colors_b, None, None, None, None, None
+        ij_b, colors_b, *rest = ctx.saved_tensors
+        shared_b = tuple(loss_b.to(rest[0].dtype) * rest.pop(0) if given else None for given in ctx.given)
+        return (loss_b.to(ij_b.dtype) * ij_b, loss_b.to(colors_b.dtype) * colors_b, None, None, None, None, None) + shared_b
 
 
-def TorchRenderViewsL2Loss(ij, colors, obs, device_scene, rasterizer, sigma=1.0, weights=None):
-    return TorchRenderViewsL2LossFunc.apply(ij, colors, obs, device_scene, rasterizer, sigma, weights)
+def TorchRenderViewsL2Loss(ij, colors, obs, device_scene, rasterizer, sigma=1.0, weights=None, texture=None, uv=None):
+    shared = () if texture is None and uv is None else (texture, uv)
+    return TorchRenderViewsL2LossFunc.apply(ij, colors, obs, device_scene, rasterizer, sigma, weights, *shared)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -208,54 +208,77 @@ class LaplacianRigidEnergyDevice:
         return 0.5 * (diff * grad).sum(), grad
 
 
+def _set_shared(device_scene, texture, uv):
+    """the texture / texture coordinates a render is to read (None: what the scene holds)"""
+    if texture is not None:
+        device_scene.set_texture(texture)
+    if uv is not None:
+        device_scene.set_uv(uv)
+
+
 class RenderViewsFunc(torch.autograd.Function):
-    """(ij [n,V,2], colors [n,V,C], shade [n,V]) -> image [n,H,W,C]: the HIP rasterizer with gradients for all three.
+    """(ij [n,V,2], colors [n,V,C], shade [n,V][, texture [Ht,Wt,C], uv [Vuv,2]]) -> image [n,H,W,C]: the HIP rasterizer with gradients for all of them.
 
     ``depths`` [n,V] and ``edgeflags`` [n,T,3] are inputs without gradient (dr.py:1017: the z buffer is not differentiated; the
     flags select which edges are antialiased).  ALL five per-view arrays are saved: the DeviceScene / workspace are shared by
     every render of a Scene3DDevice, and when another render has used them since (two cameras, or two vertex sets, in one loss)
-    the adjoint rebuilds this forward's state from its own inputs, not from whatever the scene holds now."""
+    the adjoint rebuilds this forward's state from its own inputs, not from whatever the scene holds now.
+    ``texture`` / ``uv`` (optional, trailing): rendered with these values (``DeviceScene.set_texture`` / ``set_uv``) and differentiated -- their
+    gradients are summed over the views, as the library delivers them.  Not given: the scene's own, no gradient, the same launches as ever."""
 
     @staticmethod
-    def forward(ctx, ij, colors, shade, depths, edgeflags, device_scene, rasterizer, sigma):
+    def forward(ctx, ij, colors, shade, depths, edgeflags, device_scene, rasterizer, sigma, texture=None, uv=None):
         device_scene.set_views(ij=ij.detach(), colors=colors.detach(), shade=shade.detach(), depths=depths.detach(), edgeflags=edgeflags)
+        _set_shared(device_scene, texture, uv)
         image, z = rasterizer.render(device_scene, sigma)
         ctx.ds, ctx.r, ctx.sigma, ctx.generation = device_scene, rasterizer, sigma, rasterizer.generation
-        ctx.save_for_backward(ij, colors, shade, depths, edgeflags)
+        # what the scene read its texture and uv from when they are not inputs of this op (restored like the views, see backward)
+        held = lambda given: None if given is None else given[0]
+        ctx.held = (held(device_scene._texture_given) if texture is None else None, held(device_scene._uv_given) if uv is None else None)
+        ctx.given = (texture is not None, uv is not None)
+        ctx.save_for_backward(ij, colors, shade, depths, edgeflags, *[t for t in (texture, uv) if t is not None])
         ctx.mark_non_differentiable(z)
         return image, z
 
     @staticmethod
     def backward(ctx, image_b, _z_b):
-        ij, colors, shade, depths, edgeflags = ctx.saved_tensors
+        ij, colors, shade, depths, edgeflags, *rest = ctx.saved_tensors
+        texture, uv = (rest.pop(0) if given else None for given in ctx.given)
         if ctx.r.generation != ctx.generation:  # another forward used the scene since: restore this one's inputs
             ctx.ds.set_views(ij=ij.detach(), colors=colors.detach(), shade=shade.detach(), depths=depths.detach(), edgeflags=edgeflags)
+            _set_shared(ctx.ds, ctx.held[0] if texture is None else texture, ctx.held[1] if uv is None else uv)
         g = ctx.r.render_backward(ctx.ds, image_b=image_b, generation=ctx.generation, sigma=ctx.sigma)
         ctx.uv_b, ctx.texture_b = g["uv_b"], g["texture_b"]
-        return g["ij_b"].to(ij.dtype), g["colors_b"].to(colors.dtype), g["shade_b"].to(shade.dtype), None, None, None, None, None
+        shared_b = (None if texture is None else g["texture_b"].to(texture.dtype), None if uv is None else g["uv_b"].to(uv.dtype))
+        return (g["ij_b"].to(ij.dtype), g["colors_b"].to(colors.dtype), g["shade_b"].to(shade.dtype), None, None, None, None, None) + shared_b
 
 
 class RenderViewsL2Func(torch.autograd.Function):
-    """(ij, colors, shade) -> (sum over the views of sum (image - obs)^2, image): ONE ``deodr_hip_render_scene_fit`` call renders and
+    """(ij, colors, shade[, texture, uv]) -> (sum over the views of sum (image - obs)^2, image): ONE ``deodr_hip_render_scene_fit`` call renders and
     back-propagates the residual (the forward raster knows dL/dimage of a pixel the moment the pixel is resolved), so the backward
     of this op only scales the gradients the forward left.  What the reference's colour fitters write as render, subtract, square,
     sum, render_backward (deodr/mesh_fitter.py:296-318, 533-548) -- half the rasterizer time of the two-call path.
-    ``weights`` ([n,H,W] or None): per-pixel weights of the squared residual (:meth:`HipRasterizer.render_fit`); not differentiated."""
+    ``weights`` ([n,H,W] or None): per-pixel weights of the squared residual (:meth:`HipRasterizer.render_fit`); not differentiated.
+    ``texture`` / ``uv`` (optional, trailing): as in :class:`RenderViewsFunc`."""
 
     @staticmethod
-    def forward(ctx, ij, colors, shade, depths, edgeflags, obs, device_scene, rasterizer, sigma, weights=None):
+    def forward(ctx, ij, colors, shade, depths, edgeflags, obs, device_scene, rasterizer, sigma, weights=None, texture=None, uv=None):
         device_scene.set_views(ij=ij.detach(), colors=colors.detach(), shade=shade.detach(), depths=depths.detach(), edgeflags=edgeflags)
+        _set_shared(device_scene, texture, uv)
         loss = torch.empty(1, dtype=torch.float64, device=ij.device)  # sum (image - obs)^2, from the same launches (no pass over the frame)
         image, z, g = rasterizer.render_fit(device_scene, obs, sigma, clear_grads=False, loss_out=loss, weights=weights)
-        ctx.save_for_backward(g["ij_b"].to(ij.dtype), g["colors_b"].to(colors.dtype), g["shade_b"].to(shade.dtype))
+        shared_b = [] if texture is None and uv is None else [None if texture is None else g["texture_b"].to(texture.dtype), None if uv is None else g["uv_b"].to(uv.dtype)]
+        ctx.shared_given = (texture is not None, uv is not None)
+        ctx.save_for_backward(g["ij_b"].to(ij.dtype), g["colors_b"].to(colors.dtype), g["shade_b"].to(shade.dtype), *[b for b in shared_b if b is not None])
         ctx.uv_b, ctx.texture_b = g["uv_b"], g["texture_b"]
         ctx.mark_non_differentiable(image)
         return loss[0], image
 
     @staticmethod
     def backward(ctx, loss_b, _image_b):
-        ij_b, colors_b, shade_b = ctx.saved_tensors
-        return loss_b.to(ij_b.dtype) * ij_b, loss_b.to(colors_b.dtype) * colors_b, loss_b.to(shade_b.dtype) * shade_b, None, None, None, None, None, None, None
+        ij_b, colors_b, shade_b, *rest = ctx.saved_tensors
+        shared_b = tuple(loss_b.to(rest[0].dtype) * rest.pop(0) if given else None for given in ctx.shared_given)
+        return (loss_b.to(ij_b.dtype) * ij_b, loss_b.to(colors_b.dtype) * colors_b, loss_b.to(shade_b.dtype) * shade_b, None, None, None, None, None, None, None) + shared_b
 
 
 class DeviceMesh:
@@ -343,7 +366,8 @@ class Scene3DDevice:
     def _rasterizer(self, n_views, height, width, nb_colors, textured, backface_culling):
         m = self.mesh
         key = (id(m.topology), n_views, height, width, nb_colors, textured, backface_culling, self.perspective_correct, self.integer_pixel_centers,
-               None if self.background_color is None else self.background_color.tobytes(), id(self.background_image), id(m.texture))  # fmt: skip
+               None if self.background_color is None else self.background_color.tobytes(), id(self.background_image),
+               tuple(m.texture.shape) if textured else None)  # fmt: skip  (the texture's VALUE is set at every render: _shared_inputs)
         if self._state is None or self._state[0] != key:
             V, T = m.nb_vertices, m.nb_faces
             dev, vd = m.device, m.dtype
@@ -364,25 +388,37 @@ class Scene3DDevice:
             self._state = (key, ds, keep or HipRasterizer.for_scene(ds))
         return self._state[1], self._state[2]
 
-    def _rasterize(self, camera, ij, depths, colors, shade, textured, backface_culling):
+    def _shared_inputs(self, ds, textured, texture, uv):
+        """A textured render reads the value ``mesh.texture`` / ``mesh.uv`` have at the call (an optimiser may have updated them in place, or rebound
+        them); -> the extra inputs of the autograd function: those that are differentiated, and only those"""
+        if textured and texture is None:
+            ds.set_texture(self.mesh.texture)
+        if textured and uv is None:
+            ds.set_uv(self.mesh.uv)
+        return () if texture is None and uv is None else (texture, uv)
+
+    def _rasterize(self, camera, ij, depths, colors, shade, textured, backface_culling, texture=None, uv=None):
+        """``texture`` / ``uv``: given when they are to be differentiated (``mesh.texture`` / ``mesh.uv`` requiring grad), see :meth:`render`"""
         if (self.background_image is None) == (self.background_color is None):
             raise BaseException("You need to provide either a background image or background color")
         n = camera.n_views
         ds, r = self._rasterizer(n, camera.height, camera.width, int(colors.shape[-1]), textured, backface_culling)
+        shared = self._shared_inputs(ds, textured, texture, uv)
         flags = self.mesh.topology.edge_on_silhouette(ij) if self.sigma > 0 else torch.zeros((n, self.mesh.nb_faces, 3), dtype=torch.uint8, device=ij.device)
         self.last = dict(ij=ij, depths=depths, edgeflags=flags, colors=colors, shade=shade)
-        image, z = RenderViewsFunc.apply(ij, colors, shade, depths.detach(), flags, ds, r, self.sigma)
+        image, z = RenderViewsFunc.apply(ij, colors, shade, depths.detach(), flags, ds, r, self.sigma, *shared)
         return image, z
 
-    def _rasterize_l2(self, camera, ij, depths, colors, shade, textured, backface_culling, obs, weights=None):
+    def _rasterize_l2(self, camera, ij, depths, colors, shade, textured, backface_culling, obs, weights=None, texture=None, uv=None):
         """-> (sum (image - obs)^2 over all views -- times the per-pixel weights, if any --, image [n,H,W,C]) through the one-call fit step"""
         if (self.background_image is None) == (self.background_color is None):
             raise BaseException("You need to provide either a background image or background color")
         n = camera.n_views
         ds, r = self._rasterizer(n, camera.height, camera.width, int(colors.shape[-1]), textured, backface_culling)
+        shared = self._shared_inputs(ds, textured, texture, uv)
         flags = self.mesh.topology.edge_on_silhouette(ij) if self.sigma > 0 else torch.zeros((n, self.mesh.nb_faces, 3), dtype=torch.uint8, device=ij.device)
         self.last = dict(ij=ij, depths=depths, edgeflags=flags, colors=colors, shade=shade)
-        return RenderViewsL2Func.apply(ij, colors, shade, depths.detach(), flags, obs, ds, r, self.sigma, weights)
+        return RenderViewsL2Func.apply(ij, colors, shade, depths.detach(), flags, obs, ds, r, self.sigma, weights, *shared)
 
     # ---- the reference's entry points, batched over the camera's views -----------------------------------------------
 
@@ -399,6 +435,7 @@ class Scene3DDevice:
         if weights is not None and tuple(weights.shape) not in ((n, camera.height, camera.width), (camera.height, camera.width)):
             raise ValueError(f"weights must have shape [{n}, {camera.height}, {camera.width}] or [{camera.height}, {camera.width}], not {list(weights.shape)}")
         extra = {} if weights is None else {"weights": weights}  # (only when given: a stand-in for _rasterize_l2 that knows no weights must fail, not ignore them)
+        extra.update(self._differentiated_shared())  # (the same convention)
         lum = self.vertices_luminosity(m.vertices)
         lum = lum[None].expand(n, -1) if lum.dim() == 1 else lum
         if m.uv is not None:
@@ -409,8 +446,16 @@ class Scene3DDevice:
         shade = torch.zeros((n, V), dtype=m.dtype, device=m.device)
         return self._rasterize_l2(camera, ij, depths, vc * lum[..., None], shade, False, backface_culling, obs.expand(n, -1, -1, -1).contiguous(), **extra)
 
+    def _differentiated_shared(self):
+        """{"texture": mesh.texture, "uv": mesh.uv}, each only when it requires grad: the keyword arguments a textured render passes on"""
+        m = self.mesh
+        if m.uv is None:
+            return {}
+        return {k: t for k, t in (("texture", m.texture), ("uv", m.uv)) if torch.is_tensor(t) and t.requires_grad}
+
     def render(self, camera, return_z_buffer=False, backface_culling=True):
-        """-> image [n,H,W,C] (and z_buffer [n,H,W]); dr.py:896-983"""
+        """-> image [n,H,W,C] (and z_buffer [n,H,W]); dr.py:896-983.  A textured mesh is rendered with the value ``mesh.texture`` has at the call;
+        when ``mesh.texture`` / ``mesh.uv`` require grad they receive their gradients (summed over the views)."""
         m = self.mesh
         assert m is not None, "You need to provide a mesh first."
         ij, depths = camera.project_points(m.vertices)
@@ -420,7 +465,7 @@ class Scene3DDevice:
         if m.uv is not None:
             assert m.texture is not None
             colors = torch.zeros((n, V, int(m.texture.shape[2])), dtype=m.dtype, device=m.device)
-            image, z = self._rasterize(camera, ij, depths, colors, lum, True, backface_culling)
+            image, z = self._rasterize(camera, ij, depths, colors, lum, True, backface_culling, **self._differentiated_shared())
         else:
             vc = m.vertices_colors if m.vertices_colors.dim() == 3 else m.vertices_colors[None].expand(n, -1, -1)
             shade = torch.zeros((n, V), dtype=m.dtype, device=m.device)
