@@ -12,6 +12,7 @@ import types
 _INCLUDE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
 HEADER_PATH = os.path.join(_INCLUDE, "deodr_hip.h")
 TEXTURE_HEADER_PATH = os.path.join(_INCLUDE, "deodr_hip_texture.h")  # the companion header (texture estimation), versioned on its own
+SUBDIV_HEADER_PATH = os.path.join(_INCLUDE, "deodr_hip_subdiv.h")  # the companion header (Loop subdivision), versioned on its own
 
 # C type (without `const`, without spaces around the stars) -> ctypes.  Data pointers are c_void_p: callers pass device addresses (Python
 # ints, c_void_p), None, byref(...) and small ctypes arrays, and c_void_p takes all of them.  int and unsigned long long are only ever
@@ -93,3 +94,5 @@ with open(HEADER_PATH) as _f:
     HEADER = parse(_f.read())
 with open(TEXTURE_HEADER_PATH) as _f:
     TEXTURE_HEADER = parse(_f.read(), "include/deodr_hip_texture.h")
+with open(SUBDIV_HEADER_PATH) as _f:
+    SUBDIV_HEADER = parse(_f.read(), "include/deodr_hip_subdiv.h")

@@ -58,8 +58,10 @@
 #include "../../include/deodr_hip.h"
 #include "dr_dispatch.h"
 #include "../../include/deodr_hip_texture.h"
+#include "../../include/deodr_hip_subdiv.h"
 #include "dr_fititer.h" // <- dr_finalize.h <- dr_backward.h <- dr_backward_generic.h <- dr_forward.h <- dr_forward_generic.h <- dr_setup.h <- dr_workspace.h <- dr_prims.h
 #include "dr_texfit.h"  // texture smoothness + step (include/deodr_hip_texture.h); uses grid_sum of dr_fronthalf.h
+#include "dr_subdiv.h"  // rows of a sparse matrix applied to [batch, n, D] blocks (include/deodr_hip_subdiv.h): Loop subdivision and its adjoint
 
 using namespace dr;
 using namespace dr::dispatch;
@@ -1320,6 +1322,57 @@ int deodr_hip_texture_step(void *texture, void *speed, const void *gradient, int
 		break;
 	}
 	return check_hip(hipGetLastError(), "texture_step launch");
+}
+
+// ---- Loop subdivision (include/deodr_hip_subdiv.h, kernel in dr_subdiv.h)
+
+int deodr_hip_subdiv_abi_version(void) { return DEODR_HIP_SUBDIV_ABI_VERSION; }
+
+int deodr_hip_subdiv_lanes(int n_rows, uint32_t nnz) { return n_rows > 0 ? subdiv_lanes(n_rows, nnz) : 0; }
+
+int deodr_hip_subdiv_apply(const uint32_t *offsets, const uint32_t *cols, const double *vals, int n_rows, int n_cols, uint32_t nnz, const void *x, void *y,
+						   int batch, int D, int dtype, int accumulate, void *stream)
+{
+	if (!offsets || !cols || !vals || !x || !y)
+		return fail("subdiv_apply: offsets, cols, vals, x or y == NULL");
+	if (n_rows <= 0 || n_cols <= 0 || nnz == 0)
+		return fail("subdiv_apply: n_rows, n_cols and nnz must be positive");
+	if (batch <= 0 || batch > 65535)
+		return fail("subdiv_apply: batch must be in 1 .. 65535");
+	if (D < 1 || D > DEODR_HIP_MAX_COLORS)
+		return fail("subdiv_apply: D out of range");
+	if (dtype != DEODR_HIP_F32 && dtype != DEODR_HIP_F64)
+		return fail("unknown dtype tag");
+	const size_t elem = dtype == DEODR_HIP_F64 ? 8 : 4;
+	const uintptr_t xa = (uintptr_t)x, ya = (uintptr_t)y;
+	const size_t xb = (size_t)batch * (size_t)n_cols * (size_t)D * elem, yb = (size_t)batch * (size_t)n_rows * (size_t)D * elem;
+	if (xa < ya + yb && ya < xa + xb)
+		return fail("subdiv_apply: y must not overlap x");
+	if (((xa | ya) & (elem - 1)) || ((uintptr_t)offsets & 3) || ((uintptr_t)cols & 3) || ((uintptr_t)vals & 7))
+		return fail("subdiv_apply: misaligned pointer");
+	const int lanes = subdiv_lanes(n_rows, nnz);
+	// (n_rows < 2^31 with 8 lanes, n_rows <= nnz / 32 < 2^27 with 64: at most 2^26 workgroups)
+	const unsigned long long blocks = ((unsigned long long)n_rows * (unsigned)lanes + FH_BLOCK - 1) / FH_BLOCK;
+	SubdivArgs a;
+	a.offsets = offsets, a.cols = cols, a.vals = vals, a.x = x, a.y = y;
+	a.n_rows = n_rows, a.n_cols = n_cols, a.D = D, a.accumulate = accumulate != 0;
+	const dim3 grid((unsigned)blocks, (unsigned)batch);
+	switch (2 * (lanes == SUBDIV_LANES_LONG) + (dtype == DEODR_HIP_F64))
+	{
+	case 0:
+		subdiv_launch_d<float, SUBDIV_LANES_SHORT>(a, grid, (hipStream_t)stream);
+		break;
+	case 1:
+		subdiv_launch_d<double, SUBDIV_LANES_SHORT>(a, grid, (hipStream_t)stream);
+		break;
+	case 2:
+		subdiv_launch_d<float, SUBDIV_LANES_LONG>(a, grid, (hipStream_t)stream);
+		break;
+	case 3:
+		subdiv_launch_d<double, SUBDIV_LANES_LONG>(a, grid, (hipStream_t)stream);
+		break;
+	}
+	return check_hip(hipGetLastError(), "subdiv_apply launch");
 }
 
 #ifdef DR_WAVE_TRACE

@@ -28,6 +28,8 @@ _SceneC, _FitOptionsC, ABI_VERSION = _H.structs["DeodrHipScene"], _H.structs["De
 ERR_FACES, ERR_FACES_UV, ERR_NO_TEXTURE, ERR_INTERNAL, ERR_DET_RANGE = (_H.defines["DEODR_HIP_ERR_" + n] for n in "FACES FACES_UV NO_TEXTURE INTERNAL DET_RANGE".split())
 _HT = _abi.TEXTURE_HEADER  # the companion header include/deodr_hip_texture.h (texture estimation), bound onto the same library
 TEXTURE_ABI_VERSION, MAX_COLORS = _HT.defines["DEODR_HIP_TEXTURE_ABI_VERSION"], _H.defines["DEODR_HIP_MAX_COLORS"]
+_HS = _abi.SUBDIV_HEADER  # the companion header include/deodr_hip_subdiv.h (Loop subdivision), bound onto the same library
+SUBDIV_ABI_VERSION = _HS.defines["DEODR_HIP_SUBDIV_ABI_VERSION"]
 # words of the 64-byte status block at the start of the workspace
 _STATUS_NEEDED, _STATUS_ERRORS = _H.defines["DEODR_HIP_STATUS_WORD_NEEDED_PAIRS"], _H.defines["DEODR_HIP_STATUS_WORD_SCENE_ERRORS"]
 
@@ -49,6 +51,9 @@ def lib():
         _abi.bind(L, _HT)  # (a library that lacks one of its symbols is refused by name)
         if L.deodr_hip_texture_abi_version() != TEXTURE_ABI_VERSION:
             raise ImportError("libdeodr_hip.so texture ABI version mismatch (include/deodr_hip_texture.h); rebuild it")
+        _abi.bind(L, _HS)
+        if L.deodr_hip_subdiv_abi_version() != SUBDIV_ABI_VERSION:
+            raise ImportError("libdeodr_hip.so subdivision ABI version mismatch (include/deodr_hip_subdiv.h); rebuild it")
         _lib = _abi.bind(L)
     return _lib
 
@@ -226,6 +231,56 @@ def texture_step(texture, speed, gradient, factor, step_max=None, inertia=0.0, d
         _check(lib().deodr_hip_texture_step(_ptr(texture), _ptr(speed), _ptr(gradient), *dims, float(factor), 0.0 if step_max is None else float(step_max),
                                             float(inertia), float(damping), int(clamp is not None), lo, hi, _stream(dev)))  # fmt: skip
     _touched(texture), _touched(speed)
+
+
+# ---- Loop subdivision (include/deodr_hip_subdiv.h) ------------------------------------------------------------------------------------
+
+
+def sparse_rows_lanes(n_rows, nnz):
+    """``deodr_hip_subdiv_lanes``: the kernel instance :func:`sparse_rows_apply` runs for a matrix of ``n_rows`` rows and ``nnz`` entries -- 8 adjacent
+    lanes per row, or 64 (a wavefront per row)"""
+    return int(lib().deodr_hip_subdiv_lanes(int(n_rows), int(nnz)))
+
+
+def sparse_rows_apply(offsets, cols, vals, x, out=None, accumulate=False):
+    """``deodr_hip_subdiv_apply``: ``out[b, r, :] (= | +=) sum_k vals[k] x[b, cols[k], :]`` over the entries ``k`` of row ``r`` of a matrix in compressed
+    rows -- ``offsets`` [rows + 1] and ``cols`` [nnz] as 4-byte integer tensors (uint32 bit patterns), ``vals`` [nnz] float64.  ``x`` [batch, n_cols, D]
+    float32 / float64 -> ``out`` [batch, rows, D] of the same dtype (allocated when None).  Deterministic; asynchronous on the current stream.
+    The tables are trusted (``offsets`` non-decreasing from 0 to nnz, ``cols`` < n_cols): :class:`deodr_amd.subdivision.LoopSubdivision` checks its
+    own on the host when it builds them."""
+    what = "sparse_rows_apply"
+    for name, t in (("offsets", offsets), ("cols", cols), ("vals", vals), ("x", x)):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise ValueError(f"{what}: {name} must be a ROCm tensor (deodr_amd has no CPU path)")
+        if not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be contiguous")
+        if t.device != x.device:
+            raise ValueError(f"{what}: {name} must be on the device of x")
+    if offsets.dtype not in (torch.int32, torch.uint32) or cols.dtype not in (torch.int32, torch.uint32) or offsets.dim() != 1 or cols.dim() != 1:
+        raise ValueError(f"{what}: offsets and cols must be one-dimensional 4-byte integer tensors")
+    if vals.dtype != torch.float64 or tuple(vals.shape) != tuple(cols.shape):
+        raise ValueError(f"{what}: vals must be a float64 tensor of the shape of cols")
+    if x.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"{what}: x must be float32 or float64, not {x.dtype}")
+    if x.dim() != 3 or not 1 <= x.shape[2] <= MAX_COLORS or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError(f"{what}: x must have shape [batch >= 1, n_cols >= 1, 1 <= D <= {MAX_COLORS}], not {list(x.shape)}")
+    n_rows, nnz = int(offsets.numel()) - 1, int(cols.numel())
+    if n_rows < 1 or nnz < 1:
+        raise ValueError(f"{what}: the matrix has no rows or no entries")
+    batch, n_cols, D = (int(v) for v in x.shape)
+    dev = x.device
+    with torch.cuda.device(dev):
+        if out is None:
+            if accumulate:
+                raise ValueError(f"{what}: accumulate needs out")
+            out = torch.empty((batch, n_rows, D), dtype=x.dtype, device=dev)
+        elif not torch.is_tensor(out) or out.device != dev or out.dtype != x.dtype or tuple(out.shape) != (batch, n_rows, D) or not out.is_contiguous():
+            raise ValueError(f"{what}: out must be a contiguous {x.dtype} tensor of shape {[batch, n_rows, D]} on the device of x")
+        _check(lib().deodr_hip_subdiv_apply(_ptr(offsets), _ptr(cols), _ptr(vals), n_rows, n_cols, nnz, _ptr(x), _ptr(out), batch, D,
+                                            1 if x.dtype == torch.float64 else 0, int(bool(accumulate)), _stream(dev)))  # fmt: skip
+    if accumulate:
+        _touched(out)
+    return out
 
 
 class DeviceScene:

@@ -187,20 +187,36 @@ class _DirectIteration:
 
 
 class _PoseFitter:
-    """deformable vertices + one rigid pose per view, shared machinery of the three fitters"""
+    """deformable vertices + one rigid pose per view, shared machinery of the three fitters.
+
+    ``subdivisions=k`` (0: off, every path as it is without the keyword): ``self.vertices`` [Vc,3] is the control cage of a Loop subdivision
+    surface -- still the parameter, same ``step()`` protocol, and the Laplacian rigid energy acts on it --; ``self.mesh`` is the k-times subdivided
+    mesh (faces, silhouette flags, normals, shading of the fine topology), ``self.control_mesh`` the cage.  The iteration then runs through autograd
+    (the subdivision is one kernel forward, one backward: deodr_amd/subdivision.py); ``GraphedStep`` replays it as one graph launch."""
 
     direct = True  # run an iteration as the fixed kernel sequence of _DirectIteration when the tensors allow it (False: always autograd)
 
     step_factor_vertices, step_factor_quaternion, step_factor_translation = 0.0005, 0.00006, 0.00005
 
-    def __init__(self, vertices, faces, euler_init, translation_init, cregu, inertia, damping, device, n_poses=1, clockwise=False, pixel_dtype=torch.float64):
+    def __init__(self, vertices, faces, euler_init, translation_init, cregu, inertia, damping, device, n_poses=1, clockwise=False, pixel_dtype=torch.float64,
+                 subdivisions=0):  # fmt: skip
         self.device = torch.device(device)
         self.cregu, self.inertia, self.damping = cregu, inertia, damping
         v0 = np.asarray(vertices, dtype=np.float64)
         self.mesh = DeviceMesh(np.asarray(faces), v0, clockwise=clockwise, colors=np.zeros((v0.shape[0], 0)), device=self.device)
+        # subdivisions = k > 0: `vertices` (the parameter) is the control cage of a Loop subdivision surface; what is posed, shaded and rendered is
+        # the k-times subdivided mesh S vertices, and the rigid energy acts on the cage (deodr_amd/subdivision.py)
+        self.subdivisions, self.control_mesh, self.subdivision = int(subdivisions), self.mesh, None
+        if self.subdivisions < 0:
+            raise ValueError("subdivisions must be >= 0")
+        if self.subdivisions:
+            with torch.no_grad():
+                self.mesh = self.control_mesh.subdivise(self.subdivisions)
+            self.subdivision = self.mesh.subdivision
+        self.last_vertices = {}  # with subdivisions: the centred control vertices and S of them, as the last _transformed built them (in the graph)
         self.scene = Scene3DDevice(pixel_dtype=pixel_dtype)
         self.scene.set_mesh(self.mesh)
-        self.rigid_energy = LaplacianRigidEnergyDevice(self.mesh.topology, v0, cregu)
+        self.rigid_energy = LaplacianRigidEnergyDevice(self.control_mesh.topology, v0, cregu)
         self.vertices_init = torch.as_tensor(v0, device=self.device)
         q0 = np.asarray([_quat_from_euler_zyx(e) for e in np.atleast_2d(euler_init)])
         t0 = np.atleast_2d(np.asarray(translation_init, dtype=np.float64))
@@ -231,6 +247,10 @@ class _PoseFitter:
 
         q = self.transform_quaternion_leaf / self.transform_quaternion_leaf.norm(dim=-1, keepdim=True)
         centred = vertices - vertices.mean(dim=0, keepdim=True)
+        if self.subdivisions:  # (centring commutes with S: its rows sum to 1.  Centred first, the data gradient arrives on the cage projected on zero-mean displacements)
+            control = centred
+            centred = self.subdivision.apply(control)
+            self.last_vertices = {"control": control, "fine": centred}
         if fronthalf.usable(centred, q, self.transform_translation_leaf):  # one kernel (two with its adjoint) instead of ~12 + ~25
             return fronthalf.RigidTransformFunc.apply(centred, q, self.transform_translation_leaf)
         return qrot(q, centred[None].expand(q.shape[0], -1, -1)) + self.transform_translation_leaf[:, None, :]
@@ -257,8 +277,12 @@ class _PoseFitter:
 
     def _direct_iteration(self, nb_colors, shaded):
         """-> the _DirectIteration of this fitter, or None when an iteration has to go through autograd (CPU tensors: the CPU suite;
-        a non-manifold mesh: no static table for the silhouette flags; ``direct = False``)"""
+        a non-manifold mesh: no static table for the silhouette flags; ``direct = False``; ``subdivisions > 0``: the kernels of the fixed
+        sequence fold the centring and the gradient mean into passes keyed to the RENDERED vertex array, which is then not the parameter)"""
         from . import fronthalf
+
+        if self.subdivisions:
+            return None
 
         topo = self.mesh.topology
         params = (self.vertices, self.transform_quaternion, self.transform_translation)
@@ -339,8 +363,9 @@ class _PoseFitter:
 class MeshDepthFitter(_PoseFitter):
     """Fit a deformable mesh to a depth image (reference deodr/mesh_fitter.py:20-196)."""
 
-    def __init__(self, vertices, faces, euler_init, translation_init, cregu=2000, inertia=0.96, damping=0.05, device="cuda", pixel_dtype=torch.float64):
-        super().__init__(vertices, faces, euler_init, translation_init, cregu, inertia, damping, device, pixel_dtype=pixel_dtype)
+    def __init__(self, vertices, faces, euler_init, translation_init, cregu=2000, inertia=0.96, damping=0.05, device="cuda", pixel_dtype=torch.float64,
+                 subdivisions=0):  # fmt: skip
+        super().__init__(vertices, faces, euler_init, translation_init, cregu, inertia, damping, device, pixel_dtype=pixel_dtype, subdivisions=subdivisions)
         self.camera_center = self.object_center + np.array([-0.5, 0, 5]) * self.object_radius
 
     def set_max_depth(self, max_depth):
@@ -473,12 +498,14 @@ class MeshRGBFitterWithPose(_PoseFitter):
     """Fit a deformable mesh, its pose, a directional + ambient light and one colour to a colour image (mesh_fitter.py:199-376)."""
 
     def __init__(self, vertices, faces, euler_init, translation_init, default_color, default_light_directional, default_light_ambient, cregu=2000,
-                 inertia=0.96, damping=0.05, update_lights=True, update_color=True, device="cuda", pixel_dtype=torch.float64, n_poses=1):  # fmt: skip
+                 inertia=0.96, damping=0.05, update_lights=True, update_color=True, device="cuda", pixel_dtype=torch.float64, n_poses=1,
+                 subdivisions=0):  # fmt: skip
         self.default_color = np.asarray(default_color, dtype=np.float64)
         self.default_light_directional = np.asarray(default_light_directional, dtype=np.float64)
         self.default_light_ambient = float(default_light_ambient)
         self.update_lights, self.update_color = update_lights, update_color
-        super().__init__(vertices, faces, euler_init, translation_init, cregu, inertia, damping, device, n_poses=n_poses, pixel_dtype=pixel_dtype)
+        super().__init__(vertices, faces, euler_init, translation_init, cregu, inertia, damping, device, n_poses=n_poses, pixel_dtype=pixel_dtype,
+                         subdivisions=subdivisions)  # fmt: skip
         self.camera_center = self.object_center + np.atleast_2d(np.asarray(translation_init, dtype=np.float64))[0] + np.array([0, 0, 9]) * self.object_radius
 
     def reset(self):
@@ -614,7 +641,8 @@ class MeshRGBFitterWithPoseMultiFrame(MeshRGBFitterWithPose):
     step_factor_quaternion, step_factor_translation = 0.00005, 0.00004
 
     def __init__(self, vertices, faces, euler_init, translation_init, default_color, default_light_directional, default_light_ambient, cregu=2000,
-                 cdata=1, inertia=0.97, damping=0.15, update_lights=True, update_color=True, device="cuda", pixel_dtype=torch.float64, group=None):  # fmt: skip
+                 cdata=1, inertia=0.97, damping=0.15, update_lights=True, update_color=True, device="cuda", pixel_dtype=torch.float64, group=None,
+                 subdivisions=0):  # fmt: skip
         euler_init, translation_init = np.atleast_2d(euler_init), np.atleast_2d(translation_init)
         self.cdata = cdata
         self.n_views_total = max(len(euler_init), len(translation_init))
@@ -625,7 +653,7 @@ class MeshRGBFitterWithPoseMultiFrame(MeshRGBFitterWithPose):
         self.my_views = list(dd.shard_views(self.n_views_total, self.rank, self.world))
         pick = lambda a: np.broadcast_to(a, (self.n_views_total, a.shape[1]))[self.my_views]
         super().__init__(vertices, faces, pick(euler_init), pick(translation_init), default_color, default_light_directional, default_light_ambient,
-                         cregu, inertia, damping, update_lights, update_color, device, pixel_dtype, n_poses=len(self.my_views))  # fmt: skip
+                         cregu, inertia, damping, update_lights, update_color, device, pixel_dtype, n_poses=len(self.my_views), subdivisions=subdivisions)  # fmt: skip
         self.camera_center = self.object_center + np.array([0, 0, 6]) * self.object_radius
         self._packed = None
 

@@ -287,9 +287,10 @@ class DeviceMesh:
     The counterpart of the reference's ``ColoredTriMesh`` (deodr/triangulated_mesh.py:302-360) for the attributes the renderer
     consumes.  ``vertices`` may be a leaf tensor that requires grad."""
 
-    def __init__(self, faces, vertices, clockwise=False, colors=None, uv=None, faces_uv=None, texture=None, device="cuda", dtype=torch.float64):
+    def __init__(self, faces, vertices, clockwise=False, colors=None, uv=None, faces_uv=None, texture=None, device="cuda", dtype=torch.float64,
+                 topology=None):  # fmt: skip
         self.device, self.dtype = torch.device(device), dtype
-        self.topology = MeshTopology(faces, int(np.shape(vertices)[-2]), clockwise, self.device)
+        self.topology = topology if topology is not None else MeshTopology(faces, int(np.shape(vertices)[-2]), clockwise, self.device)
         self.faces_np = np.asarray(faces).astype(np.uint32)
         self.clockwise = bool(clockwise)
         self.vertices = _t(vertices, self.device, dtype)
@@ -311,6 +312,23 @@ class DeviceMesh:
 
     def set_vertices_colors(self, colors):
         self.vertices_colors = colors
+
+    def subdivise(self, n_iter, subdivision=None):
+        """-> a new DeviceMesh, ``n_iter`` times Loop-subdivided (deodr/triangulated_mesh.py:499-562): its ``vertices`` are ``S self.vertices``
+        (differentiable: gradients reach the control vertices), its colours follow the reference's colour rule; ``mesh.subdivision`` keeps the
+        :class:`deodr_amd.subdivision.LoopSubdivision` (pass it as ``subdivision`` to subdivide other vertices of the same connectivity)."""
+        if not n_iter:
+            return self
+        if self.uv is not None:
+            raise BaseException("Textured mesh not supported yet in subdivision.")
+        from .subdivision import LoopSubdivision
+
+        sub = subdivision or LoopSubdivision(self.faces_np, self.nb_vertices, n_iter, self.clockwise, self.device)
+        colors = None if self.vertices_colors is None else sub.apply_colors(self.vertices_colors)
+        fine = DeviceMesh(sub.faces_fine, sub.apply(self.vertices), clockwise=self.clockwise, colors=colors, device=self.device, dtype=self.dtype,
+                          topology=sub.topology)  # fmt: skip
+        fine.subdivision = sub
+        return fine
 
 
 class Scene3DDevice:

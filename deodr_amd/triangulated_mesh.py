@@ -5,7 +5,7 @@
 ``vertices_colors_b``, ``uv`` / ``faces_uv`` / ``texture``, ``clockwise``, ``adjacencies``) so that ``Scene3D`` and fitter code
 written against DEODR runs on it -- but every computation is delegated to the device implementation in
 :mod:`deodr_amd.scene3d` (index arrays + batched torch ops on the ROCm device; the reference uses SciPy sparse matrices on the
-host).  File I/O, trimesh conversion and Loop subdivision are out of scope.
+host).  Loop subdivision is :mod:`deodr_amd.subdivision`.  File I/O and trimesh conversion are out of scope.
 """
 
 import numpy as np
@@ -118,6 +118,15 @@ class ColoredTriMesh(TriMesh):
         self.vertices_colors = colors
 
     def subdivise(self, n_iter):
-        if n_iter:
-            raise NotImplementedError("Loop subdivision is outside the scope of deodr_amd (SURVEY.md section 2)")
-        return self
+        """``n_iter`` levels of Loop subdivision (the reference's ``loop_subdivision``, triangulated_mesh.py:499-562) -> a new mesh with the reference's
+        vertex, face and colour arrays.  NumPy level: the composed matrices of :class:`deodr_amd.subdivision.LoopSubdivision` applied on the host."""
+        if not n_iter:
+            return self
+        if self.uv is not None:
+            raise BaseException("Textured mesh not supported yet in subdivision.")
+        from .subdivision import LoopSubdivision
+
+        sub = LoopSubdivision(self._faces, self.nb_vertices, n_iter, self.clockwise, self.device)
+        colors = None if self.vertices_colors is None else sub.colors_matrix @ np.asarray(self.vertices_colors, dtype=np.float64)
+        return ColoredTriMesh(sub.faces_fine, vertices=sub.matrix @ np.asarray(self._vertices, dtype=np.float64), clockwise=self.clockwise, colors=colors,
+                              nb_colors=self.nb_colors, compute_adjacencies=self._adjacencies is not None, device=self.device)  # fmt: skip
