@@ -304,20 +304,32 @@ class DeviceScene:
         self.faces_uv = _tensor(np.asarray(faces_uv).astype(np.int64) if not torch.is_tensor(faces_uv) else faces_uv, dev, torch.int32)
         self.textured = _tensor(textured, dev, torch.uint8)
         self.shaded = _tensor(shaded, dev, torch.uint8)
-        self.uv = _tensor(uv, dev, vertex_dtype).reshape(-1, 2).detach()
         self.height, self.width = int(height), int(width)
         self.flags = dict(clockwise=bool(clockwise), backface_culling=bool(backface_culling), strict_edge=bool(strict_edge),
                           perspective_correct=bool(perspective_correct), integer_pixel_centers=bool(integer_pixel_centers))  # fmt: skip
-        self.texture = _tensor(texture, dev, pixel_dtype).detach() if _count(texture) > 0 else None
         self._texture_given = self._uv_given = None  # (tensor last handed to set_texture / set_uv, its version): see there
         self._texture_buffer = self._uv_buffer = None
-        self.background_color = None if background_color is None else _tensor(background_color, dev, pixel_dtype).reshape(-1)
-        self.background_image = None if background_image is None else _tensor(background_image, dev, pixel_dtype)
         self.set_views(ij, depths, colors, shade, edgeflags)
-        if self.background_image is not None:
-            self.background_image = self.background_image.reshape(self.n_views, self.height, self.width, self.nb_colors).contiguous()
+        for name, a in (("uv", uv), ("texture", texture), ("background_color", background_color), ("background_image", background_image)):
+            self.upload(name, a)
         if validate:
             self.validate()
+
+    def upload(self, name, a):
+        """Replace ``uv`` [Vuv,2] (vertex dtype), ``texture`` [Ht,Wt,C], ``background_color`` [C] or ``background_image`` [n,H,W,C] (pixel dtype) by the
+        array or tensor ``a``, converted as the constructor converts them: an empty texture (or None) and a background that is None leave the scene
+        without one.  Unlike :meth:`set_texture` / :meth:`set_uv` the shape may change, and nothing is remembered about ``a``."""
+        dev, pd = self.device, self.pixel_dtype
+        if name == "uv":
+            t = _tensor(a, dev, self.vertex_dtype).reshape(-1, 2).detach()
+        elif name == "texture":
+            t = _tensor(a, dev, pd).detach() if _count(a) > 0 else None
+        elif name == "background_color":
+            t = None if a is None else _tensor(a, dev, pd).reshape(-1)
+        else:
+            assert name == "background_image"
+            t = None if a is None else _tensor(a, dev, pd).reshape(self.n_views, self.height, self.width, self.nb_colors).contiguous()
+        setattr(self, name, t)
 
     def validate(self):
         """checkSceneValid's index checks (reference H.h:2700-2712), once per topology (synchronises).  The set-up kernel
@@ -378,6 +390,10 @@ class DeviceScene:
     def set_uv(self, uv):
         """The same for the texture coordinates [Vuv,2] (vertex dtype)."""
         self._set_shared("uv", uv, self.vertex_dtype, self.uv.shape)
+
+    def shared_sources(self):
+        """-> (texture, uv): the tensors last handed to :meth:`set_texture` / :meth:`set_uv` (what the scene reads them from), None for one never set"""
+        return tuple(None if given is None else given[0] for given in (self._texture_given, self._uv_given))
 
     @property
     def nb_triangles(self):

@@ -1,28 +1,22 @@
-"""``torch.autograd.Function`` wrappers of the HIP rasterizer.
+"""The PyTorch layer over the HIP rasterizer: the reference's names and shapes on top of :mod:`deodr_amd.render_ops`.
 
 ``TorchDifferentiableRenderer2DFunc`` keeps the signature of the reference's class
 (deodr/pytorch/differentiable_renderer_pytorch.py:41-81): ``forward(ctx, ij, colors, scene)`` where ``scene`` carries a
 ``scene_2d`` (a ``Scene2D``), ``backward`` returns ``(ij_b, colors_b, None)``; like the reference it renders with sigma = 1
 unless ``scene.sigma_2d`` is set.  Unlike the reference nothing goes through NumPy: ``ij`` / ``colors`` may live on the ROCm
 device (the image then stays there) or on the CPU (results are copied back, reference behaviour).  The incoming
-``grad_output`` is never mutated.
+``grad_output`` is never mutated.  It is the one ``autograd.Function`` defined here, and its bind / stamp / restore / cast steps are those of render_ops.py.
 
-``TorchDifferentiableRenderViewsFunc`` is the batched form for ``n_views`` views of one mesh on a prepared
-:class:`deodr_amd.hip_renderer.DeviceScene` -- the unit the multi-GPU path shards.
+``TorchDifferentiableRenderViews`` / ``TorchRenderViewsL2Loss`` are the batched forms for ``n_views`` views of one mesh on a prepared
+:class:`deodr_amd.hip_renderer.DeviceScene` -- the unit the multi-GPU path shards.  They call the ops of render_ops.py (the
+ones ``Scene3DDevice`` runs) without ``shade`` / ``depths`` / ``edgeflags``: the scene's own are read.
 """
 
 import numpy as np
 import torch
 
+from .. import render_ops
 from ..hip_renderer import DeviceScene, HipRasterizer, _count, _resolve_device
-
-
-def _set_shared(device_scene, texture, uv):
-    """the texture / texture coordinates a render is to read (None: what the scene holds)"""
-    if texture is not None:
-        device_scene.set_texture(texture)
-    if uv is not None:
-        device_scene.set_uv(uv)
 
 
 def _to_np(a):
@@ -72,18 +66,9 @@ def _device_state(scene, device, pixel_dtype):
     ds = st["ds"]
     for k in big:
         new = getattr(s, k)
-        if new is st["src"][k]:
-            continue
-        st["src"][k] = new
-        if k == "uv":
-            ds.uv = torch.as_tensor(_to_np(new)).to(device=ds.device, dtype=ds.vertex_dtype).reshape(-1, 2).contiguous()
-        elif k == "texture":
-            ds.texture = torch.as_tensor(_to_np(new)).to(device=ds.device, dtype=pixel_dtype).contiguous() if _count(new) else None
-        elif k == "background_color":
-            ds.background_color = None if new is None else torch.as_tensor(_to_np(new)).to(device=ds.device, dtype=pixel_dtype).reshape(-1)
-        else:
-            ds.background_image = None if new is None else torch.as_tensor(_to_np(new)).to(device=ds.device, dtype=pixel_dtype).reshape(
-                1, s.height, s.width, nb_colors).contiguous()  # fmt: skip
+        if new is not st["src"][k]:
+            st["src"][k] = new
+            ds.upload(k, None if new is None else _to_np(new))
     return ds, st["r"]
 
 
@@ -97,63 +82,38 @@ class TorchDifferentiableRenderer2DFunc(torch.autograd.Function):
         device = ij.device if on_device else _resolve_device("cuda")
         pixel_dtype = torch.float32 if (on_device and colors.dtype == torch.float32) else torch.float64
         ds, r = _device_state(scene, device, pixel_dtype)
-        to_t = lambda a: a.detach() if torch.is_tensor(a) else torch.as_tensor(np.asarray(a))
-        per_view = dict(depths=to_t(s.depths)[None], shade=to_t(s.shade)[None], edgeflags=to_t(s.edgeflags)[None])
-        ds.set_views(ij=ij.detach()[None], colors=colors.detach()[None], **per_view)
+        to_t = lambda a: (a if torch.is_tensor(a) else torch.as_tensor(np.asarray(a)))[None]
+        views = (ij[None], colors[None], to_t(s.shade), to_t(s.depths), to_t(s.edgeflags))
+        render_ops.bind(ctx, ds, views)
         sigma = getattr(scene, "sigma_2d", 1)  # the reference hard-codes 1 (deodr/pytorch/differentiable_renderer_pytorch.py:55)
         image, z_buffer = r.render(ds, sigma)
-        ctx.ds, ctx.r, ctx.on_device, ctx.in_dtypes = ds, r, on_device, (ij.dtype, colors.dtype)
         # the workspace and `ds` are shared by every render of this scene: the stamp tells backward whether they still hold THIS
         # forward (two renders in one graph); if not, the forward state is rebuilt from the saved inputs
-        ctx.generation, ctx.per_view, ctx.sigma = r.generation, per_view, sigma
-        ctx.save_for_backward(ij, colors)
-        ctx.z_buffer = z_buffer[0]
+        render_ops.keep_forward(ctx, r, sigma, views)
+        ctx.on_device, ctx.z_buffer = on_device, z_buffer[0]
         out = image[0]
         return out if on_device else out.to(device="cpu", dtype=torch.float64)
 
     @staticmethod
     def backward(ctx, image_b):
-        ds, r = ctx.ds, ctx.r
-        if r.generation != ctx.generation:
-            ij, colors = ctx.saved_tensors
-            ds.set_views(ij=ij.detach()[None], colors=colors.detach()[None], **ctx.per_view)
-        g = r.render_backward(ds, image_b=image_b, generation=ctx.generation, sigma=ctx.sigma)
-        ij_b, colors_b = g["ij_b"][0], g["colors_b"][0]
-        if not ctx.on_device:
-            ij_b, colors_b = ij_b.cpu(), colors_b.cpu()
-        return ij_b.to(ctx.in_dtypes[0]), colors_b.to(ctx.in_dtypes[1]), None
+        render_ops.restore(ctx)
+        g = ctx.r.render_backward(ctx.ds, image_b=image_b, generation=ctx.generation, sigma=ctx.sigma)
+        ij_b, colors_b, _ = render_ops.gradients(ctx, g, ("ij", "colors", "scene"))
+        ij_b, colors_b = ij_b[0], colors_b[0]
+        return (ij_b, colors_b, None) if ctx.on_device else (ij_b.cpu(), colors_b.cpu(), None)
 
 
 TorchDifferentiableRender2D = TorchDifferentiableRenderer2DFunc.apply
 
 
-class TorchDifferentiableRenderViewsFunc(torch.autograd.Function):
+class TorchDifferentiableRenderViewsFunc:
     """n_views views in one launch: (ij [n,V,2], colors [n,V,C][, texture [Ht,Wt,C], uv [Vuv,2]]) -> image [n,H,W,C] on ``device_scene``'s GPU.
-    ``texture`` / ``uv`` (optional): rendered with these values (``DeviceScene.set_texture`` / ``set_uv``) and differentiated, their gradients summed
-    over the views; not given: the scene's own, no gradient, the launches of always."""
+    The name and ``apply``'s arguments of old over :class:`deodr_amd.render_ops.RenderViewsFunc` (``texture`` / ``uv``: see there), which reads the
+    scene's own ``shade`` / ``depths`` / ``edgeflags`` when they are None."""
 
     @staticmethod
-    def forward(ctx, ij, colors, device_scene, rasterizer, sigma, texture=None, uv=None):
-        device_scene.set_views(ij=ij.detach(), colors=colors.detach())
-        _set_shared(device_scene, texture, uv)
-        image, _ = rasterizer.render(device_scene, sigma)
-        ctx.ds, ctx.r, ctx.in_dtypes, ctx.generation, ctx.sigma = device_scene, rasterizer, (ij.dtype, colors.dtype), rasterizer.generation, sigma
-        held = lambda given: None if given is None else given[0]  # (what the scene read them from when they are not inputs: restored in backward)
-        ctx.held = (held(device_scene._texture_given) if texture is None else None, held(device_scene._uv_given) if uv is None else None)
-        ctx.given = (texture is not None, uv is not None)
-        ctx.save_for_backward(ij, colors, *[t for t in (texture, uv) if t is not None])
-        return image
-
-    @staticmethod
-    def backward(ctx, image_b):
-        ij, colors, *rest = ctx.saved_tensors
-        texture, uv = (rest.pop(0) if given else None for given in ctx.given)
-        if ctx.r.generation != ctx.generation:  # another forward has used the scene / workspace since: restore the inputs
-            ctx.ds.set_views(ij=ij.detach(), colors=colors.detach())
-            _set_shared(ctx.ds, ctx.held[0] if texture is None else texture, ctx.held[1] if uv is None else uv)
-        g = ctx.r.render_backward(ctx.ds, image_b=image_b, generation=ctx.generation, sigma=ctx.sigma)
-        shared_b = (None if texture is None else g["texture_b"].to(texture.dtype), None if uv is None else g["uv_b"].to(uv.dtype))
-        return (g["ij_b"].to(ctx.in_dtypes[0]), g["colors_b"].to(ctx.in_dtypes[1]), None, None, None) + shared_b
+    def apply(ij, colors, device_scene, rasterizer, sigma, texture=None, uv=None):
+        return render_ops.RenderViewsFunc.apply(ij, colors, None, None, None, device_scene, rasterizer, sigma, texture, uv)[0]
 
 
 def TorchDifferentiableRenderViews(ij, colors, device_scene, rasterizer, sigma=1.0, texture=None, uv=None):
@@ -161,36 +121,17 @@ def TorchDifferentiableRenderViews(ij, colors, device_scene, rasterizer, sigma=1
     return TorchDifferentiableRenderViewsFunc.apply(ij, colors, device_scene, rasterizer, sigma, *shared)
 
 
-class TorchRenderViewsL2LossFunc(torch.autograd.Function):
+class TorchRenderViewsL2LossFunc:
     """sum((render(ij, colors) - obs)**2) over ``n_views`` views as ONE op: (ij [n,V,2], colors [n,V,C][, texture, uv]) -> scalar loss.
-
-    What the reference's fitters write as ``image = render(...); loss = ((image - obs) ** 2).sum(); loss.backward()``
-    (deodr/pytorch/mesh_fitter_pytorch.py, dr.py:701-740): here the forward is one ``deodr_hip_render_scene_fit`` call that
-    renders AND back-propagates the residual (the gradient of the loss w.r.t. the image is known as soon as a pixel is
-    resolved), so ``backward`` only scales the stored gradients.  ``image`` and ``z_buffer`` of the last call are kept on
-    the context owner (``rasterizer.last_fit``) for display.  ``weights`` ([n,H,W] or [H,W], or None): the loss is
-    ``sum(weights[..., None] * (image - obs)**2)``, see :meth:`HipRasterizer.render_fit` (no gradient with respect to them).
-    ``texture`` / ``uv`` (optional): as in :class:`TorchDifferentiableRenderViewsFunc`."""
+    The name and ``apply``'s arguments of old over :class:`deodr_amd.render_ops.RenderViewsL2Func` (``weights`` / ``texture`` / ``uv``: see there) with
+    ``library_loss=False``: the loss is formed from the returned frame.  ``image`` and ``z_buffer`` of the last call are kept on the context owner
+    (``rasterizer.last_fit``) for display."""
 
     @staticmethod
-    def forward(ctx, ij, colors, obs, device_scene, rasterizer, sigma, weights=None, texture=None, uv=None):
-        device_scene.set_views(ij=ij.detach(), colors=colors.detach())
-        _set_shared(device_scene, texture, uv)
-        image, z, g = rasterizer.render_fit(device_scene, obs, sigma, clear_grads=False, weights=weights)
+    def apply(ij, colors, obs, device_scene, rasterizer, sigma, weights=None, texture=None, uv=None):
+        loss, image, z = render_ops.RenderViewsL2Func.apply(ij, colors, None, None, None, obs, device_scene, rasterizer, sigma, weights, texture, uv, False)
         rasterizer.last_fit = (image, z)
-        ctx.given = (texture is not None, uv is not None)
-        shared_b = [g[k].to(t.dtype) for k, t in (("texture_b", texture), ("uv_b", uv)) if t is not None]
-        ctx.save_for_backward(g["ij_b"].to(ij.dtype), g["colors_b"].to(colors.dtype), *shared_b)
-        r2 = (image.double() - obs.to(image.device).double()) ** 2
-        if weights is not None:
-            r2 = r2 * torch.as_tensor(weights).to(image.device).double()[..., None]
-        return r2.sum()
-
-    @staticmethod
-    def backward(ctx, loss_b):
-        ij_b, colors_b, *rest = ctx.saved_tensors
-        shared_b = tuple(loss_b.to(rest[0].dtype) * rest.pop(0) if given else None for given in ctx.given)
-        return (loss_b.to(ij_b.dtype) * ij_b, loss_b.to(colors_b.dtype) * colors_b, None, None, None, None, None) + shared_b
+        return loss
 
 
 def TorchRenderViewsL2Loss(ij, colors, obs, device_scene, rasterizer, sigma=1.0, weights=None, texture=None, uv=None):

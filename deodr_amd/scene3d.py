@@ -6,7 +6,7 @@ The reference assembles the 2.5-D scene of every frame on the host with NumPy + 
 its PyTorch layer round-trips through ``.numpy()`` (``deodr/pytorch/differentiable_renderer_pytorch.py:52-54``).  Once the
 rasterizer takes tens of microseconds that glue is the whole iteration.  Here every array lives on the ROCm device from the
 mesh vertices to the loss: the O(V) algebra is a handful of batched torch ops over ``n_views`` views (differentiated by
-autograd), the rasterizer is the HIP library behind one autograd Function, and nothing visits the host inside a fit loop.
+autograd), the rasterizer is the HIP library behind the autograd ops of render_ops.py, and nothing visits the host inside a fit loop.
 
 Same math as the reference (float64 by default), not the same code: batched over views, index_add instead of SciPy sparse
 products, adjacency as flat index arrays built once per topology.
@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from .hip_renderer import DeviceScene, HipRasterizer
+from .render_ops import RenderViewsFunc, RenderViewsL2Func  # noqa: F401  (the rasterizer under autograd; re-exported)
 
 
 def _t(a, device, dtype=torch.float64):
@@ -208,79 +209,6 @@ class LaplacianRigidEnergyDevice:
         return 0.5 * (diff * grad).sum(), grad
 
 
-def _set_shared(device_scene, texture, uv):
-    """the texture / texture coordinates a render is to read (None: what the scene holds)"""
-    if texture is not None:
-        device_scene.set_texture(texture)
-    if uv is not None:
-        device_scene.set_uv(uv)
-
-
-class RenderViewsFunc(torch.autograd.Function):
-    """(ij [n,V,2], colors [n,V,C], shade [n,V][, texture [Ht,Wt,C], uv [Vuv,2]]) -> image [n,H,W,C]: the HIP rasterizer with gradients for all of them.
-
-    ``depths`` [n,V] and ``edgeflags`` [n,T,3] are inputs without gradient (dr.py:1017: the z buffer is not differentiated; the
-    flags select which edges are antialiased).  ALL five per-view arrays are saved: the DeviceScene / workspace are shared by
-    every render of a Scene3DDevice, and when another render has used them since (two cameras, or two vertex sets, in one loss)
-    the adjoint rebuilds this forward's state from its own inputs, not from whatever the scene holds now.
-    ``texture`` / ``uv`` (optional, trailing): rendered with these values (``DeviceScene.set_texture`` / ``set_uv``) and differentiated -- their
-    gradients are summed over the views, as the library delivers them.  Not given: the scene's own, no gradient, the same launches as ever."""
-
-    @staticmethod
-    def forward(ctx, ij, colors, shade, depths, edgeflags, device_scene, rasterizer, sigma, texture=None, uv=None):
-        device_scene.set_views(ij=ij.detach(), colors=colors.detach(), shade=shade.detach(), depths=depths.detach(), edgeflags=edgeflags)
-        _set_shared(device_scene, texture, uv)
-        image, z = rasterizer.render(device_scene, sigma)
-        ctx.ds, ctx.r, ctx.sigma, ctx.generation = device_scene, rasterizer, sigma, rasterizer.generation
-        # what the scene read its texture and uv from when they are not inputs of this op (restored like the views, see backward)
-        held = lambda given: None if given is None else given[0]
-        ctx.held = (held(device_scene._texture_given) if texture is None else None, held(device_scene._uv_given) if uv is None else None)
-        ctx.given = (texture is not None, uv is not None)
-        ctx.save_for_backward(ij, colors, shade, depths, edgeflags, *[t for t in (texture, uv) if t is not None])
-        ctx.mark_non_differentiable(z)
-        return image, z
-
-    @staticmethod
-    def backward(ctx, image_b, _z_b):
-        ij, colors, shade, depths, edgeflags, *rest = ctx.saved_tensors
-        texture, uv = (rest.pop(0) if given else None for given in ctx.given)
-        if ctx.r.generation != ctx.generation:  # another forward used the scene since: restore this one's inputs
-            ctx.ds.set_views(ij=ij.detach(), colors=colors.detach(), shade=shade.detach(), depths=depths.detach(), edgeflags=edgeflags)
-            _set_shared(ctx.ds, ctx.held[0] if texture is None else texture, ctx.held[1] if uv is None else uv)
-        g = ctx.r.render_backward(ctx.ds, image_b=image_b, generation=ctx.generation, sigma=ctx.sigma)
-        ctx.uv_b, ctx.texture_b = g["uv_b"], g["texture_b"]
-        shared_b = (None if texture is None else g["texture_b"].to(texture.dtype), None if uv is None else g["uv_b"].to(uv.dtype))
-        return (g["ij_b"].to(ij.dtype), g["colors_b"].to(colors.dtype), g["shade_b"].to(shade.dtype), None, None, None, None, None) + shared_b
-
-
-class RenderViewsL2Func(torch.autograd.Function):
-    """(ij, colors, shade[, texture, uv]) -> (sum over the views of sum (image - obs)^2, image): ONE ``deodr_hip_render_scene_fit`` call renders and
-    back-propagates the residual (the forward raster knows dL/dimage of a pixel the moment the pixel is resolved), so the backward
-    of this op only scales the gradients the forward left.  What the reference's colour fitters write as render, subtract, square,
-    sum, render_backward (deodr/mesh_fitter.py:296-318, 533-548) -- half the rasterizer time of the two-call path.
-    ``weights`` ([n,H,W] or None): per-pixel weights of the squared residual (:meth:`HipRasterizer.render_fit`); not differentiated.
-    ``texture`` / ``uv`` (optional, trailing): as in :class:`RenderViewsFunc`."""
-
-    @staticmethod
-    def forward(ctx, ij, colors, shade, depths, edgeflags, obs, device_scene, rasterizer, sigma, weights=None, texture=None, uv=None):
-        device_scene.set_views(ij=ij.detach(), colors=colors.detach(), shade=shade.detach(), depths=depths.detach(), edgeflags=edgeflags)
-        _set_shared(device_scene, texture, uv)
-        loss = torch.empty(1, dtype=torch.float64, device=ij.device)  # sum (image - obs)^2, from the same launches (no pass over the frame)
-        image, z, g = rasterizer.render_fit(device_scene, obs, sigma, clear_grads=False, loss_out=loss, weights=weights)
-        shared_b = [] if texture is None and uv is None else [None if texture is None else g["texture_b"].to(texture.dtype), None if uv is None else g["uv_b"].to(uv.dtype)]
-        ctx.shared_given = (texture is not None, uv is not None)
-        ctx.save_for_backward(g["ij_b"].to(ij.dtype), g["colors_b"].to(colors.dtype), g["shade_b"].to(shade.dtype), *[b for b in shared_b if b is not None])
-        ctx.uv_b, ctx.texture_b = g["uv_b"], g["texture_b"]
-        ctx.mark_non_differentiable(image)
-        return loss[0], image
-
-    @staticmethod
-    def backward(ctx, loss_b, _image_b):
-        ij_b, colors_b, shade_b, *rest = ctx.saved_tensors
-        shared_b = tuple(loss_b.to(rest[0].dtype) * rest.pop(0) if given else None for given in ctx.shared_given)
-        return (loss_b.to(ij_b.dtype) * ij_b, loss_b.to(colors_b.dtype) * colors_b, loss_b.to(shade_b.dtype) * shade_b, None, None, None, None, None, None, None) + shared_b
-
-
 class DeviceMesh:
     """A coloured (or textured) triangle mesh on the device: topology + per-vertex attributes.
 
@@ -415,8 +343,8 @@ class Scene3DDevice:
             ds.set_uv(self.mesh.uv)
         return () if texture is None and uv is None else (texture, uv)
 
-    def _rasterize(self, camera, ij, depths, colors, shade, textured, backface_culling, texture=None, uv=None):
-        """``texture`` / ``uv``: given when they are to be differentiated (``mesh.texture`` / ``mesh.uv`` requiring grad), see :meth:`render`"""
+    def _prepare(self, camera, ij, depths, colors, shade, textured, backface_culling, texture, uv):
+        """What every rasterizer call starts with -> (DeviceScene, HipRasterizer, silhouette flags, the extra inputs of the autograd function)"""
         if (self.background_image is None) == (self.background_color is None):
             raise BaseException("You need to provide either a background image or background color")
         n = camera.n_views
@@ -424,45 +352,48 @@ class Scene3DDevice:
         shared = self._shared_inputs(ds, textured, texture, uv)
         flags = self.mesh.topology.edge_on_silhouette(ij) if self.sigma > 0 else torch.zeros((n, self.mesh.nb_faces, 3), dtype=torch.uint8, device=ij.device)
         self.last = dict(ij=ij, depths=depths, edgeflags=flags, colors=colors, shade=shade)
-        image, z = RenderViewsFunc.apply(ij, colors, shade, depths.detach(), flags, ds, r, self.sigma, *shared)
-        return image, z
+        return ds, r, flags, shared
+
+    def _rasterize(self, camera, ij, depths, colors, shade, textured, backface_culling, texture=None, uv=None):
+        """``texture`` / ``uv``: given when they are to be differentiated (``mesh.texture`` / ``mesh.uv`` requiring grad), see :meth:`render`"""
+        ds, r, flags, shared = self._prepare(camera, ij, depths, colors, shade, textured, backface_culling, texture, uv)
+        return RenderViewsFunc.apply(ij, colors, shade, depths.detach(), flags, ds, r, self.sigma, *shared)
 
     def _rasterize_l2(self, camera, ij, depths, colors, shade, textured, backface_culling, obs, weights=None, texture=None, uv=None):
         """-> (sum (image - obs)^2 over all views -- times the per-pixel weights, if any --, image [n,H,W,C]) through the one-call fit step"""
-        if (self.background_image is None) == (self.background_color is None):
-            raise BaseException("You need to provide either a background image or background color")
-        n = camera.n_views
-        ds, r = self._rasterizer(n, camera.height, camera.width, int(colors.shape[-1]), textured, backface_culling)
-        shared = self._shared_inputs(ds, textured, texture, uv)
-        flags = self.mesh.topology.edge_on_silhouette(ij) if self.sigma > 0 else torch.zeros((n, self.mesh.nb_faces, 3), dtype=torch.uint8, device=ij.device)
-        self.last = dict(ij=ij, depths=depths, edgeflags=flags, colors=colors, shade=shade)
-        return RenderViewsL2Func.apply(ij, colors, shade, depths.detach(), flags, obs, ds, r, self.sigma, weights, *shared)
+        ds, r, flags, shared = self._prepare(camera, ij, depths, colors, shade, textured, backface_culling, texture, uv)
+        return RenderViewsL2Func.apply(ij, colors, shade, depths.detach(), flags, obs, ds, r, self.sigma, weights, *shared)[:2]
 
     # ---- the reference's entry points, batched over the camera's views -----------------------------------------------
+
+    def _vertex_inputs(self, camera):
+        """-> (ij [n,V,2], depths [n,V], colors [n,V,C], shade [n,V], textured) of the mesh seen by ``camera``: a textured mesh is shaded by its
+        luminosity and coloured by its texture, any other carries ``vertices_colors`` times the luminosity as its colours"""
+        m = self.mesh
+        assert m is not None, "You need to provide a mesh first."
+        ij, depths = camera.project_points(m.vertices)
+        n, V = ij.shape[0], m.nb_vertices
+        lum = self.vertices_luminosity(m.vertices)
+        lum = lum[None].expand(n, -1) if lum.dim() == 1 else lum
+        if m.uv is not None:
+            assert m.texture is not None
+            return ij, depths, torch.zeros((n, V, int(m.texture.shape[2])), dtype=m.dtype, device=m.device), lum, True
+        vc = m.vertices_colors if m.vertices_colors.dim() == 3 else m.vertices_colors[None].expand(n, -1, -1)
+        return ij, depths, vc * lum[..., None], torch.zeros((n, V), dtype=m.dtype, device=m.device), False
 
     def render_l2(self, camera, obs, backface_culling=True, weights=None):
         """-> (sum over views and pixels of (render(camera) - obs)^2 as a differentiable scalar, the rendered images [n,H,W,C]).
         ``obs`` [n,H,W,C] in the scene's pixel dtype, contiguous (anything else is converted at every call).
         ``weights`` [n,H,W] or [H,W] (same dtype, contiguous, to avoid a conversion): the sum becomes ``sum(weights[..., None] * (image - obs)**2)`` --
         a mask or a per-pixel confidence, ``>= 0``; the images are rendered everywhere.  No gradient flows to the weights."""
-        m = self.mesh
-        assert m is not None, "You need to provide a mesh first."
-        ij, depths = camera.project_points(m.vertices)
-        n, V = ij.shape[0], m.nb_vertices
+        ij, depths, colors, shade, textured = self._vertex_inputs(camera)
+        n = ij.shape[0]
         obs = obs.to(device=ij.device, dtype=self.pixel_dtype)
         if weights is not None and tuple(weights.shape) not in ((n, camera.height, camera.width), (camera.height, camera.width)):
             raise ValueError(f"weights must have shape [{n}, {camera.height}, {camera.width}] or [{camera.height}, {camera.width}], not {list(weights.shape)}")
         extra = {} if weights is None else {"weights": weights}  # (only when given: a stand-in for _rasterize_l2 that knows no weights must fail, not ignore them)
         extra.update(self._differentiated_shared())  # (the same convention)
-        lum = self.vertices_luminosity(m.vertices)
-        lum = lum[None].expand(n, -1) if lum.dim() == 1 else lum
-        if m.uv is not None:
-            assert m.texture is not None
-            colors = torch.zeros((n, V, int(m.texture.shape[2])), dtype=m.dtype, device=m.device)
-            return self._rasterize_l2(camera, ij, depths, colors, lum, True, backface_culling, obs.expand(n, -1, -1, -1).contiguous(), **extra)
-        vc = m.vertices_colors if m.vertices_colors.dim() == 3 else m.vertices_colors[None].expand(n, -1, -1)
-        shade = torch.zeros((n, V), dtype=m.dtype, device=m.device)
-        return self._rasterize_l2(camera, ij, depths, vc * lum[..., None], shade, False, backface_culling, obs.expand(n, -1, -1, -1).contiguous(), **extra)
+        return self._rasterize_l2(camera, ij, depths, colors, shade, textured, backface_culling, obs.expand(n, -1, -1, -1).contiguous(), **extra)
 
     def _differentiated_shared(self):
         """{"texture": mesh.texture, "uv": mesh.uv}, each only when it requires grad: the keyword arguments a textured render passes on"""
@@ -474,20 +405,8 @@ class Scene3DDevice:
     def render(self, camera, return_z_buffer=False, backface_culling=True):
         """-> image [n,H,W,C] (and z_buffer [n,H,W]); dr.py:896-983.  A textured mesh is rendered with the value ``mesh.texture`` has at the call;
         when ``mesh.texture`` / ``mesh.uv`` require grad they receive their gradients (summed over the views)."""
-        m = self.mesh
-        assert m is not None, "You need to provide a mesh first."
-        ij, depths = camera.project_points(m.vertices)
-        n, V = ij.shape[0], m.nb_vertices
-        lum = self.vertices_luminosity(m.vertices)
-        lum = lum[None].expand(n, -1) if lum.dim() == 1 else lum
-        if m.uv is not None:
-            assert m.texture is not None
-            colors = torch.zeros((n, V, int(m.texture.shape[2])), dtype=m.dtype, device=m.device)
-            image, z = self._rasterize(camera, ij, depths, colors, lum, True, backface_culling, **self._differentiated_shared())
-        else:
-            vc = m.vertices_colors if m.vertices_colors.dim() == 3 else m.vertices_colors[None].expand(n, -1, -1)
-            shade = torch.zeros((n, V), dtype=m.dtype, device=m.device)
-            image, z = self._rasterize(camera, ij, depths, vc * lum[..., None], shade, False, backface_culling)
+        ij, depths, colors, shade, textured = self._vertex_inputs(camera)
+        image, z = self._rasterize(camera, ij, depths, colors, shade, textured, backface_culling, **self._differentiated_shared())
         return (image, z) if return_z_buffer else image
 
     def render_depth(self, camera, depth_scale=1.0, backface_culling=True):

@@ -224,12 +224,25 @@ class FakeLib:
         o = None if options is None else options._obj
         return np.clip(values, o.clamp_lo, o.clamp_hi) if o is not None and o.clamp else values
 
+    @staticmethod
+    def _weights(options, shape, pd):
+        """DeodrHipFitOptions::weights: [n,H,W] in the pixel dtype, as float64 (None: no weights)"""
+        w = None if options is None else _view(options._obj.weights, shape, pd)
+        return None if w is None else w.astype(np.float64)
+
+    def _pixel_loss(self, frame, obs, options, pd):
+        """[n,H,W]: (weights *) sum over the channels of (clamp(frame) - obs)^2, the loss of a fit step per pixel"""
+        n, H, W, Cc = frame.shape
+        per_pixel = ((self._clamped(frame.astype(np.float64), options) - _view(obs, (n, H, W, Cc), pd).astype(np.float64)) ** 2).sum(axis=-1)
+        w = self._weights(options, (n, H, W), pd)
+        return per_pixel if w is None else w * per_pixel
+
     def deodr_hip_background_loss(self, sc_ref, obs, options, table, ws, nbytes, stream):
         sc, a, pd = self._scene(sc_ref)
         n, H, W, Cc = sc.n_views, sc.height, sc.width, sc.nb_colors
         tx, ty = self._tiles(H, W)
         background = a["background_image"] if a["background_image"] is not None else np.broadcast_to(a["background_color"], (n, H, W, Cc))
-        per_pixel = ((self._clamped(background.astype(np.float64), options) - _view(obs, (n, H, W, Cc), pd).astype(np.float64)) ** 2).sum(axis=-1)
+        per_pixel = self._pixel_loss(background, obs, options, pd)
         out = _view(table, (1 + n * tx * ty,), np.float64)
         out[1:] = self._tile_sums(per_pixel, tx, ty).reshape(-1)
         out[0] = out[1:].sum()
@@ -239,9 +252,10 @@ class FakeLib:
         o = options._obj
         sc, a, pd = self._scene(sc_ref)
         n, H, W, Cc = sc.n_views, sc.height, sc.width, sc.nb_colors
-        if not o.clamp:
+        w = self._weights(options, (n, H, W), pd)
+        if not o.clamp and w is None:
             rc = self.deodr_hip_render_scene_fit(sc_ref, image, z_buffer, sigma, obs, clear_gradients, ws, nbytes, stream)
-        else:  # the adjoint of sum (clamp(image) - obs)^2: image_b = 2 (clamp(image) - obs) where the clamp passes
+        else:  # the adjoint of sum w (clamp(image) - obs)^2: image_b = 2 w (clamp(image) - obs) where the clamp passes
             if self._check(sc, a, True):
                 return 1
             if clear_gradients:
@@ -253,7 +267,8 @@ class FakeLib:
             self.calls["render_scene_fit"] += 1
             if not rc:
                 img, ob = _view(image, (n, H, W, Cc), pd).astype(np.float64), _view(obs, (n, H, W, Cc), pd).astype(np.float64)
-                image_b = np.where((img >= o.clamp_lo) & (img <= o.clamp_hi), 2 * (img - ob), 0.0).astype(pd)
+                image_b = np.where((img >= o.clamp_lo) & (img <= o.clamp_hi), 2 * (img - ob), 0.0) if o.clamp else 2 * (img - ob)
+                image_b = image_b.astype(pd) if w is None else w[..., None] * image_b  # (unweighted: rounded to the pixel dtype, as ever)
                 self._adjoint(sc, a, pd, sigma, 0, image_b, None, None)
         if not rc and o.done_flag:  # (the step-done flag: everything is synchronous here)
             _view(o.done_flag, (1,), np.uint32)[0] = o.done_value
@@ -261,8 +276,7 @@ class FakeLib:
             return rc
         tx, ty = self._tiles(H, W)
         table = _view(o.tile_loss, (1 + n * tx * ty,), np.float64)
-        rendered = ((self._clamped(_view(image, (n, H, W, Cc), pd).astype(np.float64), options) - _view(obs, (n, H, W, Cc), pd).astype(np.float64)) ** 2).sum(axis=-1)
-        tiles = self._tile_sums(rendered, tx, ty).reshape(-1)
+        tiles = self._tile_sums(self._pixel_loss(_view(image, (n, H, W, Cc), pd), obs, options, pd), tx, ty).reshape(-1)
         changed = tiles != table[1:]  # (the library only visits the tiles that hold primitives: the others ARE their background)
         _view(o.loss, (1,), np.float64)[0] = table[0] + (tiles[changed] - table[1:][changed]).sum()
         return 0
