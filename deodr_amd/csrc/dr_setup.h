@@ -136,10 +136,25 @@ __device__ __forceinline__ uint32_t compact_flagged_slots(const KParams &p, cons
 	const int slot0 = (edge_block * PRIM_BLOCK + tid) * per_thread;
 	uint32_t flags = 0; // bit i: slot0 + i is flagged
 	if (p.sigma > 0)
+	{
+		static_assert(EDGE_SLOTS == 4, "a thread's flags are one 32-bit word");
+		// The thread's four flags with ONE aligned 32-bit load instead of four byte loads (slot0 is a multiple of 4; a view's flags start at
+		// view * 3T bytes, not always on a word, and the last slots of the array are read by the byte).  Measured: profiles/README.md,
+		// "Finalize: the edge list, the accumulators by the line, the flags by the word".
+		if (per_thread == EDGE_SLOTS && slot0 + EDGE_SLOTS <= 3 * p.T && (((uintptr_t)edgeflags + (uintptr_t)slot0) & 3u) == 0)
+		{
+			const uint32_t four = *(const uint32_t *)(edgeflags + slot0);
 #pragma unroll
-		for (int i = 0; i < EDGE_SLOTS; i++)
-			if (i < per_thread && slot0 + i < 3 * p.T && edgeflags[slot0 + i] != 0)
-				flags |= 1u << i;
+			for (int i = 0; i < EDGE_SLOTS; i++)
+				if ((four >> (8 * i)) & 0xffu)
+					flags |= 1u << i;
+		}
+		else
+#pragma unroll
+			for (int i = 0; i < EDGE_SLOTS; i++)
+				if (i < per_thread && slot0 + i < 3 * p.T && edgeflags[slot0 + i] != 0)
+					flags |= 1u << i;
+	}
 	const uint32_t mine = (uint32_t)__popc(flags);
 	// exclusive prefix of `mine` over the lanes of the wavefront, then over the wavefronts
 	uint32_t incl = mine;
