@@ -13,6 +13,7 @@ _INCLUDE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__
 HEADER_PATH = os.path.join(_INCLUDE, "deodr_hip.h")
 TEXTURE_HEADER_PATH = os.path.join(_INCLUDE, "deodr_hip_texture.h")  # the companion header (texture estimation), versioned on its own
 SUBDIV_HEADER_PATH = os.path.join(_INCLUDE, "deodr_hip_subdiv.h")  # the companion header (Loop subdivision), versioned on its own
+RETAINED_HEADER_PATH = os.path.join(_INCLUDE, "deodr_hip_retained.h")  # the companion header (fit step into retained frames), versioned on its own
 
 # C type (without `const`, without spaces around the stars) -> ctypes.  Data pointers are c_void_p: callers pass device addresses (Python
 # ints, c_void_p), None, byref(...) and small ctypes arrays, and c_void_p takes all of them.  int and unsigned long long are only ever
@@ -45,16 +46,17 @@ def _typed_name(text, ctypes_of, declaration):
     return _ctype(c_type + ("*" if array else ""), ctypes_of, declaration), name
 
 
-def parse(text, name="include/deodr_hip.h"):
+def parse(text, name="include/deodr_hip.h", structs=None):
     """-> namespace(name, defines {name: int}, structs {name: ctypes.Structure}, functions {name: (restype, [argtypes])}) of a header text;
-    ``name``: what the header is called in error texts"""
+    ``name``: what the header is called in error texts; ``structs``: those of a header this one includes, which its prototypes may point to"""
     global _parsing
     _parsing = name
     text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
     text = re.sub(r"#ifdef __cplusplus.*?#endif", " ", text, flags=re.S)  # (the extern "C" braces)
     defines = {name: int(value) for name, value in re.findall(r"^[ \t]*#define[ \t]+(\w+)[ \t]+(-?\d+)[ \t]*$", text, flags=re.M)}
     text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
-    ctypes_of, structs, functions = dict(_CTYPES), {}, {}
+    ctypes_of, included, structs, functions = dict(_CTYPES), structs or {}, {}, {}
+    ctypes_of.update({n + "*": C.POINTER(s) for n, s in included.items()})
 
     def struct(m):
         fields = []
@@ -96,3 +98,5 @@ with open(TEXTURE_HEADER_PATH) as _f:
     TEXTURE_HEADER = parse(_f.read(), "include/deodr_hip_texture.h")
 with open(SUBDIV_HEADER_PATH) as _f:
     SUBDIV_HEADER = parse(_f.read(), "include/deodr_hip_subdiv.h")
+with open(RETAINED_HEADER_PATH) as _f:
+    RETAINED_HEADER = parse(_f.read(), "include/deodr_hip_retained.h", HEADER.structs)

@@ -914,13 +914,13 @@ __global__ __launch_bounds__(64, TEX ? 2 : EDGE_OCC) void raster_bwd_edge_kernel
 	const int lane = threadIdx.x;
 	const ViewPtrs w = view_ptrs(p, view);
 	// the last workgroups of the grid stream the background of this kernel's share of the empty tiles (fill_share)
-	const int fill_n = fill_share(p.fill_mode, 0, p.L.nwords), fill_blocks = fill_share_blocks(fill_n);
+	const int fill_n = fill_units(p.retained, p.fill_mode, 0, p.L.nwords), fill_blocks = fill_share_blocks(fill_n);
 	const int walkers = (int)gridDim.y - fill_blocks;
 	const int by = (int)blockIdx.y; // index among the walkers (>= walkers: a fill workgroup)
 	if (by >= walkers)
 	{
 		for (int i = by - walkers; i < fill_n; i += fill_blocks)
-			fill_share_word(p, 0, view, i, lane);
+			fill_unit(p, 0, view, i, lane);
 		return;
 	}
 	const uint32_t n_short = w.edge_tile_cnt[0], n_long = w.edge_tile_cnt[CNT_STRIDE], n_multi = w.edge_tile_cnt[2 * CNT_STRIDE] * CHUNKS;

@@ -95,7 +95,7 @@ __device__ __forceinline__ void finalize_body(KParams &p)
 		}
 		return;
 	}
-	const int fill_n = fill_share(p.fill_mode, 1, p.L.nwords);
+	const int fill_n = fill_units(p.retained, p.fill_mode, 1, p.L.nwords); // (units of 64 words in a retained step)
 	const int bx = (int)blockIdx.x - loss_blocks;
 	// (small launches, KParams::setup_sparse: ONE edge slot per thread, as in the set-up kernel -- a soup's 600 flagged edges are three workgroups of one
 	// round each instead of one workgroup of three rounds)
@@ -105,7 +105,7 @@ __device__ __forceinline__ void finalize_body(KParams &p)
 	{ // workgroups that stream the background of this kernel's share of the empty tiles (fill_share)
 		const int gw = fb * (PRIM_BLOCK / 64) + (int)(threadIdx.x >> 6);
 		if (fill_n > 0 && gw < p.n_views * fill_n)
-			fill_share_word(p, 1, gw / fill_n, gw % fill_n, threadIdx.x & 63);
+			fill_unit(p, 1, gw / fill_n, gw % fill_n, threadIdx.x & 63);
 		return;
 	}
 	const PrimWork pw = prim_work(p, true, loss_blocks, -1, edge_slots); // (edge-slot blocks first, as in the set-up kernel; triangle blocks first: finalize 37.5 -> 43.5 us)

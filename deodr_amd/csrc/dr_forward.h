@@ -445,10 +445,22 @@ __global__ __launch_bounds__(SCAN_BLOCK) void tile_scan_kernel(KParams p)
 		w.edge_cnt[tile] = 0;
 	}
 	const unsigned long long wm = __ballot(work);
+	// the bitmap of this forward's parity (the other one is the forward's before it: fill_unit), and whose frame it describes
+	uint32_t *const bits = tile_bitmap(p, w, w.hdr->cur);
 	if (lane == 0 && valid)
-		w.tile_bits[tile >> 5] = (uint32_t)wm;
+		bits[tile >> 5] = (uint32_t)wm;
 	if (lane == 32 && valid)
-		w.tile_bits[tile >> 5] = (uint32_t)(wm >> 32);
+		bits[tile >> 5] = (uint32_t)(wm >> 32);
+	if (blockIdx.x == 0 && threadIdx.x == 0)
+	{
+		FillRecord *const rec = fill_records(p, w) + (w.hdr->cur & 1u);
+		rec->image = (uint64_t)(uintptr_t)p.image;
+		rec->zbuf = (uint64_t)(uintptr_t)p.zbuf;
+		rec->n_views = (uint32_t)p.n_views;
+		rec->height = (uint32_t)p.H;
+		rec->width = (uint32_t)p.W;
+		rec->valid = 1u + (p.pix_f64 ? 1u : 0u);
+	}
 	// ---- compaction: rank inside the wavefront, wavefront totals through LDS, ONE atomic per class and block
 	// (fit step with fused edge tiles: every tile with edges is a long wavefront -- forward, reverse sweep, pass 1 -- and must be in
 	// the head of the list, which the workgroups compiled for that adjoint walk)
@@ -699,13 +711,17 @@ __device__ __forceinline__ void fill_run(const KParams &p, int view, int32_t *fa
 	}
 }
 
+// the tiles of bitmap word wi that exist (the last word of a view may be a partial one)
+__device__ __forceinline__ uint32_t word_tiles(const KParams &p, int wi)
+{
+	const int valid = p.L.ntiles - wi * 32;
+	return valid >= 32 ? 0xffffffffu : (valid <= 0 ? 0u : (1u << valid) - 1u);
+}
+
 template <class PixT>
-__device__ __forceinline__ void fill_word(const KParams &p, int view, int wi, int lane, int owners)
-{ // background of the empty tiles of bitmap word wi of the view (one wavefront)
-	const ViewPtrs w = view_ptrs(p, view);
-	const int base = wi * 32, valid = p.L.ntiles - base < 32 ? p.L.ntiles - base : 32;
-	uint32_t empty = ~w.tile_bits[wi] & (valid == 32 ? 0xffffffffu : (1u << valid) - 1u);
-	empty = (uint32_t)uniform((int)empty);
+__device__ __forceinline__ void fill_word_mask(const KParams &p, const ViewPtrs &w, int view, int wi, int lane, int owners, uint32_t empty)
+{ // background of the tiles `empty` (wave-uniform, existing tiles only) of bitmap word wi of the view (one wavefront)
+	const int base = wi * 32;
 	if (!empty)
 		return;
 	const int C = p.C;
@@ -777,6 +793,14 @@ __device__ __forceinline__ void fill_word(const KParams &p, int view, int wi, in
 }
 
 template <class PixT>
+__device__ __forceinline__ void fill_word(const KParams &p, int view, int wi, int lane, int owners)
+{ // background of every empty tile of bitmap word wi of the view (one wavefront)
+	const ViewPtrs w = view_ptrs(p, view);
+	const uint32_t empty = ~tile_bitmap(p, w, w.hdr->cur)[wi] & word_tiles(p, wi);
+	fill_word_mask<PixT>(p, w, view, wi, lane, owners, (uint32_t)uniform((int)empty));
+}
+
+template <class PixT>
 __global__ __launch_bounds__(64 * FILL_WAVES) void fill_kernel(KParams p, int owners)
 {
 	const int gw = blockIdx.x * FILL_WAVES + (threadIdx.x >> 6);
@@ -815,21 +839,59 @@ __host__ __device__ inline int fill_share(int fill_mode, int bit, int nwords)
 	const int extra = rest - off < 0 ? 0 : (rest - off > w ? w : rest - off);
 	return full * w + extra;
 }
-// workgroups (edge kernel: per view, along grid y, limited to 65535) that stream a share of n words: one word each up to a cap,
+// workgroups (edge kernel: per view, along grid y, limited to 65535) that stream a share of n units (fill_units): one each up to a cap,
 // beyond it (frames of more than ~4 M tiles) every workgroup takes several
 __host__ __device__ inline int fill_share_blocks(int n) { return n < 32768 ? n : 32768; }
-__device__ __forceinline__ void fill_share_word(const KParams &p, int bit, int view, int i, int lane)
-{ // the i-th word of the share of kernel `bit`
+// A retained fit step (KParams::retained) has next to nothing to fill -- the tiles that were empty in the forward before it still hold background and
+// +inf --, so its share of the words is dealt 64 to a wavefront, one per lane, instead of one to a wavefront: the UNITS of a share are what the grids
+// count and what fill_unit takes.  Without the claim a unit is a word and every grid is what it was.
+constexpr int FILL_UNIT_WORDS = 64;
+__host__ __device__ inline int fill_units(int retained, int fill_mode, int bit, int nwords)
+{
+	const int share = fill_share(fill_mode, bit, nwords);
+	return retained ? (share + FILL_UNIT_WORDS - 1) / FILL_UNIT_WORDS : share;
+}
+template <class PixT>
+__device__ __forceinline__ void fill_unit_of(const KParams &p, int bit, int view, int u, int lane)
+{
 	int den, off;
 	fill_split(p.fill_mode, bit, den, off);
 	const int w = fill_weight(bit);
+	const bool retained = p.retained != 0;
+	const ViewPtrs vw = view_ptrs(p, view);
+	const uint32_t cur = vw.hdr->cur & 1u; // (fixed by the set-up kernel for the whole step: the forward raster only advances `epoch`)
+	// the word of this lane: the u-th of the share for every lane, or (retained) word 64 u + lane of it
+	const int i = retained ? u * FILL_UNIT_WORDS + lane : u;
 	const int wi = (i / w) * den + off + i % w;
-	if (wi >= p.L.nwords)
-		return;
+	uint32_t mask = 0;
+	if (i < fill_share(p.fill_mode, bit, p.L.nwords) && wi < p.L.nwords)
+	{
+		uint32_t before = 0xffffffffu; // tiles that may hold something else than background: all of them, unless the claim is made AND checks out
+		if (retained)
+		{ // the forward before this one left a bitmap and wrote the same buffers (wave-uniform; a zero-filled workspace, an un-staged forward, a
+		  // forward without a frame, into other buffers or of another frame shape: everything is filled)
+			const FillRecord *r = fill_records(p, vw) + (1u - cur);
+			if (r->valid == 1u + (p.pix_f64 ? 1u : 0u) && p.image && p.zbuf && r->image == (uint64_t)(uintptr_t)p.image &&
+				r->zbuf == (uint64_t)(uintptr_t)p.zbuf && r->n_views == (uint32_t)p.n_views && r->height == (uint32_t)p.H && r->width == (uint32_t)p.W)
+				before = tile_bitmap(p, vw, 1u - cur)[wi];
+		}
+		mask = ~tile_bitmap(p, vw, cur)[wi] & before & word_tiles(p, wi);
+	}
+	// the lanes whose word has work, one after the other through the whole wavefront (not retained: every lane holds the same word -- lane 0's)
+	unsigned long long todo = __ballot(mask != 0) & (retained ? ~0ull : 1ull);
+	while (todo)
+	{
+		const int src = __ffsll((long long)todo) - 1;
+		todo &= todo - 1;
+		fill_word_mask<PixT>(p, vw, view, __builtin_amdgcn_readlane(wi, src), lane, 0, (uint32_t)__builtin_amdgcn_readlane((int)mask, src));
+	}
+}
+__device__ __forceinline__ void fill_unit(const KParams &p, int bit, int view, int u, int lane)
+{ // the u-th unit of the share of kernel `bit` (one wavefront)
 	if (p.pix_f64)
-		fill_word<double>(p, view, wi, lane, 0);
+		fill_unit_of<double>(p, bit, view, u, lane);
 	else
-		fill_word<float>(p, view, wi, lane, 0);
+		fill_unit_of<float>(p, bit, view, u, lane);
 }
 
 // Grid of the staged forward (1-D, one wavefront per workgroup).  Workgroup b: view (b / 8) % n_views,
@@ -1814,7 +1876,7 @@ __global__ __launch_bounds__(64, DR_FWD_WAVES) void raster_fwd_fast_kernel(KPara
 	// nothing" -- with the heavy tiles still deciding when the kernel ends.)
 	constexpr bool WGT = VAR == 3;
 	static_assert(!WGT || (FUSED && CLAMP && TEXE < 2), "weighted instances: fused, clamp-capable, one kernel");
-	const uint32_t n_walk = (uint32_t)p.n_views * p.fwd_walkers, n_fill = p.fwd_n_fill; // (= n_views * fill_share(fill_mode, 2, nwords), from the host)
+	const uint32_t n_walk = (uint32_t)p.n_views * p.fwd_walkers, n_fill = p.fwd_n_fill; // (= n_views * fill_units(retained, fill_mode, 2, nwords), from the host)
 	const uint32_t dealt = (FUSED && !TEX) ? p.fwd_dealt : 0; // groups of 64 walkers + 8 fill workgroups (the host: fuse_edges && n_walk >= 8 n_fill ? n_fill / 8 : 0)
 	uint32_t b = blockIdx.x + p.block_base; // (32-bit throughout: see fwd_tiles)
 	int fi = -1;
@@ -1837,7 +1899,7 @@ __global__ __launch_bounds__(64, DR_FWD_WAVES) void raster_fwd_fast_kernel(KPara
 		DR_WAVE_TRACE_SCOPE(2);
 		DR_WAVE_TRACE_ROLE(1u);
 		if ((uint32_t)fi < n_fill)
-			fill_share_word(p, 2, (int)((uint32_t)fi % (uint32_t)p.n_views), (int)((uint32_t)fi / (uint32_t)p.n_views), wave_lane());
+			fill_unit(p, 2, (int)((uint32_t)fi % (uint32_t)p.n_views), (int)((uint32_t)fi / (uint32_t)p.n_views), wave_lane());
 		return;
 	}
 	if constexpr (TEXE == 2)

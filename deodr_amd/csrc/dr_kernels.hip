@@ -59,6 +59,7 @@
 #include "dr_dispatch.h"
 #include "../../include/deodr_hip_texture.h"
 #include "../../include/deodr_hip_subdiv.h"
+#include "../../include/deodr_hip_retained.h"
 #include "dr_fititer.h" // <- dr_finalize.h <- dr_backward.h <- dr_backward_generic.h <- dr_forward.h <- dr_forward_generic.h <- dr_setup.h <- dr_workspace.h <- dr_prims.h
 #include "dr_texfit.h"  // texture smoothness + step (include/deodr_hip_texture.h); uses grid_sum of dr_fronthalf.h
 #include "dr_subdiv.h"  // rows of a sparse matrix applied to [batch, n, D] blocks (include/deodr_hip_subdiv.h): Loop subdivision and its adjoint
@@ -418,7 +419,7 @@ void forward_launch_constants(KParams &q)
 	q.fwd_heads = chunked ? (uint32_t)(q.tile_blocks / q.heavy_share) : 0u;
 	q.fwd_walkers = (uint32_t)q.tile_blocks;
 	const uint32_t n_walk = (uint32_t)q.n_views * q.fwd_walkers;
-	q.fwd_n_fill = (uint32_t)q.n_views * (uint32_t)fill_share(q.fill_mode, 2, q.L.nwords);
+	q.fwd_n_fill = (uint32_t)q.n_views * (uint32_t)fill_units(q.retained, q.fill_mode, 2, q.L.nwords);
 	q.fwd_dealt = (q.fuse_edges && n_walk >= 8 * q.fwd_n_fill) ? q.fwd_n_fill / 8 : 0u;
 	q.views_magic = q.n_views == 1 ? 0xffffffffu : (uint32_t)(0x100000000ull / (unsigned long long)q.n_views) + 1u; // (see div_views)
 }
@@ -468,8 +469,8 @@ int launch_forward_staged(const KParams &p, bool fused, hipStream_t stream, hipE
 			return 1;
 		*join = ss.join;
 	}
-	// (+ the workgroups that stream this kernel's share of the background of the empty tiles, one bitmap word each)
-	const dim3 grid((unsigned)p.n_views * (unsigned)q.fwd_walkers + (unsigned)p.n_views * (unsigned)fill_share(p.fill_mode, 2, p.L.nwords));
+	// (+ the workgroups that stream this kernel's share of the background of the empty tiles, one unit each: a bitmap word, or 64 in a retained step)
+	const dim3 grid((unsigned)p.n_views * (unsigned)q.fwd_walkers + (unsigned)q.fwd_n_fill);
 	const bool tex = p.texture != nullptr;
 	hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
 	if (fused && tex && p.fuse_edges)
@@ -552,7 +553,7 @@ int launch_adjoint(const DeodrHipScene *sc, KParams &p, hipStream_t st, bool own
 	// persistent waves of the edge kernel: enough to cover a silhouette-heavy single view, few enough that with many views
 	// the waves that find their sub-list exhausted cost nothing
 	const int edge_waves = p.L.ntiles < EDGE_WAVES ? p.L.ntiles : EDGE_WAVES;
-	dim3 edge_grid(sc->n_views, edge_waves + (fast ? fill_share_blocks(fill_share(p.fill_mode, 0, p.L.nwords)) : 0));
+	dim3 edge_grid(sc->n_views, edge_waves + (fast ? fill_share_blocks(fill_units(p.retained, p.fill_mode, 0, p.L.nwords)) : 0));
 	if (!fast || owner_tiles || (p.sigma > 0 && !p.fuse_edges)) // (a fit step with fused edge tiles launches nothing here)
 	{
 		ScopedKernelTimer t(KID_RASTER_BWD, st);
@@ -562,7 +563,7 @@ int launch_adjoint(const DeodrHipScene *sc, KParams &p, hipStream_t st, bool own
 	}
 	if (p.T > 0)
 	{
-		const int fill_words = fast ? sc->n_views * fill_share(p.fill_mode, 1, p.L.nwords) : 0;
+		const int fill_words = fast ? sc->n_views * fill_units(p.retained, p.fill_mode, 1, p.L.nwords) : 0; // (units: one wavefront each)
 		dim3 g2(prim_grid(p, sc->n_views, false) + (unsigned)((fill_words + PRIM_BLOCK / 64 - 1) / (PRIM_BLOCK / 64)) +
 				(p.loss_out ? 1u : 0u)); // (+ the workgroup that adds up the loss)
 		ScopedKernelTimer t(KID_FINALIZE, st);
@@ -772,7 +773,7 @@ static int l2_loss_impl(const void *image, const void *obs, int pixel_dtype, siz
 					   int clamp, double clamp_lo, double clamp_hi, const void *weights = nullptr, int nb_colors = 1);
 
 static int render_scene_fit_impl(const DeodrHipScene *sc, void *image, void *z_buffer, double sigma, const void *obs, int clear_gradients,
-								 const DeodrHipFitOptions *opt, void *workspace, size_t workspace_bytes, void *stream)
+								 const DeodrHipFitOptions *opt, void *workspace, size_t workspace_bytes, void *stream, int retained = 0)
 {
 	const double *tile_loss = opt ? opt->tile_loss : nullptr;
 	double *loss_out = opt ? opt->loss : nullptr, *loss_scratch = opt ? (double *)opt->loss_scratch : nullptr;
@@ -812,6 +813,9 @@ static int render_scene_fit_impl(const DeodrHipScene *sc, void *image, void *z_b
 	// 0.448 -> 0.451 / 0.890 -> 0.893: profiles/r05y_ab_fused_textured_edge_tiles.txt).  (sigma = 0: no edge anywhere, the lighter instances)
 	p.fuse_edges = fused && (!p.texture || sigma > 0);
 	p.fill_mode = fused ? (((sigma > 0 && !p.fuse_edges) ? 1 : 0) | (p.T > 0 ? 2 : 0) | ((p.T > 0 && p.fuse_edges) ? 4 : 0)) : 0;
+	// the caller's claim that the buffers still hold the frame of the forward before this one: only where the fill rides on the step's kernels
+	// (the stand-alone fill_kernel fills every empty tile whatever is claimed), and only believed by a fill wavefront that finds it confirmed
+	p.retained = (retained && p.fill_mode != 0) ? 1 : 0;
 	note_forward(workspace, fused);
 	hipEvent_t join = nullptr;
 	if (launch_forward(sc, p, st, &join, fused))
@@ -852,6 +856,15 @@ int deodr_hip_render_scene_fit_ex(const DeodrHipScene *sc, void *image, void *z_
 								  const DeodrHipFitOptions *options, void *workspace, size_t workspace_bytes, void *stream)
 {
 	return render_scene_fit_impl(sc, image, z_buffer, sigma, obs, clear_gradients, options, workspace, workspace_bytes, stream);
+}
+
+// ---- include/deodr_hip_retained.h
+int deodr_hip_retained_abi_version(void) { return DEODR_HIP_RETAINED_ABI_VERSION; }
+
+int deodr_hip_render_scene_fit_retained(const DeodrHipScene *sc, void *image, void *z_buffer, double sigma, const void *obs, int clear_gradients,
+										const DeodrHipFitOptions *options, int retained, void *workspace, size_t workspace_bytes, void *stream)
+{
+	return render_scene_fit_impl(sc, image, z_buffer, sigma, obs, clear_gradients, options, workspace, workspace_bytes, stream, retained);
 }
 
 static size_t loss_table_doubles(int height, int width, int n_views)
@@ -1433,7 +1446,8 @@ int deodr_hip_workspace_census(const DeodrHipScene *sc, void *workspace, size_t 
 		const char *base = (const char *)workspace + (size_t)v * p.L.view_bytes;
 		WsHeader h;
 		if (check_hip(hipMemcpy(&h, base + p.L.hdr, sizeof h, hipMemcpyDeviceToHost), "census copy") ||
-			check_hip(hipMemcpy(bits.data(), base + p.L.tile_bits, sizeof(uint32_t) * p.L.nwords, hipMemcpyDeviceToHost), "census copy") ||
+			// (the bitmap of the last forward's parity)
+			check_hip(hipMemcpy(bits.data(), base + p.L.tile_bits + sizeof(uint32_t) * p.L.nwords * (h.cur & 1u), sizeof(uint32_t) * p.L.nwords, hipMemcpyDeviceToHost), "census copy") ||
 			check_hip(hipMemcpy(saved.data(), base + p.L.edge_saved, sizeof(uint32_t) * p.L.ntiles, hipMemcpyDeviceToHost), "census copy"))
 			return 1;
 		for (int t = 0; t < p.L.ntiles; t++)

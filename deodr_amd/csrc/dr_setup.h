@@ -276,6 +276,7 @@ __global__ __launch_bounds__(PRIM_BLOCK, PRIM_WAVES) void setup_bin_kernel(KPara
 		w.hdr->edge_spill[1 - cur] = 0;
 		w.hdr->snap_count[1 - cur] = 0;
 		w.hdr->work_count[0] = w.hdr->work_count[1] = 0; // filled by tile_scan_kernel, read by the forward raster
+		fill_records(p, w)[cur].valid = 0; // no tile bitmap of this parity yet: tile_scan_kernel sets it (an un-staged forward runs none)
 	}
 	if (item <= EDGE_LISTS) // appended to by tile_scan_kernel, the next kernel on the stream
 		w.edge_tile_cnt[item * CNT_STRIDE] = 0;

@@ -91,6 +91,19 @@ static_assert(offsetof(WsHeader, all_needed_max) == 4 * DEODR_HIP_STATUS_WORD_NE
 constexpr int DONE_SUBS = 256, DONE_STRIDE = 16;
 constexpr int LOSS_SLOTS = 256; // partial sums of the loss per view (one per walker was 32 768 values for ONE workgroup to add up: 20 us)
 
+// What the forward of one parity wrote its frame into, kept per view behind the two tile bitmaps.  A fit step launched with KParams::retained
+// fills only the tiles that are empty now and were not in the forward before it -- the others still hold background and +inf from then -- and
+// its fill wavefronts believe that only when the record of the other parity says that THAT forward wrote the same buffers.  `valid`: 0 = no
+// bitmap of that parity (cleared by the set-up kernel, which every forward with triangles runs; a new workspace is zero-filled), else 1 +
+// pixel type, set by tile_scan_kernel together with the bitmap -- so a forward of the un-staged family, which runs no scan, leaves it clear.
+struct FillRecord
+{
+	uint64_t image, zbuf; // KParams::image / zbuf of that forward (0: it wrote no frame)
+	uint32_t valid, n_views;
+	uint32_t height, width; // (two frame shapes may share a tile count, and with it the workspace layout: 64 x 64 and 32 x 128)
+};
+static_assert(sizeof(FillRecord) == 32, "");
+
 struct Layout
 {
 	size_t hdr, tri_rec, tri_planes, tri_acc, edge_rec, edge_planes, edge_acc, tri_cnt, edge_cnt, edge_saved, tri_list, edge_list, tri_pool,
@@ -139,7 +152,9 @@ Layout make_layout(int T, int H, int W, int C, size_t pool_pairs)
 	// one bit per tile (the tile received a primitive) and the work list of the staged forward: one uint4 {tile, triangles,
 	// edges, sweep slot} per non-empty tile, both written by tile_scan_kernel between set-up and forward raster
 	L.nwords = (L.ntiles + 31) / 32;
-	L.tile_bits = take(sizeof(uint32_t) * L.nwords);
+	// TWO bitmaps, alternating by the parity of the forward (WsHeader::cur), and behind them one FillRecord per parity: what a retained fit
+	// step needs to know about the forward before it (fill_unit, dr_forward.h)
+	L.tile_bits = take(sizeof(uint32_t) * 2 * L.nwords + 2 * sizeof(FillRecord));
 	// one entry per non-empty tile (many-primitive tiles from the front, the others from the back) + the extra copies of the tiles of many
 	// edges, at most SPLIT_BUDGET per block of the scan kernel (tile_scan_kernel)
 	L.work_cap = L.ntiles + ((L.ntiles + SCAN_TILES - 1) / SCAN_TILES) * SPLIT_BUDGET;
@@ -183,7 +198,7 @@ struct KParams
 		// Fit step (aa_err == 0): per-pixel weights (DeodrHipFitOptions::weights), [n_views][H][W] in the pixel type, NULL: none.
 		// L = sum_p w[p] sum_c (f(image) - obs)^2, residual w[p] * fit_residual.  Read only by the instances compiled for it (WGT: fit_weight
 		// below).  The two never meet -- a fit step has no error buffer, antialiase_error takes no weights -- and sharing the slot keeps
-		// sizeof(KParams) and the kernel-argument layout of every other instance what they were measured with (see kparams_pad; the un-staged
+		// sizeof(KParams) and the kernel-argument layout of every other instance what they were measured with (see `retained`; the un-staged
 		// kernels also keep a copy of KParams in scratch).  Host code asks fit_weights(p), never p.weights alone.
 		const void *weights;
 	};
@@ -229,10 +244,12 @@ struct KParams
 	int pair_tex;		  // tile_scan_kernel: textured scenes pair their edge-free tiles too (launches of fewer than TEX_TWO_KERNELS views)
 	int setup_sparse;	  // set-up kernel: a triangle every `setup_sparse` lanes (1, or 4 for small launches: dr_setup.h)
 	uint32_t fwd_walkers; // walkers per view in the forward raster's grid: tile_blocks
-	// (4 bytes that nothing reads.  They keep the kernel-argument layout the staged forward's register allocation was measured with: without
-	// them the fields below move by 8 bytes and the spills of the textured instances move with them -- the float64 and 4-channel textured fit
-	// steps of 8 views were 1 - 2 % slower)
-	int kparams_pad;
+	// Fit step whose fill rides on its kernels (fill_mode != 0): the caller states that image / zbuf still hold what the forward before this one
+	// wrote and that the background has not changed (deodr_hip_render_scene_fit_retained).  Read by the fill wavefronts only (fill_unit), and it
+	// decides the fill part of the grids (fill_units).  (Until this flag the 4 bytes were padding nobody read: they keep the kernel-argument layout
+	// the staged forward's register allocation was measured with -- without them the fields below move by 8 bytes and the spills of the textured
+	// instances move with them: the float64 and 4-channel textured fit steps of 8 views were 1 - 2 % slower.)
+	int retained;
 	uint32_t fwd_heads;	  // walkers per view on the head of the work list: tile_blocks / heavy_share (0: the list has one class)
 	uint32_t fwd_n_fill;  // workgroups of this launch that stream the background of the forward's share of the empty tiles
 	uint32_t fwd_dealt;	  // of those, groups of eight dealt among the walkers (behind every 64), see raster_fwd_fast_kernel
@@ -352,6 +369,10 @@ __device__ __forceinline__ ViewPtrs view_ptrs(const KParams &p, int view)
 	v.edge_snap = b + p.L.edge_snap;
 	return v;
 }
+
+// the tile bitmap of one parity and the two fill records behind the bitmaps (Layout::tile_bits)
+__device__ __forceinline__ uint32_t *tile_bitmap(const KParams &p, const ViewPtrs &w, uint32_t parity) { return w.tile_bits + (size_t)(parity & 1u) * p.L.nwords; }
+__device__ __forceinline__ FillRecord *fill_records(const KParams &p, const ViewPtrs &w) { return (FillRecord *)(w.tile_bits + 2 * (size_t)p.L.nwords); }
 
 __device__ __forceinline__ SceneView scene_view(const KParams &p, int view)
 {

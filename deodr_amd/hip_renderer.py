@@ -30,6 +30,8 @@ _HT = _abi.TEXTURE_HEADER  # the companion header include/deodr_hip_texture.h (t
 TEXTURE_ABI_VERSION, MAX_COLORS = _HT.defines["DEODR_HIP_TEXTURE_ABI_VERSION"], _H.defines["DEODR_HIP_MAX_COLORS"]
 _HS = _abi.SUBDIV_HEADER  # the companion header include/deodr_hip_subdiv.h (Loop subdivision), bound onto the same library
 SUBDIV_ABI_VERSION = _HS.defines["DEODR_HIP_SUBDIV_ABI_VERSION"]
+_HR = _abi.RETAINED_HEADER  # the companion header include/deodr_hip_retained.h (fit step into retained frames), bound onto the same library
+RETAINED_ABI_VERSION = _HR.defines["DEODR_HIP_RETAINED_ABI_VERSION"]
 # words of the 64-byte status block at the start of the workspace
 _STATUS_NEEDED, _STATUS_ERRORS = _H.defines["DEODR_HIP_STATUS_WORD_NEEDED_PAIRS"], _H.defines["DEODR_HIP_STATUS_WORD_SCENE_ERRORS"]
 
@@ -54,6 +56,9 @@ def lib():
         _abi.bind(L, _HS)
         if L.deodr_hip_subdiv_abi_version() != SUBDIV_ABI_VERSION:
             raise ImportError("libdeodr_hip.so subdivision ABI version mismatch (include/deodr_hip_subdiv.h); rebuild it")
+        _abi.bind(L, _HR)
+        if L.deodr_hip_retained_abi_version() != RETAINED_ABI_VERSION:
+            raise ImportError("libdeodr_hip.so retained-frames ABI version mismatch (include/deodr_hip_retained.h); rebuild it")
         _lib = _abi.bind(L)
     return _lib
 
@@ -428,7 +433,7 @@ class DeviceScene:
 
 # What the workspace of a HipRasterizer holds the forward state of; the tensors are kept alive with it (the launches that read them may
 # still be queued).  fused: a fit step -- its forward raster has already back-propagated through the tiles without edges and kept no owner ids.
-_Forward = namedtuple("_Forward", "scene sigma antialiase_error obs image err_buffer generation fused weights")
+_Forward = namedtuple("_Forward", "scene sigma antialiase_error obs image err_buffer generation fused weights z")
 
 
 class HipRasterizer:
@@ -443,10 +448,22 @@ class HipRasterizer:
     of the workspace is copied asynchronously to pinned memory (every ``poll_every`` forwards, and after each of the first
     two) and inspected at the next call.  An overflow found that way means that frames rendered since the poll were
     incomplete: the workspace is regrown and a RuntimeError says so.  ``check_overflow=True`` on a call checks synchronously
-    (and regrows / repeats transparently)."""
+    (and regrows / repeats transparently).
 
-    def __init__(self, nb_triangles, height, width, nb_colors, n_views=1, device="cuda", pool_pairs=0, poll_every=8):
+    ``retain_frames`` (default True; an attribute, may be switched at any time): a fit loop renders into the same ``out=(image, z)`` at every
+    iteration, and two tiles out of three of a typical frame are background before and after.  :meth:`render_fit` then tells the library that
+    the buffers still hold the previous frame (``deodr_hip_render_scene_fit_retained``), and the step writes the background only into the
+    tiles that have just become empty -- same image, depth buffer and gradients, half of the bytes.  It says so only when it can see that
+    it is true: the previous forward of this very workspace allocation, on the same stream and not captured into a graph, wrote the same two
+    tensor objects; torch has counted no in-place operation on them since (``_version``); the scene's background tensor and its version are
+    the same.  Anything else -- a new ``out``, ``image.fill_()``, a regrown workspace, another background -- is a full fill, and the library
+    checks the buffer addresses again on the device.  THE ONE ASSUMPTION LEFT: torch counts what torch does.  Code that writes ``image`` / ``z``
+    or the background through raw pointers (a kernel of its own, another HipRasterizer rendering into the same tensors) must bump their
+    version (``torch.autograd.graph.increment_version``) or set ``retain_frames = False``."""
+
+    def __init__(self, nb_triangles, height, width, nb_colors, n_views=1, device="cuda", pool_pairs=0, poll_every=8, retain_frames=True):
         self.dims = (int(nb_triangles), int(height), int(width), int(nb_colors), int(n_views))
+        self.retain_frames = bool(retain_frames)
         self.device = _resolve_device(device)
         self.poll_every = int(poll_every)
         self.generation = 0
@@ -470,12 +487,14 @@ class HipRasterizer:
         self._checked = False
         self._pool_cap = None
         self._last = None  # the _Forward whose state the workspace holds
+        self._kept = None  # _frame_state() right after that forward, when it wrote a frame and a depth buffer (retain_frames)
+        self._entry_of = self._entry = None  # the library whose retained entry was looked up, and the entry (_retained_entry)
         self._loss_cache = None  # (the background-loss table belongs to one (observation, background, clamp) of one workspace)
         self.alloc_count += 1
 
     @classmethod
-    def for_scene(cls, ds, pool_pairs=0):
-        return cls(ds.nb_triangles, ds.height, ds.width, ds.nb_colors, ds.n_views, ds.device, pool_pairs)
+    def for_scene(cls, ds, pool_pairs=0, retain_frames=True):
+        return cls(ds.nb_triangles, ds.height, ds.width, ds.nb_colors, ds.n_views, ds.device, pool_pairs, retain_frames=retain_frames)
 
     # ---- status ------------------------------------------------------------------------------------------------------
 
@@ -565,10 +584,48 @@ class HipRasterizer:
         # the pool doubles every time: this is not a scene that needs more room, something is wrong
         raise RuntimeError("deodr_hip: the spill pool still overflows after 16 regrows")
 
-    def _stamp(self, ds, sigma, antialiase_error, obs, image, err_buffer=None, fused=False, weights=None):
-        """The workspace now holds the forward state of these: a new generation."""
+    def _frame_state(self, ds, image, z):
+        """what must not have changed between two forwards for the second to claim that (image, z) still hold the first one's frame: the
+        allocation, the stream, torch's count of in-place operations on the two buffers, the background (tensor and count; the tensors are part
+        of the state, so they stay alive and no new one can land on a kept address), the shape of the launch"""
+        return (self.alloc_count, torch.cuda.current_stream(self.device).cuda_stream, image._version, z._version, ds.background_color,
+                None if ds.background_color is None else ds.background_color._version, ds.background_image,
+                None if ds.background_image is None else ds.background_image._version, ds.n_views, self.dims)  # fmt: skip
+
+    @staticmethod
+    def _same_state(a, b):
+        return a is not None and b is not None and len(a) == len(b) and all(x is y if torch.is_tensor(x) or torch.is_tensor(y) else x == y for x, y in zip(a, b))
+
+    def _retained_entry(self):
+        """``deodr_hip_render_scene_fit_retained`` of the loaded library, looked up once per library object; None: it has none (the test harness's)"""
+        L = lib()
+        if self._entry_of is not L:
+            self._entry_of, self._entry = L, getattr(L, "deodr_hip_render_scene_fit_retained", None)
+        return self._entry
+
+    def _retained_claim(self, ds, image, z):
+        """-> (claim, state): 1 when this fit step may tell the library that (image, z) still hold the frame of the previous forward on this
+        workspace (see the class), and the :meth:`_frame_state` to keep once the step has been launched (None: a captured launch runs when the
+        graph is replayed, any number of times and whatever happens in between -- nothing is known afterwards).  What was kept is forgotten
+        here: a step that fails after its scan has left a bitmap of a frame that was never written, and the next one must fill everything."""
+        last, kept, self._kept = self._last, self._kept, None
+        state = None if torch.cuda.is_current_stream_capturing() else self._frame_state(ds, image, z)
+        return int(last is not None and last.image is image and last.z is z and self._same_state(kept, state)), state
+
+    _COMPUTE = object()
+
+    def _stamp(self, ds, sigma, antialiase_error, obs, image, err_buffer=None, fused=False, weights=None, z=None, state=_COMPUTE):
+        """The workspace now holds the forward state of these: a new generation.  ``z``: the depth buffer that forward wrote, when it wrote one
+        next to ``image`` (None: a forward that rendered no frame -- the next fit step claims nothing); ``state``: their :meth:`_frame_state`
+        when the caller has formed it already"""
         self.generation += 1
-        self._last = _Forward(ds, float(sigma), bool(antialiase_error), obs, image, err_buffer, self.generation, fused, weights)
+        self._last = _Forward(ds, float(sigma), bool(antialiase_error), obs, image, err_buffer, self.generation, fused, weights, z)
+        if z is None or image is None:
+            self._kept = None
+        elif state is not HipRasterizer._COMPUTE:
+            self._kept = state
+        else:  # (a captured launch: see _retained_claim)
+            self._kept = None if torch.cuda.is_current_stream_capturing() else self._frame_state(ds, image, z)
 
     # ---- calls -------------------------------------------------------------------------------------------------------
 
@@ -589,6 +646,8 @@ class HipRasterizer:
                 obs_t = _on(obs, ds.device, pd, (n, H, W, Cc), "obs")
                 err = torch.empty((n, H, W), dtype=pd, device=ds.device)
 
+            self._kept = None  # (until this forward has been launched: see _retained_claim)
+
             def launch():
                 _check(lib().deodr_hip_render_scene(C.byref(sc), _ptr(image), _ptr(z), float(sigma), int(antialiase_error), _ptr(obs_t),
                                                     _ptr(err), _ptr(self.workspace), self.nbytes, _stream(self.device)))  # fmt: skip
@@ -599,7 +658,7 @@ class HipRasterizer:
             else:
                 launch()
                 self._poll()
-        self._stamp(ds, sigma, antialiase_error, obs_t, image, err)
+        self._stamp(ds, sigma, antialiase_error, obs_t, image, err, z=z)
         return (image, z, err) if antialiase_error else (image, z)
 
     def _loss_table(self, ds, sc, obs_t, options, weights_t=None):
@@ -666,7 +725,15 @@ class HipRasterizer:
             self._inspect_poll(sc)
             if done_flag is not None and (done_flag[0].element_size() != 4 or done_flag[0].numel() != 1 or done_flag[0].device != ds.device):
                 raise ValueError("done_flag must be (a 4-byte integer tensor of one element on the scene's device, value)")
-            if loss_out is None and clamp is None and done_flag is None and weights_t is None:
+            # (a library without the entry -- the test harness's -- is called as ever)
+            retained_entry = self._retained_entry() if self.retain_frames else None
+            claim, state = self._retained_claim(ds, image, z) if retained_entry is not None else (0, HipRasterizer._COMPUTE)
+            self._kept = None  # (until this step has been launched: a step that fails is followed by a full fill)
+            plain = loss_out is None and clamp is None and done_flag is None and weights_t is None
+            if plain and retained_entry is not None:
+                _check(retained_entry(C.byref(sc), _ptr(image), _ptr(z), float(sigma), _ptr(obs_t), int(bool(clear_grads)), None, claim,
+                                      _ptr(self.workspace), self.nbytes, _stream(self.device)))  # fmt: skip
+            elif plain:
                 _check(lib().deodr_hip_render_scene_fit(C.byref(sc), _ptr(image), _ptr(z), float(sigma), _ptr(obs_t), int(bool(clear_grads)),
                                                         _ptr(self.workspace), self.nbytes, _stream(self.device)))  # fmt: skip
             else:
@@ -682,10 +749,14 @@ class HipRasterizer:
                         raise ValueError("loss_out must be a float64 tensor of one element on the scene's device")
                     table, scratch = self._loss_table(ds, sc, obs_t, options, weights_t)
                     options.tile_loss, options.loss, options.loss_scratch = table.data_ptr(), loss_out.data_ptr(), scratch.data_ptr()
-                _check(lib().deodr_hip_render_scene_fit_ex(C.byref(sc), _ptr(image), _ptr(z), float(sigma), _ptr(obs_t), int(bool(clear_grads)),
-                                                           C.byref(options), _ptr(self.workspace), self.nbytes, _stream(self.device)))  # fmt: skip
+                if retained_entry is not None:
+                    _check(retained_entry(C.byref(sc), _ptr(image), _ptr(z), float(sigma), _ptr(obs_t), int(bool(clear_grads)), C.byref(options), claim,
+                                          _ptr(self.workspace), self.nbytes, _stream(self.device)))  # fmt: skip
+                else:
+                    _check(lib().deodr_hip_render_scene_fit_ex(C.byref(sc), _ptr(image), _ptr(z), float(sigma), _ptr(obs_t), int(bool(clear_grads)),
+                                                               C.byref(options), _ptr(self.workspace), self.nbytes, _stream(self.device)))  # fmt: skip
             self._poll()
-        self._stamp(ds, sigma, False, obs_t, image, fused=True, weights=weights_t)
+        self._stamp(ds, sigma, False, obs_t, image, fused=True, weights=weights_t, z=z, state=state)
         return image, z, grads
 
     def render_backward(self, ds, image_b=None, err_buffer_b=None, grads=None, have_forward_state=True, residual_obs=None,
@@ -724,6 +795,8 @@ class HipRasterizer:
                 # and the frame -- are this scene's
                 image, _z = self.render(ds, sigma, check_overflow=False)
                 state = True
+            if not state:
+                self._kept = None  # (a forward runs inside the call)
             _check(lib().deodr_hip_render_scene_b(C.byref(sc), _ptr(image), None, _ptr(ib), sigma, int(aa), _ptr(obs_t), None, _ptr(eb),
                                                   _ptr(self.workspace), self.nbytes, int(state), _stream(self.device)))  # fmt: skip
             if not state:
