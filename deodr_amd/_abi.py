@@ -14,6 +14,7 @@ HEADER_PATH = os.path.join(_INCLUDE, "deodr_hip.h")
 TEXTURE_HEADER_PATH = os.path.join(_INCLUDE, "deodr_hip_texture.h")  # the companion header (texture estimation), versioned on its own
 SUBDIV_HEADER_PATH = os.path.join(_INCLUDE, "deodr_hip_subdiv.h")  # the companion header (Loop subdivision), versioned on its own
 RETAINED_HEADER_PATH = os.path.join(_INCLUDE, "deodr_hip_retained.h")  # the companion header (fit step into retained frames), versioned on its own
+BASIS_HEADER_PATH = os.path.join(_INCLUDE, "deodr_hip_basis.h")  # the companion header (linear bases: morphable models), versioned on its own
 
 # C type (without `const`, without spaces around the stars) -> ctypes.  Data pointers are c_void_p: callers pass device addresses (Python
 # ints, c_void_p), None, byref(...) and small ctypes arrays, and c_void_p takes all of them.  int and unsigned long long are only ever
@@ -100,3 +101,5 @@ with open(SUBDIV_HEADER_PATH) as _f:
     SUBDIV_HEADER = parse(_f.read(), "include/deodr_hip_subdiv.h")
 with open(RETAINED_HEADER_PATH) as _f:
     RETAINED_HEADER = parse(_f.read(), "include/deodr_hip_retained.h", HEADER.structs)
+with open(BASIS_HEADER_PATH) as _f:
+    BASIS_HEADER = parse(_f.read(), "include/deodr_hip_basis.h")

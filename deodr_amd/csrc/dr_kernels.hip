@@ -60,9 +60,11 @@
 #include "../../include/deodr_hip_texture.h"
 #include "../../include/deodr_hip_subdiv.h"
 #include "../../include/deodr_hip_retained.h"
+#include "../../include/deodr_hip_basis.h"
 #include "dr_fititer.h" // <- dr_finalize.h <- dr_backward.h <- dr_backward_generic.h <- dr_forward.h <- dr_forward_generic.h <- dr_setup.h <- dr_workspace.h <- dr_prims.h
 #include "dr_texfit.h"  // texture smoothness + step (include/deodr_hip_texture.h); uses grid_sum of dr_fronthalf.h
 #include "dr_subdiv.h"  // rows of a sparse matrix applied to [batch, n, D] blocks (include/deodr_hip_subdiv.h): Loop subdivision and its adjoint
+#include "dr_basis.h"   // a dense [K, N] basis applied to coefficient vectors, and its adjoint (include/deodr_hip_basis.h): morphable models
 
 using namespace dr;
 using namespace dr::dispatch;
@@ -1386,6 +1388,153 @@ int deodr_hip_subdiv_apply(const uint32_t *offsets, const uint32_t *cols, const 
 		break;
 	}
 	return check_hip(hipGetLastError(), "subdiv_apply launch");
+}
+
+// ---- linear bases (include/deodr_hip_basis.h, kernels in dr_basis.h)
+
+int deodr_hip_basis_abi_version(void) { return DEODR_HIP_BASIS_ABI_VERSION; }
+
+static const char *basis_dims(int K, int N, int batch)
+{ // -> NULL, or which limit of the header the dimensions break
+	if (K < 1 || K > BASIS_MAX_K)
+		return "K must be in 1 .. 1024";
+	if (batch < 1 || batch > BASIS_MAX_BATCH)
+		return "batch must be in 1 .. 64";
+	if (N < 1 || N > BASIS_MAX_N)
+		return "N must be in 1 .. 2^30";
+	if ((unsigned long long)K * (unsigned long long)N > 0x7fffffffull)
+		return "K * N must not exceed 2^31 - 1";
+	return NULL;
+}
+
+static int basis_fail(const char *what, const char *why)
+{
+	char text[160];
+	snprintf(text, sizeof text, "%s: %s", what, why);
+	return fail(text);
+}
+
+static bool basis_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes)
+{
+	const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+	return a && b && x < y + b_bytes && y < x + a_bytes;
+}
+
+int deodr_hip_basis_segments(int K, int N) { return basis_dims(K, N, 1) ? 0 : basis_segments(K, N); }
+
+static size_t basis_counter_bytes(int K, int batch) { return (4 * (size_t)basis_chunks(batch) * (size_t)basis_row_tiles(K) + 63) / 64 * 64; }
+
+size_t deodr_hip_basis_scratch_bytes(int K, int N, int batch)
+{
+	if (basis_dims(K, N, batch))
+		return 0;
+	return basis_counter_bytes(K, batch) +
+		   sizeof(double) * (size_t)basis_chunks(batch) * (size_t)basis_row_tiles(K) * (size_t)basis_segments(K, N) * BASIS_ROW_TILE * BASIS_CHUNK;
+}
+
+int deodr_hip_basis_apply(const void *basis, const void *mean, const double *coeffs, int K, int N, int batch, int basis_dtype, void *y, int y_dtype,
+						  void *stream)
+{
+	const char *what = "basis_apply";
+	if (!basis || !coeffs || !y)
+		return basis_fail(what, "basis, coeffs or y == NULL");
+	if (const char *why = basis_dims(K, N, batch))
+		return basis_fail(what, why);
+	if ((basis_dtype != DEODR_HIP_F32 && basis_dtype != DEODR_HIP_F64) || (y_dtype != DEODR_HIP_F32 && y_dtype != DEODR_HIP_F64))
+		return fail("unknown dtype tag");
+	const size_t be = basis_dtype == DEODR_HIP_F64 ? 8 : 4, ye = y_dtype == DEODR_HIP_F64 ? 8 : 4;
+	if ((((uintptr_t)basis | (uintptr_t)mean) & (be - 1)) || ((uintptr_t)y & (ye - 1)) || ((uintptr_t)coeffs & 7))
+		return basis_fail(what, "misaligned pointer");
+	const size_t y_bytes = (size_t)batch * (size_t)N * ye;
+	if (basis_overlap(y, y_bytes, basis, (size_t)K * (size_t)N * be) || basis_overlap(y, y_bytes, mean, (size_t)N * be) ||
+		basis_overlap(y, y_bytes, coeffs, (size_t)batch * (size_t)K * 8))
+		return basis_fail(what, "y must not overlap basis, mean or coeffs");
+	BasisArgs a = {};
+	a.basis = basis, a.mean = mean, a.coeffs = coeffs, a.y = y, a.K = K, a.N = N, a.batch = batch;
+	const int pieces = N / (int)(16 / be), blocks = (pieces + FH_BLOCK - 1) / FH_BLOCK;
+	const dim3 grid((unsigned)(blocks < 1 ? 1 : blocks), (unsigned)basis_chunks(batch)), block(FH_BLOCK);
+	const hipStream_t st = (hipStream_t)stream;
+	switch (4 * (batch > 1) + 2 * (basis_dtype == DEODR_HIP_F64) + (y_dtype == DEODR_HIP_F64))
+	{
+	case 0:
+		hipLaunchKernelGGL((basis_apply_kernel<float, float, 1>), grid, block, 0, st, a);
+		break;
+	case 1:
+		hipLaunchKernelGGL((basis_apply_kernel<float, double, 1>), grid, block, 0, st, a);
+		break;
+	case 2:
+		hipLaunchKernelGGL((basis_apply_kernel<double, float, 1>), grid, block, 0, st, a);
+		break;
+	case 3:
+		hipLaunchKernelGGL((basis_apply_kernel<double, double, 1>), grid, block, 0, st, a);
+		break;
+	case 4:
+		hipLaunchKernelGGL((basis_apply_kernel<float, float, BASIS_CHUNK>), grid, block, 0, st, a);
+		break;
+	case 5:
+		hipLaunchKernelGGL((basis_apply_kernel<float, double, BASIS_CHUNK>), grid, block, 0, st, a);
+		break;
+	case 6:
+		hipLaunchKernelGGL((basis_apply_kernel<double, float, BASIS_CHUNK>), grid, block, 0, st, a);
+		break;
+	case 7:
+		hipLaunchKernelGGL((basis_apply_kernel<double, double, BASIS_CHUNK>), grid, block, 0, st, a);
+		break;
+	}
+	return check_hip(hipGetLastError(), "basis_apply launch");
+}
+
+int deodr_hip_basis_apply_b(const void *basis, const void *g, int g_dtype, int K, int N, int batch, int basis_dtype, double *coeffs_b, int accumulate,
+							void *scratch, size_t scratch_bytes, void *stream)
+{
+	const char *what = "basis_apply_b";
+	if (!basis || !g || !coeffs_b || !scratch)
+		return basis_fail(what, "basis, g, coeffs_b or scratch == NULL");
+	if (const char *why = basis_dims(K, N, batch))
+		return basis_fail(what, why);
+	if ((basis_dtype != DEODR_HIP_F32 && basis_dtype != DEODR_HIP_F64) || (g_dtype != DEODR_HIP_F32 && g_dtype != DEODR_HIP_F64))
+		return fail("unknown dtype tag");
+	const size_t be = basis_dtype == DEODR_HIP_F64 ? 8 : 4, ge = g_dtype == DEODR_HIP_F64 ? 8 : 4;
+	if (((uintptr_t)basis & (be - 1)) || ((uintptr_t)g & (ge - 1)) || (((uintptr_t)coeffs_b | (uintptr_t)scratch) & 7))
+		return basis_fail(what, "misaligned pointer");
+	const size_t c_bytes = (size_t)batch * (size_t)K * 8;
+	if (basis_overlap(coeffs_b, c_bytes, basis, (size_t)K * (size_t)N * be) || basis_overlap(coeffs_b, c_bytes, g, (size_t)batch * (size_t)N * ge))
+		return basis_fail(what, "coeffs_b must not overlap basis or g");
+	if (scratch_bytes < deodr_hip_basis_scratch_bytes(K, N, batch))
+		return basis_fail(what, "scratch too small (deodr_hip_basis_scratch_bytes)");
+	BasisArgs a = {};
+	a.basis = basis, a.g = g, a.coeffs_b = coeffs_b, a.K = K, a.N = N, a.batch = batch, a.S = basis_segments(K, N), a.accumulate = accumulate != 0;
+	a.counters = (unsigned *)scratch, a.partials = (double *)((char *)scratch + basis_counter_bytes(K, batch));
+	const dim3 grid((unsigned)a.S, (unsigned)basis_row_tiles(K), (unsigned)basis_chunks(batch)), block(FH_BLOCK);
+	const hipStream_t st = (hipStream_t)stream;
+	switch (4 * (batch > 1) + 2 * (basis_dtype == DEODR_HIP_F64) + (g_dtype == DEODR_HIP_F64))
+	{
+	case 0:
+		hipLaunchKernelGGL((basis_apply_b_kernel<float, float, 1>), grid, block, 0, st, a);
+		break;
+	case 1:
+		hipLaunchKernelGGL((basis_apply_b_kernel<float, double, 1>), grid, block, 0, st, a);
+		break;
+	case 2:
+		hipLaunchKernelGGL((basis_apply_b_kernel<double, float, 1>), grid, block, 0, st, a);
+		break;
+	case 3:
+		hipLaunchKernelGGL((basis_apply_b_kernel<double, double, 1>), grid, block, 0, st, a);
+		break;
+	case 4:
+		hipLaunchKernelGGL((basis_apply_b_kernel<float, float, BASIS_CHUNK>), grid, block, 0, st, a);
+		break;
+	case 5:
+		hipLaunchKernelGGL((basis_apply_b_kernel<float, double, BASIS_CHUNK>), grid, block, 0, st, a);
+		break;
+	case 6:
+		hipLaunchKernelGGL((basis_apply_b_kernel<double, float, BASIS_CHUNK>), grid, block, 0, st, a);
+		break;
+	case 7:
+		hipLaunchKernelGGL((basis_apply_b_kernel<double, double, BASIS_CHUNK>), grid, block, 0, st, a);
+		break;
+	}
+	return check_hip(hipGetLastError(), "basis_apply_b launch");
 }
 
 #ifdef DR_WAVE_TRACE

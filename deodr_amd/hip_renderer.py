@@ -32,6 +32,8 @@ _HS = _abi.SUBDIV_HEADER  # the companion header include/deodr_hip_subdiv.h (Loo
 SUBDIV_ABI_VERSION = _HS.defines["DEODR_HIP_SUBDIV_ABI_VERSION"]
 _HR = _abi.RETAINED_HEADER  # the companion header include/deodr_hip_retained.h (fit step into retained frames), bound onto the same library
 RETAINED_ABI_VERSION = _HR.defines["DEODR_HIP_RETAINED_ABI_VERSION"]
+_HB = _abi.BASIS_HEADER  # the companion header include/deodr_hip_basis.h (linear bases: morphable models), bound onto the same library
+BASIS_ABI_VERSION = _HB.defines["DEODR_HIP_BASIS_ABI_VERSION"]
 # words of the 64-byte status block at the start of the workspace
 _STATUS_NEEDED, _STATUS_ERRORS = _H.defines["DEODR_HIP_STATUS_WORD_NEEDED_PAIRS"], _H.defines["DEODR_HIP_STATUS_WORD_SCENE_ERRORS"]
 
@@ -59,6 +61,9 @@ def lib():
         _abi.bind(L, _HR)
         if L.deodr_hip_retained_abi_version() != RETAINED_ABI_VERSION:
             raise ImportError("libdeodr_hip.so retained-frames ABI version mismatch (include/deodr_hip_retained.h); rebuild it")
+        _abi.bind(L, _HB)
+        if L.deodr_hip_basis_abi_version() != BASIS_ABI_VERSION:
+            raise ImportError("libdeodr_hip.so linear-basis ABI version mismatch (include/deodr_hip_basis.h); rebuild it")
         _lib = _abi.bind(L)
     return _lib
 
@@ -285,6 +290,128 @@ def sparse_rows_apply(offsets, cols, vals, x, out=None, accumulate=False):
                                             1 if x.dtype == torch.float64 else 0, int(bool(accumulate)), _stream(dev)))  # fmt: skip
     if accumulate:
         _touched(out)
+    return out
+
+
+# ---- linear bases (include/deodr_hip_basis.h) -----------------------------------------------------------------------------------------
+
+BASIS_MAX_K, BASIS_MAX_BATCH, BASIS_MAX_N = 1024, 64, 2**30  # the limits include/deodr_hip_basis.h states
+_basis_scratch_cache = {}  # (device, stream) -> the zero-filled scratch of deodr_hip_basis_apply_b, grown to the largest request
+
+
+def _basis_args(what, basis, tensors):
+    """checks before the library is called: ``basis`` a contiguous [K, N] float32 / float64 ROCm tensor within the header's limits; ``tensors``
+    [(name, tensor, dtypes, shape with None = any)]: contiguous tensors on its device; -> (K, N)"""
+    if not torch.is_tensor(basis) or not basis.is_cuda:
+        raise ValueError(f"{what}: basis must be a ROCm tensor (deodr_amd has no CPU path)")
+    if basis.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"{what}: basis must be float32 or float64, not {basis.dtype}")
+    if basis.dim() != 2 or not 1 <= basis.shape[0] <= BASIS_MAX_K or not 1 <= basis.shape[1] <= BASIS_MAX_N or basis.numel() > 2**31 - 1:
+        raise ValueError(f"{what}: basis must have shape [1 <= K <= {BASIS_MAX_K}, 1 <= N <= 2^30] with K N <= 2^31 - 1, not {list(basis.shape)}")
+    if not basis.is_contiguous():
+        raise ValueError(f"{what}: basis must be contiguous")
+    for name, t, dtypes, shape in tensors:
+        if not torch.is_tensor(t) or not t.is_cuda or t.device != basis.device:
+            raise ValueError(f"{what}: {name} must be a ROCm tensor on the device of basis (deodr_amd has no CPU path)")
+        if t.dtype not in dtypes:
+            raise ValueError(f"{what}: {name} must be {' or '.join(str(d).replace('torch.', '') for d in dtypes)}, not {t.dtype}")
+        if t.dim() != len(shape) or any(want is not None and int(have) != want for have, want in zip(t.shape, shape)):
+            raise ValueError(f"{what}: {name} must have shape [{', '.join('batch' if v is None else str(v) for v in shape)}], not {list(t.shape)}")
+        if not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be contiguous")
+    return int(basis.shape[0]), int(basis.shape[1])
+
+
+def _basis_batch(what, t):
+    if not 1 <= int(t.shape[0]) <= BASIS_MAX_BATCH:
+        raise ValueError(f"{what}: batch must be in 1 .. {BASIS_MAX_BATCH}, not {int(t.shape[0])}")
+    return int(t.shape[0])
+
+
+_FLOATS = (torch.float32, torch.float64)
+
+
+def basis_segments(K, N):
+    """``deodr_hip_basis_segments``: the number of pieces into which :func:`basis_apply_b` cuts a row of a [K, N] basis (0: outside the limits)"""
+    return int(lib().deodr_hip_basis_segments(int(K), int(N)))
+
+
+def basis_scratch(K, N, batch, device):
+    """the scratch of :func:`basis_apply_b` for a [K, N] basis and ``batch`` gradient vectors, zero-filled as the library wants it once; for a
+    caller that keeps its own (one per stream in use; a fitter whose step is captured in a graph)"""
+    need = int(lib().deodr_hip_basis_scratch_bytes(int(K), int(N), int(batch)))
+    if need == 0:
+        raise ValueError(f"basis_scratch: K = {K}, N = {N}, batch = {batch} is outside the limits of include/deodr_hip_basis.h")
+    with torch.cuda.device(device):
+        return torch.zeros(need, dtype=torch.uint8, device=device)
+
+
+def basis_apply(basis, mean, coeffs, out=None, out_dtype=None):
+    """``deodr_hip_basis_apply``: ``out[b, j] = mean[j] + sum_k coeffs[b, k] basis[k, j]``.  ``basis`` [K, N] float32 / float64, ``mean`` [N] of its
+    dtype or None (zero), ``coeffs`` [batch, K] float64 -> ``out`` [batch, N] float32 / float64 (allocated in ``out_dtype``, default float64, when
+    None).  Double arithmetic, one rounding per stored value; deterministic; asynchronous on the current stream."""
+    what = "basis_apply"
+    if torch.is_tensor(basis) and basis.dim() == 2:
+        K, N = int(basis.shape[0]), int(basis.shape[1])
+    else:
+        K = N = None
+    tensors = [("coeffs", coeffs, (torch.float64,), (None, K))]
+    if mean is not None:
+        tensors.append(("mean", mean, (getattr(basis, "dtype", None),), (N,)))
+    if out is not None:
+        tensors.append(("out", out, _FLOATS, (None, N)))
+    K, N = _basis_args(what, basis, tensors)
+    batch = _basis_batch(what, coeffs)
+    if out is not None and int(out.shape[0]) != batch:
+        raise ValueError(f"{what}: out must have shape {[batch, N]}, not {list(out.shape)}")
+    if out is None and (out_dtype or torch.float64) not in _FLOATS:
+        raise ValueError(f"{what}: out_dtype must be float32 or float64, not {out_dtype}")
+    dev = basis.device
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.empty((batch, N), dtype=out_dtype or torch.float64, device=dev)
+        _check(lib().deodr_hip_basis_apply(_ptr(basis), _ptr(mean), _ptr(coeffs), K, N, batch, 1 if basis.dtype == torch.float64 else 0, _ptr(out),
+                                           1 if out.dtype == torch.float64 else 0, _stream(dev)))  # fmt: skip
+    _touched(out)
+    return out
+
+
+def basis_apply_b(basis, g, out=None, accumulate=False, scratch=None):
+    """``deodr_hip_basis_apply_b``: ``out[b, k] (= | +=) sum_j basis[k, j] g[b, j]``.  ``basis`` [K, N] float32 / float64, ``g`` [batch, N] float32 /
+    float64 -> ``out`` [batch, K] float64 (allocated when None).  Deterministic (no atomics on values); asynchronous on the current stream.
+    ``scratch``: a :func:`basis_scratch` of the caller's, at least as large as this problem needs; None: one per device and stream, made or
+    grown at the call (not while a graph is being captured)."""
+    what = "basis_apply_b"
+    if torch.is_tensor(basis) and basis.dim() == 2:
+        K, N = int(basis.shape[0]), int(basis.shape[1])
+    else:
+        K = N = None
+    tensors = [("g", g, _FLOATS, (None, N))]
+    if out is not None:
+        tensors.append(("out", out, (torch.float64,), (None, K)))
+    if scratch is not None:
+        tensors.append(("scratch", scratch, (torch.uint8,), (None,)))
+    K, N = _basis_args(what, basis, tensors)
+    batch = _basis_batch(what, g)
+    if out is None and accumulate:
+        raise ValueError(f"{what}: accumulate needs out")
+    if out is not None and int(out.shape[0]) != batch:
+        raise ValueError(f"{what}: out must have shape {[batch, K]}, not {list(out.shape)}")
+    dev = basis.device
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.empty((batch, K), dtype=torch.float64, device=dev)
+        if scratch is None:
+            need = int(lib().deodr_hip_basis_scratch_bytes(K, N, batch))
+            key = (dev, torch.cuda.current_stream(dev).cuda_stream)
+            scratch = _basis_scratch_cache.get(key)
+            if scratch is None or scratch.numel() < need:
+                if torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError(f"{what}: pass scratch= (basis_scratch) when capturing a graph: none of this size exists for this stream yet")
+                scratch = _basis_scratch_cache[key] = basis_scratch(K, N, batch, dev)
+        _check(lib().deodr_hip_basis_apply_b(_ptr(basis), _ptr(g), 1 if g.dtype == torch.float64 else 0, K, N, batch, 1 if basis.dtype == torch.float64 else 0,
+                                             _ptr(out), int(bool(accumulate)), _ptr(scratch), scratch.numel(), _stream(dev)))  # fmt: skip
+    _touched(out)
     return out
 
 

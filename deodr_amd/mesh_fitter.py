@@ -192,14 +192,23 @@ class _PoseFitter:
     ``subdivisions=k`` (0: off, every path as it is without the keyword): ``self.vertices`` [Vc,3] is the control cage of a Loop subdivision
     surface -- still the parameter, same ``step()`` protocol, and the Laplacian rigid energy acts on it --; ``self.mesh`` is the k-times subdivided
     mesh (faces, silhouette flags, normals, shading of the fine topology), ``self.control_mesh`` the cage.  The iteration then runs through autograd
-    (the subdivision is one kernel forward, one backward: deodr_amd/subdivision.py); ``GraphedStep`` replays it as one graph launch."""
+    (the subdivision is one kernel forward, one backward: deodr_amd/subdivision.py); ``GraphedStep`` replays it as one graph launch.
+
+    ``shape_basis`` (None: off, every path as it is without the keyword): a [K,V,3] array or a :class:`deodr_amd.basis.LinearBasis` of that shape --
+    a morphable model.  The parameter is then ``self.coefficients`` [K] (float64, zeros after ``reset()``); the ``vertices`` argument is the mean and
+    ``self.vertices = mean + coefficients . basis`` is derived, refreshed every step.  The energy is the data term + the Laplacian rigid energy of the
+    derived vertices against the mean (same ``cregu``) + ``coefficient_regu sum((c / sigmas)**2)`` (``sigmas`` [K], None: ones).  The coefficient
+    gradient is the basis adjoint (one kernel, deodr_amd/basis.py) of the total vertex gradient plus the prior's; the update is the momentum rule with
+    ``step_factor_coefficients`` and the fourth entry of ``step_max``.  With ``subdivisions`` the two compose: basis, then cage, then subdivision.
+    The iteration runs through autograd, as a subdivided fit does."""
 
     direct = True  # run an iteration as the fixed kernel sequence of _DirectIteration when the tensors allow it (False: always autograd)
 
     step_factor_vertices, step_factor_quaternion, step_factor_translation = 0.0005, 0.00006, 0.00005
+    step_factor_coefficients = 0.0005  # (with an orthonormal basis a step of the coefficients moves the vertices as far as the same step of the vertices)
 
     def __init__(self, vertices, faces, euler_init, translation_init, cregu, inertia, damping, device, n_poses=1, clockwise=False, pixel_dtype=torch.float64,
-                 subdivisions=0):  # fmt: skip
+                 subdivisions=0, shape_basis=None, coefficient_regu=0.0, sigmas=None):  # fmt: skip
         self.device = torch.device(device)
         self.cregu, self.inertia, self.damping = cregu, inertia, damping
         v0 = np.asarray(vertices, dtype=np.float64)
@@ -218,6 +227,22 @@ class _PoseFitter:
         self.scene.set_mesh(self.mesh)
         self.rigid_energy = LaplacianRigidEnergyDevice(self.control_mesh.topology, v0, cregu)
         self.vertices_init = torch.as_tensor(v0, device=self.device)
+        self.shape_basis = None
+        if shape_basis is not None:
+            from .basis import LinearBasis
+
+            basis = shape_basis if isinstance(shape_basis, LinearBasis) else LinearBasis(shape_basis, device=self.device, dtype=torch.float64)
+            if basis.shape != tuple(v0.shape):
+                raise ValueError(f"shape_basis must be [K, {v0.shape[0]}, 3] (one mode per row, of the shape of vertices), not {[basis.K, *basis.shape]}")
+            if basis.mean is not None:
+                raise ValueError("shape_basis: the `vertices` argument is the mean; give a LinearBasis without one")
+            self.shape_basis = basis.with_mean(self.vertices_init)
+            K = self.shape_basis.K
+            self.coefficient_regu = float(coefficient_regu)
+            sig = np.ones(K) if sigmas is None else np.asarray(sigmas, dtype=np.float64)
+            if sig.shape != (K,) or np.any(sig <= 0):
+                raise ValueError(f"sigmas must be {K} positive numbers")
+            self._inv_sigma2 = torch.as_tensor(1.0 / sig**2, device=self.device)
         q0 = np.asarray([_quat_from_euler_zyx(e) for e in np.atleast_2d(euler_init)])
         t0 = np.atleast_2d(np.asarray(translation_init, dtype=np.float64))
         self.transform_quaternion_init = torch.as_tensor(np.broadcast_to(q0, (n_poses, 4)).copy(), device=self.device)
@@ -227,6 +252,8 @@ class _PoseFitter:
 
     def reset(self):
         self.vertices = self.vertices_init.clone()
+        if self.shape_basis is not None:
+            self.coefficients = torch.zeros(self.shape_basis.K, dtype=torch.float64, device=self.device)
         self.transform_quaternion = self.transform_quaternion_init.clone()
         self.transform_translation = self.transform_translation_init.clone()
         self.momentum = _Momentum(self.inertia, self.damping)
@@ -256,13 +283,25 @@ class _PoseFitter:
         return qrot(q, centred[None].expand(q.shape[0], -1, -1)) + self.transform_translation_leaf[:, None, :]
 
     def _leaves(self, extra=()):
-        self.vertices = self.vertices - self.vertices.mean(dim=0, keepdim=True)
+        if self.shape_basis is not None:  # the vertices are derived: mean + coefficients . basis (not centred: _transformed does that in the graph)
+            self.vertices = self.shape_basis.apply(self.coefficients)
+        else:
+            self.vertices = self.vertices - self.vertices.mean(dim=0, keepdim=True)
         self.vertices_leaf = self.vertices.detach().requires_grad_(True)
         self.transform_quaternion_leaf = self.transform_quaternion.detach().requires_grad_(True)
         self.transform_translation_leaf = self.transform_translation.detach().requires_grad_(True)
         return [self.vertices_leaf, self.transform_quaternion_leaf, self.transform_translation_leaf] + list(extra)
 
+    def coefficients_gradient(self, g_vertices):
+        """-> (basis adjoint of a vertex gradient [V,3], gradient of the prior ``coefficient_regu sum((c / sigmas)**2)``), both [K]"""
+        return self.shape_basis.apply_b(g_vertices.detach()), 2.0 * self.coefficient_regu * self._inv_sigma2 * self.coefficients
+
+    def _prior_energy(self):
+        return self.coefficient_regu * (self._inv_sigma2 * self.coefficients**2).sum()
+
     def _update_pose_and_shape(self, g_vertices, g_quaternion, g_translation, grad_rigidity, step_max, extra=()):
+        if self.shape_basis is not None:
+            return self._update_pose_and_coefficients(g_vertices, g_quaternion, g_translation, grad_rigidity, step_max, extra)
         entries = [
             ("vertices", self.vertices, g_vertices, grad_rigidity, self.step_factor_vertices, step_max[0], 0),
             ("quaternion", self.transform_quaternion, g_quaternion, None, self.step_factor_quaternion, step_max[1], 4),  # renormalised per view
@@ -270,6 +309,19 @@ class _PoseFitter:
         ] + list(extra)
         new = self.momentum.update_all(entries)
         self.vertices, self.transform_quaternion, self.transform_translation = new[:3]
+        self.iter += 1
+        return new[3:]
+
+    def _update_pose_and_coefficients(self, g_vertices, g_quaternion, g_translation, grad_rigidity, step_max, extra=()):
+        """the update of a fit with ``shape_basis``: the total vertex gradient goes through the basis adjoint, the coefficients take the momentum step"""
+        g_c, g_prior = self.coefficients_gradient(g_vertices + grad_rigidity)
+        entries = [
+            ("coefficients", self.coefficients, g_c, g_prior, self.step_factor_coefficients, step_max[3] if len(step_max) > 3 else None, 0),
+            ("quaternion", self.transform_quaternion, g_quaternion, None, self.step_factor_quaternion, step_max[1], 4),  # renormalised per view
+            ("translation", self.transform_translation, g_translation, None, self.step_factor_translation, step_max[2], 0),
+        ] + list(extra)
+        new = self.momentum.update_all(entries)
+        self.coefficients, self.transform_quaternion, self.transform_translation = new[:3]
         self.iter += 1
         return new[3:]
 
@@ -281,7 +333,7 @@ class _PoseFitter:
         sequence fold the centring and the gradient mean into passes keyed to the RENDERED vertex array, which is then not the parameter)"""
         from . import fronthalf
 
-        if self.subdivisions:
+        if self.subdivisions or self.shape_basis is not None:  # (with a basis the rendered vertex array is not the parameter either)
             return None
 
         topo = self.mesh.topology
@@ -364,8 +416,9 @@ class MeshDepthFitter(_PoseFitter):
     """Fit a deformable mesh to a depth image (reference deodr/mesh_fitter.py:20-196)."""
 
     def __init__(self, vertices, faces, euler_init, translation_init, cregu=2000, inertia=0.96, damping=0.05, device="cuda", pixel_dtype=torch.float64,
-                 subdivisions=0):  # fmt: skip
-        super().__init__(vertices, faces, euler_init, translation_init, cregu, inertia, damping, device, pixel_dtype=pixel_dtype, subdivisions=subdivisions)
+                 subdivisions=0, shape_basis=None, coefficient_regu=0.0, sigmas=None):  # fmt: skip
+        super().__init__(vertices, faces, euler_init, translation_init, cregu, inertia, damping, device, pixel_dtype=pixel_dtype, subdivisions=subdivisions,
+                         shape_basis=shape_basis, coefficient_regu=coefficient_regu, sigmas=sigmas)  # fmt: skip
         self.camera_center = self.object_center + np.array([-0.5, 0, 5]) * self.object_radius
 
     def set_max_depth(self, max_depth):
@@ -432,8 +485,9 @@ class MeshDepthFitter(_PoseFitter):
         leaves = self._leaves()
         e_data, e_rigid, g_rigid, depth, diff_image = self.energy()
         g_v, g_q, g_t = torch.autograd.grad(e_data, leaves)
-        self._update_pose_and_shape(g_v, g_q, g_t, g_rigid, (1, 0.1, 0.1))
-        return e_data + e_rigid, depth.detach(), diff_image.detach()
+        energy = e_data + e_rigid if self.shape_basis is None else e_data + e_rigid + self._prior_energy()  # (of the parameters the gradients were taken at)
+        self._update_pose_and_shape(g_v, g_q, g_t, g_rigid, (1, 0.1, 0.1, 1))
+        return energy, depth.detach(), diff_image.detach()
 
     def step(self):
         """-> (energy, synthetic depth [H,W], squared difference [H,W]) as a float and NumPy arrays, like the reference"""
@@ -499,13 +553,13 @@ class MeshRGBFitterWithPose(_PoseFitter):
 
     def __init__(self, vertices, faces, euler_init, translation_init, default_color, default_light_directional, default_light_ambient, cregu=2000,
                  inertia=0.96, damping=0.05, update_lights=True, update_color=True, device="cuda", pixel_dtype=torch.float64, n_poses=1,
-                 subdivisions=0):  # fmt: skip
+                 subdivisions=0, shape_basis=None, coefficient_regu=0.0, sigmas=None):  # fmt: skip
         self.default_color = np.asarray(default_color, dtype=np.float64)
         self.default_light_directional = np.asarray(default_light_directional, dtype=np.float64)
         self.default_light_ambient = float(default_light_ambient)
         self.update_lights, self.update_color = update_lights, update_color
         super().__init__(vertices, faces, euler_init, translation_init, cregu, inertia, damping, device, n_poses=n_poses, pixel_dtype=pixel_dtype,
-                         subdivisions=subdivisions)  # fmt: skip
+                         subdivisions=subdivisions, shape_basis=shape_basis, coefficient_regu=coefficient_regu, sigmas=sigmas)  # fmt: skip
         self.camera_center = self.object_center + np.atleast_2d(np.asarray(translation_init, dtype=np.float64))[0] + np.array([0, 0, 9]) * self.object_radius
 
     def reset(self):
@@ -609,9 +663,10 @@ class MeshRGBFitterWithPose(_PoseFitter):
         if self.update_color:
             extra.append(("mesh_color", self.mesh_color, g_col, None, 0.00001, None, 0))
             names.append("mesh_color")
-        for name, value in zip(names, self._update_pose_and_shape(g_v, g_q, g_t, g_rigid, (0.5, 0.05, 0.1), extra)):
+        energy = e_data + e_rigid if self.shape_basis is None else e_data + e_rigid + self._prior_energy()  # (of the parameters the gradients were taken at)
+        for name, value in zip(names, self._update_pose_and_shape(g_v, g_q, g_t, g_rigid, (0.5, 0.05, 0.1, 0.5), extra)):
             setattr(self, name, value.reshape(()) if name == "light_ambient" else value)
-        return e_data + e_rigid, image.detach()
+        return energy, image.detach()
 
     def step(self):
         """-> (energy, image [H,W,C], squared difference [H,W]) as a float and NumPy arrays, the reference's protocol (synchronises;
@@ -642,7 +697,7 @@ class MeshRGBFitterWithPoseMultiFrame(MeshRGBFitterWithPose):
 
     def __init__(self, vertices, faces, euler_init, translation_init, default_color, default_light_directional, default_light_ambient, cregu=2000,
                  cdata=1, inertia=0.97, damping=0.15, update_lights=True, update_color=True, device="cuda", pixel_dtype=torch.float64, group=None,
-                 subdivisions=0):  # fmt: skip
+                 subdivisions=0, shape_basis=None, coefficient_regu=0.0, sigmas=None):  # fmt: skip
         euler_init, translation_init = np.atleast_2d(euler_init), np.atleast_2d(translation_init)
         self.cdata = cdata
         self.n_views_total = max(len(euler_init), len(translation_init))
@@ -653,7 +708,8 @@ class MeshRGBFitterWithPoseMultiFrame(MeshRGBFitterWithPose):
         self.my_views = list(dd.shard_views(self.n_views_total, self.rank, self.world))
         pick = lambda a: np.broadcast_to(a, (self.n_views_total, a.shape[1]))[self.my_views]
         super().__init__(vertices, faces, pick(euler_init), pick(translation_init), default_color, default_light_directional, default_light_ambient,
-                         cregu, inertia, damping, update_lights, update_color, device, pixel_dtype, n_poses=len(self.my_views), subdivisions=subdivisions)  # fmt: skip
+                         cregu, inertia, damping, update_lights, update_color, device, pixel_dtype, n_poses=len(self.my_views), subdivisions=subdivisions,
+                         shape_basis=shape_basis, coefficient_regu=coefficient_regu, sigmas=sigmas)  # fmt: skip
         self.camera_center = self.object_center + np.array([0, 0, 6]) * self.object_radius
         self._packed = None
 
@@ -747,12 +803,23 @@ class MeshTextureFitterMultiFrame:
     rasterizer's one-call fit step (image, data energy, ``texture_b``), ``deodr_hip_texture_smoothness`` into the same ``texture_b``,
     ``deodr_hip_texture_step`` in place -- no autograd graph, no tensor rebound, so ``GraphedStep(fitter)`` replays it as it is.  On CPU tensors the same
     two formulas run as torch ops around ``Scene3DDevice._rasterize_l2`` under autograd (which has no CPU implementation in the product: tests put a
-    checker-backed stand-in there)."""
+    checker-backed stand-in there).
+
+    ``texture_basis`` (None: off, every path as it is without the keyword): a [K,Ht,Wt,C] array or a :class:`deodr_amd.basis.LinearBasis` of that
+    shape -- an eigen-texture model, the reference's deodr/examples/eigen_faces.py.  The parameter is then ``self.coefficients`` [K] (float64, zeros
+    after ``reset()``), ``texture_init`` is the mean and ``self.texture = mean + coefficients . basis`` is written IN PLACE in the pixel dtype at the
+    start of every iteration (the scene keeps reading the same tensor).  The energy is data + smoothness + ``coefficient_regu sum((c / sigmas)**2)``.
+    One device iteration stays a fixed sequence: ``deodr_hip_basis_apply``, the fit step, the smoothness kernel when ``smoothness > 0``, one
+    element-wise op that writes the prior's gradient into the coefficient gradient, ``deodr_hip_basis_apply_b`` accumulating onto it,
+    ``deodr_hip_momentum_update`` of the coefficients (``step_factor_coefficients``, ``step_max``).  With a basis the texture is NOT clamped
+    (``clamp`` is ignored), as in the reference's example: a clamp is not a linear function of the coefficients."""
 
     step_factor_texture = 0.5
+    step_factor_coefficients = 0.5  # (for a basis of orthonormal rows: a step of the coefficients then moves the texture as far as the same step of the texels)
 
     def __init__(self, vertices, faces, uv, faces_uv, texture_init, light_directional, light_ambient, poses=None, cameras=None, smoothness=0.1,
-                 inertia=0.9, damping=0.05, clamp=(0.0, 1.0), step_max=None, clockwise=False, sigma=1.0, device="cuda", pixel_dtype=torch.float32):  # fmt: skip
+                 inertia=0.9, damping=0.05, clamp=(0.0, 1.0), step_max=None, clockwise=False, sigma=1.0, device="cuda", pixel_dtype=torch.float32,
+                 texture_basis=None, coefficient_regu=0.0, sigmas=None):  # fmt: skip
         if (poses is None) == (cameras is None):
             raise ValueError("MeshTextureFitterMultiFrame: give either poses = (euler [n,3], translations [n,3]) or cameras")
         self.device, self.pixel_dtype = torch.device(device), pixel_dtype
@@ -761,6 +828,23 @@ class MeshTextureFitterMultiFrame:
         self.texture_init = torch.as_tensor(np.asarray(texture_init, dtype=np.float64), device=self.device).to(pixel_dtype).contiguous()
         if self.texture_init.dim() != 3:
             raise ValueError("texture_init must have shape [Ht, Wt, C]")
+        self.texture_basis = None
+        if texture_basis is not None:
+            from .basis import LinearBasis
+
+            basis = texture_basis if isinstance(texture_basis, LinearBasis) else LinearBasis(texture_basis, device=self.device, dtype=pixel_dtype)
+            if basis.shape != tuple(self.texture_init.shape):
+                raise ValueError(f"texture_basis must be [K, {', '.join(str(int(v)) for v in self.texture_init.shape)}] (one mode per row, of the shape of "
+                                 f"texture_init), not {[basis.K, *basis.shape]}")  # fmt: skip
+            if basis.mean is not None:
+                raise ValueError("texture_basis: `texture_init` is the mean; give a LinearBasis without one")
+            self.texture_basis = basis.with_mean(np.asarray(texture_init, dtype=np.float64))
+            sig = np.ones(basis.K) if sigmas is None else np.asarray(sigmas, dtype=np.float64)
+            if sig.shape != (basis.K,) or np.any(sig <= 0):
+                raise ValueError(f"sigmas must be {basis.K} positive numbers")
+            self.coefficient_regu = float(coefficient_regu)
+            self._inv_sigma2 = torch.as_tensor(1.0 / sig**2, device=self.device)
+            self._prior_scale = 2.0 * self.coefficient_regu * self._inv_sigma2  # gradient of the prior = this * coefficients
         self.mesh = DeviceMesh(np.asarray(faces), v0, clockwise=clockwise, uv=uv, faces_uv=faces_uv, texture=None, device=self.device)
         self.scene = Scene3DDevice(sigma=sigma, pixel_dtype=pixel_dtype)
         self.scene.set_mesh(self.mesh)
@@ -776,6 +860,10 @@ class MeshTextureFitterMultiFrame:
         self.mesh.texture = self.texture  # (the scene renders the value this tensor has at every call; it is updated in place)
         self.momentum = _Momentum(self.inertia, self.damping)
         self.momentum.speed["texture"] = torch.zeros_like(self.texture)
+        if self.texture_basis is not None:
+            z = lambda: torch.zeros(self.texture_basis.K, dtype=torch.float64, device=self.device)
+            self.coefficients, self.coefficients_b, self.momentum.speed["coefficients"] = z(), z(), z()
+            self.e_prior, self._prior_terms = torch.zeros(1, dtype=torch.float64, device=self.device), z()
         self.iter = 0
 
     def set_background_color(self, background_color):
@@ -836,6 +924,8 @@ class MeshTextureFitterMultiFrame:
             ds.set_texture(self.texture)
             self._direct = (ds, r, ds.zero_grads(), out)
             self._scratch = hip_renderer.texture_scratch(dev)  # (its own: a captured step replays on the addresses it was captured with)
+            if self.texture_basis is not None:
+                self._basis_scratch = hip_renderer.basis_scratch(self.texture_basis.K, self.texture_basis.N, 1, dev)
         self.iter = 0
 
     def _gradient(self):
@@ -849,7 +939,8 @@ class MeshTextureFitterMultiFrame:
             ds.set_texture(self.texture)
             image, _z, _g = r.render_fit(ds, self._obs, self.scene.sigma, grads=grads, out=out, clear_grads=True, loss_out=self.e_data, weights=self.weights)
             texture_b = grads["texture_b"]
-            hip_renderer.texture_smoothness(self.texture, texture_b, self.smoothness, self.e_smooth, scratch=self._scratch)
+            if self.texture_basis is None or self.smoothness > 0:
+                hip_renderer.texture_smoothness(self.texture, texture_b, self.smoothness, self.e_smooth, scratch=self._scratch)
             return texture_b, image
         leaf = self.texture.detach().requires_grad_(True)
         extra = {} if self.weights is None else {"weights": self.weights}
@@ -863,6 +954,10 @@ class MeshTextureFitterMultiFrame:
     def energy(self):
         """-> data energy + smoothness energy of the current texture (a device tensor of one element); nothing is updated"""
         assert self._views is not None, "call set_images first"
+        if self.texture_basis is not None:
+            self._texture_from_coefficients()
+            self._gradient()
+            return self.e_data + self.e_smooth + self.coefficient_regu * (self._inv_sigma2 * self.coefficients**2).sum()
         self._gradient()
         return self.e_data + self.e_smooth
 
@@ -872,11 +967,45 @@ class MeshTextureFitterMultiFrame:
         from . import hip_renderer
 
         assert self._views is not None, "call set_images first"
+        if self.texture_basis is not None:
+            return self._step_basis()
         texture_b, image = self._gradient()
         speed = self.momentum.speed["texture"]
         update = hip_renderer.texture_step if self._direct is not None else texture_step_torch
         update(self.texture, speed, texture_b, self.step_factor_texture, self.step_max, self.inertia, self.damping, self.clamp)
         torch.add(self.e_data, self.e_smooth, out=self._energy)
+        self.iter += 1
+        return self._energy, image
+
+    def _texture_from_coefficients(self):
+        """``self.texture = mean + coefficients . basis`` in place, in the pixel dtype (one kernel on the device)"""
+        B = self.texture_basis
+        B.run(self.coefficients[None], out=self.texture.view(1, B.N))
+
+    def _step_basis(self):
+        """the iteration of a fit with ``texture_basis``: the same storage every step, no autograd graph on the device"""
+        from . import fronthalf
+
+        B, c, c_b, speed = self.texture_basis, self.coefficients, self.coefficients_b, self.momentum.speed["coefficients"]
+        self._texture_from_coefficients()
+        texture_b, image = self._gradient()
+        torch.mul(c, self._prior_scale, out=c_b)  # the prior's gradient 2 coefficient_regu c / sigmas^2; the data + smoothness gradient is added to it
+        if self.coefficient_regu:
+            torch.mul(c, c_b, out=self._prior_terms)
+            torch.sum(self._prior_terms, dim=0, keepdim=True, out=self.e_prior)
+            self.e_prior.mul_(0.5)
+        if self._direct is not None:
+            B.run_b(texture_b.view(1, B.N), out=c_b[None], accumulate=True, scratch=self._basis_scratch)
+            fronthalf.momentum_update([(c, speed, c_b, None, self.step_factor_coefficients, self.step_max, 0)], self.inertia, self.damping)
+        else:
+            c_b += B.run_b(texture_b.reshape(1, B.N))[0]
+            step = -self.step_factor_coefficients * c_b
+            if self.step_max is not None and self.step_max > 0:
+                step = step.clamp(-self.step_max, self.step_max)
+            speed.copy_((1 - self.damping) * (self.inertia * speed + (1 - self.inertia) * step))
+            c += speed
+        torch.add(self.e_data, self.e_smooth, out=self._energy)
+        self._energy += self.e_prior
         self.iter += 1
         return self._energy, image
 
