@@ -11,10 +11,14 @@ import types
 
 _INCLUDE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
 HEADER_PATH = os.path.join(_INCLUDE, "deodr_hip.h")
-TEXTURE_HEADER_PATH = os.path.join(_INCLUDE, "deodr_hip_texture.h")  # the companion header (texture estimation), versioned on its own
-SUBDIV_HEADER_PATH = os.path.join(_INCLUDE, "deodr_hip_subdiv.h")  # the companion header (Loop subdivision), versioned on its own
-RETAINED_HEADER_PATH = os.path.join(_INCLUDE, "deodr_hip_retained.h")  # the companion header (fit step into retained frames), versioned on its own
-BASIS_HEADER_PATH = os.path.join(_INCLUDE, "deodr_hip_basis.h")  # the companion header (linear bases: morphable models), versioned on its own
+# The companion headers, each versioned on its own and bound onto the same library: (the parsed header's name here -- its path is that name + _PATH --,
+# the file, whether its prototypes may point to the structs of deodr_hip.h)
+_COMPANIONS = (
+    ("TEXTURE_HEADER", "deodr_hip_texture.h", False),  # texture estimation
+    ("SUBDIV_HEADER", "deodr_hip_subdiv.h", False),  # Loop subdivision
+    ("RETAINED_HEADER", "deodr_hip_retained.h", True),  # fit step into retained frames
+    ("BASIS_HEADER", "deodr_hip_basis.h", False),  # linear bases: morphable models
+)
 
 # C type (without `const`, without spaces around the stars) -> ctypes.  Data pointers are c_void_p: callers pass device addresses (Python
 # ints, c_void_p), None, byref(...) and small ctypes arrays, and c_void_p takes all of them.  int and unsigned long long are only ever
@@ -93,13 +97,12 @@ def bind(library, header=None):
     return library
 
 
-with open(HEADER_PATH) as _f:
-    HEADER = parse(_f.read())
-with open(TEXTURE_HEADER_PATH) as _f:
-    TEXTURE_HEADER = parse(_f.read(), "include/deodr_hip_texture.h")
-with open(SUBDIV_HEADER_PATH) as _f:
-    SUBDIV_HEADER = parse(_f.read(), "include/deodr_hip_subdiv.h")
-with open(RETAINED_HEADER_PATH) as _f:
-    RETAINED_HEADER = parse(_f.read(), "include/deodr_hip_retained.h", HEADER.structs)
-with open(BASIS_HEADER_PATH) as _f:
-    BASIS_HEADER = parse(_f.read(), "include/deodr_hip_basis.h")
+def _parse_file(path, structs=None):
+    with open(path) as f:
+        return parse(f.read(), "include/" + os.path.basename(path), structs)
+
+
+HEADER = _parse_file(HEADER_PATH)
+for _name, _file, _sees_structs in _COMPANIONS:
+    globals()[_name + "_PATH"] = os.path.join(_INCLUDE, _file)
+    globals()[_name] = _parse_file(globals()[_name + "_PATH"], HEADER.structs if _sees_structs else None)

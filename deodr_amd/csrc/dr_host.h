@@ -1,0 +1,48 @@
+// deodr_amd/csrc/dr_host.h -- what every entry point of the C ABI asks of its arguments before it launches: the size of a dtype tag's elements,
+// whether two buffers overlap, the grid of a kernel that strides beyond a capped number of workgroups, and the layout of the scratch buffers
+// (counter words, then doubles).  Host only, plain C++17, nothing of HIP in it: dr_kernels.hip calls these from its entry points,
+// tests/sim/host_sim.cpp compiles the same header for the CPU and tests/test_host_helpers.py pins the edge cases.
+#pragma once
+
+#include <stddef.h>
+#include <stdint.h>
+
+namespace dr::host
+{
+
+// Bytes per element of a dtype tag of include/deodr_hip.h (DEODR_HIP_F32 = 0, DEODR_HIP_F64 = 1; dr_kernels.hip asserts the two values); 0: no such tag.
+constexpr size_t elem_bytes(int dtype_tag) { return dtype_tag == 0 ? 4 : dtype_tag == 1 ? 8 : 0; }
+
+// Do [a, a + a_bytes) and [b, b + b_bytes) share a byte?  A NULL pointer (an optional array that was not given) and an empty range overlap nothing.
+// Written with differences of addresses, so a range that ends at the top of the address space does not wrap.
+inline bool ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes)
+{
+	const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+	if (!a || !b || !a_bytes || !b_bytes)
+		return false;
+	return x <= y ? y - x < a_bytes : x - y < b_bytes;
+}
+
+// Workgroups of a grid-stride kernel: one per `per_block` items of `count`, at least 1, at most `cap`.
+constexpr unsigned capped_blocks(size_t count, size_t per_block, unsigned cap)
+{
+	const size_t want = count / per_block + (count % per_block != 0);
+	return want < 1 ? 1u : want < cap ? (unsigned)want : cap;
+}
+
+// The scratch of the fit-iteration, data-term and texture kernels: SCRATCH_COUNTER_WORDS counter words (zero between launches: the caller allocates
+// the buffer zero-filled once, every kernel leaves its counter at zero), then doubles.
+constexpr int SCRATCH_COUNTER_WORDS = 16;
+constexpr size_t SCRATCH_COUNTER_BYTES = 4 * SCRATCH_COUNTER_WORDS;
+constexpr size_t scratch_need(size_t doubles) { return SCRATCH_COUNTER_BYTES + sizeof(double) * doubles; }
+
+struct Scratch
+{
+	void *base;
+	size_t bytes;
+	bool holds(size_t need) const { return base && bytes >= need; }
+	unsigned *counter(int word) const { return (unsigned *)base + word; }
+	double *doubles() const { return (double *)((char *)base + SCRATCH_COUNTER_BYTES); }
+};
+
+} // namespace dr::host

@@ -34,7 +34,8 @@
 // wave primitives) . dr_setup.h (setup_bin_kernel) . dr_forward.h (tile_scan_kernel, fill,
 // raster_fwd_fast_kernel) . dr_backward.h (raster_bwd_fast_kernel, raster_bwd_edge_kernel) . dr_finalize.h (finalize_kernel) .
 // dr_forward_generic.h / dr_backward_generic.h (the un-staged family, edge ordering) . dr_math.h / dr_prims.h (per-primitive math) .
-// dr_fronthalf.h / dr_fititer.h (fit iteration).
+// dr_fronthalf.h / dr_fititer.h (fit iteration) . dr_host.h (host only: what the entry points ask of their arguments -- element size of a dtype tag,
+// overlap of two buffers, capped grids -- and the layout of the scratch buffers).
 //
 // No MFMA anywhere: the path is gather / scatter + streaming writes.  The workspace is self-cleaning (tile counters are
 // zeroed by the scan kernel, spill counters are double-buffered by the parity of the forward count, list counters are zeroed
@@ -57,6 +58,7 @@
 
 #include "../../include/deodr_hip.h"
 #include "dr_dispatch.h"
+#include "dr_host.h"
 #include "../../include/deodr_hip_texture.h"
 #include "../../include/deodr_hip_subdiv.h"
 #include "../../include/deodr_hip_retained.h"
@@ -68,6 +70,7 @@
 
 using namespace dr;
 using namespace dr::dispatch;
+using namespace dr::host;
 
 namespace
 {
@@ -79,6 +82,12 @@ thread_local char g_error[256] = "";
 int fail(const char *msg)
 {
 	snprintf(g_error, sizeof g_error, "%s", msg);
+	return 1;
+}
+
+int fail(const char *what, const char *why) // "what: why"
+{
+	snprintf(g_error, sizeof g_error, "%s: %s", what, why);
 	return 1;
 }
 
@@ -108,7 +117,7 @@ int fill_params(const DeodrHipScene *sc, double sigma, void *workspace, size_t w
 		return fail("more than 2^30 triangles");
 	if (sc->height > 32767 || sc->width > 32767)
 		return fail("image larger than 32767 pixels (pixel coordinates are 16-bit, as in the reference)");
-	if ((sc->vertex_dtype != DEODR_HIP_F32 && sc->vertex_dtype != DEODR_HIP_F64) || (sc->pixel_dtype != DEODR_HIP_F32 && sc->pixel_dtype != DEODR_HIP_F64))
+	if (!elem_bytes(sc->vertex_dtype) || !elem_bytes(sc->pixel_dtype))
 		return fail("unknown dtype tag");
 	if (sc->texture && (sc->texture_height < 2 || sc->texture_width < 2))
 		return fail("texture must be at least 2 x 2");
@@ -300,6 +309,16 @@ int launch_from(const char *no_instance, const Inst (&table)[N], const Inst &wan
 // The pixel-dtype tag as a type: f(double{}) or f(float{}) for a generic lambda.
 template <class F>
 auto with_pixel_type(bool f64, F f) { return f64 ? f(double{}) : f(float{}); }
+
+// A dtype tag of the ABI (one that elem_bytes knows: the entry points check first) as a type, for the operators whose arrays each carry a tag of their
+// own.  (with_pixel_type is not a call of this: the order of the two branches is the order of the kernels in the code object, float first here.)
+static_assert(elem_bytes(DEODR_HIP_F32) == sizeof(float) && elem_bytes(DEODR_HIP_F64) == sizeof(double), "dr_host.h restates the dtype tags");
+template <class F>
+auto with_dtype(int tag, F f) { return tag == DEODR_HIP_F32 ? f(float{}) : f(double{}); }
+
+// One of two template arguments: f(std::integral_constant<int, A>{}), or with B when `second`.
+template <int A, int B, class F>
+auto with_constant(bool second, F f) { return !second ? f(std::integral_constant<int, A>{}) : f(std::integral_constant<int, B>{}); }
 
 template <class PixT>
 int launch_adjoint_raster(const KParams &p, bool fast, bool owner_tiles, dim3 grid4, dim3 edge_grid, hipStream_t st)
@@ -631,6 +650,31 @@ __global__ __launch_bounds__(256) void copy_probe_kernel(probe_u4 *dst, const pr
 		((uint32_t *)dst)[0] = acc.x; // (never true for real data: keeps the loads alive)
 }
 
+// ---- scratch of the fit-iteration kernels and the data terms: Scratch of dr_host.h, one counter word per kernel
+size_t fh_blocks(long long count) { return (size_t)((count + FH_BLOCK - 1) / FH_BLOCK); }
+size_t fit_scratch_need_pose_b(int, int n) { return scratch_need((size_t)POSE_B_BLOCKS * (size_t)(7 * n + 3)); }
+size_t fit_scratch_need_shade_b(int V, int n) { return scratch_need(3 * (size_t)n * V + 7 * fh_blocks((long long)n * V * GATHER_LANES)); }
+size_t fit_scratch_need_rigid(int V) { return scratch_need(fh_blocks((long long)V * GATHER_LANES)); }
+size_t fit_scratch_need_l2(void) { return scratch_need((size_t)L2_BLOCKS); }
+size_t fit_scratch_need_momentum(int most) { return scratch_need((size_t)MOMENTUM_MAX * 3 * fh_blocks(most)); }
+enum FitCounter
+{
+	FC_POSE_B = 0,
+	FC_SHADE_B = 1,
+	FC_RIGID = 2,
+	FC_L2 = 3,
+	FC_MOMENTUM = 4 // ... + MOMENTUM_MAX
+};
+static_assert(FC_MOMENTUM + MOMENTUM_MAX <= SCRATCH_COUNTER_WORDS, "the counter words of the scratch");
+
+// The kernels that walk the views of a vertex: one thread per vertex for a single view, GATHER_LANES adjacent lanes otherwise.
+// launch(the lane count as a constant, the workgroups that gives for V vertices).
+template <class F>
+auto with_gather_lanes(int V, int n, F launch)
+{
+	return n == 1 ? launch(std::integral_constant<int, 1>{}, fh_blocks(V)) : launch(std::integral_constant<int, GATHER_LANES>{}, fh_blocks((long long)V * GATHER_LANES));
+}
+
 } // namespace
 
 extern "C" {
@@ -796,8 +840,7 @@ static int render_scene_fit_impl(const DeodrHipScene *sc, void *image, void *z_b
 	if (clear_gradients)
 	{
 		p.clear_grads = 1; // vertex arrays: zeroed by the set-up kernel; the texture gradient (large, if any) by a fill
-		const size_t ps = sc->pixel_dtype == DEODR_HIP_F64 ? 8 : 4;
-		if (p.texture_b && check_hip(hipMemsetAsync(p.texture_b, 0, (size_t)p.tex_h * p.tex_w * p.C * ps, st), "clear texture_b"))
+		if (p.texture_b && check_hip(hipMemsetAsync(p.texture_b, 0, (size_t)p.tex_h * p.tex_w * p.C * elem_bytes(sc->pixel_dtype), st), "clear texture_b"))
 			return 1;
 	}
 	const bool fused = staged_adjoint(sc, p);
@@ -834,10 +877,10 @@ static int render_scene_fit_impl(const DeodrHipScene *sc, void *image, void *z_b
 		return 1;
 	if (loss_out && !loss_in_kernels)
 	{ // un-staged kernels (more than 4 channels) or a scene without triangles: one pass over the finished frame
-		if (check_hip(hipMemsetAsync(loss_scratch, 0, 64 + 8 * (size_t)L2_BLOCKS, st), "loss scratch"))
+		if (check_hip(hipMemsetAsync(loss_scratch, 0, fit_scratch_need_l2(), st), "loss scratch"))
 			return 1;
 		if (l2_loss_impl(image, obs, sc->pixel_dtype, (size_t)sc->n_views * sc->height * sc->width * sc->nb_colors, loss_out, loss_scratch,
-						 64 + 8 * (size_t)L2_BLOCKS, stream, p.clamp, p.clamp_lo, p.clamp_hi, fit_weights(p), sc->nb_colors))
+						 fit_scratch_need_l2(), stream, p.clamp, p.clamp_lo, p.clamp_hi, fit_weights(p), sc->nb_colors))
 			return 1;
 	}
 	if (done_flag && !fin_signals)
@@ -963,22 +1006,6 @@ int deodr_hip_silhouette_flags(const double *ij, const uint32_t *faces, const ui
 	return check_hip(hipGetLastError(), "silhouette_flags launch");
 }
 
-// scratch of the fit-iteration kernels: 16 counter words (zero between launches: allocate zero-filled once), then doubles
-static size_t fh_blocks(long long count) { return (size_t)((count + FH_BLOCK - 1) / FH_BLOCK); }
-static size_t fit_scratch_need_pose_b(int, int n) { return 64 + 8 * (size_t)POSE_B_BLOCKS * (size_t)(7 * n + 3); }
-static size_t fit_scratch_need_shade_b(int V, int n) { return 64 + 8 * (3 * (size_t)n * V + 7 * fh_blocks((long long)n * V * GATHER_LANES)); }
-static size_t fit_scratch_need_rigid(int V) { return 64 + 8 * fh_blocks((long long)V * GATHER_LANES); }
-static size_t fit_scratch_need_l2(void) { return 64 + 8 * (size_t)L2_BLOCKS; }
-static size_t fit_scratch_need_momentum(int most) { return 64 + 8 * (size_t)MOMENTUM_MAX * 3 * fh_blocks(most); }
-enum FitCounter
-{
-	FC_POSE_B = 0,
-	FC_SHADE_B = 1,
-	FC_RIGID = 2,
-	FC_L2 = 3,
-	FC_MOMENTUM = 4 // ... + MOMENTUM_MAX
-};
-
 size_t deodr_hip_fit_scratch_bytes(int V, int n)
 {
 	if (V <= 0 || n <= 0)
@@ -1018,12 +1045,13 @@ int deodr_hip_momentum_update(int n_tensors, double *const *x, double *const *sp
 		means = means || a.mean_out[k];
 		most = count[k] > most ? count[k] : most;
 	}
-	if (means && (!scratch || scratch_bytes < fit_scratch_need_momentum(most)))
+	const Scratch sc = {scratch, scratch_bytes};
+	if (means && !sc.holds(fit_scratch_need_momentum(most)))
 		return fail("momentum_update: mean_out needs the fit scratch (deodr_hip_fit_scratch_bytes)");
 	a.n = n_tensors, a.inertia = inertia, a.damping = damping;
 	a.energy = energy, a.data_energy = data_energy, a.data_weight = data_weight;
-	a.counters = scratch ? (unsigned *)scratch + FC_MOMENTUM : nullptr;
-	a.partials = scratch ? (double *)((char *)scratch + 64) : nullptr;
+	a.counters = scratch ? sc.counter(FC_MOMENTUM) : nullptr;
+	a.partials = scratch ? sc.doubles() : nullptr;
 	hipLaunchKernelGGL(momentum_update_kernel, dim3((most + FH_BLOCK - 1) / FH_BLOCK, n_tensors), dim3(FH_BLOCK), 0, (hipStream_t)stream, a);
 	return check_hip(hipGetLastError(), "momentum_update launch");
 }
@@ -1034,12 +1062,10 @@ int deodr_hip_fit_pose_project(double *vertices, const double *vertices_mean, co
 {
 	if (!vertices || !quaternions || !translations || !extrinsic || !intrinsic || !posed || !ij || !depths || V <= 0 || n <= 0)
 		return fail("fit_pose_project: bad arguments");
-	if (n == 1)
-		hipLaunchKernelGGL(fit_pose_project_kernel<1>, dim3(fh_blocks(V)), dim3(FH_BLOCK), 0, (hipStream_t)stream, vertices, vertices_mean, quaternions, translations,
-					   extrinsic, intrinsic, distortion, posed, ij, depths, depth_colors, depth_scale, V, n);
-	else
-		hipLaunchKernelGGL(fit_pose_project_kernel<GATHER_LANES>, dim3(fh_blocks((long long)V * GATHER_LANES)), dim3(FH_BLOCK), 0, (hipStream_t)stream, vertices, vertices_mean, quaternions, translations,
-					   extrinsic, intrinsic, distortion, posed, ij, depths, depth_colors, depth_scale, V, n);
+	with_gather_lanes(V, n, [&](auto lanes, size_t blocks) {
+		hipLaunchKernelGGL(fit_pose_project_kernel<decltype(lanes)::value>, dim3(blocks), dim3(FH_BLOCK), 0, (hipStream_t)stream, vertices, vertices_mean, quaternions,
+						   translations, extrinsic, intrinsic, distortion, posed, ij, depths, depth_colors, depth_scale, V, n);
+	});
 	return check_hip(hipGetLastError(), "fit_pose_project launch");
 }
 
@@ -1054,16 +1080,14 @@ int deodr_hip_fit_pose_project_b(const double *vertices, const double *quaternio
 		return fail("fit_pose_project_b: at most 64 views per call");
 	if (colors_sum && (!colors_b || nb_colors <= 0 || nb_colors > 4))
 		return fail("fit_pose_project_b: colors_sum needs colors_b with 1 - 4 channels");
-	if (!scratch || scratch_bytes < fit_scratch_need_pose_b(V, n))
+	const Scratch sc = {scratch, scratch_bytes};
+	if (!sc.holds(fit_scratch_need_pose_b(V, n)))
 		return fail("fit_pose_project_b: scratch too small (deodr_hip_fit_scratch_bytes)");
-	const size_t pose_blocks = fh_blocks(n == 1 ? (long long)V : (long long)V * GATHER_LANES);
-	const dim3 pose_grid((unsigned)(pose_blocks < (size_t)POSE_B_BLOCKS ? pose_blocks : (size_t)POSE_B_BLOCKS));
-	if (n == 1)
-		hipLaunchKernelGGL(fit_pose_project_b_kernel<1>, pose_grid, dim3(FH_BLOCK), 0, (hipStream_t)stream, vertices, quaternions, posed, extrinsic, intrinsic,
-					   distortion, posed_b, ij_b, depths_b, depths_b_scale, vertices_b, out, (double *)((char *)scratch + 64), (unsigned *)scratch + FC_POSE_B, V, n, colors_b, nb_colors, colors_sum);
-	else
-		hipLaunchKernelGGL(fit_pose_project_b_kernel<GATHER_LANES>, pose_grid, dim3(FH_BLOCK), 0, (hipStream_t)stream, vertices, quaternions, posed, extrinsic, intrinsic,
-					   distortion, posed_b, ij_b, depths_b, depths_b_scale, vertices_b, out, (double *)((char *)scratch + 64), (unsigned *)scratch + FC_POSE_B, V, n, colors_b, nb_colors, colors_sum);
+	with_gather_lanes(V, n, [&](auto lanes, size_t blocks) {
+		hipLaunchKernelGGL(fit_pose_project_b_kernel<decltype(lanes)::value>, dim3(capped_blocks(blocks, 1, POSE_B_BLOCKS)), dim3(FH_BLOCK), 0, (hipStream_t)stream,
+						   vertices, quaternions, posed, extrinsic, intrinsic, distortion, posed_b, ij_b, depths_b, depths_b_scale, vertices_b, out, sc.doubles(),
+						   sc.counter(FC_POSE_B), V, n, colors_b, nb_colors, colors_sum);
+	});
 	return check_hip(hipGetLastError(), "fit_pose_project_b launch");
 }
 
@@ -1075,12 +1099,10 @@ int deodr_hip_views_gradient_sum(const double *posed, const double *extrinsic, c
 		return fail("views_gradient_sum: bad arguments");
 	if (colors_sum && (!colors_b || nb_colors <= 0 || nb_colors > 4))
 		return fail("views_gradient_sum: colors_sum needs colors_b with 1 - 4 channels");
-	if (n == 1)
-		hipLaunchKernelGGL(views_gradient_sum_kernel<1>, dim3(fh_blocks(V)), dim3(FH_BLOCK), 0, (hipStream_t)stream, posed, extrinsic, intrinsic, distortion, ij_b,
-						   depths_b, depths_b_scale, vertices_b, V, n, colors_b, nb_colors, colors_sum);
-	else
-		hipLaunchKernelGGL(views_gradient_sum_kernel<GATHER_LANES>, dim3(fh_blocks((long long)V * GATHER_LANES)), dim3(FH_BLOCK), 0, (hipStream_t)stream, posed,
-						   extrinsic, intrinsic, distortion, ij_b, depths_b, depths_b_scale, vertices_b, V, n, colors_b, nb_colors, colors_sum);
+	with_gather_lanes(V, n, [&](auto lanes, size_t blocks) {
+		hipLaunchKernelGGL(views_gradient_sum_kernel<decltype(lanes)::value>, dim3(blocks), dim3(FH_BLOCK), 0, (hipStream_t)stream, posed, extrinsic, intrinsic,
+						   distortion, ij_b, depths_b, depths_b_scale, vertices_b, V, n, colors_b, nb_colors, colors_sum);
+	});
 	return check_hip(hipGetLastError(), "views_gradient_sum launch");
 }
 
@@ -1122,12 +1144,13 @@ int deodr_hip_vertex_shade_b(const double *posed, const uint32_t *faces, const u
 		return 1;
 	if ((!luminosity_b && !colors_b) || (colors_b && !color) || !posed_b || !out)
 		return fail("vertex_shade_b: bad arguments");
-	if (!scratch || scratch_bytes < fit_scratch_need_shade_b(V, n))
+	const Scratch sc = {scratch, scratch_bytes};
+	if (!sc.holds(fit_scratch_need_shade_b(V, n)))
 		return fail("vertex_shade_b: scratch too small (deodr_hip_fit_scratch_bytes)");
 	hipStream_t st = (hipStream_t)stream;
-	double *acc_b = (double *)((char *)scratch + 64), *partials = acc_b + 3 * (size_t)n * V;
+	double *acc_b = sc.doubles(), *partials = acc_b + 3 * (size_t)n * V;
 	hipLaunchKernelGGL(vertex_shade_b1_kernel, dim3(fh_blocks((long long)n * V * GATHER_LANES)), dim3(FH_BLOCK), 0, st, a, luminosity_b, colors_b, acc_b, out, partials,
-					   (unsigned *)scratch + FC_SHADE_B);
+					   sc.counter(FC_SHADE_B));
 	hipLaunchKernelGGL(vertex_shade_b2_kernel, dim3(fh_blocks((long long)V * GATHER_LANES), n), dim3(FH_BLOCK), 0, st, a, (const double *)acc_b, posed_b);
 	return check_hip(hipGetLastError(), "vertex_shade_b launch");
 }
@@ -1138,10 +1161,10 @@ int deodr_hip_rigid_energy(const double *vertices, const double *vertices_ref, c
 {
 	if (!vertices || !vertices_ref || !m_offsets || !m_cols || !m_vals || !gradient || !energy || V <= 0)
 		return fail("rigid_energy: bad arguments");
-	if (!scratch || scratch_bytes < fit_scratch_need_rigid(V))
+	const Scratch sc = {scratch, scratch_bytes};
+	if (!sc.holds(fit_scratch_need_rigid(V)))
 		return fail("rigid_energy: scratch too small (deodr_hip_fit_scratch_bytes)");
-	const RigidArgs a = {vertices, vertices_ref, m_offsets, m_cols, m_vals, cregu, gradient, energy, data_energy, data_weight, (double *)((char *)scratch + 64),
-						 (unsigned *)scratch + FC_RIGID, V};
+	const RigidArgs a = {vertices, vertices_ref, m_offsets, m_cols, m_vals, cregu, gradient, energy, data_energy, data_weight, sc.doubles(), sc.counter(FC_RIGID), V};
 	hipLaunchKernelGGL(rigid_energy_kernel, dim3(fh_blocks((long long)V * GATHER_LANES)), dim3(FH_BLOCK), 0, (hipStream_t)stream, a);
 	return check_hip(hipGetLastError(), "rigid_energy launch");
 }
@@ -1176,10 +1199,10 @@ int deodr_hip_fit_front(const double *ij, const uint32_t *faces, const uint32_t 
 	{
 		if (!vertices || !vertices_ref || !m_offsets || !m_cols || !m_vals || !energy)
 			return fail("fit_front: the rigid energy needs vertices, reference, the CSR of L^T L and energy[2]");
-		if (!scratch || scratch_bytes < fit_scratch_need_rigid(V))
+		const Scratch sc = {scratch, scratch_bytes};
+		if (!sc.holds(fit_scratch_need_rigid(V)))
 			return fail("fit_front: scratch too small (deodr_hip_fit_scratch_bytes)");
-		a.rigid = RigidArgs{vertices, vertices_ref, m_offsets, m_cols, m_vals, cregu, gradient, energy, nullptr, 0.0, (double *)((char *)scratch + 64),
-							(unsigned *)scratch + FC_RIGID, V};
+		a.rigid = RigidArgs{vertices, vertices_ref, m_offsets, m_cols, m_vals, cregu, gradient, energy, nullptr, 0.0, sc.doubles(), sc.counter(FC_RIGID), V};
 		a.rigid_blocks = (unsigned)fh_blocks((long long)V * GATHER_LANES);
 	}
 	const unsigned blocks = a.rigid_blocks + (a.shade_x + a.sil_x) * (unsigned)n;
@@ -1192,16 +1215,16 @@ int deodr_hip_fit_front(const double *ij, const uint32_t *faces, const uint32_t 
 static int l2_loss_impl(const void *image, const void *obs, int pixel_dtype, size_t count, double *out, void *scratch, size_t scratch_bytes, void *stream,
 					   int clamp, double clamp_lo, double clamp_hi, const void *weights, int nb_colors)
 { // weights != NULL: one weight per pixel of nb_colors channels (count = pixels * nb_colors)
-	if (!image || !obs || !out || count == 0 || (pixel_dtype != DEODR_HIP_F32 && pixel_dtype != DEODR_HIP_F64))
+	if (!image || !obs || !out || count == 0 || !elem_bytes(pixel_dtype))
 		return fail("l2_loss: bad arguments");
-	if (!scratch || scratch_bytes < fit_scratch_need_l2())
+	const Scratch sc = {scratch, scratch_bytes};
+	if (!sc.holds(fit_scratch_need_l2()))
 		return fail("l2_loss: scratch too small (deodr_hip_fit_scratch_bytes)");
 	if (((uintptr_t)image | (uintptr_t)obs) & 31)
 		return fail("l2_loss: image and obs must be 32-byte aligned");
-	const size_t want = (count + FH_BLOCK * 32 - 1) / (FH_BLOCK * 32);
-	const dim3 grid((unsigned)(want < (size_t)L2_BLOCKS ? want : (size_t)L2_BLOCKS));
-	double *partials = (double *)((char *)scratch + 64);
-	unsigned *counter = (unsigned *)scratch + FC_L2;
+	const dim3 grid(capped_blocks(count, FH_BLOCK * 32, L2_BLOCKS));
+	double *partials = sc.doubles();
+	unsigned *counter = sc.counter(FC_L2);
 	with_pixel_type(pixel_dtype == DEODR_HIP_F64, [&](auto pix) {
 		using PixT = decltype(pix);
 		if (weights)
@@ -1222,14 +1245,14 @@ int deodr_hip_l2_loss(const void *image, const void *obs, int pixel_dtype, size_
 int deodr_hip_depth_residual(const void *image, int pixel_dtype, const double *obs, double max_depth, size_t count, double *depth, double *diff, void *image_b,
 							 double *loss, void *scratch, size_t scratch_bytes, void *stream)
 {
-	if (!image || !obs || !depth || !diff || !image_b || !loss || count == 0 || (pixel_dtype != DEODR_HIP_F32 && pixel_dtype != DEODR_HIP_F64))
+	if (!image || !obs || !depth || !diff || !image_b || !loss || count == 0 || !elem_bytes(pixel_dtype))
 		return fail("depth_residual: bad arguments");
-	if (!scratch || scratch_bytes < fit_scratch_need_l2())
+	const Scratch sc = {scratch, scratch_bytes};
+	if (!sc.holds(fit_scratch_need_l2()))
 		return fail("depth_residual: scratch too small (deodr_hip_fit_scratch_bytes)");
-	const size_t want = (count + FH_BLOCK * 4 - 1) / (FH_BLOCK * 4);
-	const dim3 grid((unsigned)(want < (size_t)L2_BLOCKS ? want : (size_t)L2_BLOCKS));
-	double *partials = (double *)((char *)scratch + 64);
-	unsigned *counter = (unsigned *)scratch + FC_L2;
+	const dim3 grid(capped_blocks(count, FH_BLOCK * 4, L2_BLOCKS));
+	double *partials = sc.doubles();
+	unsigned *counter = sc.counter(FC_L2);
 	with_pixel_type(pixel_dtype == DEODR_HIP_F64, [&](auto pix) {
 		using PixT = decltype(pix);
 		hipLaunchKernelGGL(depth_residual_kernel<PixT>, grid, dim3(FH_BLOCK), 0, (hipStream_t)stream, (const PixT *)image, obs, max_depth, count, depth, diff,
@@ -1242,64 +1265,43 @@ int deodr_hip_depth_residual(const void *image, int pixel_dtype, const double *o
 
 int deodr_hip_texture_abi_version(void) { return DEODR_HIP_TEXTURE_ABI_VERSION; }
 
-static int texture_dims(const char *&why, int Ht, int Wt, int C, int pixel_dtype)
-{ // -> number of elements, or 0 with the reason
+static const char *texture_dims(int Ht, int Wt, int C, int pixel_dtype)
+{ // -> NULL (the texture has Ht * Wt * C <= 2^30 elements), or why not
 	if (Ht < 2 || Wt < 2)
-		why = "texture must be at least 2 x 2";
-	else if (C < 1 || C > DEODR_HIP_MAX_COLORS)
-		why = "nb_colors out of range";
-	else if (pixel_dtype != DEODR_HIP_F32 && pixel_dtype != DEODR_HIP_F64)
-		why = "unknown dtype tag";
-	else if ((unsigned long long)Ht * (unsigned long long)Wt * (unsigned long long)C > (1ull << 30))
-		why = "texture larger than 2^30 elements";
-	else
-		return Ht * Wt * C;
-	return 0;
+		return "texture must be at least 2 x 2";
+	if (C < 1 || C > DEODR_HIP_MAX_COLORS)
+		return "nb_colors out of range";
+	if (!elem_bytes(pixel_dtype))
+		return "unknown dtype tag";
+	if ((unsigned long long)Ht * (unsigned long long)Wt * (unsigned long long)C > (1ull << 30))
+		return "texture larger than 2^30 elements";
+	return NULL;
 }
 
-static bool texture_overlap(const void *a, const void *b, size_t bytes)
-{
-	const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-	return x < y + bytes && y < x + bytes;
-}
-
-size_t deodr_hip_texture_scratch_bytes(int Ht, int Wt, int C)
-{
-	const char *why;
-	return texture_dims(why, Ht, Wt, C, DEODR_HIP_F32) ? 64 + sizeof(double) * TEX_SMOOTH_BLOCKS : 0;
-}
+size_t deodr_hip_texture_scratch_bytes(int Ht, int Wt, int C) { return texture_dims(Ht, Wt, C, DEODR_HIP_F32) ? 0 : scratch_need(TEX_SMOOTH_BLOCKS); }
 
 int deodr_hip_texture_smoothness(const void *texture, int Ht, int Wt, int C, int pixel_dtype, double weight, void *gradient, double *energy, void *scratch,
 								 size_t scratch_bytes, void *stream)
 {
 	if (!texture || !gradient || !energy)
 		return fail("texture_smoothness: texture, gradient or energy == NULL");
-	const char *why = "";
-	const int N = texture_dims(why, Ht, Wt, C, pixel_dtype);
-	if (!N)
+	if (const char *why = texture_dims(Ht, Wt, C, pixel_dtype))
 		return fail(why);
-	if (!scratch || scratch_bytes < deodr_hip_texture_scratch_bytes(Ht, Wt, C))
+	const Scratch sc = {scratch, scratch_bytes};
+	if (!sc.holds(deodr_hip_texture_scratch_bytes(Ht, Wt, C)))
 		return fail("texture_smoothness: scratch too small (deodr_hip_texture_scratch_bytes)");
-	const size_t elem = pixel_dtype == DEODR_HIP_F64 ? 8 : 4;
-	if (texture_overlap(texture, gradient, (size_t)N * elem))
+	const int N = Ht * Wt * C;
+	const size_t elem = elem_bytes(pixel_dtype);
+	if (ranges_overlap(texture, (size_t)N * elem, gradient, (size_t)N * elem))
 		return fail("texture_smoothness: gradient must not overlap texture");
 	if ((((uintptr_t)texture | (uintptr_t)gradient) & (elem - 1)) || ((uintptr_t)scratch & 7))
 		return fail("texture_smoothness: misaligned pointer");
 	TexSmoothArgs a;
 	a.texture = texture, a.gradient = gradient, a.energy = energy;
-	a.counter = (unsigned *)scratch, a.partials = (double *)((char *)scratch + 64);
+	a.counter = sc.counter(0), a.partials = sc.doubles();
 	a.weight = weight, a.Ht = Ht, a.R = Wt * C, a.C = C, a.N = N;
-	const int pieces = N / (int)(16 / elem), want = (pieces + FH_BLOCK - 1) / FH_BLOCK;
-	const dim3 grid((unsigned)(want < 1 ? 1 : (want < TEX_SMOOTH_BLOCKS ? want : TEX_SMOOTH_BLOCKS)));
-	switch (pixel_dtype)
-	{
-	case DEODR_HIP_F32:
-		hipLaunchKernelGGL(texture_smoothness_kernel<float>, grid, dim3(FH_BLOCK), 0, (hipStream_t)stream, a);
-		break;
-	case DEODR_HIP_F64:
-		hipLaunchKernelGGL(texture_smoothness_kernel<double>, grid, dim3(FH_BLOCK), 0, (hipStream_t)stream, a);
-		break;
-	}
+	const dim3 grid(capped_blocks(N / (16 / elem), FH_BLOCK, TEX_SMOOTH_BLOCKS)); // (16-byte pieces)
+	with_dtype(pixel_dtype, [&](auto pix) { hipLaunchKernelGGL(texture_smoothness_kernel<decltype(pix)>, grid, dim3(FH_BLOCK), 0, (hipStream_t)stream, a); });
 	return check_hip(hipGetLastError(), "texture_smoothness launch");
 }
 
@@ -1308,14 +1310,13 @@ int deodr_hip_texture_step(void *texture, void *speed, const void *gradient, int
 {
 	if (!texture || !speed || !gradient)
 		return fail("texture_step: texture, speed or gradient == NULL");
-	const char *why = "";
-	const int N = texture_dims(why, Ht, Wt, C, pixel_dtype);
-	if (!N)
+	if (const char *why = texture_dims(Ht, Wt, C, pixel_dtype))
 		return fail(why);
-	const size_t elem = pixel_dtype == DEODR_HIP_F64 ? 8 : 4;
-	if (texture_overlap(texture, gradient, (size_t)N * elem))
+	const int N = Ht * Wt * C;
+	const size_t elem = elem_bytes(pixel_dtype), bytes = (size_t)N * elem;
+	if (ranges_overlap(texture, bytes, gradient, bytes))
 		return fail("texture_step: gradient must not overlap texture");
-	if (texture_overlap(texture, speed, (size_t)N * elem) || texture_overlap(speed, gradient, (size_t)N * elem))
+	if (ranges_overlap(texture, bytes, speed, bytes) || ranges_overlap(speed, bytes, gradient, bytes))
 		return fail("texture_step: speed must not overlap texture or gradient");
 	if (((uintptr_t)texture | (uintptr_t)speed | (uintptr_t)gradient) & (elem - 1))
 		return fail("texture_step: misaligned pointer");
@@ -1325,17 +1326,8 @@ int deodr_hip_texture_step(void *texture, void *speed, const void *gradient, int
 	a.texture = texture, a.speed = speed, a.gradient = gradient;
 	a.factor = factor, a.step_max = step_max, a.inertia = inertia, a.damping = damping, a.clamp_lo = clamp_lo, a.clamp_hi = clamp_hi;
 	a.clamp = clamp != 0, a.N = N;
-	const int pieces = N / (int)(16 / elem), want = (pieces + FH_BLOCK - 1) / FH_BLOCK;
-	const dim3 grid((unsigned)(want < 1 ? 1 : (want < TEX_STEP_BLOCKS ? want : TEX_STEP_BLOCKS)));
-	switch (pixel_dtype)
-	{
-	case DEODR_HIP_F32:
-		hipLaunchKernelGGL(texture_step_kernel<float>, grid, dim3(FH_BLOCK), 0, (hipStream_t)stream, a);
-		break;
-	case DEODR_HIP_F64:
-		hipLaunchKernelGGL(texture_step_kernel<double>, grid, dim3(FH_BLOCK), 0, (hipStream_t)stream, a);
-		break;
-	}
+	const dim3 grid(capped_blocks(N / (16 / elem), FH_BLOCK, TEX_STEP_BLOCKS)); // (16-byte pieces)
+	with_dtype(pixel_dtype, [&](auto pix) { hipLaunchKernelGGL(texture_step_kernel<decltype(pix)>, grid, dim3(FH_BLOCK), 0, (hipStream_t)stream, a); });
 	return check_hip(hipGetLastError(), "texture_step launch");
 }
 
@@ -1356,14 +1348,12 @@ int deodr_hip_subdiv_apply(const uint32_t *offsets, const uint32_t *cols, const 
 		return fail("subdiv_apply: batch must be in 1 .. 65535");
 	if (D < 1 || D > DEODR_HIP_MAX_COLORS)
 		return fail("subdiv_apply: D out of range");
-	if (dtype != DEODR_HIP_F32 && dtype != DEODR_HIP_F64)
+	const size_t elem = elem_bytes(dtype);
+	if (!elem)
 		return fail("unknown dtype tag");
-	const size_t elem = dtype == DEODR_HIP_F64 ? 8 : 4;
-	const uintptr_t xa = (uintptr_t)x, ya = (uintptr_t)y;
-	const size_t xb = (size_t)batch * (size_t)n_cols * (size_t)D * elem, yb = (size_t)batch * (size_t)n_rows * (size_t)D * elem;
-	if (xa < ya + yb && ya < xa + xb)
+	if (ranges_overlap(x, (size_t)batch * (size_t)n_cols * (size_t)D * elem, y, (size_t)batch * (size_t)n_rows * (size_t)D * elem))
 		return fail("subdiv_apply: y must not overlap x");
-	if (((xa | ya) & (elem - 1)) || ((uintptr_t)offsets & 3) || ((uintptr_t)cols & 3) || ((uintptr_t)vals & 7))
+	if ((((uintptr_t)x | (uintptr_t)y) & (elem - 1)) || ((uintptr_t)offsets & 3) || ((uintptr_t)cols & 3) || ((uintptr_t)vals & 7))
 		return fail("subdiv_apply: misaligned pointer");
 	const int lanes = subdiv_lanes(n_rows, nnz);
 	// (n_rows < 2^31 with 8 lanes, n_rows <= nnz / 32 < 2^27 with 64: at most 2^26 workgroups)
@@ -1372,21 +1362,9 @@ int deodr_hip_subdiv_apply(const uint32_t *offsets, const uint32_t *cols, const 
 	a.offsets = offsets, a.cols = cols, a.vals = vals, a.x = x, a.y = y;
 	a.n_rows = n_rows, a.n_cols = n_cols, a.D = D, a.accumulate = accumulate != 0;
 	const dim3 grid((unsigned)blocks, (unsigned)batch);
-	switch (2 * (lanes == SUBDIV_LANES_LONG) + (dtype == DEODR_HIP_F64))
-	{
-	case 0:
-		subdiv_launch_d<float, SUBDIV_LANES_SHORT>(a, grid, (hipStream_t)stream);
-		break;
-	case 1:
-		subdiv_launch_d<double, SUBDIV_LANES_SHORT>(a, grid, (hipStream_t)stream);
-		break;
-	case 2:
-		subdiv_launch_d<float, SUBDIV_LANES_LONG>(a, grid, (hipStream_t)stream);
-		break;
-	case 3:
-		subdiv_launch_d<double, SUBDIV_LANES_LONG>(a, grid, (hipStream_t)stream);
-		break;
-	}
+	with_constant<SUBDIV_LANES_SHORT, SUBDIV_LANES_LONG>(lanes == SUBDIV_LANES_LONG, [&](auto row_lanes) {
+		with_dtype(dtype, [&](auto elem_type) { subdiv_launch_d<decltype(elem_type), decltype(row_lanes)::value>(a, grid, (hipStream_t)stream); });
+	});
 	return check_hip(hipGetLastError(), "subdiv_apply launch");
 }
 
@@ -1407,19 +1385,6 @@ static const char *basis_dims(int K, int N, int batch)
 	return NULL;
 }
 
-static int basis_fail(const char *what, const char *why)
-{
-	char text[160];
-	snprintf(text, sizeof text, "%s: %s", what, why);
-	return fail(text);
-}
-
-static bool basis_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes)
-{
-	const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-	return a && b && x < y + b_bytes && y < x + a_bytes;
-}
-
 int deodr_hip_basis_segments(int K, int N) { return basis_dims(K, N, 1) ? 0 : basis_segments(K, N); }
 
 static size_t basis_counter_bytes(int K, int batch) { return (4 * (size_t)basis_chunks(batch) * (size_t)basis_row_tiles(K) + 63) / 64 * 64; }
@@ -1437,50 +1402,28 @@ int deodr_hip_basis_apply(const void *basis, const void *mean, const double *coe
 {
 	const char *what = "basis_apply";
 	if (!basis || !coeffs || !y)
-		return basis_fail(what, "basis, coeffs or y == NULL");
+		return fail(what, "basis, coeffs or y == NULL");
 	if (const char *why = basis_dims(K, N, batch))
-		return basis_fail(what, why);
-	if ((basis_dtype != DEODR_HIP_F32 && basis_dtype != DEODR_HIP_F64) || (y_dtype != DEODR_HIP_F32 && y_dtype != DEODR_HIP_F64))
+		return fail(what, why);
+	const size_t be = elem_bytes(basis_dtype), ye = elem_bytes(y_dtype);
+	if (!be || !ye)
 		return fail("unknown dtype tag");
-	const size_t be = basis_dtype == DEODR_HIP_F64 ? 8 : 4, ye = y_dtype == DEODR_HIP_F64 ? 8 : 4;
 	if ((((uintptr_t)basis | (uintptr_t)mean) & (be - 1)) || ((uintptr_t)y & (ye - 1)) || ((uintptr_t)coeffs & 7))
-		return basis_fail(what, "misaligned pointer");
+		return fail(what, "misaligned pointer");
 	const size_t y_bytes = (size_t)batch * (size_t)N * ye;
-	if (basis_overlap(y, y_bytes, basis, (size_t)K * (size_t)N * be) || basis_overlap(y, y_bytes, mean, (size_t)N * be) ||
-		basis_overlap(y, y_bytes, coeffs, (size_t)batch * (size_t)K * 8))
-		return basis_fail(what, "y must not overlap basis, mean or coeffs");
+	if (ranges_overlap(y, y_bytes, basis, (size_t)K * (size_t)N * be) || ranges_overlap(y, y_bytes, mean, (size_t)N * be) ||
+		ranges_overlap(y, y_bytes, coeffs, (size_t)batch * (size_t)K * 8))
+		return fail(what, "y must not overlap basis, mean or coeffs");
 	BasisArgs a = {};
 	a.basis = basis, a.mean = mean, a.coeffs = coeffs, a.y = y, a.K = K, a.N = N, a.batch = batch;
 	const int pieces = N / (int)(16 / be), blocks = (pieces + FH_BLOCK - 1) / FH_BLOCK;
 	const dim3 grid((unsigned)(blocks < 1 ? 1 : blocks), (unsigned)basis_chunks(batch)), block(FH_BLOCK);
 	const hipStream_t st = (hipStream_t)stream;
-	switch (4 * (batch > 1) + 2 * (basis_dtype == DEODR_HIP_F64) + (y_dtype == DEODR_HIP_F64))
-	{
-	case 0:
-		hipLaunchKernelGGL((basis_apply_kernel<float, float, 1>), grid, block, 0, st, a);
-		break;
-	case 1:
-		hipLaunchKernelGGL((basis_apply_kernel<float, double, 1>), grid, block, 0, st, a);
-		break;
-	case 2:
-		hipLaunchKernelGGL((basis_apply_kernel<double, float, 1>), grid, block, 0, st, a);
-		break;
-	case 3:
-		hipLaunchKernelGGL((basis_apply_kernel<double, double, 1>), grid, block, 0, st, a);
-		break;
-	case 4:
-		hipLaunchKernelGGL((basis_apply_kernel<float, float, BASIS_CHUNK>), grid, block, 0, st, a);
-		break;
-	case 5:
-		hipLaunchKernelGGL((basis_apply_kernel<float, double, BASIS_CHUNK>), grid, block, 0, st, a);
-		break;
-	case 6:
-		hipLaunchKernelGGL((basis_apply_kernel<double, float, BASIS_CHUNK>), grid, block, 0, st, a);
-		break;
-	case 7:
-		hipLaunchKernelGGL((basis_apply_kernel<double, double, BASIS_CHUNK>), grid, block, 0, st, a);
-		break;
-	}
+	with_constant<1, BASIS_CHUNK>(batch > 1, [&](auto chunk) {
+		with_dtype(basis_dtype, [&](auto b) {
+			with_dtype(y_dtype, [&](auto out) { hipLaunchKernelGGL((basis_apply_kernel<decltype(b), decltype(out), decltype(chunk)::value>), grid, block, 0, st, a); });
+		});
+	});
 	return check_hip(hipGetLastError(), "basis_apply launch");
 }
 
@@ -1489,51 +1432,29 @@ int deodr_hip_basis_apply_b(const void *basis, const void *g, int g_dtype, int K
 {
 	const char *what = "basis_apply_b";
 	if (!basis || !g || !coeffs_b || !scratch)
-		return basis_fail(what, "basis, g, coeffs_b or scratch == NULL");
+		return fail(what, "basis, g, coeffs_b or scratch == NULL");
 	if (const char *why = basis_dims(K, N, batch))
-		return basis_fail(what, why);
-	if ((basis_dtype != DEODR_HIP_F32 && basis_dtype != DEODR_HIP_F64) || (g_dtype != DEODR_HIP_F32 && g_dtype != DEODR_HIP_F64))
+		return fail(what, why);
+	const size_t be = elem_bytes(basis_dtype), ge = elem_bytes(g_dtype);
+	if (!be || !ge)
 		return fail("unknown dtype tag");
-	const size_t be = basis_dtype == DEODR_HIP_F64 ? 8 : 4, ge = g_dtype == DEODR_HIP_F64 ? 8 : 4;
 	if (((uintptr_t)basis & (be - 1)) || ((uintptr_t)g & (ge - 1)) || (((uintptr_t)coeffs_b | (uintptr_t)scratch) & 7))
-		return basis_fail(what, "misaligned pointer");
+		return fail(what, "misaligned pointer");
 	const size_t c_bytes = (size_t)batch * (size_t)K * 8;
-	if (basis_overlap(coeffs_b, c_bytes, basis, (size_t)K * (size_t)N * be) || basis_overlap(coeffs_b, c_bytes, g, (size_t)batch * (size_t)N * ge))
-		return basis_fail(what, "coeffs_b must not overlap basis or g");
+	if (ranges_overlap(coeffs_b, c_bytes, basis, (size_t)K * (size_t)N * be) || ranges_overlap(coeffs_b, c_bytes, g, (size_t)batch * (size_t)N * ge))
+		return fail(what, "coeffs_b must not overlap basis or g");
 	if (scratch_bytes < deodr_hip_basis_scratch_bytes(K, N, batch))
-		return basis_fail(what, "scratch too small (deodr_hip_basis_scratch_bytes)");
+		return fail(what, "scratch too small (deodr_hip_basis_scratch_bytes)");
 	BasisArgs a = {};
 	a.basis = basis, a.g = g, a.coeffs_b = coeffs_b, a.K = K, a.N = N, a.batch = batch, a.S = basis_segments(K, N), a.accumulate = accumulate != 0;
 	a.counters = (unsigned *)scratch, a.partials = (double *)((char *)scratch + basis_counter_bytes(K, batch));
 	const dim3 grid((unsigned)a.S, (unsigned)basis_row_tiles(K), (unsigned)basis_chunks(batch)), block(FH_BLOCK);
 	const hipStream_t st = (hipStream_t)stream;
-	switch (4 * (batch > 1) + 2 * (basis_dtype == DEODR_HIP_F64) + (g_dtype == DEODR_HIP_F64))
-	{
-	case 0:
-		hipLaunchKernelGGL((basis_apply_b_kernel<float, float, 1>), grid, block, 0, st, a);
-		break;
-	case 1:
-		hipLaunchKernelGGL((basis_apply_b_kernel<float, double, 1>), grid, block, 0, st, a);
-		break;
-	case 2:
-		hipLaunchKernelGGL((basis_apply_b_kernel<double, float, 1>), grid, block, 0, st, a);
-		break;
-	case 3:
-		hipLaunchKernelGGL((basis_apply_b_kernel<double, double, 1>), grid, block, 0, st, a);
-		break;
-	case 4:
-		hipLaunchKernelGGL((basis_apply_b_kernel<float, float, BASIS_CHUNK>), grid, block, 0, st, a);
-		break;
-	case 5:
-		hipLaunchKernelGGL((basis_apply_b_kernel<float, double, BASIS_CHUNK>), grid, block, 0, st, a);
-		break;
-	case 6:
-		hipLaunchKernelGGL((basis_apply_b_kernel<double, float, BASIS_CHUNK>), grid, block, 0, st, a);
-		break;
-	case 7:
-		hipLaunchKernelGGL((basis_apply_b_kernel<double, double, BASIS_CHUNK>), grid, block, 0, st, a);
-		break;
-	}
+	with_constant<1, BASIS_CHUNK>(batch > 1, [&](auto chunk) {
+		with_dtype(basis_dtype, [&](auto b) {
+			with_dtype(g_dtype, [&](auto grad) { hipLaunchKernelGGL((basis_apply_b_kernel<decltype(b), decltype(grad), decltype(chunk)::value>), grid, block, 0, st, a); });
+		});
+	});
 	return check_hip(hipGetLastError(), "basis_apply_b launch");
 }
 

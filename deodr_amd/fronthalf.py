@@ -7,13 +7,7 @@ import ctypes as C
 
 import torch
 
-from .hip_renderer import _check, _ptr, _stream, lib
-
-
-def _launch(function, device, *args):
-    """one call of the library on the current stream of `device` (every function here takes the stream last)"""
-    with torch.cuda.device(device):
-        _check(function(*args, _stream(device)))
+from .hip_renderer import _dtype_tag, _launch, _ptr, lib
 
 
 def usable(*tensors):
@@ -219,7 +213,7 @@ def rigid_energy(vertices, vertices_ref, topology, cregu, gradient, energy, scra
 def l2_loss(image, obs, out, scratch):
     """out[0] = sum (image - obs)^2, image and obs contiguous tensors of one pixel dtype (float32 / float64) and one shape"""
     assert image.dtype == obs.dtype and image.shape == obs.shape and image.is_contiguous() and obs.is_contiguous()
-    _launch(lib().deodr_hip_l2_loss, image.device, _ptr(image), _ptr(obs), 1 if image.dtype == torch.float64 else 0, image.numel(), _ptr(out),
+    _launch(lib().deodr_hip_l2_loss, image.device, _ptr(image), _ptr(obs), _dtype_tag(image), image.numel(), _ptr(out),
             _ptr(scratch), scratch.numel())  # fmt: skip
 
 
@@ -228,7 +222,7 @@ def depth_residual(image, obs, max_depth, depth, diff, image_b, loss, scratch):
     image_b = d sum(diff) / d image in the pixel dtype, loss[0] = sum diff (deodr/mesh_fitter.py:108-123)"""
     assert obs.dtype == torch.float64 and depth.dtype == torch.float64 and diff.dtype == torch.float64 and image_b.dtype == image.dtype
     assert all(t.is_contiguous() and t.numel() == image.numel() for t in (image, obs, depth, diff, image_b))
-    _launch(lib().deodr_hip_depth_residual, image.device, _ptr(image), 1 if image.dtype == torch.float64 else 0, _ptr(obs), float(max_depth),
+    _launch(lib().deodr_hip_depth_residual, image.device, _ptr(image), _dtype_tag(image), _ptr(obs), float(max_depth),
             image.numel(), _ptr(depth), _ptr(diff), _ptr(image_b), _ptr(loss), _ptr(scratch), scratch.numel())  # fmt: skip
 
 

@@ -26,14 +26,18 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libdeodr_hip.so")
 _H = _abi.HEADER  # the structs, the constants and (in lib()) the signatures are read from include/deodr_hip.h: deodr_amd/_abi.py
 _SceneC, _FitOptionsC, ABI_VERSION = _H.structs["DeodrHipScene"], _H.structs["DeodrHipFitOptions"], _H.defines["DEODR_HIP_ABI_VERSION"]
 ERR_FACES, ERR_FACES_UV, ERR_NO_TEXTURE, ERR_INTERNAL, ERR_DET_RANGE = (_H.defines["DEODR_HIP_ERR_" + n] for n in "FACES FACES_UV NO_TEXTURE INTERNAL DET_RANGE".split())
-_HT = _abi.TEXTURE_HEADER  # the companion header include/deodr_hip_texture.h (texture estimation), bound onto the same library
-TEXTURE_ABI_VERSION, MAX_COLORS = _HT.defines["DEODR_HIP_TEXTURE_ABI_VERSION"], _H.defines["DEODR_HIP_MAX_COLORS"]
-_HS = _abi.SUBDIV_HEADER  # the companion header include/deodr_hip_subdiv.h (Loop subdivision), bound onto the same library
-SUBDIV_ABI_VERSION = _HS.defines["DEODR_HIP_SUBDIV_ABI_VERSION"]
-_HR = _abi.RETAINED_HEADER  # the companion header include/deodr_hip_retained.h (fit step into retained frames), bound onto the same library
-RETAINED_ABI_VERSION = _HR.defines["DEODR_HIP_RETAINED_ABI_VERSION"]
-_HB = _abi.BASIS_HEADER  # the companion header include/deodr_hip_basis.h (linear bases: morphable models), bound onto the same library
-BASIS_ABI_VERSION = _HB.defines["DEODR_HIP_BASIS_ABI_VERSION"]
+MAX_COLORS, _F32, _F64 = (_H.defines["DEODR_HIP_" + n] for n in ("MAX_COLORS", "F32", "F64"))
+# The companion headers, bound onto the same library and versioned each on its own: (header, KEY of deodr_hip_KEY_abi_version() and of
+# DEODR_HIP_KEY_ABI_VERSION, what a version mismatch is called)
+_COMPANIONS = (
+    (_abi.TEXTURE_HEADER, "texture", "texture"),  # texture estimation
+    (_abi.SUBDIV_HEADER, "subdiv", "subdivision"),  # Loop subdivision
+    (_abi.RETAINED_HEADER, "retained", "retained-frames"),  # fit step into retained frames
+    (_abi.BASIS_HEADER, "basis", "linear-basis"),  # linear bases: morphable models
+)
+TEXTURE_ABI_VERSION, SUBDIV_ABI_VERSION, RETAINED_ABI_VERSION, BASIS_ABI_VERSION = (
+    h.defines[f"DEODR_HIP_{key.upper()}_ABI_VERSION"] for h, key, _ in _COMPANIONS
+)
 # words of the 64-byte status block at the start of the workspace
 _STATUS_NEEDED, _STATUS_ERRORS = _H.defines["DEODR_HIP_STATUS_WORD_NEEDED_PAIRS"], _H.defines["DEODR_HIP_STATUS_WORD_SCENE_ERRORS"]
 
@@ -52,18 +56,10 @@ def lib():
         L = C.CDLL(LIB_PATH)
         if L.deodr_hip_abi_version() != ABI_VERSION:
             raise ImportError("libdeodr_hip.so ABI version mismatch; rebuild it")
-        _abi.bind(L, _HT)  # (a library that lacks one of its symbols is refused by name)
-        if L.deodr_hip_texture_abi_version() != TEXTURE_ABI_VERSION:
-            raise ImportError("libdeodr_hip.so texture ABI version mismatch (include/deodr_hip_texture.h); rebuild it")
-        _abi.bind(L, _HS)
-        if L.deodr_hip_subdiv_abi_version() != SUBDIV_ABI_VERSION:
-            raise ImportError("libdeodr_hip.so subdivision ABI version mismatch (include/deodr_hip_subdiv.h); rebuild it")
-        _abi.bind(L, _HR)
-        if L.deodr_hip_retained_abi_version() != RETAINED_ABI_VERSION:
-            raise ImportError("libdeodr_hip.so retained-frames ABI version mismatch (include/deodr_hip_retained.h); rebuild it")
-        _abi.bind(L, _HB)
-        if L.deodr_hip_basis_abi_version() != BASIS_ABI_VERSION:
-            raise ImportError("libdeodr_hip.so linear-basis ABI version mismatch (include/deodr_hip_basis.h); rebuild it")
+        for header, key, words in _COMPANIONS:
+            _abi.bind(L, header)  # (a library that lacks one of its symbols is refused by name)
+            if getattr(L, f"deodr_hip_{key}_abi_version")() != header.defines[f"DEODR_HIP_{key.upper()}_ABI_VERSION"]:
+                raise ImportError(f"libdeodr_hip.so {words} ABI version mismatch ({header.name}); rebuild it")
         _lib = _abi.bind(L)
     return _lib
 
@@ -130,6 +126,17 @@ def _stream(device=None):
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+def _launch(function, device, *args):
+    """one call of the library on the current stream of `device` (every function that launches takes the stream last)"""
+    with torch.cuda.device(device):
+        _check(function(*args, _stream(device)))
+
+
+def _dtype_tag(t):
+    """the dtype tag of include/deodr_hip.h for a float32 / float64 tensor"""
+    return _F64 if t.dtype == torch.float64 else _F32
+
+
 def _resolve_device(device):
     """the ROCm device a scene or a workspace lives on (there is no CPU path: anything else is refused)"""
     dev = torch.device(device)
@@ -170,25 +177,62 @@ def _pixels(t, ds):
     return t if tuple(t.shape) == shape else t.expand(shape).contiguous()  # pass [n,H,W,C] to avoid this copy
 
 
-# ---- texture estimation (include/deodr_hip_texture.h) ---------------------------------------------------------------------------------
+# ---- what the operator wrappers below share: one checker of tensor arguments, one cache of scratch buffers --------------------------------
 
-_texture_scratch_cache = {}  # (device, stream) -> the zero-filled scratch of deodr_hip_texture_smoothness
+_FLOATS = (torch.float32, torch.float64)
+_NO_CPU = "(deodr_amd has no CPU path)"
+
+
+def _rocm_tensor(what, name, t):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise ValueError(f"{what}: {name} must be a ROCm tensor {_NO_CPU}")
+
+
+def _check_tensors(what, anchor, device, rows):
+    """checks before the library is called.  ``rows`` [(name, tensor, dtypes, shape[, says])]: each a ROCm tensor on ``device`` (that of the argument
+    called ``anchor``), of one of ``dtypes``, of ``shape`` (None: any shape; an entry None: any size, printed as "batch"), contiguous -- checked in
+    this order, row by row.  ``says``: the one sentence a row gives for everything but contiguity, where the wrapper has always had one."""
+    for name, t, dtypes, shape, *says in rows:
+        said = f"{what}: {says[0]}" if says else None
+        if not torch.is_tensor(t) or not t.is_cuda or t.device != device:
+            raise ValueError(said or f"{what}: {name} must be a ROCm tensor on the device of {anchor} {_NO_CPU}")
+        if t.dtype not in dtypes:
+            raise ValueError(said or f"{what}: {name} must be {' or '.join(str(d).replace('torch.', '') for d in dtypes)}, not {t.dtype}")
+        if shape is not None and (t.dim() != len(shape) or any(want is not None and int(have) != want for have, want in zip(t.shape, shape))):
+            raise ValueError(said or f"{what}: {name} must have shape [{', '.join('batch' if v is None else str(v) for v in shape)}], not {list(t.shape)}")
+        if not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be contiguous")
+
+
+_scratch_cache = {}  # (whose, device, stream) -> a zero-filled scratch of the library, grown to the largest request
+
+
+def _cached_scratch(whose, device, need, make, when_capturing):
+    """the scratch ``whose`` kernels use on the current stream of ``device``, at least ``need`` bytes: made (``make()``) or grown at the call, which a
+    stream that is being captured into a graph cannot do -- RuntimeError(``when_capturing``)"""
+    key = (whose, device, torch.cuda.current_stream(device).cuda_stream)
+    scratch = _scratch_cache.get(key)
+    if scratch is None or scratch.numel() < need:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(when_capturing)
+        scratch = _scratch_cache[key] = make()
+    return scratch
+
+
+# ---- texture estimation (include/deodr_hip_texture.h) ---------------------------------------------------------------------------------
 
 
 def _texture_args(what, texture, others):
-    """checks before the library is called: a [Ht,Wt,C] float32 / float64 contiguous ROCm tensor, `others` {name: tensor} of its shape, dtype and device"""
-    if not torch.is_tensor(texture) or not texture.is_cuda:
-        raise ValueError(f"{what}: texture must be a ROCm tensor (deodr_amd has no CPU path)")
+    """checks before the library is called: a [Ht,Wt,C] float32 / float64 contiguous ROCm tensor, `others` {name: tensor} of its shape, dtype and device;
+    -> (Ht, Wt, C, dtype tag)"""
+    _rocm_tensor(what, "texture", texture)
     if texture.dim() != 3 or texture.shape[0] < 2 or texture.shape[1] < 2 or not 1 <= texture.shape[2] <= MAX_COLORS:
         raise ValueError(f"{what}: texture must have shape [Ht >= 2, Wt >= 2, 1 <= C <= {MAX_COLORS}], not {list(texture.shape)}")
-    if texture.dtype not in (torch.float32, torch.float64):
-        raise ValueError(f"{what}: texture must be float32 or float64, not {texture.dtype}")
-    for name, t in [("texture", texture)] + list(others.items()):
-        if not torch.is_tensor(t) or t.device != texture.device or t.dtype != texture.dtype or tuple(t.shape) != tuple(texture.shape):
-            raise ValueError(f"{what}: {name} must be a tensor of the texture's shape, dtype and device")
-        if not t.is_contiguous():
-            raise ValueError(f"{what}: {name} must be contiguous")
-    return (int(texture.shape[0]), int(texture.shape[1]), int(texture.shape[2]), 1 if texture.dtype == torch.float64 else 0)
+    shape = tuple(int(v) for v in texture.shape)
+    rows = [("texture", texture, _FLOATS, None)]
+    rows += [(name, t, (texture.dtype,), shape, f"{name} must be a tensor of the texture's shape, dtype and device") for name, t in others.items()]
+    _check_tensors(what, "texture", texture.device, rows)
+    return (*shape, _dtype_tag(texture))
 
 
 def texture_scratch(device):
@@ -202,24 +246,20 @@ def texture_smoothness(texture, gradient, weight, energy_out=None, scratch=None)
     boundary; ``dE/dtexture`` is ACCUMULATED into ``gradient`` (same shape and dtype -- typically the rasterizer's ``texture_b``); -> ``energy_out``
     (a float64 device tensor of one element, allocated when None) holding E.  Deterministic; asynchronous on the current stream.  ``scratch``: a
     :func:`texture_scratch` of the caller's (a fitter whose step is captured in a graph keeps one); None: one per device and stream, made at the first call."""
-    dims = _texture_args("texture_smoothness", texture, {"gradient": gradient})
+    what = "texture_smoothness"
+    dims = _texture_args(what, texture, {"gradient": gradient})
     dev = texture.device
     with torch.cuda.device(dev):
         if energy_out is None:
             energy_out = torch.empty(1, dtype=torch.float64, device=dev)
         if energy_out.dtype != torch.float64 or energy_out.device != dev or energy_out.numel() != 1:
-            raise ValueError("texture_smoothness: energy_out must be a float64 tensor of one element on the texture's device")
-        key = (dev, torch.cuda.current_stream(dev).cuda_stream)
+            raise ValueError(f"{what}: energy_out must be a float64 tensor of one element on the texture's device")
         if scratch is None:
-            scratch = _texture_scratch_cache.get(key)
+            scratch = _cached_scratch("texture", dev, 0, lambda: texture_scratch(dev),
+                                      f"{what}: pass scratch= (texture_scratch) when capturing a graph: none exists for this stream yet")  # fmt: skip
         elif scratch.device != dev or scratch.dtype != torch.uint8 or not scratch.is_contiguous():
-            raise ValueError("texture_smoothness: scratch must be a texture_scratch() of the texture's device")
-        if scratch is None:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("texture_smoothness: pass scratch= (texture_scratch) when capturing a graph: none exists for this stream yet")
-            scratch = _texture_scratch_cache[key] = texture_scratch(dev)
-        _check(lib().deodr_hip_texture_smoothness(_ptr(texture), *dims, float(weight), _ptr(gradient), _ptr(energy_out), _ptr(scratch), scratch.numel(),
-                                                  _stream(dev)))  # fmt: skip
+            raise ValueError(f"{what}: scratch must be a texture_scratch() of the texture's device")
+    _launch(lib().deodr_hip_texture_smoothness, dev, _ptr(texture), *dims, float(weight), _ptr(gradient), _ptr(energy_out), _ptr(scratch), scratch.numel())
     return energy_out
 
 
@@ -235,15 +275,15 @@ def texture_step(texture, speed, gradient, factor, step_max=None, inertia=0.0, d
     IN PLACE on ``texture`` and ``speed`` (``_Momentum.update`` for a pixel-typed array); ``clamp`` = (lo, hi): the texture is clipped to it and the
     speed set to 0 where it clipped.  ``gradient`` is only read.  Asynchronous on the current stream."""
     dims = _texture_args("texture_step", texture, {"speed": speed, "gradient": gradient})
-    dev = texture.device
     lo, hi = (0.0, 0.0) if clamp is None else (float(clamp[0]), float(clamp[1]))
-    with torch.cuda.device(dev):
-        _check(lib().deodr_hip_texture_step(_ptr(texture), _ptr(speed), _ptr(gradient), *dims, float(factor), 0.0 if step_max is None else float(step_max),
-                                            float(inertia), float(damping), int(clamp is not None), lo, hi, _stream(dev)))  # fmt: skip
+    _launch(lib().deodr_hip_texture_step, texture.device, _ptr(texture), _ptr(speed), _ptr(gradient), *dims, float(factor),
+            0.0 if step_max is None else float(step_max), float(inertia), float(damping), int(clamp is not None), lo, hi)  # fmt: skip
     _touched(texture), _touched(speed)
 
 
 # ---- Loop subdivision (include/deodr_hip_subdiv.h) ------------------------------------------------------------------------------------
+
+_INDICES = (torch.int32, torch.uint32)
 
 
 def sparse_rows_lanes(n_rows, nnz):
@@ -259,19 +299,17 @@ def sparse_rows_apply(offsets, cols, vals, x, out=None, accumulate=False):
     The tables are trusted (``offsets`` non-decreasing from 0 to nnz, ``cols`` < n_cols): :class:`deodr_amd.subdivision.LoopSubdivision` checks its
     own on the host when it builds them."""
     what = "sparse_rows_apply"
-    for name, t in (("offsets", offsets), ("cols", cols), ("vals", vals), ("x", x)):
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise ValueError(f"{what}: {name} must be a ROCm tensor (deodr_amd has no CPU path)")
+    for name, t in (("offsets", offsets), ("cols", cols), ("vals", vals), ("x", x)):  # (all four are tensors before anything is asked of one of them)
+        _rocm_tensor(what, name, t)
         if not t.is_contiguous():
             raise ValueError(f"{what}: {name} must be contiguous")
         if t.device != x.device:
             raise ValueError(f"{what}: {name} must be on the device of x")
-    if offsets.dtype not in (torch.int32, torch.uint32) or cols.dtype not in (torch.int32, torch.uint32) or offsets.dim() != 1 or cols.dim() != 1:
-        raise ValueError(f"{what}: offsets and cols must be one-dimensional 4-byte integer tensors")
-    if vals.dtype != torch.float64 or tuple(vals.shape) != tuple(cols.shape):
-        raise ValueError(f"{what}: vals must be a float64 tensor of the shape of cols")
-    if x.dtype not in (torch.float32, torch.float64):
-        raise ValueError(f"{what}: x must be float32 or float64, not {x.dtype}")
+    tables = "offsets and cols must be one-dimensional 4-byte integer tensors"
+    _check_tensors(what, "x", x.device, [
+        ("offsets", offsets, _INDICES, (None,), tables), ("cols", cols, _INDICES, (None,), tables),
+        ("vals", vals, (torch.float64,), tuple(cols.shape), "vals must be a float64 tensor of the shape of cols"), ("x", x, _FLOATS, None),
+    ])  # fmt: skip
     if x.dim() != 3 or not 1 <= x.shape[2] <= MAX_COLORS or x.shape[0] < 1 or x.shape[1] < 1:
         raise ValueError(f"{what}: x must have shape [batch >= 1, n_cols >= 1, 1 <= D <= {MAX_COLORS}], not {list(x.shape)}")
     n_rows, nnz = int(offsets.numel()) - 1, int(cols.numel())
@@ -279,15 +317,15 @@ def sparse_rows_apply(offsets, cols, vals, x, out=None, accumulate=False):
         raise ValueError(f"{what}: the matrix has no rows or no entries")
     batch, n_cols, D = (int(v) for v in x.shape)
     dev = x.device
-    with torch.cuda.device(dev):
-        if out is None:
-            if accumulate:
-                raise ValueError(f"{what}: accumulate needs out")
+    if out is None:
+        if accumulate:
+            raise ValueError(f"{what}: accumulate needs out")
+        with torch.cuda.device(dev):
             out = torch.empty((batch, n_rows, D), dtype=x.dtype, device=dev)
-        elif not torch.is_tensor(out) or out.device != dev or out.dtype != x.dtype or tuple(out.shape) != (batch, n_rows, D) or not out.is_contiguous():
-            raise ValueError(f"{what}: out must be a contiguous {x.dtype} tensor of shape {[batch, n_rows, D]} on the device of x")
-        _check(lib().deodr_hip_subdiv_apply(_ptr(offsets), _ptr(cols), _ptr(vals), n_rows, n_cols, nnz, _ptr(x), _ptr(out), batch, D,
-                                            1 if x.dtype == torch.float64 else 0, int(bool(accumulate)), _stream(dev)))  # fmt: skip
+    elif not torch.is_tensor(out) or out.device != dev or out.dtype != x.dtype or tuple(out.shape) != (batch, n_rows, D) or not out.is_contiguous():
+        raise ValueError(f"{what}: out must be a contiguous {x.dtype} tensor of shape {[batch, n_rows, D]} on the device of x")
+    _launch(lib().deodr_hip_subdiv_apply, dev, _ptr(offsets), _ptr(cols), _ptr(vals), n_rows, n_cols, nnz, _ptr(x), _ptr(out), batch, D, _dtype_tag(x),
+            int(bool(accumulate)))  # fmt: skip
     if accumulate:
         _touched(out)
     return out
@@ -296,29 +334,19 @@ def sparse_rows_apply(offsets, cols, vals, x, out=None, accumulate=False):
 # ---- linear bases (include/deodr_hip_basis.h) -----------------------------------------------------------------------------------------
 
 BASIS_MAX_K, BASIS_MAX_BATCH, BASIS_MAX_N = 1024, 64, 2**30  # the limits include/deodr_hip_basis.h states
-_basis_scratch_cache = {}  # (device, stream) -> the zero-filled scratch of deodr_hip_basis_apply_b, grown to the largest request
 
 
 def _basis_args(what, basis, tensors):
-    """checks before the library is called: ``basis`` a contiguous [K, N] float32 / float64 ROCm tensor within the header's limits; ``tensors``
-    [(name, tensor, dtypes, shape with None = any)]: contiguous tensors on its device; -> (K, N)"""
-    if not torch.is_tensor(basis) or not basis.is_cuda:
-        raise ValueError(f"{what}: basis must be a ROCm tensor (deodr_amd has no CPU path)")
-    if basis.dtype not in (torch.float32, torch.float64):
+    """checks before the library is called: ``basis`` a contiguous [K, N] float32 / float64 ROCm tensor within the header's limits; ``tensors``: rows
+    of :func:`_check_tensors`, tensors on its device; -> (K, N)"""
+    _rocm_tensor(what, "basis", basis)
+    if basis.dtype not in _FLOATS:
         raise ValueError(f"{what}: basis must be float32 or float64, not {basis.dtype}")
     if basis.dim() != 2 or not 1 <= basis.shape[0] <= BASIS_MAX_K or not 1 <= basis.shape[1] <= BASIS_MAX_N or basis.numel() > 2**31 - 1:
         raise ValueError(f"{what}: basis must have shape [1 <= K <= {BASIS_MAX_K}, 1 <= N <= 2^30] with K N <= 2^31 - 1, not {list(basis.shape)}")
     if not basis.is_contiguous():
         raise ValueError(f"{what}: basis must be contiguous")
-    for name, t, dtypes, shape in tensors:
-        if not torch.is_tensor(t) or not t.is_cuda or t.device != basis.device:
-            raise ValueError(f"{what}: {name} must be a ROCm tensor on the device of basis (deodr_amd has no CPU path)")
-        if t.dtype not in dtypes:
-            raise ValueError(f"{what}: {name} must be {' or '.join(str(d).replace('torch.', '') for d in dtypes)}, not {t.dtype}")
-        if t.dim() != len(shape) or any(want is not None and int(have) != want for have, want in zip(t.shape, shape)):
-            raise ValueError(f"{what}: {name} must have shape [{', '.join('batch' if v is None else str(v) for v in shape)}], not {list(t.shape)}")
-        if not t.is_contiguous():
-            raise ValueError(f"{what}: {name} must be contiguous")
+    _check_tensors(what, "basis", basis.device, tensors)
     return int(basis.shape[0]), int(basis.shape[1])
 
 
@@ -326,9 +354,6 @@ def _basis_batch(what, t):
     if not 1 <= int(t.shape[0]) <= BASIS_MAX_BATCH:
         raise ValueError(f"{what}: batch must be in 1 .. {BASIS_MAX_BATCH}, not {int(t.shape[0])}")
     return int(t.shape[0])
-
-
-_FLOATS = (torch.float32, torch.float64)
 
 
 def basis_segments(K, N):
@@ -367,11 +392,10 @@ def basis_apply(basis, mean, coeffs, out=None, out_dtype=None):
     if out is None and (out_dtype or torch.float64) not in _FLOATS:
         raise ValueError(f"{what}: out_dtype must be float32 or float64, not {out_dtype}")
     dev = basis.device
-    with torch.cuda.device(dev):
-        if out is None:
+    if out is None:
+        with torch.cuda.device(dev):
             out = torch.empty((batch, N), dtype=out_dtype or torch.float64, device=dev)
-        _check(lib().deodr_hip_basis_apply(_ptr(basis), _ptr(mean), _ptr(coeffs), K, N, batch, 1 if basis.dtype == torch.float64 else 0, _ptr(out),
-                                           1 if out.dtype == torch.float64 else 0, _stream(dev)))  # fmt: skip
+    _launch(lib().deodr_hip_basis_apply, dev, _ptr(basis), _ptr(mean), _ptr(coeffs), K, N, batch, _dtype_tag(basis), _ptr(out), _dtype_tag(out))
     _touched(out)
     return out
 
@@ -402,15 +426,10 @@ def basis_apply_b(basis, g, out=None, accumulate=False, scratch=None):
         if out is None:
             out = torch.empty((batch, K), dtype=torch.float64, device=dev)
         if scratch is None:
-            need = int(lib().deodr_hip_basis_scratch_bytes(K, N, batch))
-            key = (dev, torch.cuda.current_stream(dev).cuda_stream)
-            scratch = _basis_scratch_cache.get(key)
-            if scratch is None or scratch.numel() < need:
-                if torch.cuda.is_current_stream_capturing():
-                    raise RuntimeError(f"{what}: pass scratch= (basis_scratch) when capturing a graph: none of this size exists for this stream yet")
-                scratch = _basis_scratch_cache[key] = basis_scratch(K, N, batch, dev)
-        _check(lib().deodr_hip_basis_apply_b(_ptr(basis), _ptr(g), 1 if g.dtype == torch.float64 else 0, K, N, batch, 1 if basis.dtype == torch.float64 else 0,
-                                             _ptr(out), int(bool(accumulate)), _ptr(scratch), scratch.numel(), _stream(dev)))  # fmt: skip
+            scratch = _cached_scratch("basis", dev, int(lib().deodr_hip_basis_scratch_bytes(K, N, batch)), lambda: basis_scratch(K, N, batch, dev),
+                                      f"{what}: pass scratch= (basis_scratch) when capturing a graph: none of this size exists for this stream yet")  # fmt: skip
+    _launch(lib().deodr_hip_basis_apply_b, dev, _ptr(basis), _ptr(g), _dtype_tag(g), K, N, batch, _dtype_tag(basis), _ptr(out), int(bool(accumulate)),
+            _ptr(scratch), scratch.numel())  # fmt: skip
     _touched(out)
     return out
 

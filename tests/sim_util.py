@@ -1,4 +1,4 @@
-"""ctypes front-end of tests/sim/libtile_sim.so (host instantiation of the kernels' per-primitive code) and libdispatch_sim.so; tests only."""
+"""ctypes front-end of tests/sim/libtile_sim.so (host instantiation of the kernels' per-primitive code), libdispatch_sim.so and libhost_sim.so; tests only."""
 
 import ctypes as C
 import os
@@ -39,6 +39,27 @@ def lib():
 def dispatch_lib():
     """tests/sim/libdispatch_sim.so: the instance rules and tables of deodr_amd/csrc/dr_dispatch.h (tests/sim/dispatch_sim.cpp)."""
     return _built(os.path.join(HERE, "sim", "dispatch_sim.cpp"), os.path.join(HERE, "sim", "libdispatch_sim.so"), ("dr_dispatch.h",))
+
+
+def host_lib():
+    """tests/sim/libhost_sim.so: the argument checks and the scratch view of deodr_amd/csrc/dr_host.h (tests/sim/host_sim.cpp)."""
+    L = _built(os.path.join(HERE, "sim", "host_sim.cpp"), os.path.join(HERE, "sim", "libhost_sim.so"), ("dr_host.h",))
+    for name, restype, argtypes in (
+        ("host_elem_bytes", C.c_size_t, [C.c_int]), ("host_ranges_overlap", C.c_int, [C.c_size_t] * 4),
+        ("host_capped_blocks", C.c_uint, [C.c_size_t, C.c_size_t, C.c_uint]), ("host_scratch_need", C.c_size_t, [C.c_size_t]),
+        ("host_scratch_holds", C.c_int, [C.c_size_t] * 3), ("host_scratch_counter", C.c_size_t, [C.c_void_p, C.c_int]),
+        ("host_scratch_doubles", C.c_size_t, [C.c_void_p]),
+    ):  # fmt: skip
+        getattr(L, name).restype, getattr(L, name).argtypes = restype, argtypes
+    return L
+
+
+def host_program(directory):
+    """tests/sim/host_sim.cpp as a program of its own (its main walks the edge cases) with the address and undefined-behaviour sanitizers; -> its path"""
+    out = os.path.join(directory, "host_sim")
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-DHOST_SIM_MAIN", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", out,
+                    os.path.join(HERE, "sim", "host_sim.cpp")], check=True)  # fmt: skip
+    return out
 
 
 def declared_symbols():
