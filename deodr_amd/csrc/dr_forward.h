@@ -372,7 +372,8 @@ __device__ __forceinline__ void fill_background_tile(const KParams &p, int view,
 //
 // Between set-up and the staged forward raster: one thread per tile turns the per-tile counters that binning left into
 //   * the work list of the forward: one uint4 {tile, triangles, edges, sweep slot} per NON-EMPTY tile -- the tiles with more
-//     than FIRST_PRIMS triangles or edges from the front of the array (the long poles start first), the others from the back;
+//     than FIRST_PRIMS triangles or edges from the front of the array (the long poles start first), the others from the back
+//     (a fit step with fused edge tiles: every tile with an edge, and the edge-free ones of more than HEAD_TRIS triangles);
 //   * the tile bitmap (bit = the tile received a primitive) that the fill waves of the forward and the adjoint's owner-tile
 //     kernel read;
 //   * edge_saved[tile] (edge count + whether the forward will save its sweep), and the counters zeroed for the next forward.
@@ -382,6 +383,14 @@ __device__ __forceinline__ void fill_background_tile(const KParams &p, int view,
 constexpr int SCAN_BLOCK = SCAN_TILES, WORK_CHUNK = 64;
 constexpr uint32_t PAIR_FLAG = 0x80000000u; // in WorkEntry::tile of a pair of tiles (fwd_pair_tiles); then WorkEntry::ntri = nA | nB << 16
 static_assert(FIRST_PRIMS <= 8, "a paired tile carries at most eight triangle ids (two 16-byte pieces of its inline list)");
+// Fit step of an untextured scene (fused edge tiles): a tile WITHOUT silhouette edges belongs in the head only if it is long -- more than one
+// staging batch of triangles.  With FIRST_PRIMS as the bound the head of a view of the benchmark scene held 200 - 450 edge-free tiles of
+// 9 .. 16 triangles (~14 k cycles each) next to its 572 - 656 edge tiles (37 k on average, 100 k the longest): 781 - 1 093 entries on 768
+// head walkers, so that up to 335 walkers per view walked two entries, chosen by list position alone -- and the forward raster is as long as
+// its unluckiest walker.  In the rest of the list those tiles are walked by the edge-free instance (no pass-2 state to spill), one entry
+// each, unpaired.  The un-fused forward and the textured forms keep FIRST_PRIMS.
+constexpr int HEAD_TRIS = TB;
+static_assert(HEAD_TRIS >= FIRST_PRIMS && HEAD_TRIS <= K_TRI, "tiles between the two bounds are listed, unpaired, with their inline list");
 // One tile workgroup in `heavy_share` walks the list of the many-primitive tiles (the head of the grid: dispatched first).  One in
 // eight, unless the head of all views together would then take more than ~40 % of the chip's wave slots (5 120 at five waves per
 // SIMD): with every slot of the first dispatch round on a 25 - 50 us tile the short tiles -- whose arithmetic hides those tiles'
@@ -395,6 +404,8 @@ __host__ inline int heavy_share_for(int n_views, int tile_blocks, bool fuse_edge
 	const long long want = ((long long)n_views * tile_blocks + (fuse_edges ? 4095 : 2047)) / (fuse_edges ? 4096 : 2048);
 	// (the final code of round 3, fit step of the benchmark scene, same-box A/B: 8 views 1/2 0.1316, 1/4 0.1305, 1/8 0.1328, 1/16 0.148 ms;
 	// 16 views 1/4 0.2538, 1/16 0.2483; 32 views 1/4 0.515, 1/16 0.500: about one head entry per head walker up to 8 views of 1024^2)
+	// (with HEAD_TRIS: at most one, 614 - 716 entries for 768 walkers.  Measured again on that head: 16 views 1/4 0.1814 0.1850, 1/8 0.1782 0.1848,
+	// 1/16 0.1806 0.1839 ms; 32 views 0.3411 0.3398, 0.3387 0.3423, 0.3412 0.3418 -- level, the crowd ends those launches: profiles/r09a_ab_neighbours.txt)
 	if (fuse_edges && want <= 8)
 		return 4;
 	int share = 4;
@@ -464,8 +475,10 @@ __global__ __launch_bounds__(SCAN_BLOCK) void tile_scan_kernel(KParams p)
 	// ---- compaction: rank inside the wavefront, wavefront totals through LDS, ONE atomic per class and block
 	// (fit step with fused edge tiles: every tile with edges is a long wavefront -- forward, reverse sweep, pass 1 -- and must be in
 	// the head of the list, which the workgroups compiled for that adjoint walk)
+	// (by_cost: such a step's edge-free tiles of FIRST_PRIMS + 1 .. HEAD_TRIS triangles are entries of the rest of the list, see HEAD_TRIS)
+	const bool by_cost = p.fuse_edges && !p.texture;
 	const bool heavy = work && p.tile_blocks % (8 * WORK_CHUNK) == 0 &&
-					   (ntri > (uint32_t)FIRST_PRIMS || nedge > (uint32_t)(p.fuse_edges ? 0 : FIRST_PRIMS));
+					   (ntri > (uint32_t)(by_cost ? HEAD_TRIS : FIRST_PRIMS) || nedge > (uint32_t)(p.fuse_edges ? 0 : FIRST_PRIMS));
 	const int elist = nedge == 0 ? -1 : (nedge <= (uint32_t)PRIO_EDGES ? 0 : (nedge <= (uint32_t)TB ? 1 : 2));
 	// Pairs for fwd_pair_tiles (fit step, untextured scene, even number of tile columns so that the left tile of a pair is an even
 	// lane and its right neighbour the next lane): tiles (2 i, 2 i + 1) of a tile row, both with triangles, neither with an edge nor
@@ -477,7 +490,8 @@ __global__ __launch_bounds__(SCAN_BLOCK) void tile_scan_kernel(KParams p)
 	// are a kernel of their own and the critical path, pairs among the others bought nothing there and cost 11 %: profiles/r06tp_*)
 	if (p.fuse_edges && (!p.texture || p.pair_tex) && (p.L.tiles_x & 1) == 0 && p.tile_blocks % (8 * WORK_CHUNK) == 0)
 	{
-		const bool plain = work && !heavy && nedge == 0 && ntri > 0;
+		// (at most FIRST_PRIMS triangles each: the edge-free tiles that HEAD_TRIS keeps out of the head are walked alone)
+		const bool plain = work && !heavy && nedge == 0 && ntri > 0 && ntri <= (uint32_t)FIRST_PRIMS;
 		const uint32_t n_next = (uint32_t)__shfl_down((int)(plain ? ntri : 0u), 1, 64), n_prev = (uint32_t)__shfl_up((int)(plain ? ntri : 0u), 1, 64);
 		pair_left = plain && !(lane & 1) && n_next > 0 && ntri + n_next <= (uint32_t)ENTRY_IDS;
 		pair_right = plain && (lane & 1) && n_prev > 0 && ntri + n_prev <= (uint32_t)ENTRY_IDS;
@@ -915,7 +929,8 @@ __host__ __device__ inline int fwd_tile_blocks(int ntiles, int n_views, bool dea
   // of those pair up: about one entry per walker) -- a sixth from 8 views up in a fit step of an untextured scene (dealt_fill): with the
   // fill workgroups dealt among the walkers, fewer
   // and longer walkers win there (same-box A/B, 8 views of the benchmark scene: /4 0.1242 - 0.1252, /5 0.1208 - 0.1214, /6 0.1211 - 0.1213,
-  // /8 0.1271 - 0.1280 ms; 8 views of the hand 0.103 -> 0.096; 1 / 2 / 4 views lose 1 - 3 % at /6, 16 views are level: profiles/r04n)
+  // /8 0.1271 - 0.1280 ms; 8 views of the hand 0.103 -> 0.096; 1 / 2 / 4 views lose 1 - 3 % at /6, 16 views are level: profiles/r04n;
+  // again with HEAD_TRIS: /4 0.1114 0.1117, /5 0.1043 0.1048, /6 0.1023 0.1042 ms, 16 views level: profiles/r09a_ab_neighbours.txt)
 	const int unit = 8 * WORK_CHUNK;
 	const int div = (dealt_fill && n_views >= 8) ? 6 : 4;
 	const int g = ((ntiles / div + unit - 1) / unit) * unit;

@@ -29,6 +29,8 @@
 #    compiled twice, is in the product since commit 3de053c)
 #   (tools/variants/span_rcp.patch, dyn_walkers_view_interleaved.patch, head_tickets.patch: round-6 experiments, measured and not adopted, against code
 #    that has since been removed -- they fit the sources of commit 8cd22f9: `git worktree add /tmp/r6 8cd22f9` and apply them there)
+#   (tools/variants/head_neighbours.patch: four one-line neighbours of the forward's walker divisor and head share against the sources that carry
+#    HEAD_TRIS -- one hunk per variant, measured and not adopted, profiles/r09a_ab_neighbours.txt)
 #   <name>     EXTRA="-D..."    anything else: the product sources with the flags of $EXTRA
 ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 OUT=$ROOT/tools/variants

@@ -17,6 +17,20 @@ if "--lib" in sys.argv:
 dev = torch.device("cuda:0")
 
 
+def walkers(ntiles, n_views, dealt_fill, fuse_edges):
+    """(walkers per view, head walkers per view): fwd_tile_blocks and heavy_share_for of dr_forward.h"""
+    unit = 512
+    g = -(-(ntiles // (6 if dealt_fill and n_views >= 8 else 4)) // unit) * unit
+    G = g if 0 < g <= ntiles else ntiles
+    if G % unit:
+        return G, 0
+    want = -(-n_views * G // (4096 if fuse_edges else 2048))
+    share = 4
+    while not (fuse_edges and want <= 8) and share < 16 and share < want:
+        share *= 2
+    return G, G // share
+
+
 def census(name, views):
     s0 = views[0]
     stack = lambda n: np.stack([np.asarray(getattr(v, n)) for v in views])
@@ -33,8 +47,13 @@ def census(name, views):
         else:
             r.render(ds, 1.0, check_overflow=True)
         torch.cuda.synchronize()
-        words = r.workspace.view(torch.uint8)[:64].cpu().numpy().view(np.uint32)  # WsHeader of view 0 (dr_workspace.h)
-        print(f"{name}, {n} view(s), {'fit step' if fit else 'render'}: head entries {words[13]}, other entries {words[14]}, tiles {(H // 8) * (W // 8)}, census {hr.tile_census(r, ds)}", flush=True)
+        ws = r.workspace.view(torch.uint8).cpu().numpy()
+        words = np.stack([ws[v * (r.nbytes // n) :][:64].view(np.uint32) for v in range(n)])  # WsHeader of every view (dr_workspace.h)
+        G, Gh = walkers((H // 8) * (W // 8), n, fit, fit)  # (sigma > 0: a fit step fuses its edge tiles, textured or not)
+        rows = lambda count, stride: int(-(-int(count) // stride)) if stride else 0  # the longest run of entries one walker gets
+        print(f"{name}, {n} view(s), {'fit step' if fit else 'render'}: head entries {words[:, 13].tolist()}, other entries {words[:, 14].tolist()}, tiles {(H // 8) * (W // 8)}, "
+              f"{G} walkers per view, {Gh} on the head: at most {rows(words[:, 13].max(), Gh)} head entries and {rows(words[:, 14].max(), G - Gh)} other entries per walker, "
+              f"census {hr.tile_census(r, ds)}", flush=True)  # fmt: skip
 
 
 for nv in (1, 8):
