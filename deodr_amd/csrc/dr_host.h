@@ -23,6 +23,31 @@ inline bool ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t 
 	return x <= y ? y - x < a_bytes : x - y < b_bytes;
 }
 
+// The same for entry points with many arrays: does any of `outputs` share a byte with any of `inputs`; is any of `pointers` (NULL: not given) not
+// a multiple of `alignment` (a power of two).
+struct Range
+{
+	const void *p;
+	size_t bytes;
+};
+template <size_t NO, size_t NI>
+inline bool any_overlap(const Range (&outputs)[NO], const Range (&inputs)[NI])
+{
+	for (const Range &o : outputs)
+		for (const Range &i : inputs)
+			if (ranges_overlap(o.p, o.bytes, i.p, i.bytes))
+				return true;
+	return false;
+}
+template <size_t N>
+inline bool any_misaligned(const void *const (&pointers)[N], size_t alignment)
+{
+	uintptr_t bits = 0;
+	for (const void *p : pointers)
+		bits |= (uintptr_t)p;
+	return (bits & (alignment - 1)) != 0;
+}
+
 // Workgroups of a grid-stride kernel: one per `per_block` items of `count`, at least 1, at most `cap`.
 constexpr unsigned capped_blocks(size_t count, size_t per_block, unsigned cap)
 {

@@ -63,10 +63,12 @@
 #include "../../include/deodr_hip_subdiv.h"
 #include "../../include/deodr_hip_retained.h"
 #include "../../include/deodr_hip_basis.h"
+#include "../../include/deodr_hip_camera.h"
 #include "dr_fititer.h" // <- dr_finalize.h <- dr_backward.h <- dr_backward_generic.h <- dr_forward.h <- dr_forward_generic.h <- dr_setup.h <- dr_workspace.h <- dr_prims.h
 #include "dr_texfit.h"  // texture smoothness + step (include/deodr_hip_texture.h); uses grid_sum of dr_fronthalf.h
 #include "dr_subdiv.h"  // rows of a sparse matrix applied to [batch, n, D] blocks (include/deodr_hip_subdiv.h): Loop subdivision and its adjoint
 #include "dr_basis.h"   // a dense [K, N] basis applied to coefficient vectors, and its adjoint (include/deodr_hip_basis.h): morphable models
+#include "dr_camera.h"  // the camera as a differentiable input: full adjoint of the projection, calibration parameters <-> matrices (include/deodr_hip_camera.h)
 
 using namespace dr;
 using namespace dr::dispatch;
@@ -1456,6 +1458,112 @@ int deodr_hip_basis_apply_b(const void *basis, const void *g, int g_dtype, int K
 		});
 	});
 	return check_hip(hipGetLastError(), "basis_apply_b launch");
+}
+
+// ---- camera calibration (include/deodr_hip_camera.h, kernels in dr_camera.h)
+
+int deodr_hip_camera_abi_version(void) { return DEODR_HIP_CAMERA_ABI_VERSION; }
+
+static const char *camera_dims(int V, int n)
+{ // -> NULL, or which limit of the header the dimensions break
+	if (n < 1 || n > FIT_MAX_VIEWS)
+		return "n must be in 1 .. 64";
+	if (V < 1 || V > CAMERA_MAX_VERTICES)
+		return "V must be in 1 .. 2^24";
+	return NULL;
+}
+
+int deodr_hip_camera_blocks(int V, int n) { return camera_dims(V, n) ? 0 : camera_blocks(V, n); }
+
+static size_t camera_counter_bytes(int n) { return (2 * 4 * (size_t)n + 63) / 64 * 64; } // two counter words per view
+
+size_t deodr_hip_camera_scratch_bytes(int V, int n)
+{
+	if (camera_dims(V, n))
+		return 0;
+	return camera_counter_bytes(n) + sizeof(double) * (size_t)n * (size_t)camera_blocks(V, n) * CAMERA_SUMS;
+}
+
+int deodr_hip_camera_project_b(const double *points, const double *extrinsic, const double *intrinsic, const double *distortion, const double *ij_b,
+							   const double *depths_b, double *points_b, double *extrinsic_b, double *intrinsic_b, double *distortion_b, int V, int n,
+							   int accumulate, void *scratch, size_t scratch_bytes, void *stream)
+{
+	const char *what = "camera_project_b";
+	if (!points || !extrinsic || !intrinsic || !ij_b || !extrinsic_b || !intrinsic_b || !scratch)
+		return fail(what, "points, extrinsic, intrinsic, ij_b, extrinsic_b, intrinsic_b or scratch == NULL");
+	if ((distortion == nullptr) != (distortion_b == nullptr))
+		return fail(what, "distortion and distortion_b go together");
+	if (const char *why = camera_dims(V, n))
+		return fail(what, why);
+	const void *const all[] = {points, extrinsic, intrinsic, distortion, ij_b, depths_b, points_b, extrinsic_b, intrinsic_b, distortion_b, scratch};
+	if (any_misaligned(all, 8))
+		return fail(what, "misaligned pointer");
+	if (scratch_bytes < deodr_hip_camera_scratch_bytes(V, n))
+		return fail(what, "scratch too small (deodr_hip_camera_scratch_bytes)");
+	const size_t nv = (size_t)n * (size_t)V * 8, nb = (size_t)n * 8;
+	const Range outputs[] = {{points_b, 3 * nv}, {extrinsic_b, 12 * nb}, {intrinsic_b, 9 * nb}, {distortion_b, 5 * nb}};
+	const Range inputs[] = {{points, 3 * nv}, {extrinsic, 12 * nb}, {intrinsic, 9 * nb}, {distortion, 5 * nb}, {ij_b, 2 * nv}, {depths_b, nv}};
+	if (any_overlap(outputs, inputs))
+		return fail(what, "an output must not overlap an input");
+	CameraProjectBArgs a = {};
+	a.points = points, a.extrinsic = extrinsic, a.intrinsic = intrinsic, a.distortion = distortion, a.ij_b = ij_b, a.depths_b = depths_b;
+	a.points_b = points_b, a.extrinsic_b = extrinsic_b, a.intrinsic_b = intrinsic_b, a.distortion_b = distortion_b;
+	a.counters = (unsigned *)scratch, a.partials = (double *)((char *)scratch + camera_counter_bytes(n));
+	a.V = V, a.accumulate = accumulate != 0;
+	hipLaunchKernelGGL(camera_project_b_kernel, dim3((unsigned)camera_blocks(V, n), (unsigned)n), dim3(FH_BLOCK), 0, (hipStream_t)stream, a);
+	return check_hip(hipGetLastError(), "camera_project_b launch");
+}
+
+int deodr_hip_camera_assemble(const double *quaternions, const double *translations, const double *focal, const double *center,
+							  const double *distortion_in, int shared, double *extrinsic, double *intrinsic, double *distortion_out, int n, void *stream)
+{
+	const char *what = "camera_assemble";
+	if (!quaternions || !translations || !focal || !center || !extrinsic || !intrinsic)
+		return fail(what, "quaternions, translations, focal, center, extrinsic or intrinsic == NULL");
+	if ((distortion_in == nullptr) != (distortion_out == nullptr))
+		return fail(what, "distortion_in and distortion_out go together");
+	if (const char *why = camera_dims(1, n))
+		return fail(what, why);
+	const void *const all[] = {quaternions, translations, focal, center, distortion_in, extrinsic, intrinsic, distortion_out};
+	if (any_misaligned(all, 8))
+		return fail(what, "misaligned pointer");
+	const size_t nb = (size_t)n * 8, ni = shared ? 8 : nb;
+	const Range outputs[] = {{extrinsic, 12 * nb}, {intrinsic, 9 * nb}, {distortion_out, 5 * nb}};
+	const Range inputs[] = {{quaternions, 4 * nb}, {translations, 3 * nb}, {focal, 2 * ni}, {center, 2 * ni}, {distortion_in, 5 * ni}};
+	if (any_overlap(outputs, inputs))
+		return fail(what, "an output must not overlap an input");
+	CameraAssembleArgs a = {};
+	a.quaternions = quaternions, a.translations = translations, a.focal = focal, a.center = center, a.distortion_in = distortion_in;
+	a.extrinsic = extrinsic, a.intrinsic = intrinsic, a.distortion_out = distortion_out, a.shared = shared != 0, a.n = n;
+	hipLaunchKernelGGL(camera_assemble_kernel, dim3(1), dim3(FIT_MAX_VIEWS), 0, (hipStream_t)stream, a);
+	return check_hip(hipGetLastError(), "camera_assemble launch");
+}
+
+int deodr_hip_camera_assemble_b(const double *quaternions, const double *extrinsic_b, const double *intrinsic_b, const double *distortion_b, int shared,
+								double *quaternions_b, double *translations_b, double *focal_b, double *center_b, double *distortion_in_b, int n,
+								void *stream)
+{
+	const char *what = "camera_assemble_b";
+	if (!quaternions || !extrinsic_b || !intrinsic_b || !quaternions_b || !translations_b || !focal_b || !center_b)
+		return fail(what, "quaternions, extrinsic_b, intrinsic_b, quaternions_b, translations_b, focal_b or center_b == NULL");
+	if ((distortion_b == nullptr) != (distortion_in_b == nullptr))
+		return fail(what, "distortion_b and distortion_in_b go together");
+	if (const char *why = camera_dims(1, n))
+		return fail(what, why);
+	const void *const all[] = {quaternions, extrinsic_b, intrinsic_b, distortion_b, quaternions_b, translations_b, focal_b, center_b, distortion_in_b};
+	if (any_misaligned(all, 8))
+		return fail(what, "misaligned pointer");
+	const size_t nb = (size_t)n * 8, ni = shared ? 8 : nb;
+	const Range outputs[] = {{quaternions_b, 4 * nb}, {translations_b, 3 * nb}, {focal_b, 2 * ni}, {center_b, 2 * ni}, {distortion_in_b, 5 * ni}};
+	const Range inputs[] = {{quaternions, 4 * nb}, {extrinsic_b, 12 * nb}, {intrinsic_b, 9 * nb}, {distortion_b, 5 * nb}};
+	if (any_overlap(outputs, inputs))
+		return fail(what, "an output must not overlap an input");
+	CameraAssembleBArgs a = {};
+	a.quaternions = quaternions, a.extrinsic_b = extrinsic_b, a.intrinsic_b = intrinsic_b, a.distortion_b = distortion_b;
+	a.quaternions_b = quaternions_b, a.translations_b = translations_b, a.focal_b = focal_b, a.center_b = center_b, a.distortion_in_b = distortion_in_b;
+	a.shared = shared != 0, a.n = n;
+	hipLaunchKernelGGL(camera_assemble_b_kernel, dim3(1), dim3(FIT_MAX_VIEWS), 0, (hipStream_t)stream, a);
+	return check_hip(hipGetLastError(), "camera_assemble_b launch");
 }
 
 #ifdef DR_WAVE_TRACE

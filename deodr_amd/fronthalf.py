@@ -7,6 +7,7 @@ import ctypes as C
 
 import torch
 
+from . import hip_renderer as hr
 from .hip_renderer import _dtype_tag, _launch, _ptr, lib
 
 
@@ -71,10 +72,92 @@ class ProjectPointsFunc(torch.autograd.Function):
         n, V = pts.shape[0], pts.shape[1]
         ij_b = ij_b.contiguous()
         depths_b = None if depths_b is None else depths_b.contiguous()
+        if any(ctx.needs_input_grad[1:]):  # a camera tensor is being fitted: the full adjoint, every requested gradient from one launch
+            if V > hr.CAMERA_MAX_VERTICES:
+                raise RuntimeError(f"ProjectPointsFunc: the gradient of a camera is available for at most 2^24 vertices per view (include/deodr_hip_camera.h), "
+                                   f"not {V}; detach extrinsic, intrinsic and distortion, or project the points in pieces")  # fmt: skip
+            want = ctx.needs_input_grad[0]
+            pts_b = torch.empty_like(pts) if want else None
+            e_b, k_b = torch.empty_like(extrinsic), torch.empty_like(intrinsic)
+            d_b = None if ctx.distortion is None else torch.empty_like(ctx.distortion)
+            step = hr.CAMERA_MAX_VIEWS  # (the kernel takes at most 64 views per launch; the views are independent: more go in slices)
+            for b in range(0, n, step):
+                cut = lambda t: None if t is None else t[b : b + step]
+                hr.camera_project_b(cut(pts), cut(extrinsic), cut(intrinsic), cut(ctx.distortion), cut(ij_b), cut(depths_b), points_b=cut(pts_b),
+                                    extrinsic_b=cut(e_b), intrinsic_b=cut(k_b), distortion_b=cut(d_b), want_points_b=False,
+                                    scratch=_camera_scratch(pts.device, V, min(step, n - b)))  # fmt: skip
+            return pts_b, e_b if ctx.needs_input_grad[1] else None, k_b if ctx.needs_input_grad[2] else None, d_b if ctx.needs_input_grad[3] else None
         pts_b = torch.empty_like(pts)
         _launch(lib().deodr_hip_project_points_b, pts.device, _ptr(pts), _ptr(extrinsic), _ptr(intrinsic), _ptr(ctx.distortion), _ptr(ij_b),
                 _ptr(depths_b), _ptr(pts_b), V, n)  # fmt: skip
         return pts_b, None, None, None
+
+
+_camera_scratches = {}  # (device, V, n) -> the zero-filled scratch of camera_project_b for the autograd wrapper (kernels of one stream run in order)
+
+
+def _camera_scratch(device, V, n):
+    key = (device, int(V), int(n))
+    if key not in _camera_scratches:
+        _camera_scratches[key] = hr.camera_scratch(V, n, device)
+    return _camera_scratches[key]
+
+
+def camera_assemble_torch(quaternions, translations, focal, center, distortion, shared):
+    """the formulas of ``deodr_hip_camera_assemble`` as torch ops (differentiable by autograd): what runs on tensors the kernels do not take"""
+    n = quaternions.shape[0]
+    q = quaternions / quaternions.norm(dim=1, keepdim=True)
+    x, y, z, w = q.unbind(1)
+    rot = torch.stack((1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y),
+                       2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
+                       2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)), dim=1).reshape(n, 3, 3)  # fmt: skip
+    extrinsic = torch.cat((rot, translations[:, :, None]), dim=2)
+    f, c = (focal[None].expand(n, 2), center[None].expand(n, 2)) if shared else (focal, center)
+    zero, one = torch.zeros_like(f[:, 0]), torch.ones_like(f[:, 0])
+    intrinsic = torch.stack((f[:, 0], zero, c[:, 0], zero, f[:, 1], c[:, 1], zero, zero, one), dim=1).reshape(n, 3, 3)
+    if distortion is None:
+        return extrinsic, intrinsic, None
+    return extrinsic, intrinsic, (distortion[None].expand(n, 5) if shared else distortion).contiguous()
+
+
+class CameraAssembleFunc(torch.autograd.Function):
+    """(quaternions [n,4] raw, translations [n,3], focal, center [2] | [n,2], distortion [5] | [n,5] | None; shared) -> (extrinsic [n,3,4],
+    intrinsic [n,3,3], distortion [n,5] | None): ``deodr_hip_camera_assemble`` and its adjoint, one launch each"""
+
+    @staticmethod
+    def forward(ctx, quaternions, translations, focal, center, distortion, shared):
+        q, t, f, c = quaternions.contiguous(), translations.contiguous(), focal.contiguous(), center.contiguous()
+        d = None if distortion is None else distortion.contiguous()
+        e, k, dist = hr.camera_assemble(q, t, f, c, d, shared=shared)
+        ctx.save_for_backward(q)
+        ctx.shared, ctx.distorted = bool(shared), d is not None
+        if dist is None:
+            dist = q.new_zeros(0)  # (an autograd function returns tensors: the caller drops this one)
+            ctx.mark_non_differentiable(dist)
+        return e, k, dist
+
+    @staticmethod
+    def backward(ctx, e_b, k_b, d_b):
+        (q,) = ctx.saved_tensors
+        n = q.shape[0]
+        e_b = q.new_zeros((n, 3, 4)) if e_b is None else e_b.contiguous()
+        k_b = q.new_zeros((n, 3, 3)) if k_b is None else k_b.contiguous()
+        if ctx.distorted:
+            d_b = q.new_zeros((n, 5)) if d_b is None else d_b.contiguous()
+        else:
+            d_b = None
+        q_b, t_b, f_b, c_b, din_b = hr.camera_assemble_b(q, e_b, k_b, d_b, shared=ctx.shared)
+        return q_b, t_b, f_b, c_b, din_b, None
+
+
+def camera_assemble(quaternions, translations, focal, center, distortion=None, shared=True):
+    """-> (extrinsic, intrinsic, distortion | None) of the views, differentiable in all five inputs: the kernels on float64 ROCm tensors, the same
+    formulas as torch ops otherwise (CPU tensors; more than the 64 views the kernels take per launch)"""
+    tensors = [quaternions, translations, focal, center] + ([] if distortion is None else [distortion])
+    if usable(*tensors) and quaternions.shape[0] <= hr.CAMERA_MAX_VIEWS:
+        e, k, d = CameraAssembleFunc.apply(quaternions, translations, focal, center, distortion, bool(shared))
+        return e, k, (None if distortion is None else d)
+    return camera_assemble_torch(quaternions, translations, focal, center, distortion, shared)
 
 
 def silhouette_flags(ij, faces_u32, edge_faces_u32, clockwise, out=None):

@@ -34,8 +34,9 @@ _COMPANIONS = (
     (_abi.SUBDIV_HEADER, "subdiv", "subdivision"),  # Loop subdivision
     (_abi.RETAINED_HEADER, "retained", "retained-frames"),  # fit step into retained frames
     (_abi.BASIS_HEADER, "basis", "linear-basis"),  # linear bases: morphable models
+    (_abi.CAMERA_HEADER, "camera", "camera"),  # camera calibration
 )
-TEXTURE_ABI_VERSION, SUBDIV_ABI_VERSION, RETAINED_ABI_VERSION, BASIS_ABI_VERSION = (
+TEXTURE_ABI_VERSION, SUBDIV_ABI_VERSION, RETAINED_ABI_VERSION, BASIS_ABI_VERSION, CAMERA_ABI_VERSION = (
     h.defines[f"DEODR_HIP_{key.upper()}_ABI_VERSION"] for h, key, _ in _COMPANIONS
 )
 # words of the 64-byte status block at the start of the workspace
@@ -432,6 +433,145 @@ def basis_apply_b(basis, g, out=None, accumulate=False, scratch=None):
             _ptr(scratch), scratch.numel())  # fmt: skip
     _touched(out)
     return out
+
+
+# ---- camera calibration (include/deodr_hip_camera.h) ----------------------------------------------------------------------------------
+
+CAMERA_MAX_VIEWS, CAMERA_MAX_VERTICES = 64, 2**24  # the limits include/deodr_hip_camera.h states
+_F64_ONLY = (torch.float64,)
+
+
+def _camera_views(what, anchor_name, anchor, tail):
+    """checks before the library is called: ``anchor`` a float64 ROCm tensor [n, *tail] with n within the header's limit; -> n"""
+    _rocm_tensor(what, anchor_name, anchor)
+    if anchor.dim() != 1 + len(tail) or not 1 <= int(anchor.shape[0]) <= CAMERA_MAX_VIEWS:
+        raise ValueError(f"{what}: {anchor_name} must have shape [1 <= n <= {CAMERA_MAX_VIEWS}, {', '.join(map(str, tail))}], not {list(anchor.shape)}")
+    return int(anchor.shape[0])
+
+
+def camera_blocks(V, n):
+    """``deodr_hip_camera_blocks``: the workgroups per view :func:`camera_project_b` launches for V vertices and n views (0: outside the limits)"""
+    return int(lib().deodr_hip_camera_blocks(int(V), int(n)))
+
+
+def camera_scratch(V, n, device):
+    """the scratch of :func:`camera_project_b` for V vertices and n views, zero-filled as the library wants it once (one per stream in use)"""
+    need = int(lib().deodr_hip_camera_scratch_bytes(int(V), int(n)))
+    if need == 0:
+        raise ValueError(f"camera_scratch: V = {V}, n = {n} is outside the limits of include/deodr_hip_camera.h")
+    with torch.cuda.device(device):
+        return torch.zeros(need, dtype=torch.uint8, device=device)
+
+
+def camera_project_b(points, extrinsic, intrinsic, distortion, ij_b, depths_b=None, points_b=None, extrinsic_b=None, intrinsic_b=None,
+                     distortion_b=None, accumulate=False, scratch=None, want_points_b=True):
+    """``deodr_hip_camera_project_b``: the full adjoint of the camera projection in one launch.  ``points`` [n,V,3], ``extrinsic`` [n,3,4],
+    ``intrinsic`` [n,3,3], ``distortion`` [n,5] | None, ``ij_b`` [n,V,2], ``depths_b`` [n,V] | None, all contiguous float64 ROCm tensors ->
+    (points_b [n,V,3] | None, extrinsic_b [n,3,4], intrinsic_b [n,3,3], distortion_b [n,5] | None), allocated where not given (``points_b`` only
+    with ``want_points_b``).  ``accumulate``: added to the three camera adjoints, which must then be given.  Deterministic; asynchronous on the
+    current stream.  ``scratch``: a :func:`camera_scratch` of the caller's; None: one per device and stream, made or grown at the call."""
+    what = "camera_project_b"
+    n = _camera_views(what, "extrinsic", extrinsic, (3, 4))
+    if not torch.is_tensor(points) or points.dim() != 3 or int(points.shape[0]) != n or int(points.shape[2]) != 3 or not 1 <= int(points.shape[1]) <= CAMERA_MAX_VERTICES:
+        raise ValueError(f"{what}: points must have shape [{n}, 1 <= V <= 2^24, 3], not {list(getattr(points, 'shape', ()))}")
+    V = int(points.shape[1])
+    rows = [("extrinsic", extrinsic, _F64_ONLY, (n, 3, 4)), ("points", points, _F64_ONLY, (n, V, 3)), ("intrinsic", intrinsic, _F64_ONLY, (n, 3, 3)),
+            ("ij_b", ij_b, _F64_ONLY, (n, V, 2))]  # fmt: skip
+    optional = [("distortion", distortion, (n, 5)), ("depths_b", depths_b, (n, V)), ("points_b", points_b, (n, V, 3)), ("extrinsic_b", extrinsic_b, (n, 3, 4)),
+                ("intrinsic_b", intrinsic_b, (n, 3, 3)), ("distortion_b", distortion_b, (n, 5))]  # fmt: skip
+    rows += [(name, t, _F64_ONLY, shape) for name, t, shape in optional if t is not None]
+    if scratch is not None:
+        rows.append(("scratch", scratch, (torch.uint8,), (None,)))
+    _check_tensors(what, "extrinsic", extrinsic.device, rows)
+    if distortion is None and distortion_b is not None:
+        raise ValueError(f"{what}: distortion_b without distortion")
+    if accumulate and (extrinsic_b is None or intrinsic_b is None or (distortion is not None and distortion_b is None)):
+        raise ValueError(f"{what}: accumulate needs extrinsic_b, intrinsic_b and (with distortion) distortion_b")
+    dev = extrinsic.device
+    with torch.cuda.device(dev):
+        if points_b is None and want_points_b:
+            points_b = torch.empty_like(points)
+        if extrinsic_b is None:
+            extrinsic_b = torch.empty((n, 3, 4), dtype=torch.float64, device=dev)
+        if intrinsic_b is None:
+            intrinsic_b = torch.empty((n, 3, 3), dtype=torch.float64, device=dev)
+        if distortion is not None and distortion_b is None:
+            distortion_b = torch.empty((n, 5), dtype=torch.float64, device=dev)
+        if scratch is None:
+            scratch = _cached_scratch("camera", dev, int(lib().deodr_hip_camera_scratch_bytes(V, n)), lambda: camera_scratch(V, n, dev),
+                                      f"{what}: pass scratch= (camera_scratch) when capturing a graph: none of this size exists for this stream yet")  # fmt: skip
+    _launch(lib().deodr_hip_camera_project_b, dev, _ptr(points), _ptr(extrinsic), _ptr(intrinsic), _ptr(distortion), _ptr(ij_b), _ptr(depths_b),
+            _ptr(points_b), _ptr(extrinsic_b), _ptr(intrinsic_b), _ptr(distortion_b), V, n, int(bool(accumulate)), _ptr(scratch), scratch.numel())  # fmt: skip
+    for t in (points_b, extrinsic_b, intrinsic_b, distortion_b):
+        if t is not None:
+            _touched(t)
+    return points_b, extrinsic_b, intrinsic_b, distortion_b
+
+
+def _camera_parameters(what, n, shared, rows):
+    """rows of :func:`_check_tensors` for focal / center / distortion-like tensors [(name, tensor | None, width)]: [width] when shared, else [n, width]"""
+    return [(name, t, _F64_ONLY, (width,) if shared else (n, width)) for name, t, width in rows if t is not None]
+
+
+def camera_assemble(quaternions, translations, focal, center, distortion=None, shared=True, out=None):
+    """``deodr_hip_camera_assemble``: quaternions [n,4] = (x, y, z, w) (normalised inside), translations [n,3], focal and center [2] (``shared``) or
+    [n,2], distortion [5] / [n,5] | None -> (extrinsic [n,3,4] = [R(q) | t], intrinsic [n,3,3], distortion [n,5] | None): the per-view matrices the
+    projection kernels index.  ``out``: that triple, to be written in place.  Contiguous float64 ROCm tensors; asynchronous on the current stream."""
+    what = "camera_assemble"
+    n = _camera_views(what, "quaternions", quaternions, (4,))
+    rows = [("quaternions", quaternions, _F64_ONLY, (n, 4)), ("translations", translations, _F64_ONLY, (n, 3))]
+    rows += _camera_parameters(what, n, shared, [("focal", focal, 2), ("center", center, 2), ("distortion", distortion, 5)])
+    if focal is None or center is None:
+        raise ValueError(f"{what}: focal and center are required")
+    e, k, d = out if out is not None else (None, None, None)
+    rows += [(name, t, _F64_ONLY, shape) for name, t, shape in (("extrinsic", e, (n, 3, 4)), ("intrinsic", k, (n, 3, 3)), ("distortion out", d, (n, 5))) if t is not None]
+    _check_tensors(what, "quaternions", quaternions.device, rows)
+    dev = quaternions.device
+    with torch.cuda.device(dev):
+        e = torch.empty((n, 3, 4), dtype=torch.float64, device=dev) if e is None else e
+        k = torch.empty((n, 3, 3), dtype=torch.float64, device=dev) if k is None else k
+        if distortion is not None and d is None:
+            d = torch.empty((n, 5), dtype=torch.float64, device=dev)
+    if distortion is None:
+        d = None
+    _launch(lib().deodr_hip_camera_assemble, dev, _ptr(quaternions), _ptr(translations), _ptr(focal), _ptr(center), _ptr(distortion), int(bool(shared)),
+            _ptr(e), _ptr(k), _ptr(d), n)  # fmt: skip
+    for t in (e, k, d):
+        if t is not None:
+            _touched(t)
+    return e, k, d
+
+
+def camera_assemble_b(quaternions, extrinsic_b, intrinsic_b, distortion_b=None, shared=True, out=None):
+    """``deodr_hip_camera_assemble_b``: the adjoint of :func:`camera_assemble` -> (quaternions_b [n,4] with respect to the raw quaternions,
+    translations_b [n,3], focal_b, center_b, distortion_b of the parameters' shapes ([2], [2], [5] summed over the views when ``shared``) | None).
+    ``out``: that quintuple, to be written in place."""
+    what = "camera_assemble_b"
+    n = _camera_views(what, "quaternions", quaternions, (4,))
+    rows = [("quaternions", quaternions, _F64_ONLY, (n, 4)), ("extrinsic_b", extrinsic_b, _F64_ONLY, (n, 3, 4)), ("intrinsic_b", intrinsic_b, _F64_ONLY, (n, 3, 3))]
+    if distortion_b is not None:
+        rows.append(("distortion_b", distortion_b, _F64_ONLY, (n, 5)))
+    q_b, t_b, f_b, c_b, d_b = out if out is not None else (None,) * 5
+    rows += [(name, t, _F64_ONLY, shape) for name, t, shape in (("quaternions_b", q_b, (n, 4)), ("translations_b", t_b, (n, 3))) if t is not None]
+    rows += _camera_parameters(what, n, shared, [("focal_b", f_b, 2), ("center_b", c_b, 2), ("distortion_in_b", d_b, 5)])
+    _check_tensors(what, "quaternions", quaternions.device, rows)
+    dev = quaternions.device
+    width = lambda w: (w,) if shared else (n, w)
+    with torch.cuda.device(dev):
+        q_b = torch.empty((n, 4), dtype=torch.float64, device=dev) if q_b is None else q_b
+        t_b = torch.empty((n, 3), dtype=torch.float64, device=dev) if t_b is None else t_b
+        f_b = torch.empty(width(2), dtype=torch.float64, device=dev) if f_b is None else f_b
+        c_b = torch.empty(width(2), dtype=torch.float64, device=dev) if c_b is None else c_b
+        if distortion_b is not None and d_b is None:
+            d_b = torch.empty(width(5), dtype=torch.float64, device=dev)
+    if distortion_b is None:
+        d_b = None
+    _launch(lib().deodr_hip_camera_assemble_b, dev, _ptr(quaternions), _ptr(extrinsic_b), _ptr(intrinsic_b), _ptr(distortion_b), int(bool(shared)),
+            _ptr(q_b), _ptr(t_b), _ptr(f_b), _ptr(c_b), _ptr(d_b), n)  # fmt: skip
+    for t in (q_b, t_b, f_b, c_b, d_b):
+        if t is not None:
+            _touched(t)
+    return q_b, t_b, f_b, c_b, d_b
 
 
 class DeviceScene:

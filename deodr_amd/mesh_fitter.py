@@ -1014,3 +1014,273 @@ class MeshTextureFitterMultiFrame:
         energy, image = self.step_device()
         image = image.to(torch.float64)
         return float(energy[0]), image.cpu().numpy(), ((image - self.mesh_image) ** 2).sum(dim=-1).cpu().numpy()
+
+
+# ---- camera calibration -----------------------------------------------------------------------------------------------------------------
+
+
+class CameraFitterMultiFrame:
+    """Fit the CAMERAS of ``n`` photographs of a known mesh: the world -> camera transform of every view (a quaternion (x, y, z, w) and a translation) and
+    the focal lengths (fx, fy), the principal point (cx, cy) and OpenCV's distortion (k1, k2, p1, p2, k3) -- one physical camera shared by the views
+    (``shared_intrinsics``, the default) or one per view.  The mesh is given as it is in the world: ``vertices``, ``faces`` and either per-vertex
+    ``colors`` [V,C] or ``uv`` / ``faces_uv`` / ``texture``, plus a directional and an ambient light.  The energy is
+    ``sum(weights * (image - photograph)**2)`` over all views.
+
+    ``update`` chooses what moves -- any of "extrinsic", "focal", "center", "distortion"; what is not listed keeps its initial value to the bit.  That is
+    how the gauge is fixed: a near-planar object cannot tell the focal length from its distance, a small one cannot tell the principal point from a
+    rotation.  The update is the momentum rule of the other fitters with one ``step_factor_*`` / ``step_max_*`` per group (class attributes);
+    quaternions are renormalised per view.  The factors are those of 4 views of 128 x 128; the gradients of the summed squared residual grow with the
+    number of views and of pixels, so every factor is multiplied by ``step_scale`` -- None: ``min(1, 4 * 128**2 / (n * H * W))``, set in
+    :meth:`set_images` -- while the clamps stay what they are.
+
+    ``sigmas`` (None: no prior, every path as it is without the keyword): {parameter name: standard deviation(s)} for any of "quaternions",
+    "translations", "focal", "center", "distortion" -- a number or an array that broadcasts to the parameter.  The energy gains
+    ``sum(((parameter - its initial value) / sigma)**2)`` for each, which holds a weakly observed parameter near its prior calibration.
+
+    The vertices, their luminosity and colours do not depend on the cameras: they are computed ONCE, in :meth:`set_images`.  An iteration on float64
+    ROCm tensors is then a fixed kernel sequence over persistent buffers -- ``deodr_hip_camera_assemble``, ``deodr_hip_project_points``, silhouette
+    flags, the rasterizer's one-call fit step, ``deodr_hip_camera_project_b`` (the 23 sums per view, deterministic), ``deodr_hip_camera_assemble_b``, one
+    ``deodr_hip_momentum_update`` of all groups -- no autograd graph, no tensor rebound, so ``GraphedStep(fitter)`` replays it as it is.  On CPU
+    tensors, or with ``direct = False``, the same iteration runs as autograd through ``DeviceCamera.from_pose`` and ``Scene3DDevice.render_l2``."""
+
+    direct = True
+    GROUPS = ("extrinsic", "focal", "center", "distortion")
+    # tuned on 2 - 4 views of 64 x 64 to 128 x 128 (tests/test_camera_fit_host.py, tests/test_camera_gpu.py); multiplied by ``step_scale`` (above)
+    PARAMETERS = ("quaternions", "translations", "focal", "center", "distortion")
+    step_factor_quaternion, step_factor_translation, step_factor_focal, step_factor_center, step_factor_distortion = 5e-6, 3e-5, 0.15, 0.005, 1e-4
+    step_max_quaternion, step_max_translation, step_max_focal, step_max_center, step_max_distortion = 0.005, 0.02, 0.5, 1.0, 0.005
+
+    def __init__(self, vertices, faces, quaternions_init, translations_init, focal_init, center_init, distortion_init=None, colors=None, uv=None,
+                 faces_uv=None, texture=None, light_directional=None, light_ambient=1.0, update=GROUPS, shared_intrinsics=True, sigmas=None, sigma=1.0,
+                 inertia=0.9, damping=0.05, step_scale=None, clockwise=False, device="cuda", pixel_dtype=torch.float64):  # fmt: skip
+        unknown = [g for g in update if g not in self.GROUPS]
+        if unknown:
+            raise ValueError(f"CameraFitterMultiFrame: update may list {self.GROUPS}, not {unknown}")
+        if (colors is None) == (uv is None):
+            raise ValueError("CameraFitterMultiFrame: give either per-vertex colors [V,C] or uv / faces_uv / texture")
+        self.device, self.pixel_dtype = torch.device(device), pixel_dtype
+        self.update, self.shared_intrinsics, self.inertia, self.damping = tuple(update), bool(shared_intrinsics), inertia, damping
+        t = lambda a: torch.as_tensor(np.array(a, dtype=np.float64), device=self.device).contiguous()
+        self.quaternions_init, self.translations_init = t(np.atleast_2d(quaternions_init)), t(np.atleast_2d(translations_init))
+        n = self.n_views = int(self.quaternions_init.shape[0])
+        if tuple(self.quaternions_init.shape) != (n, 4) or tuple(self.translations_init.shape) != (n, 3):
+            raise ValueError("CameraFitterMultiFrame: quaternions_init must be [n,4] = (x, y, z, w) and translations_init [n,3]")
+        if distortion_init is None and "distortion" in self.update:
+            distortion_init = np.zeros(5)
+        per_view = lambda a, width: a if self.shared_intrinsics else np.broadcast_to(np.asarray(a, dtype=np.float64), (n, width))
+        self.focal_init, self.center_init = t(per_view(np.broadcast_to(focal_init, (2,)) if np.ndim(focal_init) == 0 else focal_init, 2)), t(per_view(center_init, 2))
+        self.distortion_init = None if distortion_init is None else t(per_view(distortion_init, 5))
+        width = lambda k: (k,) if self.shared_intrinsics else (n, k)
+        for name, a, shape in (("focal_init", self.focal_init, width(2)), ("center_init", self.center_init, width(2)), ("distortion_init", self.distortion_init, width(5))):
+            if a is not None and tuple(a.shape) != shape:
+                raise ValueError(f"CameraFitterMultiFrame: {name} must have shape {list(shape)}, not {list(a.shape)}")
+        v0 = np.asarray(vertices, dtype=np.float64)
+        if uv is None:
+            self.mesh = DeviceMesh(np.asarray(faces), v0, clockwise=clockwise, colors=np.asarray(colors, dtype=np.float64), device=self.device)
+        else:
+            tex = torch.as_tensor(np.asarray(texture, dtype=np.float64), device=self.device).to(pixel_dtype).contiguous()
+            self.mesh = DeviceMesh(np.asarray(faces), v0, clockwise=clockwise, uv=uv, faces_uv=faces_uv, texture=None, device=self.device)
+            self.mesh.texture = tex  # (in the pixel dtype, as the rasterizer reads it)
+        self.scene = Scene3DDevice(sigma=sigma, pixel_dtype=pixel_dtype)
+        self.scene.set_mesh(self.mesh)
+        self.scene.set_light(light_directional, light_ambient)
+        self.weights = self._views = self._direct = None
+        self._step_scale_given, self.step_scale = step_scale, 1.0 if step_scale is None else float(step_scale)
+        self._inv_sigma2 = {}  # parameter name -> 1 / sigma^2 of its prior, of the parameter's shape
+        for name, sig in (sigmas or {}).items():
+            init = getattr(self, name + "_init", None) if name in self.PARAMETERS else None
+            if init is None:
+                raise ValueError(f"CameraFitterMultiFrame: sigmas may name {self.PARAMETERS} (distortion only when the camera has one), not {name!r}")
+            sig = np.asarray(sig, dtype=np.float64)
+            if np.any(sig <= 0):
+                raise ValueError(f"CameraFitterMultiFrame: sigmas[{name!r}] must be positive")
+            self._inv_sigma2[name] = t(np.broadcast_to(1.0 / sig**2, tuple(init.shape)))
+        self.reset()
+
+    def reset(self):
+        self.quaternions, self.translations = self.quaternions_init.clone(), self.translations_init.clone()
+        self.focal, self.center = self.focal_init.clone(), self.center_init.clone()
+        self.distortion = None if self.distortion_init is None else self.distortion_init.clone()
+        self.momentum = _Momentum(self.inertia, self.damping)
+        self.iter = 0
+
+    def set_background_color(self, background_color):
+        self.scene.set_background_color(background_color)
+
+    def _parameters(self):
+        """[(name, group, tensor, step factor, step_max, normalize_rows)] of the parameters that exist"""
+        rows = [("quaternions", "extrinsic", self.quaternions, self.step_factor_quaternion, self.step_max_quaternion, 4),
+                ("translations", "extrinsic", self.translations, self.step_factor_translation, self.step_max_translation, 0),
+                ("focal", "focal", self.focal, self.step_factor_focal, self.step_max_focal, 0),
+                ("center", "center", self.center, self.step_factor_center, self.step_max_center, 0),
+                ("distortion", "distortion", self.distortion, self.step_factor_distortion, self.step_max_distortion, 0)]  # fmt: skip
+        return [(name, group, x, self.step_scale * factor, step_max, rows_) for name, group, x, factor, step_max, rows_ in rows if x is not None]
+
+    def _prior(self):
+        """-> (sum(((parameter - initial value) / sigma)**2) over the parameters with a prior [1], {parameter name: its gradient}); (None, {}) without"""
+        energy, grads = None, {}
+        for name, inv in self._inv_sigma2.items():
+            delta = getattr(self, name) - getattr(self, name + "_init")
+            grads[name] = 2.0 * inv * delta
+            e = (inv * delta * delta).sum().reshape(1)
+            energy = e if energy is None else energy + e
+        return energy, grads
+
+    def set_images(self, images, weights=None):
+        """``images`` [n,H,W,C]: one photograph per view.  ``weights`` [H,W] or [n,H,W], ``>= 0`` (or None): per-pixel weights of the squared residual,
+        handed to the fit step (a mask on what is not the object, a view to leave out)."""
+        from . import fronthalf, hip_renderer
+
+        imgs = np.stack([np.asarray(im, dtype=np.float64) for im in images])
+        n, height, width, nb_colors = imgs.shape
+        if n != self.n_views:
+            raise ValueError(f"{n} images for {self.n_views} cameras")
+        dev, mesh = self.device, self.mesh
+        self.height, self.width = height, width
+        self.mesh_image = torch.as_tensor(imgs, device=dev)
+        self._obs = self.mesh_image.to(self.pixel_dtype).contiguous()
+        if weights is not None:
+            w = np.asarray(weights.detach().cpu() if torch.is_tensor(weights) else weights, dtype=np.float64)
+            if w.shape not in ((height, width), (n, height, width)):
+                raise ValueError(f"weights must have shape [{height}, {width}] or [{n}, {height}, {width}] (one value per pixel), not {list(w.shape)}")
+            weights = torch.as_tensor(np.array(np.broadcast_to(w, (n, height, width))), device=dev).to(self.pixel_dtype).contiguous()
+        self.weights = weights
+        self.e_data, self._energy = torch.zeros(1, dtype=torch.float64, device=dev), torch.zeros(1, dtype=torch.float64, device=dev)
+        if self._step_scale_given is None:
+            self.step_scale = min(1.0, 4 * 128**2 / (n * height * width))
+        self._direct = None
+        topo = mesh.topology
+        params = [p[2] for p in self._parameters()]
+        if self.direct and fronthalf.usable(mesh.vertices, *params) and topo._edge_faces is not None and n <= hip_renderer.CAMERA_MAX_VIEWS:
+            self._direct = self._direct_buffers(n, height, width, nb_colors)
+        self.iter = 0
+
+    def _direct_buffers(self, n, height, width, nb_colors):
+        """everything the fixed kernel sequence reads and writes, allocated once; the shading, which no camera parameter moves, computed once"""
+        from types import SimpleNamespace
+
+        from . import hip_renderer
+
+        dev, mesh, V = self.device, self.mesh, self.mesh.nb_vertices
+        z = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=dev)
+        d = SimpleNamespace()
+        d.points = mesh.vertices.detach()[None].expand(n, -1, -1).contiguous()  # the same world vertices for every view
+        d.extrinsic, d.intrinsic = z(n, 3, 4), z(n, 3, 3)
+        d.dist = None if self.distortion is None else z(n, 5)
+        d.ij, d.depths = z(n, V, 2), z(n, V)
+        d.flags = torch.zeros((n, mesh.nb_faces, 3), dtype=torch.uint8, device=dev)
+        with torch.no_grad():
+            lum = self.scene.vertices_luminosity(mesh.vertices)
+            lum = lum[None].expand(n, -1).contiguous()
+            textured = mesh.uv is not None
+            if textured:
+                colors, shade = z(n, V, nb_colors), lum
+            else:
+                colors, shade = (mesh.vertices_colors[None].expand(n, -1, -1) * lum[..., None]).contiguous(), z(n, V)
+        if int(colors.shape[-1]) != nb_colors:
+            raise ValueError(f"the images have {nb_colors} channels, the mesh {int(colors.shape[-1])}")
+        d.views = dict(ij=d.ij, depths=d.depths, colors=colors, shade=shade, edgeflags=d.flags)
+        if (self.scene.background_image is None) == (self.scene.background_color is None):
+            raise BaseException("You need to provide either a background image or background color")
+        d.ds, d.rasterizer = self.scene._rasterizer(n, height, width, nb_colors, textured, True)
+        d.ds.set_views(**d.views)
+        d.grads = d.ds.zero_grads()
+        pd = self.pixel_dtype
+        d.out = (torch.empty((n, height, width, nb_colors), dtype=pd, device=dev), torch.empty((n, height, width), dtype=pd, device=dev))
+        d.extrinsic_b, d.intrinsic_b = z(n, 3, 4), z(n, 3, 3)
+        d.dist_b = None if d.dist is None else z(n, 5)
+        d.grad = {"quaternions": z(n, 4), "translations": z(n, 3), "focal": torch.zeros_like(self.focal), "center": torch.zeros_like(self.center),
+                  "distortion": None if self.distortion is None else torch.zeros_like(self.distortion)}  # fmt: skip
+        d.scratch = hip_renderer.camera_scratch(V, n, dev)  # (its own: a captured step replays on the addresses it was captured with)
+        return d
+
+    def _gradients_direct(self):
+        """the fixed kernel sequence up to the gradients -> ({parameter name: gradient}, image); the data energy lands in ``self.e_data``"""
+        from . import fronthalf, hip_renderer
+
+        d, topo, n, V = self._direct, self.mesh.topology, self.n_views, self.mesh.nb_vertices
+        hip_renderer.camera_assemble(self.quaternions, self.translations, self.focal, self.center, self.distortion, shared=self.shared_intrinsics,
+                                     out=(d.extrinsic, d.intrinsic, d.dist))  # fmt: skip
+        hip_renderer._launch(hip_renderer.lib().deodr_hip_project_points, self.device, hip_renderer._ptr(d.points), hip_renderer._ptr(d.extrinsic),
+                             hip_renderer._ptr(d.intrinsic), hip_renderer._ptr(d.dist), hip_renderer._ptr(d.ij), hip_renderer._ptr(d.depths), V, n)  # fmt: skip
+        if self.scene.sigma > 0:
+            fronthalf.silhouette_flags(d.ij, topo._faces_u32, topo._edge_faces, topo.clockwise, out=d.flags)
+        d.ds.set_views(**d.views)  # (no copies: the tensors are used as they are; another render of the scene may have rebound them)
+        if self.mesh.uv is not None:
+            d.ds.set_texture(self.mesh.texture)
+        image, _z, _g = d.rasterizer.render_fit(d.ds, self._obs, self.scene.sigma, grads=d.grads, out=d.out, clear_grads=True, loss_out=self.e_data,
+                                                weights=self.weights)  # fmt: skip
+        hip_renderer.camera_project_b(d.points, d.extrinsic, d.intrinsic, d.dist, d.grads["ij_b"], None, extrinsic_b=d.extrinsic_b, intrinsic_b=d.intrinsic_b,
+                                      distortion_b=d.dist_b, scratch=d.scratch, want_points_b=False)  # fmt: skip
+        g = d.grad
+        hip_renderer.camera_assemble_b(self.quaternions, d.extrinsic_b, d.intrinsic_b, d.dist_b, shared=self.shared_intrinsics,
+                                       out=(g["quaternions"], g["translations"], g["focal"], g["center"], g["distortion"]))  # fmt: skip
+        return g, image
+
+    def _gradients_autograd(self):
+        """the same iteration under autograd -> ({parameter name: gradient}, image); the data energy lands in ``self.e_data``"""
+        rows = self._parameters()
+        leaves = {name: x.detach().requires_grad_(group in self.update) for name, group, x, *_ in rows}
+        camera = DeviceCamera.from_pose(leaves["quaternions"], leaves["translations"], leaves["focal"], leaves["center"], self.height, self.width,
+                                        leaves.get("distortion"), shared_intrinsics=self.shared_intrinsics, device=self.device)  # fmt: skip
+        loss, image = self.scene.render_l2(camera, self._obs, weights=self.weights)
+        wanted = [name for name, group, *_ in rows if group in self.update]
+        grads = dict(zip(wanted, torch.autograd.grad(loss, [leaves[k] for k in wanted]))) if wanted else {}
+        self.e_data.copy_(loss.detach().reshape(1))
+        return grads, image.detach()
+
+    def _data_gradients(self):
+        return self._gradients_direct() if self._direct is not None else self._gradients_autograd()
+
+    def _total_energy(self, e_prior):
+        if e_prior is None:
+            return self.e_data
+        torch.add(self.e_data, e_prior, out=self._energy)
+        return self._energy
+
+    def gradients(self):
+        """-> ({parameter name: d energy / d parameter}, image [n,H,W,C]) of the current parameters, prior included; nothing is updated"""
+        assert self._obs is not None, "call set_images first"
+        grads, image = self._data_gradients()
+        _e, g_prior = self._prior()
+        return {k: (g + g_prior[k] if k in g_prior else g) for k, g in grads.items()}, image
+
+    def energy(self):
+        """-> the energy of the current cameras, data term + prior (a device tensor of one element); nothing is updated"""
+        self._data_gradients()
+        return self._total_energy(self._prior()[0])
+
+    def cameras(self):
+        """the cameras of the current parameters, as a :class:`DeviceCamera` of ``n`` views (detached)"""
+        with torch.no_grad():
+            return DeviceCamera.from_pose(self.quaternions, self.translations, self.focal, self.center, self.height, self.width, self.distortion,
+                                          shared_intrinsics=self.shared_intrinsics, device=self.device)  # fmt: skip
+
+    def step_device(self):
+        """One iteration on the device -> (energy BEFORE the update [1], image [n,H,W,C]).  On the direct path the parameters and the momentum speeds are
+        updated in place and the returned tensors are the same storage every step (clone what is to be kept); :meth:`step` converts at once."""
+        from . import fronthalf
+
+        grads, image = self._data_gradients()
+        e_prior, g_prior = self._prior()  # (of the parameters the gradients were taken at)
+        rows = [r for r in self._parameters() if r[1] in self.update]
+        if self._direct is not None:
+            entries = []
+            for name, _group, x, factor, step_max, normalize_rows in rows:
+                if name not in self.momentum.speed:
+                    self.momentum.speed[name] = torch.zeros_like(x)
+                entries.append((x, self.momentum.speed[name], grads[name], g_prior.get(name), factor, step_max, normalize_rows))
+            if entries:
+                fronthalf.momentum_update(entries, self.inertia, self.damping)
+        elif rows:
+            new = self.momentum.update_all([(name, x, grads[name], g_prior.get(name), factor, step_max, normalize_rows) for name, _g, x, factor, step_max, normalize_rows in rows])
+            for (name, *_), value in zip(rows, new):
+                setattr(self, name, value)
+        self.iter += 1
+        return self._total_energy(e_prior), image
+
+    def step(self):
+        """-> (energy, images [n,H,W,C], squared difference per pixel [n,H,W]) as a float and NumPy arrays (synchronises)"""
+        energy, image = self.step_device()
+        image = image.to(torch.float64)
+        return float(energy[0]), image.cpu().numpy(), ((image - self.mesh_image) ** 2).sum(dim=-1).cpu().numpy()

@@ -6,6 +6,7 @@ energy with SciPy on the host, deodr/pytorch/laplacian_rigid_energy_pytorch.py:3
 import torch
 
 from ..mesh_fitter import (  # noqa: F401
+    CameraFitterMultiFrame,
     MeshDepthFitter,
     MeshDepthFitterEnergy,
     MeshDepthFitterPytorchOptim,

@@ -60,6 +60,19 @@ class DeviceCamera:
         return cls(np.stack([np.asarray(c.extrinsic) for c in cameras]), np.stack([np.asarray(c.intrinsic) for c in cameras]), c0.height,
                    c0.width, dist, device, dtype)  # fmt: skip
 
+    @classmethod
+    def from_pose(cls, quaternions, translations, focal, center, height, width, distortion=None, shared_intrinsics=True, device="cuda", dtype=torch.float64):
+        """``n`` cameras from what a calibration moves: quaternions [n,4] = (x, y, z, w) (normalised here) and translations [n,3] of the world ->
+        camera transforms, focal = (fx, fy), center = (cx, cy) and distortion (k1, k2, p1, p2, k3) | None -- one set shared by the views ([2], [2],
+        [5]) or per view ([n,2], [n,2], [n,5]).  Differentiable in all five (``deodr_hip_camera_assemble`` on float64 ROCm tensors)."""
+        from . import fronthalf
+
+        dev = torch.device(device)
+        q, t, f, c = (_t(a, dev, dtype) for a in (quaternions, translations, focal, center))
+        d = None if distortion is None else _t(distortion, dev, dtype)
+        extrinsic, intrinsic, dist = fronthalf.camera_assemble(q, t, f, c, d, shared=shared_intrinsics)
+        return cls(extrinsic, intrinsic, height, width, dist, device, dtype)
+
     def world_to_camera(self, points_3d):
         """[V,3] (shared by the views) or [n,V,3] -> [n,V,3]"""
         p = points_3d if points_3d.dim() == 3 else points_3d[None].expand(self.n_views, -1, -1)

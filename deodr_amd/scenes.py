@@ -257,3 +257,30 @@ def hand_scene(mesh_path, size=1024, angle=0.0, textured=True, nb_colors=3, seed
     vertices, faces = load_hand_mesh(mesh_path)
     rot = np.diag([1.0, -1.0, -1.0]) @ roty(angle)  # camera orientation of deodr/mesh_fitter.py:258-282
     return mesh_scene(vertices, faces, size, size, nb_colors=nb_colors, rot=rot, fov=2 * np.rad2deg(np.arctan(0.25)), seed=seed, textured=textured, texture_size=256)
+
+
+def calibration_scene(vertices, n_views=4, size=128, perturbation=1.0, seed=0, distortion=(-0.25, 0.08, 0.003, -0.002, 0.0), arc=2 * np.pi):
+    """A camera-calibration problem: ``n_views`` cameras on a ring (``arc``: the part of it they are spread over) around a centred mesh, all one physical camera (focal, principal point, OpenCV
+    distortion), looking at it like the fitters' camera does (rot = diag(1, -1, -1), deodr/mesh_fitter.py:258-282).
+    -> dict: ``truth`` and ``start`` = {quaternions [n,4] (x, y, z, w), translations [n,3], focal [2], center [2], distortion [5]} -- the start is the
+    truth moved by ``perturbation`` times (0.03 rad about a random axis, 0.4 % of the distance, 3 % of the focal, 2 pixels, 30 % of the distortion)."""
+    from scipy.spatial.transform import Rotation
+
+    rs = np.random.RandomState(seed)
+    v = np.asarray(vertices, dtype=np.float64)
+    radius = float(np.max(np.std(v, axis=0)))
+    distance, focal = 6 * radius, 1.0 * size  # (the object fills most of the frame: the distortion is seen at its rim)
+    rots = [np.diag([1.0, -1.0, -1.0]) @ rotx(0.25) @ roty(0.3 + arc * k / n_views) for k in range(n_views)]
+    truth = {
+        "quaternions": np.stack([Rotation.from_matrix(r).as_quat() for r in rots]), "translations": np.tile([0.0, 0.0, distance], (n_views, 1)),
+        "focal": np.array([focal, 1.02 * focal]), "center": np.array([size / 2 + 1.5, size / 2 - 1.0]), "distortion": np.asarray(distortion, dtype=np.float64),
+    }  # fmt: skip
+    axis = rs.randn(n_views, 3)
+    wobble = Rotation.from_rotvec(0.03 * perturbation * axis / np.linalg.norm(axis, axis=1, keepdims=True))
+    start = {
+        "quaternions": np.stack([(w * Rotation.from_matrix(r)).as_quat() for w, r in zip(wobble, rots)]),
+        "translations": truth["translations"] + 0.004 * perturbation * distance * rs.randn(n_views, 3),
+        "focal": truth["focal"] * (1 + 0.03 * perturbation * np.array([1.0, -0.7])), "center": truth["center"] + 2.0 * perturbation * np.array([-1.0, 0.8]),
+        "distortion": truth["distortion"] * (1 - 0.3 * perturbation),
+    }  # fmt: skip
+    return {"truth": truth, "start": start, "height": size, "width": size}
