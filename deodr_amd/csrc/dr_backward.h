@@ -1191,7 +1191,7 @@ __device__ __forceinline__ void bwd_err_tile(const KParams &p, const ViewPtrs &w
 	for (int cc = 0; cc < CH; cc++)
 		g[cc] = (cc < C && inb) ? -2 * (ob[cc] - base[cc]) * eb : 0.0;
 	lds_sync();
-	owner_adjoint<PixT, TEX>(p, w, lane, x, y, owner, kind, g, tap, L, (double *)&S.rec[0], (uint32_t *)&S.cover[0][0], 384);
+	owner_adjoint<PixT, TEX>(p, w, lane, x, y, owner, kind, g, tap, L, (double *)&S.rec[0], (uint32_t *)&S.cover[0][0], WIN_CAP_DEFAULT);
 }
 
 // persistent waves over the lists of tiles that hold silhouette edges, as raster_bwd_edge_kernel (a tile of several batches is listed once here)

@@ -312,9 +312,16 @@ __device__ __forceinline__ uint32_t stage_edge_batch(WaveLds &S, const EdgeSort 
 	return inb ? gather_column_bits(&S.cover[lane >> 3][0], lane & 7) : 0u;
 }
 
+// Entries (doubles) of the texture-gradient window of owner_adjoint (dr_backward.h).  WIN_CAP_DEFAULT: the staging area of the wave, what a tile with
+// silhouette edges, the two-call kernels and bwd_err_tile have to spare.  WIN_CAP_WAVE_LDS: a fit step's tile without edges -- and a pair of them -- has
+// the whole LDS of the wavefront.  (tests/texture_window_cases.py reads both numbers from these lines.)
+constexpr int WIN_CAP_DEFAULT = 384;
+constexpr int WIN_CAP_WAVE_LDS = (int)((sizeof(WaveLds) + sizeof(EdgeSort)) / sizeof(double));
+static_assert(WIN_CAP_WAVE_LDS == 768, "the window capacity of the edge-free tiles (DESIGN.md); the tests place their cases at this number");
+
 template <class PixT, bool TEX>
 __device__ __forceinline__ void owner_adjoint(const KParams &p, const ViewPtrs &w, int lane, double x, double y, int owner, int kind, const double *g,
-											  const Tap &tap, double L, double *tab, uint32_t *own, int win_cap = 384);
+											  const Tap &tap, double L, double *tab, uint32_t *own, int win_cap = WIN_CAP_DEFAULT);
 
 template <int NPIX>
 __device__ __forceinline__ void owner_adjoint_slots(const KParams &p, const ViewPtrs &w, int lane, int x0, int y0, const int (&slot)[NPIX],
@@ -1164,7 +1171,7 @@ __device__ __forceinline__ void fwd_pair_tiles(const KParams &p, const ViewPtrs 
 		return;
 	}
 	// (a tile without edges: the whole LDS of the wavefront -- staging area and edge order -- is the texture-gradient window, as in the single-tile path)
-	constexpr int WIN = TEX ? (int)((sizeof(WaveLds) + sizeof(EdgeSort)) / sizeof(double)) : 384;
+	constexpr int WIN = TEX ? WIN_CAP_WAVE_LDS : WIN_CAP_DEFAULT;
 	double g[CH];
 	if (__ballot(kA >= 0) != 0)
 	{
@@ -1833,7 +1840,7 @@ __device__ __forceinline__ void fwd_tiles(const KParams &p, WaveLds *s_lds, Edge
 			// 0.1130 with the pairs alone, profiles/r05g_*)
 			// (a tile without edges: the whole LDS of the wavefront -- staging area and edge order -- is idle: twice the window)
 			owner_adjoint<PixT, TEX>(p, w, lane, x, y, st.kbest, st.kbest >= 0 ? st.kind : (int)KIND_NONE, g, tap, L, (double *)&S.rec[0],
-									(uint32_t *)&S.cover[0][0], (int)((sizeof(WaveLds) + sizeof(EdgeSort)) / sizeof(double)));
+									(uint32_t *)&S.cover[0][0], WIN_CAP_WAVE_LDS);
 		}
 		}
 		}

@@ -336,6 +336,7 @@ def compare_fit_step(api, views, sigma, dt, seed=11):
     torch.cuda.synchronize()
     assert torch.equal(image, image2) and torch.equal(z, z2), "the fused forward writes the same frame"
     tol_img, tol = TOL[dt]
+    uv_ref, tex_ref = 0.0, 0.0  # (shared by the views: the sum of the per-view references)
     for i, s in enumerate(views):
         ref = checker(api)
         img_ref, z_ref = ref.render(s, sigma)
@@ -348,11 +349,13 @@ def compare_fit_step(api, views, sigma, dt, seed=11):
             # (float32 frames: the fit step of an untextured scene sums a tile's residuals in float32 -- owner_adjoint_slots --, the two-call
             # path in double)
             assert rel_err(g[k][i].cpu().numpy(), g2[k][i].cpu().numpy()) < (1e-9 if dt == F64 else 5e-6), (k, "vs two calls")
-        if n == 1:
-            assert rel_err(g["uv_b"].cpu().numpy(), g_ref["uv_b"]) < tol, "uv_b"
-            if g["texture_b"] is not None and np.size(s.texture):
-                assert rel_err(g["texture_b"].cpu().numpy(), g_fix["texture_b"]) < tol, "texture_b"
+        uv_ref, tex_ref = uv_ref + g_ref["uv_b"], tex_ref + g_fix["texture_b"]
+    assert rel_err(g["uv_b"].cpu().numpy(), uv_ref) < tol, "uv_b"
     assert rel_err(g["uv_b"].cpu().numpy(), g2["uv_b"].cpu().numpy()) < 1e-9
+    if g["texture_b"] is not None and np.size(views[0].texture):
+        assert rel_err(g["texture_b"].cpu().numpy(), tex_ref) < tol, "texture_b (vs repaired reference, defect D1)"
+        # float64 frames: round-off of the atomics' order; float32 texture_b: float32 atomics in both paths (tests/test_hip_round5.py)
+        assert rel_err(g["texture_b"].cpu().numpy(), g2["texture_b"].cpu().numpy()) < (1e-9 if dt == F64 else 1e-5), ("texture_b", "vs two calls")
 
 
 def HipRasterizer_for(ds):
