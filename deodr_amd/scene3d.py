@@ -82,6 +82,8 @@ class DeviceCamera:
         """-> (image coordinates [n,V,2] with x = column first, depths [n,V]); differentiable (dr.py:341-395)."""
         from . import fronthalf
 
+        if points_3d.dtype != self.dtype:  # (a float32 mesh seen by a float64 camera: projected in the camera's arithmetic, its gradient cast back by autograd)
+            points_3d = points_3d.to(self.dtype)
         batch_ok = points_3d.dim() == 2 or int(points_3d.shape[0]) == self.n_views  # (else: the torch path below broadcasts, or raises)
         if batch_ok and fronthalf.usable(points_3d, self.extrinsic, self.intrinsic) and (self.distortion is None or fronthalf.usable(self.distortion)):
             # one kernel (two with its adjoint) instead of ~15 + ~25 torch kernels
