@@ -64,11 +64,13 @@
 #include "../../include/deodr_hip_retained.h"
 #include "../../include/deodr_hip_basis.h"
 #include "../../include/deodr_hip_camera.h"
+#include "../../include/deodr_hip_lighting.h"
 #include "dr_fititer.h" // <- dr_finalize.h <- dr_backward.h <- dr_backward_generic.h <- dr_forward.h <- dr_forward_generic.h <- dr_setup.h <- dr_workspace.h <- dr_prims.h
 #include "dr_texfit.h"  // texture smoothness + step (include/deodr_hip_texture.h); uses grid_sum of dr_fronthalf.h
 #include "dr_subdiv.h"  // rows of a sparse matrix applied to [batch, n, D] blocks (include/deodr_hip_subdiv.h): Loop subdivision and its adjoint
 #include "dr_basis.h"   // a dense [K, N] basis applied to coefficient vectors, and its adjoint (include/deodr_hip_basis.h): morphable models
 #include "dr_camera.h"  // the camera as a differentiable input: full adjoint of the projection, calibration parameters <-> matrices (include/deodr_hip_camera.h)
+#include "dr_lighting.h" // spherical-harmonic lighting and per-vertex albedo beside vertex_shade_* of dr_fititer.h (include/deodr_hip_lighting.h)
 
 using namespace dr;
 using namespace dr::dispatch;
@@ -1564,6 +1566,126 @@ int deodr_hip_camera_assemble_b(const double *quaternions, const double *extrins
 	a.shared = shared != 0, a.n = n;
 	hipLaunchKernelGGL(camera_assemble_b_kernel, dim3(1), dim3(FIT_MAX_VIEWS), 0, (hipStream_t)stream, a);
 	return check_hip(hipGetLastError(), "camera_assemble_b launch");
+}
+
+// ---- spherical-harmonic lighting (include/deodr_hip_lighting.h, kernels in dr_lighting.h)
+
+int deodr_hip_lighting_abi_version(void) { return DEODR_HIP_LIGHTING_ABI_VERSION; }
+
+static const char *sh_dims(int V, int n, int C, int S)
+{ // -> NULL, or which limit of the header the dimensions break
+	if (n < 1 || n > FIT_MAX_VIEWS)
+		return "n must be in 1 .. 64";
+	if (V < 1 || V > SH_MAX_VERTICES)
+		return "V must be in 1 .. 2^24";
+	if (C < 1 || C > 3)
+		return "C must be in 1 .. 3";
+	if (S != 1 && S != C)
+		return "S must be 1 or C";
+	return NULL;
+}
+
+int deodr_hip_sh_blocks(int V, int n) { return sh_dims(V, n, 1, 1) ? 0 : sh_blocks(V, n); }
+
+size_t deodr_hip_sh_scratch_bytes(int V, int n, int C)
+{
+	if (sh_dims(V, n, C, 1))
+		return 0;
+	return scratch_need((size_t)n * V * (3 + (size_t)C) + (size_t)sh_blocks(V, n) * SH_SUMS);
+}
+
+// what the two entry points ask of their common arguments -> 0 and `a`, or the refusal
+static int sh_args(const char *what, SHArgs &a, const double *posed, const uint32_t *faces, const uint32_t *vf_offsets, const uint32_t *vf_corners,
+				   const double *sh, int S, const double *albedo, int albedo_per_vertex, int C, const void *lum, const void *colors, int V, int n, int clockwise)
+{
+	if (!posed || !faces || !vf_offsets || !vf_corners || !sh)
+		return fail(what, "posed, faces, vf_offsets, vf_corners or sh == NULL");
+	if (const char *why = sh_dims(V, n, C, S))
+		return fail(what, why);
+	if (!lum && !colors)
+		return fail(what, "no output requested: neither luminosity nor colors (forward), neither of their adjoints (backward)");
+	if ((albedo == nullptr) != (colors == nullptr))
+		return fail(what, "albedo and colors go together");
+	if (lum && S != 1)
+		return fail(what, "luminosity needs S = 1");
+	a.mesh = ShadeArgs{posed, faces, vf_offsets, vf_corners, nullptr, nullptr, nullptr, albedo ? C : 0, V, n, clockwise ? -1.0 : 1.0};
+	a.sh = sh, a.albedo = albedo, a.S = S, a.per_vertex = albedo_per_vertex != 0;
+	return 0;
+}
+
+int deodr_hip_sh_shade(const double *posed, const uint32_t *faces, const uint32_t *vf_offsets, const uint32_t *vf_corners, const double *sh, int S,
+					   const double *albedo, int albedo_per_vertex, int C, double *luminosity, double *colors, int V, int n, int clockwise, void *stream)
+{
+	const char *what = "sh_shade";
+	SHArgs a;
+	if (sh_args(what, a, posed, faces, vf_offsets, vf_corners, sh, S, albedo, albedo_per_vertex, C, luminosity, colors, V, n, clockwise))
+		return 1;
+	const void *const doubles[] = {posed, sh, albedo, luminosity, colors};
+	const void *const words[] = {faces, vf_offsets, vf_corners};
+	if (any_misaligned(doubles, 8) || any_misaligned(words, 4))
+		return fail(what, "misaligned pointer");
+	const size_t nv = (size_t)n * (size_t)V * 8;
+	const Range outputs[] = {{luminosity, nv}, {colors, nv * C}};
+	const Range inputs[] = {{posed, 3 * nv}, {faces, 12}, {vf_offsets, 4 * ((size_t)V + 1)}, {vf_corners, 12}, {sh, 72 * (size_t)S},
+							{albedo, 8 * (size_t)C * (a.per_vertex ? (size_t)V : 1)}};
+	if (any_overlap(outputs, inputs) || ranges_overlap(luminosity, nv, colors, nv * C))
+		return fail(what, "an output must not overlap an input or the other output");
+	hipLaunchKernelGGL(sh_shade_kernel, dim3(fh_blocks((long long)V * GATHER_LANES), n), dim3(FH_BLOCK), 0, (hipStream_t)stream, a, luminosity, colors);
+	return check_hip(hipGetLastError(), "sh_shade launch");
+}
+
+int deodr_hip_sh_shade_b(const double *posed, const uint32_t *faces, const uint32_t *vf_offsets, const uint32_t *vf_corners, const double *sh, int S,
+						 const double *albedo, int albedo_per_vertex, int C, const double *luminosity_b, const double *colors_b, double *posed_b,
+						 double *sh_b, double *albedo_b, int accumulate, void *scratch, size_t scratch_bytes, int V, int n, int clockwise, void *stream)
+{
+	const char *what = "sh_shade_b";
+	SHArgs a;
+	if (sh_args(what, a, posed, faces, vf_offsets, vf_corners, sh, S, albedo, albedo_per_vertex, C, luminosity_b, colors_b, V, n, clockwise))
+		return 1;
+	if (!scratch)
+		return fail(what, "scratch == NULL");
+	if (!posed_b && !sh_b && !albedo_b)
+		return fail(what, "no output requested (posed_b, sh_b, albedo_b)");
+	if (albedo_b && !albedo)
+		return fail(what, "albedo_b without albedo");
+	const void *const doubles[] = {posed, sh, albedo, luminosity_b, colors_b, posed_b, sh_b, albedo_b, scratch};
+	const void *const words[] = {faces, vf_offsets, vf_corners};
+	if (any_misaligned(doubles, 8) || any_misaligned(words, 4))
+		return fail(what, "misaligned pointer");
+	const Scratch sc = {scratch, scratch_bytes};
+	if (!sc.holds(deodr_hip_sh_scratch_bytes(V, n, C)))
+		return fail(what, "scratch too small (deodr_hip_sh_scratch_bytes)");
+	const size_t nv = (size_t)n * (size_t)V * 8, alb = 8 * (size_t)C * (a.per_vertex ? (size_t)V : 1);
+	const Range outputs[] = {{posed_b, 3 * nv}, {sh_b, 72 * (size_t)S}, {albedo_b, alb}, {scratch, scratch_bytes}};
+	const Range inputs[] = {{posed, 3 * nv}, {faces, 12}, {vf_offsets, 4 * ((size_t)V + 1)}, {vf_corners, 12}, {sh, 72 * (size_t)S}, {albedo, alb},
+							{luminosity_b, nv}, {colors_b, nv * C}};
+	const Range written[] = {{posed_b, 3 * nv}, {sh_b, 72 * (size_t)S}, {albedo_b, alb}};
+	const Range scratch_range[] = {{scratch, scratch_bytes}};
+	if (any_overlap(outputs, inputs) || any_overlap(written, scratch_range) || ranges_overlap(posed_b, 3 * nv, sh_b, 72 * (size_t)S) ||
+		ranges_overlap(posed_b, 3 * nv, albedo_b, alb) || ranges_overlap(sh_b, 72 * (size_t)S, albedo_b, alb))
+		return fail(what, "an output must not overlap an input, the scratch or another output");
+	hipStream_t st = (hipStream_t)stream;
+	const unsigned blocks = (unsigned)sh_blocks(V, n);
+	SHBackArgs o = {};
+	o.lum_b = luminosity_b, o.colors_b = colors_b, o.accumulate = accumulate != 0;
+	o.acc_b = sc.doubles();
+	double *products = o.acc_b + 3 * (size_t)n * V;
+	o.partials = products + (size_t)n * V * C;
+	o.counters = sc.counter(0);
+	o.sh_b = sh_b;
+	const bool vertex_albedo_b = a.per_vertex && albedo_b;
+	o.albedo_b = a.per_vertex ? nullptr : albedo_b;
+	// (several views of a per-vertex albedo: the products colors_b E are left in the scratch whether or not albedo_b is asked for -- the header's
+	// "scratch after the call" -- so that a caller with a sum over the views of its own in a later launch needs no launch for it here)
+	o.products = a.per_vertex && colors_b && n > 1 ? products : nullptr;
+	o.albedo_direct = vertex_albedo_b && n == 1 ? albedo_b : nullptr;
+	hipLaunchKernelGGL(sh_shade_b1_kernel, dim3(blocks), dim3(FH_BLOCK), 0, st, a, o);
+	if (o.products && albedo_b)
+		hipLaunchKernelGGL(sh_albedo_sum_kernel, dim3(fh_blocks((long long)V * C)), dim3(FH_BLOCK), 0, st, (const double *)products, albedo_b, (size_t)V * C, n,
+						   o.accumulate);
+	if (posed_b)
+		hipLaunchKernelGGL(vertex_shade_b2_kernel, dim3(fh_blocks((long long)V * GATHER_LANES), n), dim3(FH_BLOCK), 0, st, a.mesh, (const double *)o.acc_b, posed_b);
+	return check_hip(hipGetLastError(), "sh_shade_b launch");
 }
 
 #ifdef DR_WAVE_TRACE

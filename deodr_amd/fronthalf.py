@@ -348,3 +348,72 @@ class RigidEnergyFunc(torch.autograd.Function):
     def backward(ctx, energy_b, _grad_b):
         (grad,) = ctx.saved_tensors
         return energy_b * grad, None, None, None
+
+
+_sh_scratches = {}  # (device, stream) -> the zero-filled scratch of sh_shade_b for the autograd wrapper, grown to the largest shape asked for
+
+
+def _sh_scratch(device, V, n, C):
+    """one scratch per device and stream (the header: used by one stream at a time), kept at the largest size seen; a larger one than a call needs
+    serves it (the layout is the call's, the counter words are zero between calls)"""
+    key = (device, torch.cuda.current_stream(device).cuda_stream)
+    need = int(lib().deodr_hip_sh_scratch_bytes(int(V), int(n), int(C)))
+    if key not in _sh_scratches or _sh_scratches[key].numel() < need:
+        _sh_scratches[key] = hr.sh_scratch(V, n, C, device)
+    return _sh_scratches[key]
+
+
+class SHShadeFunc(torch.autograd.Function):
+    """(posed [n,V,3], sh [9] | [9,S], albedo None | [C] | [V,C]) -> luminosity [n,V] (no albedo) or colors [n,V,C]: spherical-harmonic lighting of
+    the vertex normals times the albedo (``deodr_amd/lighting.py`` has the formulas) in one launch; the adjoint -- gradients to all three -- in two
+    or three (``deodr_hip_sh_shade_b``).  More than the 64 views a launch takes go in slices, the sums over the views accumulated in slice order."""
+
+    @staticmethod
+    def forward(ctx, posed, sh, albedo, topology):
+        posed, sh = posed.contiguous(), sh.contiguous()
+        albedo = None if albedo is None else albedo.contiguous()
+        n, V = posed.shape[0], posed.shape[1]
+        out = torch.empty((n, V) if albedo is None else (n, V, albedo.shape[-1]), dtype=torch.float64, device=posed.device)
+        step = hr.SH_MAX_VIEWS
+        for b in range(0, n, step):
+            hr.sh_shade(posed[b : b + step], topology._faces_u32, topology._vf_offsets, topology._vf_corners, sh, albedo,
+                        luminosity=out[b : b + step] if albedo is None else None, colors=None if albedo is None else out[b : b + step],
+                        clockwise=topology.clockwise)  # fmt: skip
+        ctx.save_for_backward(posed, sh, *(() if albedo is None else (albedo,)))
+        ctx.topology = topology
+        return out
+
+    @staticmethod
+    def backward(ctx, out_b):
+        posed, sh, *rest = ctx.saved_tensors
+        albedo = rest[0] if rest else None
+        topology, out_b = ctx.topology, out_b.contiguous()
+        n, V = posed.shape[0], posed.shape[1]
+        C = 1 if albedo is None else int(albedo.shape[-1])
+        want = (ctx.needs_input_grad[0], True, albedo is not None)  # (the two sums come with the launch that everything else needs)
+        posed_b = torch.empty_like(posed) if want[0] else None
+        sh_b = torch.empty_like(sh)
+        albedo_b = None if albedo is None else torch.empty_like(albedo)
+        step = hr.SH_MAX_VIEWS
+        for b in range(0, n, step):
+            cut = lambda t: None if t is None else t[b : b + step]
+            hr.sh_shade_b(posed[b : b + step], topology._faces_u32, topology._vf_offsets, topology._vf_corners, sh, albedo,
+                          luminosity_b=cut(out_b) if albedo is None else None, colors_b=None if albedo is None else cut(out_b), posed_b=cut(posed_b),
+                          sh_b=sh_b, albedo_b=albedo_b, accumulate=b > 0, scratch=_sh_scratch(posed.device, V, min(step, n - b), C),
+                          clockwise=topology.clockwise, want=want)  # fmt: skip
+        return posed_b, sh_b, albedo_b, None
+
+
+def sh_shade(posed, sh, albedo, topology):
+    """-> luminosity [n,V] (``albedo`` None) or colors [n,V,C] of the posed vertices [n,V,3] (or [V,3]) under the SH lighting ``sh``, differentiable in
+    all three: the kernels on float64 ROCm tensors, the same formulas as torch ops (``lighting.sh_shade_torch``) otherwise"""
+    from . import lighting
+
+    tensors = [posed, sh] + ([] if albedo is None else [albedo])
+    n_columns = 1 if sh.dim() == 1 else int(sh.shape[1])
+    channels = n_columns if albedo is None else int(albedo.shape[-1])
+    fits = topology.nb_faces and posed.shape[-2] <= hr.SH_MAX_VERTICES and 1 <= channels <= 3 and n_columns in (1, channels)
+    if usable(*tensors) and fits and (albedo is None or albedo.dim() in (1, 2)):
+        out = SHShadeFunc.apply(posed if posed.dim() == 3 else posed[None], sh, albedo, topology)
+        return out if posed.dim() == 3 else out[0]
+    return lighting.sh_shade_torch(posed, topology, sh, albedo)

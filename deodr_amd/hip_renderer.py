@@ -35,8 +35,9 @@ _COMPANIONS = (
     (_abi.RETAINED_HEADER, "retained", "retained-frames"),  # fit step into retained frames
     (_abi.BASIS_HEADER, "basis", "linear-basis"),  # linear bases: morphable models
     (_abi.CAMERA_HEADER, "camera", "camera"),  # camera calibration
+    (_abi.LIGHTING_HEADER, "lighting", "lighting"),  # spherical-harmonic lighting, per-vertex albedo
 )
-TEXTURE_ABI_VERSION, SUBDIV_ABI_VERSION, RETAINED_ABI_VERSION, BASIS_ABI_VERSION, CAMERA_ABI_VERSION = (
+TEXTURE_ABI_VERSION, SUBDIV_ABI_VERSION, RETAINED_ABI_VERSION, BASIS_ABI_VERSION, CAMERA_ABI_VERSION, LIGHTING_ABI_VERSION = (
     h.defines[f"DEODR_HIP_{key.upper()}_ABI_VERSION"] for h, key, _ in _COMPANIONS
 )
 # words of the 64-byte status block at the start of the workspace
@@ -1102,6 +1103,122 @@ class HipRasterizer:
             return self.render_backward(ds, image_b=image_b, err_buffer_b=err_buffer_b, have_forward_state=False)
 
         return self._until_it_fits(ds, launch)
+
+
+# ---- spherical-harmonic lighting and per-vertex albedo (include/deodr_hip_lighting.h) ---------------------------------------------------
+
+SH_MAX_VIEWS, SH_MAX_VERTICES, SH_COEFFS = 64, 2**24, 9  # the limits include/deodr_hip_lighting.h states
+_I32_ONLY = (torch.int32,)  # (uint32 index arrays travel as int32 tensors, as MeshTopology keeps them)
+
+
+def sh_blocks(V, n):
+    """``deodr_hip_sh_blocks``: the workgroups of the per-(view, vertex) kernel of :func:`sh_shade_b` (0: outside the limits)"""
+    return int(lib().deodr_hip_sh_blocks(int(V), int(n)))
+
+
+def sh_scratch(V, n, C, device):
+    """the scratch of :func:`sh_shade_b` for V vertices, n views and C channels, zero-filled as the library wants it once (one per stream in use)"""
+    need = int(lib().deodr_hip_sh_scratch_bytes(int(V), int(n), int(C)))
+    if need == 0:
+        raise ValueError(f"sh_scratch: V = {V}, n = {n}, C = {C} is outside the limits of include/deodr_hip_lighting.h")
+    with torch.cuda.device(device):
+        return torch.zeros(need, dtype=torch.uint8, device=device)
+
+
+def sh_products(scratch, V, n, C):
+    """the view [n,V,C] of a :func:`sh_scratch` that :func:`sh_shade_b` leaves the products ``colors_b * E`` in when the albedo is per vertex and n > 1
+    (include/deodr_hip_lighting.h, "the scratch after the call"): their sum over the views is ``albedo_b``"""
+    at = 64 + 8 * 3 * n * V
+    return scratch[at : at + 8 * n * V * C].view(torch.float64).view(n, V, C)
+
+
+def _sh_args(what, posed, faces, vf_offsets, vf_corners, sh, albedo):
+    """checks before the library is called -> (n, V, S, C, per_vertex, rows of :func:`_check_tensors` for the inputs)"""
+    _rocm_tensor(what, "posed", posed)
+    if posed.dim() != 3 or int(posed.shape[2]) != 3 or not 1 <= int(posed.shape[0]) <= SH_MAX_VIEWS or not 1 <= int(posed.shape[1]) <= SH_MAX_VERTICES:
+        raise ValueError(f"{what}: posed must have shape [1 <= n <= {SH_MAX_VIEWS}, 1 <= V <= 2^24, 3], not {list(posed.shape)}")
+    n, V = int(posed.shape[0]), int(posed.shape[1])
+    if not torch.is_tensor(sh) or sh.dim() not in (1, 2) or int(sh.shape[0]) != SH_COEFFS:
+        raise ValueError(f"{what}: sh must have shape [9] or [9, S], not {list(getattr(sh, 'shape', ()))}")
+    S = 1 if sh.dim() == 1 else int(sh.shape[1])
+    C, per_vertex = 1, False
+    rows = [("posed", posed, _F64_ONLY, (n, V, 3)), ("sh", sh, _F64_ONLY, None), ("faces", faces, _I32_ONLY, (None, 3)),
+            ("vf_offsets", vf_offsets, _I32_ONLY, (V + 1,))]  # fmt: skip
+    if not torch.is_tensor(faces) or faces.dim() != 2 or int(faces.shape[0]) < 1:
+        raise ValueError(f"{what}: faces must have shape [T >= 1, 3]")
+    rows.append(("vf_corners", vf_corners, _I32_ONLY, (3 * int(faces.shape[0]),)))
+    if albedo is not None:
+        if not torch.is_tensor(albedo) or albedo.dim() not in (1, 2) or not 1 <= int(albedo.shape[-1]) <= 3 or (albedo.dim() == 2 and int(albedo.shape[0]) != V):
+            raise ValueError(f"{what}: albedo must have shape [1 <= C <= 3] or [{V}, C], not {list(getattr(albedo, 'shape', ()))}")
+        C, per_vertex = int(albedo.shape[-1]), albedo.dim() == 2
+        rows.append(("albedo", albedo, _F64_ONLY, None))
+    if S != 1 and S != C:
+        raise ValueError(f"{what}: sh must have 1 column or one per channel ({C}), not {S}")
+    return n, V, S, C, per_vertex, rows
+
+
+def sh_shade(posed, faces, vf_offsets, vf_corners, sh, albedo=None, luminosity=None, colors=None, clockwise=False, want_luminosity=None):
+    """``deodr_hip_sh_shade``: order-2 spherical-harmonic lighting of the vertex normals in one launch.  ``posed`` [n,V,3], ``sh`` [9] | [9,S], ``albedo``
+    None | [C] | [V,C], float64 ROCm tensors; ``faces`` [T,3], ``vf_offsets`` [V+1], ``vf_corners`` [3T] the int32 tensors of a ``MeshTopology``
+    -> (luminosity [n,V] | None, colors [n,V,C] | None): colours with an albedo, the luminosity without one (or with ``want_luminosity``, S = 1)."""
+    what = "sh_shade"
+    n, V, S, C, per_vertex, rows = _sh_args(what, posed, faces, vf_offsets, vf_corners, sh, albedo)
+    if want_luminosity is None:
+        want_luminosity = albedo is None or luminosity is not None
+    rows += [(name, t, _F64_ONLY, shape) for name, t, shape in (("luminosity", luminosity, (n, V)), ("colors", colors, (n, V, C))) if t is not None]
+    _check_tensors(what, "posed", posed.device, rows)
+    if colors is not None and albedo is None:
+        raise ValueError(f"{what}: colors without albedo")
+    dev = posed.device
+    with torch.cuda.device(dev):
+        if luminosity is None and want_luminosity:
+            luminosity = torch.empty((n, V), dtype=torch.float64, device=dev)
+        if colors is None and albedo is not None:
+            colors = torch.empty((n, V, C), dtype=torch.float64, device=dev)
+    _launch(lib().deodr_hip_sh_shade, dev, _ptr(posed), _ptr(faces), _ptr(vf_offsets), _ptr(vf_corners), _ptr(sh), S, _ptr(albedo), int(per_vertex), C,
+            _ptr(luminosity), _ptr(colors), V, n, int(bool(clockwise)))  # fmt: skip
+    for t in (luminosity, colors):
+        if t is not None:
+            _touched(t)
+    return luminosity, colors
+
+
+def sh_shade_b(posed, faces, vf_offsets, vf_corners, sh, albedo=None, luminosity_b=None, colors_b=None, posed_b=None, sh_b=None, albedo_b=None,
+               accumulate=False, scratch=None, clockwise=False, want=(True, True, True)):
+    """``deodr_hip_sh_shade_b``: the adjoint of :func:`sh_shade` -> (posed_b [n,V,3] | None, sh_b of ``sh``'s shape | None, albedo_b of ``albedo``'s shape |
+    None), allocated where not given and ``want`` = (posed_b, sh_b, albedo_b) asks for them.  ``accumulate``: added to sh_b and albedo_b, which must then
+    be given.  Deterministic; asynchronous on the current stream.  ``scratch``: a :func:`sh_scratch` of the caller's; None: one per device and stream."""
+    what = "sh_shade_b"
+    n, V, S, C, per_vertex, rows = _sh_args(what, posed, faces, vf_offsets, vf_corners, sh, albedo)
+    optional = [("luminosity_b", luminosity_b, (n, V)), ("colors_b", colors_b, (n, V, C)), ("posed_b", posed_b, (n, V, 3)), ("sh_b", sh_b, tuple(sh.shape)),
+                ("albedo_b", albedo_b, None if albedo is None else tuple(albedo.shape))]  # fmt: skip
+    rows += [(name, t, _F64_ONLY, shape) for name, t, shape in optional if t is not None]
+    if scratch is not None:
+        rows.append(("scratch", scratch, (torch.uint8,), (None,)))
+    _check_tensors(what, "posed", posed.device, rows)
+    if albedo is None and albedo_b is not None:
+        raise ValueError(f"{what}: albedo_b without albedo")
+    want_posed, want_sh, want_albedo = want
+    if accumulate and ((want_sh and sh_b is None) or (want_albedo and albedo is not None and albedo_b is None)):
+        raise ValueError(f"{what}: accumulate needs sh_b and (with an albedo) albedo_b")
+    dev = posed.device
+    with torch.cuda.device(dev):
+        if posed_b is None and want_posed:
+            posed_b = torch.empty_like(posed)
+        if sh_b is None and want_sh:
+            sh_b = torch.empty_like(sh)
+        if albedo_b is None and want_albedo and albedo is not None:
+            albedo_b = torch.empty_like(albedo)
+        if scratch is None:
+            scratch = _cached_scratch("sh", dev, int(lib().deodr_hip_sh_scratch_bytes(V, n, C)), lambda: sh_scratch(V, n, C, dev),
+                                      f"{what}: pass scratch= (sh_scratch) when capturing a graph: none of this size exists for this stream yet")  # fmt: skip
+    _launch(lib().deodr_hip_sh_shade_b, dev, _ptr(posed), _ptr(faces), _ptr(vf_offsets), _ptr(vf_corners), _ptr(sh), S, _ptr(albedo), int(per_vertex), C,
+            _ptr(luminosity_b), _ptr(colors_b), _ptr(posed_b), _ptr(sh_b), _ptr(albedo_b), int(bool(accumulate)), _ptr(scratch), scratch.numel(), V, n,
+            int(bool(clockwise)))  # fmt: skip
+    for t in (posed_b, sh_b, albedo_b):
+        if t is not None:
+            _touched(t)
+    return posed_b, sh_b, albedo_b
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -146,7 +146,9 @@ class _DirectIteration:
     What ``step_device`` returns on this path (energy, image, ...) are views of these buffers: the next step overwrites them (``step()``
     converts them to a float and NumPy arrays at once, as the reference's protocol wants)."""
 
-    def __init__(self, fitter, nb_colors, shaded):
+    def __init__(self, fitter, nb_colors, shaded, sh=None):
+        """``sh`` = (shape of the SH coefficients, per-vertex albedo or not): the iteration of a fitter with spherical-harmonic lighting, whose shared
+        block is [sh_b 9S | albedo_b (C or V C) | data energy 1 | vertices_b 3V | mean 3] instead"""
         from . import fronthalf
 
         f, topo, cam = fitter, fitter.mesh.topology, fitter.camera
@@ -156,11 +158,25 @@ class _DirectIteration:
         self.flags = torch.zeros((n, T, 3), dtype=torch.uint8, device=dev)
         self.posed_b = z(n, V, 3) if shaded else None
         self.scratch = fronthalf.fit_scratch(V, n, dev)
-        self.flat = z(5 + C + 3 * V + 3 + 7 * n)
-        self.shade_out, self.e_data = self.flat[: 4 + C], self.flat[4 + C : 5 + C]
-        self.vertices_b = self.flat[5 + C : 5 + C + 3 * V].view(V, 3)
-        self.pose_out = self.flat[5 + C + 3 * V :]  # mean of vertices_b [3], quaternion adjoints [n,4], translation adjoints [n,3]
-        self.shared = self.flat[: 5 + C + 3 * V + 3]
+        head = 4 + C  # light_b 3 | ambient_b 1 | colour_b C
+        if sh is not None:
+            from . import hip_renderer as hr
+
+            sh_shape, per_vertex = sh
+            n_sh, n_albedo = int(np.prod(sh_shape)), (V * C if per_vertex else C)
+            head = n_sh + n_albedo
+            self.sh_scratch = hr.sh_scratch(V, n, C, dev)
+            self.g_albedo = z(V, C) if per_vertex else None
+            self.albedo_ref = z(V, C) if per_vertex else None  # the smoothness term is the Laplacian energy against zero
+            self.energy3 = z(3)  # albedo smoothness, rigid + albedo smoothness, data_weight * data + both
+        self.flat = z(head + 1 + 3 * V + 3 + 7 * n)
+        self.shade_out, self.e_data = self.flat[:head], self.flat[head : head + 1]
+        if sh is not None:
+            self.sh_b = self.shade_out[:n_sh].view(sh_shape)
+            self.albedo_b = self.shade_out[n_sh:].view((V, C) if per_vertex else (C,))
+        self.vertices_b = self.flat[head + 1 : head + 1 + 3 * V].view(V, 3)
+        self.pose_out = self.flat[head + 1 + 3 * V :]  # mean of vertices_b [3], quaternion adjoints [n,4], translation adjoints [n,3]
+        self.shared = self.flat[: head + 1 + 3 * V + 3]
         self.g_rigid, self.energy, self.vmean = z(V, 3), z(2), z(3)  # energy: rigid, data_weight * data + rigid
         sc = f.scene
         if (sc.background_image is None) == (sc.background_color is None):
@@ -327,7 +343,7 @@ class _PoseFitter:
 
     # ---- the iteration as a fixed kernel sequence (float64 ROCm tensors, manifold mesh) ------------------------------------------
 
-    def _direct_iteration(self, nb_colors, shaded):
+    def _direct_iteration(self, nb_colors, shaded, sh=None):
         """-> the _DirectIteration of this fitter, or None when an iteration has to go through autograd (CPU tensors: the CPU suite;
         a non-manifold mesh: no static table for the silhouette flags; ``direct = False``; ``subdivisions > 0``: the kernels of the fixed
         sequence fold the centring and the gradient mean into passes keyed to the RENDERED vertex array, which is then not the parameter)"""
@@ -342,8 +358,10 @@ class _PoseFitter:
                 and self.camera.n_views <= 64):  # (deodr_hip_fit_pose_project_b: at most 64 views per call)
             return None
         key = (id(self.camera), nb_colors, shaded, self.scene.pixel_dtype, id(self.scene.background_color), id(self.scene.background_image))
+        if sh is not None:
+            key += (sh,)
         if self._direct_state is None or self._direct_state[0] != key:
-            self._direct_state = (key, _DirectIteration(self, nb_colors, shaded))
+            self._direct_state = (key, _DirectIteration(self, nb_colors, shaded) if sh is None else _DirectIteration(self, nb_colors, shaded, sh))
         d = self._direct_state[1]
         d.sync(self)
         return d
@@ -362,14 +380,15 @@ class _PoseFitter:
                             ambient=ambient, color=color, colors=d.colors if shade is not None else None, vertices=self.vertices,
                             vertices_ref=self.rigid_energy.vertices_ref, cregu=self.cregu, gradient=d.g_rigid, energy=d.energy)  # fmt: skip
 
-    def _direct_backward_and_update(self, d, depths_b, step_max, data_weight, extra=(), depths_b_scale=1.0):
+    def _direct_backward_and_update(self, d, depths_b, step_max, data_weight, extra=(), depths_b_scale=1.0, energy=None, views_sum=None):
         """adjoint of pose + projection, (all-reduce of the shared block,) momentum update of every parameter in place (which also adds the
         data energy to the rigid energy of :meth:`_direct_forward`)"""
         from . import fronthalf
 
         n = d.posed.shape[0]
+        extra_sum = {} if views_sum is None else dict(colors_b=views_sum[0], colors_sum=views_sum[1])  # ([n,V,C] summed over the views -> [V,C])
         fronthalf.fit_pose_project_b(self.vertices, self.transform_quaternion, d.posed, self.camera, d.posed_b, d.grads["ij_b"], depths_b, d.vertices_b,
-                                     d.pose_out, d.scratch, depths_b_scale)  # fmt: skip
+                                     d.pose_out, d.scratch, depths_b_scale, **extra_sum)  # fmt: skip
         self._allreduce_shared(d.shared)
         def speed(name, x):
             if name not in self.momentum.speed:
@@ -382,10 +401,11 @@ class _PoseFitter:
              step_max[1], 4, data_weight, None, None),
             (self.transform_translation, speed("translation", self.transform_translation), d.pose_out[3 + 4 * n :], None, self.step_factor_translation,
              step_max[2], 0, data_weight, None, None),
-        ] + [(x, speed(name, x), g, None, factor, None, 0, data_weight, None, None) for name, x, g, factor in extra]  # fmt: skip
-        fronthalf.momentum_update(entries, self.inertia, self.damping, scratch=d.scratch, energy=d.energy, data_energy=d.e_data, data_weight=data_weight)
+        ] + [(x, speed(name, x), g, g2[0] if g2 else None, factor, None, 0, data_weight, None, None) for name, x, g, factor, *g2 in extra]  # fmt: skip
+        energy = d.energy if energy is None else energy  # ([what the data energy is added to, the sum]; an extra entry may carry a second gradient)
+        fronthalf.momentum_update(entries, self.inertia, self.damping, scratch=d.scratch, energy=energy, data_energy=d.e_data, data_weight=data_weight)
         self.iter += 1
-        return d.energy[1]
+        return energy[1]
 
     def _allreduce_shared(self, shared):
         pass  # single process, every view local
@@ -553,8 +573,9 @@ class MeshRGBFitterWithPose(_PoseFitter):
 
     def __init__(self, vertices, faces, euler_init, translation_init, default_color, default_light_directional, default_light_ambient, cregu=2000,
                  inertia=0.96, damping=0.05, update_lights=True, update_color=True, device="cuda", pixel_dtype=torch.float64, n_poses=1,
-                 subdivisions=0, shape_basis=None, coefficient_regu=0.0, sigmas=None):  # fmt: skip
+                 subdivisions=0, shape_basis=None, coefficient_regu=0.0, sigmas=None, light_sh_init=None, vertex_albedo=False, albedo_regu=0.0):  # fmt: skip
         self.default_color = np.asarray(default_color, dtype=np.float64)
+        self._init_lighting(light_sh_init, vertex_albedo, albedo_regu)
         self.default_light_directional = np.asarray(default_light_directional, dtype=np.float64)
         self.default_light_ambient = float(default_light_ambient)
         self.update_lights, self.update_color = update_lights, update_color
@@ -562,10 +583,34 @@ class MeshRGBFitterWithPose(_PoseFitter):
                          subdivisions=subdivisions, shape_basis=shape_basis, coefficient_regu=coefficient_regu, sigmas=sigmas)  # fmt: skip
         self.camera_center = self.object_center + np.atleast_2d(np.asarray(translation_init, dtype=np.float64))[0] + np.array([0, 0, 9]) * self.object_radius
 
+    step_factor_light_sh, step_factor_albedo = 0.0001, 0.00001  # (those of the directional light and of the single colour)
+
+    def _init_lighting(self, light_sh_init, vertex_albedo, albedo_regu):
+        """``light_sh_init`` ([9] or [9,3]; None: off, every path as it is without the keyword): spherical-harmonic lighting of bands 0 - 2
+        (deodr_amd/lighting.py) instead of the directional + ambient pair, which is then ignored for rendering; the parameter is ``self.light_sh``
+        (``update_lights``).  ``vertex_albedo``: ``self.mesh_color`` is [V,3], initialised from ``default_color`` (``update_color``), and the energy
+        gains ``0.5 albedo_regu sum_c a_c^T (L^T L) a_c`` over the Laplacian L of the rendered mesh."""
+        self.light_sh_init = None if light_sh_init is None else np.asarray(light_sh_init, dtype=np.float64)
+        if self.light_sh_init is not None and self.light_sh_init.shape not in ((9,), (9, 3)):
+            raise ValueError(f"light_sh_init must have shape [9] or [9, 3], not {list(self.light_sh_init.shape)}")
+        self.vertex_albedo, self.albedo_regu = bool(vertex_albedo), float(albedo_regu)
+        if self.vertex_albedo and self.light_sh_init is None:
+            raise ValueError("vertex_albedo needs light_sh_init (lighting.sh_from_directional gives the coefficients of a directional + ambient pair)")
+        if self.vertex_albedo and self.albedo_regu and self.default_color.size != 3:
+            raise ValueError(f"albedo_regu needs a colour of 3 channels (the smoothness term runs on [V,3] arrays), not {self.default_color.size}")
+        self.light_sh = self._albedo_energy = None
+
     def reset(self):
         super().reset()
         t = lambda a: torch.as_tensor(np.asarray(a, dtype=np.float64), device=self.device)
         self.mesh_color, self.light_directional, self.light_ambient = t(self.default_color), t(self.default_light_directional), t(self.default_light_ambient)
+        if self.light_sh_init is not None:
+            self.light_sh = t(self.light_sh_init)
+            if self.vertex_albedo:
+                V = self.mesh.nb_vertices
+                self.mesh_color = t(np.broadcast_to(self.default_color, (V, self.default_color.size)).copy())
+                if self.albedo_regu and self._albedo_energy is None:
+                    self._albedo_energy = LaplacianRigidEnergyDevice(self.mesh.topology, np.zeros((V, 3)), self.albedo_regu)
 
     def set_background_color(self, background_color):
         self.scene.set_background_color(background_color)
@@ -582,12 +627,19 @@ class MeshRGBFitterWithPose(_PoseFitter):
 
     def _appearance_leaves(self):
         self.mesh_color_leaf = self.mesh_color.detach().requires_grad_(True)
+        if self.light_sh is not None:
+            self.light_sh_leaf = self.light_sh.detach().requires_grad_(True)
+            return [self.mesh_color_leaf, self.light_sh_leaf]
         self.light_directional_leaf = self.light_directional.detach().requires_grad_(True)
         self.light_ambient_leaf = self.light_ambient.detach().requires_grad_(True)
         return [self.mesh_color_leaf, self.light_directional_leaf, self.light_ambient_leaf]
 
     def _pose_scene(self):
         self.mesh.set_vertices(self._transformed(self.vertices_leaf))
+        if self.light_sh is not None:  # one launch: albedo ([3] or [V,3]) times the SH irradiance (Scene3DDevice._vertex_inputs)
+            self.scene.light_sh, self.scene.light_directional, self.scene.light_ambient = self.light_sh_leaf, None, 0.0
+            self.mesh.set_vertices_colors(self.mesh_color_leaf)
+            return
         self.scene.light_directional, self.scene.light_ambient = self.light_directional_leaf, self.light_ambient_leaf
         self.mesh.set_vertices_colors(self.mesh_color_leaf[None, :].expand(self.mesh.nb_vertices, -1))
 
@@ -639,6 +691,67 @@ class MeshRGBFitterWithPose(_PoseFitter):
         energy = self._direct_backward_and_update(d, None, (0.5, 0.05, 0.1), self.data_weight, extra)
         return energy, image
 
+    def _albedo_smoothness(self):
+        """-> (0.5 albedo_regu sum_c a_c^T (L^T L) a_c, its gradient [V,3]) or (0, None) without the term"""
+        if self._albedo_energy is None:
+            return 0.0, None
+        return self._albedo_energy.evaluate(self.mesh_color.detach())
+
+    def _step_direct_sh(self, d):
+        """the iteration with SH lighting as a fixed kernel sequence: the front launch without shading, one ``sh_shade`` launch, the rasterizer's fit
+        step, the SH adjoint (``sh_shade_b``: two launches; the sum over the views of a per-vertex albedo's adjoint rides in ``fit_pose_project_b``), the albedo smoothness (one), the rest
+        as :meth:`_step_direct`"""
+        from . import fronthalf
+        from . import hip_renderer as hr
+
+        topo = self.mesh.topology
+        mesh = (topo._faces_u32, topo._vf_offsets, topo._vf_corners)
+        self._direct_forward(d)
+        hr.sh_shade(d.posed, *mesh, self.light_sh, self.mesh_color, colors=d.colors, clockwise=topo.clockwise, want_luminosity=False)
+        image, _z, _g = d.rasterizer.render_fit(d.ds, self._observation(), self.scene.sigma, grads=d.grads, out=(d.image, d.z), clear_grads=True,
+                                                loss_out=d.e_data, weights=self._fit_weights())  # fmt: skip
+        # a per-vertex albedo under several views: sh_shade_b leaves the products colors_b E of every view in its scratch and their sum over the views
+        # rides in fit_pose_project_b (its colors_sum), a launch the iteration has anyway
+        views_sum = (hr.sh_products(d.sh_scratch, *d.posed.shape[1::-1], d.albedo_b.shape[-1]), d.albedo_b) if self.vertex_albedo and d.posed.shape[0] > 1 else None
+        hr.sh_shade_b(d.posed, *mesh, self.light_sh, self.mesh_color, colors_b=d.grads["colors_b"], posed_b=d.posed_b, sh_b=d.sh_b,
+                      albedo_b=None if views_sum else d.albedo_b, scratch=d.sh_scratch, clockwise=topo.clockwise, want=(False, False, False))  # fmt: skip
+        energy, g_albedo = None, None
+        if self._albedo_energy is not None:
+            # energy3 = [albedo smoothness, rigid energy + it, data_weight * data + both]: the kernel adds the rigid energy of the front launch, the
+            # momentum update the data term
+            fronthalf.rigid_energy(self.mesh_color, d.albedo_ref, topo, self.albedo_regu, d.g_albedo, d.energy3[:2], d.scratch, data_energy=d.energy[:1])
+            energy, g_albedo = d.energy3[1:], d.g_albedo
+        extra = []
+        if self.update_lights:
+            extra.append(("light_sh", self.light_sh, d.sh_b, self.step_factor_light_sh))
+        if self.update_color:
+            extra.append(("mesh_color", self.mesh_color, d.albedo_b, self.step_factor_albedo) + (() if g_albedo is None else (g_albedo,)))
+        return self._direct_backward_and_update(d, None, (0.5, 0.05, 0.1), self.data_weight, extra, energy=energy, views_sum=views_sum), image
+
+    def _step_device_sh(self):
+        """:meth:`step_device` of a fitter with ``light_sh_init``"""
+        C = int(self.mesh_color.shape[-1])
+        d = self._direct_iteration(C, True, sh=(tuple(self.light_sh.shape), self.vertex_albedo))
+        if d is not None and fronthalf_usable(self.mesh_color, self.light_sh) and self.light_sh.is_contiguous() and self.mesh_color.is_contiguous():
+            return self._step_direct_sh(d)
+        leaves = self._leaves(self._appearance_leaves())
+        e_data, image = self._data_energy()
+        e_rigid, g_rigid = self.rigid_energy.evaluate(self.vertices_leaf.detach())
+        e_albedo, g_albedo = self._albedo_smoothness()
+        g_v, g_q, g_t, g_col, g_sh = torch.autograd.grad(e_data, leaves)
+        g_v, g_col, g_sh, e_data = self._reduce_shared([g_v, g_col, g_sh, e_data.detach()])
+        extra, names = [], []
+        if self.update_lights:
+            extra.append(("light_sh", self.light_sh, g_sh, None, self.step_factor_light_sh, None, 0))
+            names.append("light_sh")
+        if self.update_color:
+            extra.append(("mesh_color", self.mesh_color, g_col, g_albedo, self.step_factor_albedo, None, 0))
+            names.append("mesh_color")
+        energy = e_data + e_rigid + e_albedo if self.shape_basis is None else e_data + e_rigid + e_albedo + self._prior_energy()
+        for name, value in zip(names, self._update_pose_and_shape(g_v, g_q, g_t, g_rigid, (0.5, 0.05, 0.1, 0.5), extra)):
+            setattr(self, name, value)
+        return energy, image.detach()
+
     def step_device(self):
         """One iteration on the device -> (energy, image, difference image) as device tensors.
 
@@ -647,6 +760,8 @@ class MeshRGBFitterWithPose(_PoseFitter):
         storage every step: they are updated in place, so a value kept across iterations (a trajectory, an energy history) must be
         ``.clone()``d by the caller.  The autograd path (CPU tensors, float32, non-manifold meshes) rebinds fresh tensors each step,
         as the reference does.  ``step()`` is safe either way: it converts to a float and NumPy arrays at once."""
+        if self.light_sh is not None:
+            return self._step_device_sh()
         d = None if self.light_directional is None else self._direct_iteration(int(self.mesh_color.numel()), True)
         if d is not None and fronthalf_usable(self.mesh_color, self.light_directional, self.light_ambient):
             return self._step_direct(d)
@@ -697,7 +812,7 @@ class MeshRGBFitterWithPoseMultiFrame(MeshRGBFitterWithPose):
 
     def __init__(self, vertices, faces, euler_init, translation_init, default_color, default_light_directional, default_light_ambient, cregu=2000,
                  cdata=1, inertia=0.97, damping=0.15, update_lights=True, update_color=True, device="cuda", pixel_dtype=torch.float64, group=None,
-                 subdivisions=0, shape_basis=None, coefficient_regu=0.0, sigmas=None):  # fmt: skip
+                 subdivisions=0, shape_basis=None, coefficient_regu=0.0, sigmas=None, light_sh_init=None, vertex_albedo=False, albedo_regu=0.0):  # fmt: skip
         euler_init, translation_init = np.atleast_2d(euler_init), np.atleast_2d(translation_init)
         self.cdata = cdata
         self.n_views_total = max(len(euler_init), len(translation_init))
@@ -709,7 +824,8 @@ class MeshRGBFitterWithPoseMultiFrame(MeshRGBFitterWithPose):
         pick = lambda a: np.broadcast_to(a, (self.n_views_total, a.shape[1]))[self.my_views]
         super().__init__(vertices, faces, pick(euler_init), pick(translation_init), default_color, default_light_directional, default_light_ambient,
                          cregu, inertia, damping, update_lights, update_color, device, pixel_dtype, n_poses=len(self.my_views), subdivisions=subdivisions,
-                         shape_basis=shape_basis, coefficient_regu=coefficient_regu, sigmas=sigmas)  # fmt: skip
+                         shape_basis=shape_basis, coefficient_regu=coefficient_regu, sigmas=sigmas, light_sh_init=light_sh_init,
+                         vertex_albedo=vertex_albedo, albedo_regu=albedo_regu)  # fmt: skip
         self.camera_center = self.object_center + np.array([0, 0, 6]) * self.object_radius
         self._packed = None
 

@@ -286,6 +286,7 @@ class Scene3DDevice:
         self.pixel_dtype = pixel_dtype
         self.mesh = None
         self.light_directional, self.light_ambient = None, 0.0
+        self.light_sh = None  # [9] | [9,S]: spherical-harmonic lighting instead of the directional + ambient pair (set_light_sh)
         self.background_color, self.background_image = None, None
         self._state = None  # (key, DeviceScene, HipRasterizer)
         self.last = {}
@@ -296,6 +297,14 @@ class Scene3DDevice:
     def set_light(self, light_directional, light_ambient):
         self.light_directional = None if light_directional is None else _t(light_directional, self.mesh.device if self.mesh else "cuda")
         self.light_ambient = light_ambient
+        self.light_sh = None
+
+    def set_light_sh(self, sh):
+        """Spherical-harmonic lighting of bands 0 - 2 (``deodr_amd/lighting.py``) in place of the directional + ambient pair: ``sh`` [9] (monochrome)
+        or [9,C] (one column per colour channel), unclamped irradiance ``sum_k sh[k] Y_k(normal)``.  ``lighting.sh_from_directional`` gives the
+        coefficients that approximate a directional + ambient pair."""
+        self.light_sh = _t(sh, self.mesh.device if self.mesh else "cuda")
+        self.light_directional, self.light_ambient = None, 0.0
 
     def set_background_color(self, background_color):
         if self.background_image is not None:
@@ -311,6 +320,10 @@ class Scene3DDevice:
 
     def vertices_luminosity(self, vertices):
         """max(0, -n . l) + ambient per vertex (dr.py:814-822); vertices [..., V, 3]"""
+        if self.light_sh is not None:
+            from . import fronthalf
+
+            return fronthalf.sh_shade(vertices, self.light_sh, None, self.mesh.topology)  # (one column: a luminosity)
         amb = self.light_ambient
         if self.light_directional is None:
             return torch.zeros(vertices.shape[:-1], dtype=vertices.dtype, device=vertices.device) + amb
@@ -388,6 +401,12 @@ class Scene3DDevice:
         assert m is not None, "You need to provide a mesh first."
         ij, depths = camera.project_points(m.vertices)
         n, V = ij.shape[0], m.nb_vertices
+        if self.light_sh is not None and m.uv is None and m.vertices_colors.dim() in (1, 2):
+            from . import fronthalf
+
+            posed = m.vertices if m.vertices.dim() == 3 else m.vertices[None]  # (vertices shared by the views: shaded once)
+            colors = fronthalf.sh_shade(posed, self.light_sh, m.vertices_colors, m.topology)  # one launch: albedo [C] | [V,C] times the irradiance
+            return ij, depths, colors.expand(n, -1, -1), torch.zeros((n, V), dtype=m.dtype, device=m.device), False
         lum = self.vertices_luminosity(m.vertices)
         lum = lum[None].expand(n, -1) if lum.dim() == 1 else lum
         if m.uv is not None:
