@@ -795,6 +795,10 @@ int deodr_hip_render_scene_b(const DeodrHipScene *sc, const void *image, const v
 	{
 		if (!obs || !err_buffer_b)
 			return fail("antialiase_error needs obs and err_buffer_b");
+		// (the staged kernels read the frame of the tiles without silhouette edges from `image`, bwd_fast_tile; refused for the un-staged
+		// family too, which recomputes the colour: one contract for the mode)
+		if (!image)
+			return fail("antialiase_error needs image: the frame deodr_hip_render_scene wrote in this mode");
 	}
 	else if (!image_b && !(image && obs))
 		return fail("image_b == NULL (or, for the residual mode, image and obs)");

@@ -102,6 +102,8 @@ int deodr_hip_render_scene(const DeodrHipScene *scene, void *image, void *z_buff
  * antialiase_error != 0 (`image` = the frame deodr_hip_render_scene wrote in this mode, `obs`, `err_buffer_b`): nb_colors <= 4 runs on
  * the LDS-staged kernels since round 6 (tiles without silhouette edges: image_b = -2 (obs - image) err_buffer_b, H.h:3054-3060; tiles with:
  * a staged sweep over the error buffer, H.h:2200-2368, 2481-2618); more channels, and the deterministic mode, on the un-staged ones.
+ * `image` must be the frame the forward wrote for this scene, sigma and obs (the tiles without silhouette edges read it; nothing recomputes
+ * it): image == NULL is refused before anything is launched, on either kernel family, and the gradient arrays are left untouched.
  * have_forward_state != 0: the workspace still holds the state of the matching deodr_hip_render_scene call (same scene
  * arrays, same sigma) and is reused; 0: the forward state is recomputed first (stateless use, as the reference).  After a
  * deodr_hip_render_scene_fit on the same workspace the state is always recomputed (the fused forward does not keep the

@@ -243,18 +243,25 @@ def build_ref():
 _cache = {}
 
 
-def port(fixed=False):
-    """Our C restatement.  fixed=False reproduces the reference as shipped (defects D1, D2 included);
-    fixed=True repairs them.  The switch is a process-wide global of the library, set on every call here."""
+def _port_handle():
+    """The cached handle of libdeodr_oracle.so (built and loaded on first use); the defect switch is not touched."""
     if "port" not in _cache:
         _cache["port"] = CpuRenderer(build_port(), "deodr_oracle")
-    _cache["port"].lib.deodr_oracle_set_reference_defects(0 if fixed else 1)
     return _cache["port"]
 
 
+def port(fixed=False):
+    """Our C restatement.  fixed=False reproduces the reference as shipped (defects D1, D2 included);
+    fixed=True repairs them.  The switch is a process-wide global of the library, set on every call here."""
+    handle = _port_handle()
+    handle.lib.deodr_oracle_set_reference_defects(0 if fixed else 1)
+    return handle
+
+
 def min_abs_T(reset=True):
-    """Smallest |T| the restatement's adjoint divided by since the last reset (diagnostic: see deodr_oracle_min_abs_T)."""
-    lib = port().lib
+    """Smallest |T| the restatement's adjoint divided by since the last reset (diagnostic: see deodr_oracle_min_abs_T).
+    Reads the cached library and leaves the defect switch as the last port() call set it: a handle from port(fixed=True) stays repaired."""
+    lib = _port_handle().lib
     lib.deodr_oracle_min_abs_T.restype = C.c_double
     lib.deodr_oracle_min_abs_T.argtypes = [C.c_int]
     return float(lib.deodr_oracle_min_abs_T(int(reset)))

@@ -179,6 +179,9 @@ class FakeLib:
         image_b, obs, err_buffer_b = _view(image_b, (n, H, W, Cc), pd), _view(obs, (n, H, W, Cc), pd), _view(err_buffer_b, (n, H, W), pd)
         if antialiase_error and (obs is None or err_buffer_b is None):
             return self._fail("antialiase_error needs obs and err_buffer_b")
+        if antialiase_error and image is None:
+            # the real ABI reads the frame the forward wrote through this pointer (tiles without silhouette edges): NULL is refused
+            return self._fail("antialiase_error needs image: the frame deodr_hip_render_scene wrote in this mode")
         if not antialiase_error and image_b is None and obs is None:
             return self._fail("image_b == NULL (or, for the residual mode, image and obs)")
         self._adjoint(sc, a, pd, sigma, antialiase_error, image_b, obs, err_buffer_b, _view(image, (n, H, W, Cc), pd))
