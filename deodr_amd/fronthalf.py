@@ -60,8 +60,7 @@ class ProjectPointsFunc(torch.autograd.Function):
         _check_cameras(n, extrinsic, intrinsic, distortion)
         ij = torch.empty((n, V, 2), dtype=torch.float64, device=pts.device)
         depths = torch.empty((n, V), dtype=torch.float64, device=pts.device)
-        _launch(lib().deodr_hip_project_points, pts.device, _ptr(pts), _ptr(extrinsic), _ptr(intrinsic), _ptr(distortion), _ptr(ij),
-                _ptr(depths), V, n)  # fmt: skip
+        project_points(pts, extrinsic, intrinsic, distortion, ij, depths)
         ctx.save_for_backward(pts, extrinsic, intrinsic)
         ctx.distortion = distortion
         return ij, depths
@@ -167,6 +166,13 @@ def silhouette_flags(ij, faces_u32, edge_faces_u32, clockwise, out=None):
     flags = torch.empty((n, T, 3), dtype=torch.uint8, device=ij.device) if out is None else out
     _launch(lib().deodr_hip_silhouette_flags, ij.device, _ptr(ij), _ptr(faces_u32), _ptr(edge_faces_u32), _ptr(flags), T, V, n, int(bool(clockwise)))
     return flags
+
+
+def project_points(points, extrinsic, intrinsic, distortion, ij, depths):
+    """points [n,V,3] through the cameras of the views (one matrix per view, :func:`_check_cameras`; distortion [n,5] | None) into ``ij`` [n,V,2] and
+    ``depths`` [n,V], both written in place: the plain launch, no checks, no gradient (:class:`ProjectPointsFunc` is the differentiable one)"""
+    n, V = points.shape[0], points.shape[1]
+    _launch(lib().deodr_hip_project_points, points.device, _ptr(points), _ptr(extrinsic), _ptr(intrinsic), _ptr(distortion), _ptr(ij), _ptr(depths), V, n)
 
 
 def momentum_update(entries, inertia, damping, scratch=None, energy=None, data_energy=None, data_weight=1.0):

@@ -31,41 +31,144 @@ def _quat_from_euler_zyx(euler):
     return scipy.spatial.transform.Rotation.from_euler("zyx", euler).as_quat()
 
 
+# ---- what the fitters share: weights, default camera, raster state, prior, momentum, step() protocol ------------------------------------
+
+
+def _weights_nhw(weights, shape, hint=" (one value per pixel)"):
+    """``weights`` of a ``set_image(s)``: [H,W] (every view) or ``shape`` = [n,H,W], ``>= 0``, not checked for sign -> float64 NumPy [n,H,W]; None stays None"""
+    if weights is None:
+        return None
+    n, height, width = shape
+    w = np.asarray(weights.detach().cpu() if torch.is_tensor(weights) else weights, dtype=np.float64)
+    if w.shape not in ((height, width), (n, height, width)):
+        raise ValueError(f"weights must have shape [{height}, {width}] or [{n}, {height}, {width}]{hint}, not {list(w.shape)}")
+    return np.array(np.broadcast_to(w, (n, height, width)))
+
+
+def _pixel_weights(weights, shape, device, pixel_dtype):
+    """:func:`_weights_nhw` on the device, cast to the pixel dtype at once (the texture and camera fitters, whose frame does not change after ``set_images``;
+    the pose fitters keep float64 and cast lazily, :meth:`_PoseFitter._fit_weights`)"""
+    w = _weights_nhw(weights, shape)
+    return None if w is None else torch.as_tensor(w, device=device).to(pixel_dtype).contiguous()
+
+
+def _kernel_clamp(step_max):
+    """the kernels' convention for the clamp of a step: None or not positive means none"""
+    return step_max if step_max is not None and step_max > 0 else None
+
+
+def _default_camera(height, width, focal, camera_center):
+    """-> (extrinsic [3,4], intrinsic [3,3]) of the camera of a fit: looking down -z from ``camera_center``, focal ``2 * width`` unless given, centred principal point"""
+    focal = 2 * width if focal is None else focal
+    rot = np.diag([1.0, -1.0, -1.0])
+    intrinsic = np.array([[focal, 0, width / 2], [0, focal, height / 2], [0, 0, 1.0]])
+    return np.column_stack((rot, -rot.T.dot(camera_center))), intrinsic
+
+
+def _raster_state(scene, frame, textured, views):
+    """Raster state of a fixed kernel sequence over ``frame`` = (n, H, W, C): -> (scene arrays with ``views`` bound -- no copies, the tensors are used as
+    they are --, rasterizer, the (image, z) output pair in the pixel dtype).  The gradient buffers are the caller's."""
+    if (scene.background_image is None) == (scene.background_color is None):
+        raise BaseException("You need to provide either a background image or background color")
+    n, height, width, nb_colors = frame
+    ds, rasterizer = scene._rasterizer(n, height, width, nb_colors, textured, True)
+    pd, dev = scene.pixel_dtype, views["ij"].device
+    out = (torch.empty((n, height, width, nb_colors), dtype=pd, device=dev), torch.empty((n, height, width), dtype=pd, device=dev))
+    ds.set_views(**views)
+    return ds, rasterizer, out
+
+
+class _GaussianPrior:
+    """``regu * sum((c / sigmas)**2)`` on K coefficients (``sigmas`` [K] positive, None: ones): holds ``1 / sigmas**2``, gives energy and gradient"""
+
+    def __init__(self, sigmas, K, regu, device):
+        sig = np.ones(K) if sigmas is None else np.asarray(sigmas, dtype=np.float64)
+        if sig.shape != (K,) or np.any(sig <= 0):
+            raise ValueError(f"sigmas must be {K} positive numbers")
+        self.regu, self.inv_sigma2 = float(regu), torch.as_tensor(1.0 / sig**2, device=device)
+
+    def energy(self, c):
+        return self.regu * (self.inv_sigma2 * c**2).sum()
+
+    def gradient(self, c=None):
+        return _prior_gradient(self.regu, self.inv_sigma2, c)
+
+
+def _prior_gradient(regu, inv_sigma2, delta=None):
+    """gradient of ``regu * sum(inv_sigma2 * delta**2)``; without ``delta``: the constant it is a multiple of ``delta`` by"""
+    scale = 2.0 * regu * inv_sigma2
+    return scale if delta is None else scale * delta
+
+
+def _squared_difference(image, target):
+    """squared difference per pixel [n,H,W] (what the reference's step returns for display, mesh_fitter.py:313-316)"""
+    return ((image.to(torch.float64) - target) ** 2).sum(dim=-1)
+
+
+def _to_host(energy, image, difference):
+    """the ``step()`` protocol of the reference: a float and NumPy arrays (synchronises)"""
+    return float(energy.detach()), image.to(torch.float64).cpu().numpy(), difference.cpu().numpy()
+
+
+def _step_all_views(fitter):
+    """-> (energy, images [n,H,W,C], squared difference per pixel [n,H,W]) as a float and NumPy arrays (synchronises): ``step()`` of the multi-view fitters"""
+    energy, image = fitter.step_device()
+    image = image.to(torch.float64)
+    return _to_host(energy, image, _squared_difference(image, fitter.mesh_image))
+
+
 class _Momentum:
     """x <- x + s,  s <- (1 - damping) (inertia s + (1 - inertia) clamp(-factor grad, +-step_max))   (mesh_fitter.py:153-190)"""
 
     def __init__(self, inertia, damping):
         self.inertia, self.damping, self.speed = inertia, damping, {}
 
+    def speed_of(self, name, like):
+        """the speed of this name, created as zeros of the shape of ``like`` when it is missing"""
+        if name not in self.speed:
+            self.speed[name] = torch.zeros_like(like, memory_format=torch.contiguous_format)
+        return self.speed[name]
+
+    def rule(self, speed, grad, factor, step_max=None):
+        """-> the new speed (the rule, written once; ``step_max`` None: no clamp -- what 0 means is the caller's convention)"""
+        step = grad * -factor
+        if step_max is not None:
+            step = step.clamp(-step_max, step_max)
+        return (1 - self.damping) * (speed * self.inertia + (1 - self.inertia) * step)
+
     def update_all(self, entries):
-        """entries: [(name, x, grad, grad2 | None, factor, step_max | None, normalize_rows)] -> the new x of every entry.  On float64
-        ROCm tensors: ONE kernel for all of them (in place on contiguous copies of x); otherwise the formulas below, entry by entry."""
+        """The REBINDING update (autograd paths; ``GraphedStep`` finds the state by it).  entries: [(name, x, grad, grad2 | None, factor,
+        step_max | None, normalize_rows)] -> the new x of every entry.  On float64 ROCm tensors: ONE kernel for all of them (in place on contiguous
+        copies of x; ``step_max`` 0 or None: no clamp); otherwise the rule entry by entry (clamped whenever ``step_max`` is not None)."""
         from . import fronthalf
 
         if all(fronthalf.usable(e[1], e[2]) and (e[3] is None or fronthalf.usable(e[3])) for e in entries) and len(entries) <= 8:
-            rows = []
-            for name, x, grad, grad2, factor, step_max, normalize_rows in entries:
-                if name not in self.speed:
-                    self.speed[name] = torch.zeros_like(x, memory_format=torch.contiguous_format)
-                rows.append((x.contiguous().clone() if not x.is_contiguous() else x.clone(), self.speed[name], grad.contiguous(), None if grad2 is None else grad2.contiguous(),
-                             factor, step_max, normalize_rows))  # fmt: skip
+            rows = [(x.contiguous().clone() if not x.is_contiguous() else x.clone(), self.speed_of(name, x), grad.contiguous(), None if grad2 is None else grad2.contiguous(),
+                     factor, step_max, normalize_rows) for name, x, grad, grad2, factor, step_max, normalize_rows in entries]  # fmt: skip
             fronthalf.momentum_update(rows, self.inertia, self.damping)
             return [r[0] for r in rows]
         out = []
         for name, x, grad, grad2, factor, step_max, normalize_rows in entries:
-            new = self.update(name, x, grad if grad2 is None else grad + grad2, factor, step_max)
+            self.speed[name] = self.rule(self.speed_of(name, x), grad if grad2 is None else grad + grad2, factor, step_max)
+            new = x + self.speed[name]
             out.append(new / new.norm(dim=-1, keepdim=True) if normalize_rows else new)
         return out
 
-    def update(self, name, x, grad, factor, step_max=None):
-        step = -grad * factor
-        if step_max is not None:
-            step = step.clamp(-step_max, step_max)
-        s = self.speed.get(name)
-        s = torch.zeros_like(x) if s is None else s
-        s = (1 - self.damping) * (s * self.inertia + (1 - self.inertia) * step)
-        self.speed[name] = s
-        return x + s
+    def update_in_place(self, entries, **energy):
+        """The IN-PLACE update (fixed kernel sequences: x and speed keep their storage).  entries: [(name, x, grad, grad2 | None, factor, step_max | None,
+        normalize_rows, ...)] and ``energy`` as :func:`fronthalf.momentum_update` takes them: on float64 ROCm tensors that one launch; elsewhere the
+        rule as torch ops, with the kernel's convention for the clamp (``step_max`` None or not positive: none)."""
+        from . import fronthalf
+
+        rows = [(x, self.speed_of(name, x)) + tuple(rest) for name, x, *rest in entries]
+        if fronthalf.usable(*(r[0] for r in rows)):
+            return fronthalf.momentum_update(rows, self.inertia, self.damping, **energy)
+        assert not energy and all(len(r) == 7 for r in rows)
+        for x, speed, grad, grad2, factor, step_max, normalize_rows in rows:
+            speed.copy_(self.rule(speed, grad if grad2 is None else grad + grad2, factor, _kernel_clamp(step_max)))
+            x += speed
+            if normalize_rows:
+                x /= x.norm(dim=-1, keepdim=True)
 
 
 class GraphedStep:
@@ -178,11 +281,8 @@ class _DirectIteration:
         self.pose_out = self.flat[head + 1 + 3 * V :]  # mean of vertices_b [3], quaternion adjoints [n,4], translation adjoints [n,3]
         self.shared = self.flat[: head + 1 + 3 * V + 3]
         self.g_rigid, self.energy, self.vmean = z(V, 3), z(2), z(3)  # energy: rigid, data_weight * data + rigid
-        sc = f.scene
-        if (sc.background_image is None) == (sc.background_color is None):
-            raise BaseException("You need to provide either a background image or background color")
-        self.ds, self.rasterizer = sc._rasterizer(n, cam.height, cam.width, C, False, True)
-        self.ds.set_views(ij=self.ij, depths=self.depths, colors=self.colors, shade=self.shade, edgeflags=self.flags)  # (used as they are)
+        self.views = dict(ij=self.ij, depths=self.depths, colors=self.colors, shade=self.shade, edgeflags=self.flags)
+        self.ds, self.rasterizer, (self.image, self.z) = _raster_state(f.scene, (n, cam.height, cam.width, C), False, self.views)
         assert self.ds.ij.data_ptr() == self.ij.data_ptr() and self.ds.colors.data_ptr() == self.colors.data_ptr()
         sizes = [("ij_b", (n, V, 2)), ("colors_b", (n, V, C)), ("shade_b", (n, V)), ("uv_b", tuple(self.ds.uv.shape))]
         self.grads_flat = z(sum(int(np.prod(shape)) for _, shape in sizes))  # one buffer: one fill clears all of them
@@ -190,8 +290,6 @@ class _DirectIteration:
         for name, shape in sizes:
             self.grads[name] = self.grads_flat[at : at + int(np.prod(shape))].view(shape)
             at += int(np.prod(shape))
-        pd = sc.pixel_dtype
-        self.image, self.z = torch.empty((n, cam.height, cam.width, C), dtype=pd, device=dev), torch.empty((n, cam.height, cam.width), dtype=pd, device=dev)
         self.bound = self.depth = self.diff = self.image_b = None
 
     def sync(self, fitter):
@@ -253,12 +351,8 @@ class _PoseFitter:
             if basis.mean is not None:
                 raise ValueError("shape_basis: the `vertices` argument is the mean; give a LinearBasis without one")
             self.shape_basis = basis.with_mean(self.vertices_init)
-            K = self.shape_basis.K
             self.coefficient_regu = float(coefficient_regu)
-            sig = np.ones(K) if sigmas is None else np.asarray(sigmas, dtype=np.float64)
-            if sig.shape != (K,) or np.any(sig <= 0):
-                raise ValueError(f"sigmas must be {K} positive numbers")
-            self._inv_sigma2 = torch.as_tensor(1.0 / sig**2, device=self.device)
+            self._prior = _GaussianPrior(sigmas, self.shape_basis.K, self.coefficient_regu, self.device)
         q0 = np.asarray([_quat_from_euler_zyx(e) for e in np.atleast_2d(euler_init)])
         t0 = np.atleast_2d(np.asarray(translation_init, dtype=np.float64))
         self.transform_quaternion_init = torch.as_tensor(np.broadcast_to(q0, (n_poses, 4)).copy(), device=self.device)
@@ -277,11 +371,7 @@ class _PoseFitter:
         self._direct_state = None
 
     def _camera(self, height, width, focal, distortion, camera_center):
-        focal = 2 * width if focal is None else focal
-        rot = np.diag([1.0, -1.0, -1.0])
-        intrinsic = np.array([[focal, 0, width / 2], [0, focal, height / 2], [0, 0, 1.0]])
-        extrinsic = np.column_stack((rot, -rot.T.dot(camera_center)))
-        return DeviceCamera(extrinsic, intrinsic, height, width, distortion, self.device)
+        return DeviceCamera(*_default_camera(height, width, focal, camera_center), height, width, distortion, self.device)
 
     def _transformed(self, vertices):
         """centred vertices moved by every pose: [n_poses, V, 3] (the centring is part of the graph: the data gradient comes out
@@ -310,34 +400,28 @@ class _PoseFitter:
 
     def coefficients_gradient(self, g_vertices):
         """-> (basis adjoint of a vertex gradient [V,3], gradient of the prior ``coefficient_regu sum((c / sigmas)**2)``), both [K]"""
-        return self.shape_basis.apply_b(g_vertices.detach()), 2.0 * self.coefficient_regu * self._inv_sigma2 * self.coefficients
+        return self.shape_basis.apply_b(g_vertices.detach()), self._prior.gradient(self.coefficients)
 
-    def _prior_energy(self):
-        return self.coefficient_regu * (self._inv_sigma2 * self.coefficients**2).sum()
+    def _energy_with_prior(self, energy):
+        """``energy`` + the coefficient prior of a fit with ``shape_basis`` (of the parameters the gradients were taken at)"""
+        return energy if self.shape_basis is None else energy + self._prior.energy(self.coefficients)
 
     def _update_pose_and_shape(self, g_vertices, g_quaternion, g_translation, grad_rigidity, step_max, extra=()):
-        if self.shape_basis is not None:
-            return self._update_pose_and_coefficients(g_vertices, g_quaternion, g_translation, grad_rigidity, step_max, extra)
+        """the rebinding momentum update of the shape (the vertices; with ``shape_basis`` the coefficients: the total vertex gradient goes through the
+        basis adjoint), the poses and the ``extra`` entries -> the new values of the extras"""
+        if self.shape_basis is None:
+            shape = ("vertices", self.vertices, g_vertices, grad_rigidity, self.step_factor_vertices, step_max[0], 0)
+        else:
+            g_c, g_prior = self.coefficients_gradient(g_vertices + grad_rigidity)
+            shape = ("coefficients", self.coefficients, g_c, g_prior, self.step_factor_coefficients, step_max[3] if len(step_max) > 3 else None, 0)
         entries = [
-            ("vertices", self.vertices, g_vertices, grad_rigidity, self.step_factor_vertices, step_max[0], 0),
+            shape,
             ("quaternion", self.transform_quaternion, g_quaternion, None, self.step_factor_quaternion, step_max[1], 4),  # renormalised per view
             ("translation", self.transform_translation, g_translation, None, self.step_factor_translation, step_max[2], 0),
         ] + list(extra)
         new = self.momentum.update_all(entries)
-        self.vertices, self.transform_quaternion, self.transform_translation = new[:3]
-        self.iter += 1
-        return new[3:]
-
-    def _update_pose_and_coefficients(self, g_vertices, g_quaternion, g_translation, grad_rigidity, step_max, extra=()):
-        """the update of a fit with ``shape_basis``: the total vertex gradient goes through the basis adjoint, the coefficients take the momentum step"""
-        g_c, g_prior = self.coefficients_gradient(g_vertices + grad_rigidity)
-        entries = [
-            ("coefficients", self.coefficients, g_c, g_prior, self.step_factor_coefficients, step_max[3] if len(step_max) > 3 else None, 0),
-            ("quaternion", self.transform_quaternion, g_quaternion, None, self.step_factor_quaternion, step_max[1], 4),  # renormalised per view
-            ("translation", self.transform_translation, g_translation, None, self.step_factor_translation, step_max[2], 0),
-        ] + list(extra)
-        new = self.momentum.update_all(entries)
-        self.coefficients, self.transform_quaternion, self.transform_translation = new[:3]
+        setattr(self, shape[0], new[0])
+        self.transform_quaternion, self.transform_translation = new[1:3]
         self.iter += 1
         return new[3:]
 
@@ -372,7 +456,7 @@ class _PoseFitter:
         from . import fronthalf
 
         topo = self.mesh.topology
-        d.ds.set_views(ij=d.ij, depths=d.depths, colors=d.colors, shade=d.shade, edgeflags=d.flags)  # (no copies; another render may have rebound them)
+        d.ds.set_views(**d.views)  # (no copies; another render may have rebound them)
         fronthalf.fit_pose_project(self.vertices, d.vmean, self.transform_quaternion, self.transform_translation, self.camera, d.posed, d.ij, d.depths,
                                    depth_colors, depth_scale)  # fmt: skip
         light, ambient, color = shade if shade is not None else (None, None, None)
@@ -390,20 +474,13 @@ class _PoseFitter:
         fronthalf.fit_pose_project_b(self.vertices, self.transform_quaternion, d.posed, self.camera, d.posed_b, d.grads["ij_b"], depths_b, d.vertices_b,
                                      d.pose_out, d.scratch, depths_b_scale, **extra_sum)  # fmt: skip
         self._allreduce_shared(d.shared)
-        def speed(name, x):
-            if name not in self.momentum.speed:
-                self.momentum.speed[name] = torch.zeros_like(x)
-            return self.momentum.speed[name]
-
         entries = [
-            (self.vertices, speed("vertices", self.vertices), d.vertices_b, d.g_rigid, self.step_factor_vertices, step_max[0], 0, data_weight, d.pose_out[:3], d.vmean),
-            (self.transform_quaternion, speed("quaternion", self.transform_quaternion), d.pose_out[3 : 3 + 4 * n], None, self.step_factor_quaternion,
-             step_max[1], 4, data_weight, None, None),
-            (self.transform_translation, speed("translation", self.transform_translation), d.pose_out[3 + 4 * n :], None, self.step_factor_translation,
-             step_max[2], 0, data_weight, None, None),
-        ] + [(x, speed(name, x), g, g2[0] if g2 else None, factor, None, 0, data_weight, None, None) for name, x, g, factor, *g2 in extra]  # fmt: skip
+            ("vertices", self.vertices, d.vertices_b, d.g_rigid, self.step_factor_vertices, step_max[0], 0, data_weight, d.pose_out[:3], d.vmean),
+            ("quaternion", self.transform_quaternion, d.pose_out[3 : 3 + 4 * n], None, self.step_factor_quaternion, step_max[1], 4, data_weight, None, None),
+            ("translation", self.transform_translation, d.pose_out[3 + 4 * n :], None, self.step_factor_translation, step_max[2], 0, data_weight, None, None),
+        ] + [(name, x, g, g2, factor, None, 0, data_weight, None, None) for name, x, g, g2, factor in extra]  # fmt: skip
         energy = d.energy if energy is None else energy  # ([what the data energy is added to, the sum]; an extra entry may carry a second gradient)
-        fronthalf.momentum_update(entries, self.inertia, self.damping, scratch=d.scratch, energy=energy, data_energy=d.e_data, data_weight=data_weight)
+        self.momentum.update_in_place(entries, scratch=d.scratch, energy=energy, data_energy=d.e_data, data_weight=data_weight)
         self.iter += 1
         return energy[1]
 
@@ -412,16 +489,10 @@ class _PoseFitter:
 
     weights = None  # per-pixel weights of the data term [n,H,W] (float64, this fitter's device), or None: set_image(s)(..., weights=...)
 
-    def _set_weights(self, weights, n, height, width):
-        """``weights`` of ``set_image`` / ``set_images``: [H,W] (all views) or [n,H,W], ``>= 0``, not checked for sign; None: an unweighted fit"""
+    def _set_weights(self, w):
+        """the :func:`_weights_nhw` of ``set_image`` / ``set_images`` (None: an unweighted fit), kept in float64: :meth:`_fit_weights` casts when a step needs them"""
         self._weights_key = None
-        if weights is None:
-            self.weights = None
-            return
-        w = np.asarray(weights.detach().cpu() if torch.is_tensor(weights) else weights, dtype=np.float64)
-        if w.shape not in ((height, width), (n, height, width)):
-            raise ValueError(f"weights must have shape [{height}, {width}] or [{n}, {height}, {width}] (one value per pixel), not {list(w.shape)}")
-        self.weights = torch.as_tensor(np.array(np.broadcast_to(w, (n, height, width))), device=self.device)
+        self.weights = None if w is None else torch.as_tensor(w, device=self.device)
 
     def _fit_weights(self):
         """the weights as the rasterizer's fit step takes them: [n,H,W] in its pixel dtype, converted once (None: no weights)"""
@@ -453,7 +524,7 @@ class MeshDepthFitter(_PoseFitter):
         returned no depth (a hole), so that whatever ``mesh_image`` holds there does not pull on the mesh.  Both the direct path (hence
         ``GraphedStep``) and the autograd path use them; the difference image a step returns for display stays un-weighted."""
         assert np.ndim(mesh_image) == 2
-        self._set_weights(weights, 1, *np.shape(mesh_image))
+        self._set_weights(_weights_nhw(weights, (1, *np.shape(mesh_image))))
         self.height, self.width = mesh_image.shape
         self.mesh_image = torch.as_tensor(np.asarray(mesh_image, dtype=np.float64), device=self.device)
         self.camera = self._camera(self.height, self.width, focal, distortion, self.camera_center)
@@ -505,14 +576,13 @@ class MeshDepthFitter(_PoseFitter):
         leaves = self._leaves()
         e_data, e_rigid, g_rigid, depth, diff_image = self.energy()
         g_v, g_q, g_t = torch.autograd.grad(e_data, leaves)
-        energy = e_data + e_rigid if self.shape_basis is None else e_data + e_rigid + self._prior_energy()  # (of the parameters the gradients were taken at)
+        energy = self._energy_with_prior(e_data + e_rigid)
         self._update_pose_and_shape(g_v, g_q, g_t, g_rigid, (1, 0.1, 0.1, 1))
         return energy, depth.detach(), diff_image.detach()
 
     def step(self):
         """-> (energy, synthetic depth [H,W], squared difference [H,W]) as a float and NumPy arrays, like the reference"""
-        energy, depth, diff_image = self.step_device()
-        return float(energy.detach()), depth.cpu().numpy(), diff_image.cpu().numpy()
+        return _to_host(*self.step_device())
 
 
 class MeshDepthFitterEnergy(torch.nn.Module):
@@ -619,7 +689,7 @@ class MeshRGBFitterWithPose(_PoseFitter):
         """``weights`` [H,W], ``>= 0`` (or None): the data term becomes ``sum(weights[..., None] * (image - mesh_image)**2)`` -- a foreground
         mask, an occluder to ignore, a confidence map.  Used by the direct path (hence ``GraphedStep``) and by the autograd path alike."""
         assert np.ndim(mesh_image) == 3
-        self._set_weights(weights, 1, *np.shape(mesh_image)[:2])
+        self._set_weights(_weights_nhw(weights, (1, *np.shape(mesh_image)[:2])))
         self.height, self.width = mesh_image.shape[:2]
         self.mesh_image = torch.as_tensor(np.asarray(mesh_image, dtype=np.float64), device=self.device)[None]
         self.camera = self._camera(self.height, self.width, focal, distortion, self.camera_center)
@@ -666,30 +736,10 @@ class MeshRGBFitterWithPose(_PoseFitter):
 
     def diff_image(self, image):
         """squared difference per pixel [n,H,W] (what the reference's step returns for display, mesh_fitter.py:313-316)"""
-        return ((image.to(torch.float64) - self.mesh_image) ** 2).sum(dim=-1)
+        return _squared_difference(image, self.mesh_image)
 
     def _reduce_shared(self, grads):
         return grads  # single process, every view local
-
-    def _step_direct(self, d):
-        from . import fronthalf
-
-        topo = self.mesh.topology
-        self._direct_forward(d, shade=(self.light_directional, self.light_ambient, self.mesh_color))
-        obs = self._observation()
-        # image, gradients AND the data energy from the rasterizer's four launches (the residual of every pixel is in the tile walkers'
-        # registers; a separate pass over the 8-view frame was 73 us of a 350 us iteration)
-        image, _z, _g = d.rasterizer.render_fit(d.ds, obs, self.scene.sigma, grads=d.grads, out=(d.image, d.z), clear_grads=True, loss_out=d.e_data,
-                                                weights=self._fit_weights())  # fmt: skip
-        fronthalf.vertex_shade_b(d.posed, topo, self.light_directional, self.light_ambient, self.mesh_color, None, d.grads["colors_b"], d.posed_b, d.shade_out,
-                                 d.scratch)  # fmt: skip
-        extra = []
-        if self.update_lights:
-            extra += [("light_directional", self.light_directional, d.shade_out[:3], 0.0001), ("light_ambient", self.light_ambient, d.shade_out[3:4], 0.0001)]
-        if self.update_color:
-            extra.append(("mesh_color", self.mesh_color, d.shade_out[4:], 0.00001))
-        energy = self._direct_backward_and_update(d, None, (0.5, 0.05, 0.1), self.data_weight, extra)
-        return energy, image
 
     def _albedo_smoothness(self):
         """-> (0.5 albedo_regu sum_c a_c^T (L^T L) a_c, its gradient [V,3]) or (0, None) without the term"""
@@ -697,97 +747,97 @@ class MeshRGBFitterWithPose(_PoseFitter):
             return 0.0, None
         return self._albedo_energy.evaluate(self.mesh_color.detach())
 
-    def _step_direct_sh(self, d):
-        """the iteration with SH lighting as a fixed kernel sequence: the front launch without shading, one ``sh_shade`` launch, the rasterizer's fit
-        step, the SH adjoint (``sh_shade_b``: two launches; the sum over the views of a per-vertex albedo's adjoint rides in ``fit_pose_project_b``), the albedo smoothness (one), the rest
-        as :meth:`_step_direct`"""
+    # The two lighting models -- the directional + ambient pair with one colour, and spherical harmonics (``light_sh``) with one colour or a per-vertex
+    # albedo -- differ in four places: the leaves (:meth:`_appearance_leaves`), the appearance parameters a step updates with their step factors
+    # (:meth:`_appearance_updates`), the shading launch and its adjoint on the direct path (:meth:`_step_direct`, :meth:`_direct_shade_b`), and the
+    # albedo-smoothness energy, which only the second has.  One autograd step and one direct step serve both.
+
+    def _appearance_updates(self, g_color, g_lights, g_albedo=None):
+        """-> [(name, parameter, gradient, second gradient | None, step factor)] of what ``update_lights`` / ``update_color`` let move"""
+        updates = []
+        if self.update_lights and self.light_sh is not None:
+            updates.append(("light_sh", self.light_sh, g_lights[0], None, self.step_factor_light_sh))
+        elif self.update_lights:
+            updates += [("light_directional", self.light_directional, g_lights[0], None, 0.0001), ("light_ambient", self.light_ambient, g_lights[1], None, 0.0001)]
+        if self.update_color:
+            updates.append(("mesh_color", self.mesh_color, g_color, g_albedo, self.step_factor_albedo if self.light_sh is not None else 0.00001))
+        return updates
+
+    def _direct_shade_b(self, d):
+        """adjoint of the shading -> (appearance updates, [what the data energy is added to, the sum] | None, views_sum | None)"""
         from . import fronthalf
         from . import hip_renderer as hr
 
         topo = self.mesh.topology
-        mesh = (topo._faces_u32, topo._vf_offsets, topo._vf_corners)
-        self._direct_forward(d)
-        hr.sh_shade(d.posed, *mesh, self.light_sh, self.mesh_color, colors=d.colors, clockwise=topo.clockwise, want_luminosity=False)
-        image, _z, _g = d.rasterizer.render_fit(d.ds, self._observation(), self.scene.sigma, grads=d.grads, out=(d.image, d.z), clear_grads=True,
-                                                loss_out=d.e_data, weights=self._fit_weights())  # fmt: skip
-        # a per-vertex albedo under several views: sh_shade_b leaves the products colors_b E of every view in its scratch and their sum over the views
-        # rides in fit_pose_project_b (its colors_sum), a launch the iteration has anyway
+        if self.light_sh is None:
+            fronthalf.vertex_shade_b(d.posed, topo, self.light_directional, self.light_ambient, self.mesh_color, None, d.grads["colors_b"], d.posed_b,
+                                     d.shade_out, d.scratch)  # fmt: skip
+            return self._appearance_updates(d.shade_out[4:], (d.shade_out[:3], d.shade_out[3:4])), None, None
+        # SH: two launches.  A per-vertex albedo under several views: sh_shade_b leaves the products colors_b E of every view in its scratch and their sum
+        # over the views rides in fit_pose_project_b (its colors_sum), a launch the iteration has anyway
         views_sum = (hr.sh_products(d.sh_scratch, *d.posed.shape[1::-1], d.albedo_b.shape[-1]), d.albedo_b) if self.vertex_albedo and d.posed.shape[0] > 1 else None
-        hr.sh_shade_b(d.posed, *mesh, self.light_sh, self.mesh_color, colors_b=d.grads["colors_b"], posed_b=d.posed_b, sh_b=d.sh_b,
-                      albedo_b=None if views_sum else d.albedo_b, scratch=d.sh_scratch, clockwise=topo.clockwise, want=(False, False, False))  # fmt: skip
+        hr.sh_shade_b(d.posed, topo._faces_u32, topo._vf_offsets, topo._vf_corners, self.light_sh, self.mesh_color, colors_b=d.grads["colors_b"], posed_b=d.posed_b,
+                      sh_b=d.sh_b, albedo_b=None if views_sum else d.albedo_b, scratch=d.sh_scratch, clockwise=topo.clockwise, want=(False, False, False))  # fmt: skip
         energy, g_albedo = None, None
         if self._albedo_energy is not None:
-            # energy3 = [albedo smoothness, rigid energy + it, data_weight * data + both]: the kernel adds the rigid energy of the front launch, the
-            # momentum update the data term
+            # the albedo smoothness, one launch.  energy3 = [albedo smoothness, rigid energy + it, data_weight * data + both]: the kernel adds the rigid
+            # energy of the front launch, the momentum update the data term
             fronthalf.rigid_energy(self.mesh_color, d.albedo_ref, topo, self.albedo_regu, d.g_albedo, d.energy3[:2], d.scratch, data_energy=d.energy[:1])
             energy, g_albedo = d.energy3[1:], d.g_albedo
-        extra = []
-        if self.update_lights:
-            extra.append(("light_sh", self.light_sh, d.sh_b, self.step_factor_light_sh))
-        if self.update_color:
-            extra.append(("mesh_color", self.mesh_color, d.albedo_b, self.step_factor_albedo) + (() if g_albedo is None else (g_albedo,)))
-        return self._direct_backward_and_update(d, None, (0.5, 0.05, 0.1), self.data_weight, extra, energy=energy, views_sum=views_sum), image
+        return self._appearance_updates(d.albedo_b, (d.sh_b,), g_albedo), energy, views_sum
 
-    def _step_device_sh(self):
-        """:meth:`step_device` of a fitter with ``light_sh_init``"""
-        C = int(self.mesh_color.shape[-1])
-        d = self._direct_iteration(C, True, sh=(tuple(self.light_sh.shape), self.vertex_albedo))
-        if d is not None and fronthalf_usable(self.mesh_color, self.light_sh) and self.light_sh.is_contiguous() and self.mesh_color.is_contiguous():
-            return self._step_direct_sh(d)
+    def _step_direct(self, d):
+        """the iteration as a fixed kernel sequence: the front launch (with the directional shading, or followed by the SH shading), the rasterizer's fit
+        step, the adjoint of the shading, the adjoint of pose + projection and one momentum update of every parameter"""
+        if self.light_sh is None:  # (the directional shading rides in the front launch)
+            self._direct_forward(d, shade=(self.light_directional, self.light_ambient, self.mesh_color))
+        else:
+            from . import hip_renderer as hr
+
+            topo = self.mesh.topology
+            self._direct_forward(d)
+            hr.sh_shade(d.posed, topo._faces_u32, topo._vf_offsets, topo._vf_corners, self.light_sh, self.mesh_color, colors=d.colors, clockwise=topo.clockwise,
+                        want_luminosity=False)  # fmt: skip
+        # image, gradients AND the data energy from the rasterizer's four launches (the residual of every pixel is in the tile walkers'
+        # registers; a separate pass over the 8-view frame was 73 us of a 350 us iteration)
+        image, _z, _g = d.rasterizer.render_fit(d.ds, self._observation(), self.scene.sigma, grads=d.grads, out=(d.image, d.z), clear_grads=True,
+                                                loss_out=d.e_data, weights=self._fit_weights())  # fmt: skip
+        updates, energy, views_sum = self._direct_shade_b(d)
+        return self._direct_backward_and_update(d, None, (0.5, 0.05, 0.1), self.data_weight, updates, energy=energy, views_sum=views_sum), image
+
+    def _step_autograd(self):
+        sh = self.light_sh is not None
         leaves = self._leaves(self._appearance_leaves())
         e_data, image = self._data_energy()
         e_rigid, g_rigid = self.rigid_energy.evaluate(self.vertices_leaf.detach())
-        e_albedo, g_albedo = self._albedo_smoothness()
-        g_v, g_q, g_t, g_col, g_sh = torch.autograd.grad(e_data, leaves)
-        g_v, g_col, g_sh, e_data = self._reduce_shared([g_v, g_col, g_sh, e_data.detach()])
-        extra, names = [], []
-        if self.update_lights:
-            extra.append(("light_sh", self.light_sh, g_sh, None, self.step_factor_light_sh, None, 0))
-            names.append("light_sh")
-        if self.update_color:
-            extra.append(("mesh_color", self.mesh_color, g_col, g_albedo, self.step_factor_albedo, None, 0))
-            names.append("mesh_color")
-        energy = e_data + e_rigid + e_albedo if self.shape_basis is None else e_data + e_rigid + e_albedo + self._prior_energy()
-        for name, value in zip(names, self._update_pose_and_shape(g_v, g_q, g_t, g_rigid, (0.5, 0.05, 0.1, 0.5), extra)):
-            setattr(self, name, value)
+        e_albedo, g_albedo = self._albedo_smoothness() if sh else (None, None)
+        g_v, g_q, g_t, g_col, *g_lights = torch.autograd.grad(e_data, leaves)
+        g_v, g_col, *g_lights, e_data = self._reduce_shared([g_v, g_col, *g_lights, e_data.detach()])
+        updates = self._appearance_updates(g_col, g_lights, g_albedo)
+        energy = self._energy_with_prior(e_data + e_rigid + e_albedo if sh else e_data + e_rigid)
+        flat = lambda t: t.reshape(1) if t.dim() == 0 else t  # (``light_ambient`` is a scalar tensor: one row of one element for the update, () again after it)
+        new = self._update_pose_and_shape(g_v, g_q, g_t, g_rigid, (0.5, 0.05, 0.1, 0.5),
+                                          [(name, flat(x), flat(g), g2, factor, None, 0) for name, x, g, g2, factor in updates])  # fmt: skip
+        for (name, x, *_), value in zip(updates, new):
+            setattr(self, name, value.reshape(()) if x.dim() == 0 else value)
         return energy, image.detach()
 
     def step_device(self):
-        """One iteration on the device -> (energy, image, difference image) as device tensors.
-
-        OUTPUT LIFETIME: on the direct path (float64 ROCm tensors, manifold mesh: a fixed kernel sequence over persistent buffers,
-        `_DirectIteration`) the returned tensors -- and ``self.vertices``, the pose, light and colour parameters -- are the SAME
-        storage every step: they are updated in place, so a value kept across iterations (a trajectory, an energy history) must be
-        ``.clone()``d by the caller.  The autograd path (CPU tensors, float32, non-manifold meshes) rebinds fresh tensors each step,
-        as the reference does.  ``step()`` is safe either way: it converts to a float and NumPy arrays at once."""
+        """One iteration on the device -> (energy, image [n,H,W,C]) as device tensors.  OUTPUT LIFETIME: as :meth:`MeshDepthFitter.step_device` -- on the
+        direct path the returned tensors and every parameter, light and colour included, are the same storage every step: ``.clone()`` what is kept."""
         if self.light_sh is not None:
-            return self._step_device_sh()
-        d = None if self.light_directional is None else self._direct_iteration(int(self.mesh_color.numel()), True)
-        if d is not None and fronthalf_usable(self.mesh_color, self.light_directional, self.light_ambient):
-            return self._step_direct(d)
-        leaves = self._leaves(self._appearance_leaves())
-        e_data, image = self._data_energy()
-        e_rigid, g_rigid = self.rigid_energy.evaluate(self.vertices_leaf.detach())
-        g_v, g_q, g_t, g_col, g_dir, g_amb = torch.autograd.grad(e_data, leaves)
-        g_v, g_col, g_dir, g_amb, e_data = self._reduce_shared([g_v, g_col, g_dir, g_amb, e_data.detach()])
-        extra, names = [], []
-        if self.update_lights:
-            extra += [("light_directional", self.light_directional, g_dir, None, 0.0001, None, 0),
-                      ("light_ambient", self.light_ambient.reshape(1), g_amb.reshape(1), None, 0.0001, None, 0)]  # fmt: skip
-            names += ["light_directional", "light_ambient"]
-        if self.update_color:
-            extra.append(("mesh_color", self.mesh_color, g_col, None, 0.00001, None, 0))
-            names.append("mesh_color")
-        energy = e_data + e_rigid if self.shape_basis is None else e_data + e_rigid + self._prior_energy()  # (of the parameters the gradients were taken at)
-        for name, value in zip(names, self._update_pose_and_shape(g_v, g_q, g_t, g_rigid, (0.5, 0.05, 0.1, 0.5), extra)):
-            setattr(self, name, value.reshape(()) if name == "light_ambient" else value)
-        return energy, image.detach()
+            d = self._direct_iteration(int(self.mesh_color.shape[-1]), True, sh=(tuple(self.light_sh.shape), self.vertex_albedo))
+            direct = d is not None and fronthalf_usable(self.mesh_color, self.light_sh) and self.light_sh.is_contiguous() and self.mesh_color.is_contiguous()
+        else:
+            d = None if self.light_directional is None else self._direct_iteration(int(self.mesh_color.numel()), True)
+            direct = d is not None and fronthalf_usable(self.mesh_color, self.light_directional, self.light_ambient)
+        return self._step_direct(d) if direct else self._step_autograd()
 
     def step(self):
         """-> (energy, image [H,W,C], squared difference [H,W]) as a float and NumPy arrays, the reference's protocol (synchronises;
         a loop that never needs them on the host calls step_device -- or a GraphedStep of it -- instead)"""
         energy, image = self.step_device()
-        return float(energy.detach()), image[0].to(torch.float64).cpu().numpy(), self.diff_image(image)[0].cpu().numpy()
+        return _to_host(energy, image[0], self.diff_image(image)[0])
 
 
 class MeshRGBFitterWithPoseMultiFrame(MeshRGBFitterWithPose):
@@ -839,12 +889,8 @@ class MeshRGBFitterWithPoseMultiFrame(MeshRGBFitterWithPose):
         of ALL views as well -- sharded with the images (``distributed.shard_views``) --, ``>= 0``: the data term of view v becomes
         ``sum(weights[v][..., None] * (image_v - mesh_images[v])**2)``; a view of weight 0 everywhere does not pull on the shared parameters."""
         imgs = np.stack([np.asarray(mesh_images[i], dtype=np.float64) for i in self.my_views])
-        if weights is not None:
-            w = np.asarray(weights.detach().cpu() if torch.is_tensor(weights) else weights, dtype=np.float64)
-            if w.shape not in (imgs.shape[1:3], (self.n_views_total,) + imgs.shape[1:3]):
-                raise ValueError(f"weights must have shape {list(imgs.shape[1:3])} or {[self.n_views_total] + list(imgs.shape[1:3])}, not {list(w.shape)}")
-            weights = w if w.ndim == 2 else w[self.my_views]
-        self._set_weights(weights, len(self.my_views), *imgs.shape[1:3])
+        w = _weights_nhw(weights, (self.n_views_total, *imgs.shape[1:3]), hint="")
+        self._set_weights(None if w is None else w[self.my_views])
         self.height, self.width = imgs.shape[1:3]
         self.mesh_image = torch.as_tensor(imgs, device=self.device)
         cam = self._camera(self.height, self.width, focal, distortion, self.camera_center)
@@ -868,9 +914,7 @@ class MeshRGBFitterWithPoseMultiFrame(MeshRGBFitterWithPose):
 
             dist.all_reduce(shared, op=dist.ReduceOp.SUM, group=self.group)  # (the shared gradients are contiguous by construction)
 
-    def step(self):
-        energy, image = self.step_device()
-        return float(energy.detach()), image.to(torch.float64).cpu().numpy(), self.diff_image(image).cpu().numpy()
+    step = _step_all_views
 
 
 # ---- texture estimation -----------------------------------------------------------------------------------------------------------------
@@ -892,11 +936,9 @@ def texture_smoothness_torch(texture, gradient, weight):
 
 
 def texture_step_torch(texture, speed, gradient, factor, step_max=None, inertia=0.0, damping=0.0, clamp=None):
-    """``deodr_hip_texture_step`` as torch ops (:meth:`_Momentum.update` plus the clamp), in place on ``texture`` and ``speed``; float64 arithmetic"""
-    step = -factor * gradient.to(torch.float64)
-    if step_max is not None and step_max > 0:
-        step = step.clamp(-step_max, step_max)
-    s = (1 - damping) * (inertia * speed.to(torch.float64) + (1 - inertia) * step)
+    """``deodr_hip_texture_step`` as torch ops (:meth:`_Momentum.rule` plus the clamp of the texture; ``step_max`` None or not positive: no clamp of the
+    step), in place on ``texture`` and ``speed``; float64 arithmetic"""
+    s = _Momentum(inertia, damping).rule(speed.to(torch.float64), gradient.to(torch.float64), factor, _kernel_clamp(step_max))
     t = texture.detach().to(torch.float64) + s
     if clamp is not None:
         clipped = (t < clamp[0]) | (t > clamp[1])
@@ -955,12 +997,9 @@ class MeshTextureFitterMultiFrame:
             if basis.mean is not None:
                 raise ValueError("texture_basis: `texture_init` is the mean; give a LinearBasis without one")
             self.texture_basis = basis.with_mean(np.asarray(texture_init, dtype=np.float64))
-            sig = np.ones(basis.K) if sigmas is None else np.asarray(sigmas, dtype=np.float64)
-            if sig.shape != (basis.K,) or np.any(sig <= 0):
-                raise ValueError(f"sigmas must be {basis.K} positive numbers")
-            self.coefficient_regu = float(coefficient_regu)
-            self._inv_sigma2 = torch.as_tensor(1.0 / sig**2, device=self.device)
-            self._prior_scale = 2.0 * self.coefficient_regu * self._inv_sigma2  # gradient of the prior = this * coefficients
+            self._prior = _GaussianPrior(sigmas, basis.K, coefficient_regu, self.device)
+            self.coefficient_regu = self._prior.regu
+            self._prior_scale = self._prior.gradient()  # gradient of the prior = this * coefficients (a constant: the fixed sequence multiplies in place)
         self.mesh = DeviceMesh(np.asarray(faces), v0, clockwise=clockwise, uv=uv, faces_uv=faces_uv, texture=None, device=self.device)
         self.scene = Scene3DDevice(sigma=sigma, pixel_dtype=pixel_dtype)
         self.scene.set_mesh(self.mesh)
@@ -1000,10 +1039,7 @@ class MeshTextureFitterMultiFrame:
             posed = mesh.vertices
         else:
             euler, translation = (np.atleast_2d(np.asarray(a, dtype=np.float64)) for a in self.poses)
-            focal = 2 * width if focal is None else focal
-            rot = np.diag([1.0, -1.0, -1.0])
-            intrinsic = np.array([[focal, 0, width / 2], [0, focal, height / 2], [0, 0, 1.0]])
-            extrinsic = np.column_stack((rot, -rot.T.dot(self.camera_center)))
+            extrinsic, intrinsic = _default_camera(height, width, focal, self.camera_center)
             cam = DeviceCamera(np.broadcast_to(extrinsic, (n, 3, 4)).copy(), np.broadcast_to(intrinsic, (n, 3, 3)).copy(), height, width, distortion, dev)
             q = torch.as_tensor(np.broadcast_to(np.asarray([_quat_from_euler_zyx(e) for e in euler]), (n, 4)).copy(), device=dev)
             t = torch.as_tensor(np.broadcast_to(translation, (n, 3)).copy(), device=dev)
@@ -1021,22 +1057,12 @@ class MeshTextureFitterMultiFrame:
         self._views = dict(ij=ij.contiguous(), depths=depths.contiguous(), colors=colors, shade=lum.contiguous(), edgeflags=flags.contiguous())
         self.mesh_image = torch.as_tensor(imgs, device=dev)
         self._obs = self.mesh_image.to(self.pixel_dtype).contiguous()
-        if weights is not None:
-            w = np.asarray(weights.detach().cpu() if torch.is_tensor(weights) else weights, dtype=np.float64)
-            if w.shape not in ((height, width), (n, height, width)):
-                raise ValueError(f"weights must have shape [{height}, {width}] or [{n}, {height}, {width}] (one value per pixel), not {list(w.shape)}")
-            weights = torch.as_tensor(np.array(np.broadcast_to(w, (n, height, width))), device=dev).to(self.pixel_dtype).contiguous()
-        self.weights = weights
+        self.weights = _pixel_weights(weights, (n, height, width), dev, self.pixel_dtype)
         z = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=dev)
         self.e_data, self.e_smooth, self._energy = z(1), z(1), z(1)
         self._direct = None
         if self.device.type == "cuda":
-            if (self.scene.background_image is None) == (self.scene.background_color is None):
-                raise BaseException("You need to provide either a background image or background color")
-            ds, r = self.scene._rasterizer(n, height, width, nb_colors, True, True)
-            pd = self.pixel_dtype
-            out = (torch.empty((n, height, width, nb_colors), dtype=pd, device=dev), torch.empty((n, height, width), dtype=pd, device=dev))
-            ds.set_views(**self._views)
+            ds, r, out = _raster_state(self.scene, (n, height, width, nb_colors), True, self._views)
             ds.set_texture(self.texture)
             self._direct = (ds, r, ds.zero_grads(), out)
             self._scratch = hip_renderer.texture_scratch(dev)  # (its own: a captured step replays on the addresses it was captured with)
@@ -1072,10 +1098,9 @@ class MeshTextureFitterMultiFrame:
         assert self._views is not None, "call set_images first"
         if self.texture_basis is not None:
             self._texture_from_coefficients()
-            self._gradient()
-            return self.e_data + self.e_smooth + self.coefficient_regu * (self._inv_sigma2 * self.coefficients**2).sum()
         self._gradient()
-        return self.e_data + self.e_smooth
+        energy = self.e_data + self.e_smooth
+        return energy if self.texture_basis is None else energy + self._prior.energy(self.coefficients)
 
     def step_device(self):
         """One iteration on the device -> (energy BEFORE the update [1], image [n,H,W,C]).  ``self.texture`` and the momentum speed are updated in place,
@@ -1100,9 +1125,7 @@ class MeshTextureFitterMultiFrame:
 
     def _step_basis(self):
         """the iteration of a fit with ``texture_basis``: the same storage every step, no autograd graph on the device"""
-        from . import fronthalf
-
-        B, c, c_b, speed = self.texture_basis, self.coefficients, self.coefficients_b, self.momentum.speed["coefficients"]
+        B, c, c_b = self.texture_basis, self.coefficients, self.coefficients_b
         self._texture_from_coefficients()
         texture_b, image = self._gradient()
         torch.mul(c, self._prior_scale, out=c_b)  # the prior's gradient 2 coefficient_regu c / sigmas^2; the data + smoothness gradient is added to it
@@ -1112,24 +1135,15 @@ class MeshTextureFitterMultiFrame:
             self.e_prior.mul_(0.5)
         if self._direct is not None:
             B.run_b(texture_b.view(1, B.N), out=c_b[None], accumulate=True, scratch=self._basis_scratch)
-            fronthalf.momentum_update([(c, speed, c_b, None, self.step_factor_coefficients, self.step_max, 0)], self.inertia, self.damping)
         else:
             c_b += B.run_b(texture_b.reshape(1, B.N))[0]
-            step = -self.step_factor_coefficients * c_b
-            if self.step_max is not None and self.step_max > 0:
-                step = step.clamp(-self.step_max, self.step_max)
-            speed.copy_((1 - self.damping) * (self.inertia * speed + (1 - self.inertia) * step))
-            c += speed
+        self.momentum.update_in_place([("coefficients", c, c_b, None, self.step_factor_coefficients, self.step_max, 0)])
         torch.add(self.e_data, self.e_smooth, out=self._energy)
         self._energy += self.e_prior
         self.iter += 1
         return self._energy, image
 
-    def step(self):
-        """-> (energy, images [n,H,W,C], squared difference per pixel [n,H,W]) as a float and NumPy arrays (synchronises)"""
-        energy, image = self.step_device()
-        image = image.to(torch.float64)
-        return float(energy[0]), image.cpu().numpy(), ((image - self.mesh_image) ** 2).sum(dim=-1).cpu().numpy()
+    step = _step_all_views
 
 
 # ---- camera calibration -----------------------------------------------------------------------------------------------------------------
@@ -1237,8 +1251,8 @@ class CameraFitterMultiFrame:
         energy, grads = None, {}
         for name, inv in self._inv_sigma2.items():
             delta = getattr(self, name) - getattr(self, name + "_init")
-            grads[name] = 2.0 * inv * delta
-            e = (inv * delta * delta).sum().reshape(1)
+            grads[name] = _prior_gradient(1.0, inv, delta)
+            e = (inv * delta * delta).sum().reshape(1)  # (not _GaussianPrior.energy: (inv delta) delta rounds differently from inv delta**2)
             energy = e if energy is None else energy + e
         return energy, grads
 
@@ -1255,13 +1269,8 @@ class CameraFitterMultiFrame:
         self.height, self.width = height, width
         self.mesh_image = torch.as_tensor(imgs, device=dev)
         self._obs = self.mesh_image.to(self.pixel_dtype).contiguous()
-        if weights is not None:
-            w = np.asarray(weights.detach().cpu() if torch.is_tensor(weights) else weights, dtype=np.float64)
-            if w.shape not in ((height, width), (n, height, width)):
-                raise ValueError(f"weights must have shape [{height}, {width}] or [{n}, {height}, {width}] (one value per pixel), not {list(w.shape)}")
-            weights = torch.as_tensor(np.array(np.broadcast_to(w, (n, height, width))), device=dev).to(self.pixel_dtype).contiguous()
-        self.weights = weights
-        self.e_data, self._energy = torch.zeros(1, dtype=torch.float64, device=dev), torch.zeros(1, dtype=torch.float64, device=dev)
+        self.weights = _pixel_weights(weights, (n, height, width), dev, self.pixel_dtype)
+        self.e_data, self._energy =torch.zeros(1, dtype=torch.float64, device=dev), torch.zeros(1, dtype=torch.float64, device=dev)
         if self._step_scale_given is None:
             self.step_scale = min(1.0, 4 * 128**2 / (n * height * width))
         self._direct = None
@@ -1296,13 +1305,8 @@ class CameraFitterMultiFrame:
         if int(colors.shape[-1]) != nb_colors:
             raise ValueError(f"the images have {nb_colors} channels, the mesh {int(colors.shape[-1])}")
         d.views = dict(ij=d.ij, depths=d.depths, colors=colors, shade=shade, edgeflags=d.flags)
-        if (self.scene.background_image is None) == (self.scene.background_color is None):
-            raise BaseException("You need to provide either a background image or background color")
-        d.ds, d.rasterizer = self.scene._rasterizer(n, height, width, nb_colors, textured, True)
-        d.ds.set_views(**d.views)
+        d.ds, d.rasterizer, d.out = _raster_state(self.scene, (n, height, width, nb_colors), textured, d.views)
         d.grads = d.ds.zero_grads()
-        pd = self.pixel_dtype
-        d.out = (torch.empty((n, height, width, nb_colors), dtype=pd, device=dev), torch.empty((n, height, width), dtype=pd, device=dev))
         d.extrinsic_b, d.intrinsic_b = z(n, 3, 4), z(n, 3, 3)
         d.dist_b = None if d.dist is None else z(n, 5)
         d.grad = {"quaternions": z(n, 4), "translations": z(n, 3), "focal": torch.zeros_like(self.focal), "center": torch.zeros_like(self.center),
@@ -1314,11 +1318,10 @@ class CameraFitterMultiFrame:
         """the fixed kernel sequence up to the gradients -> ({parameter name: gradient}, image); the data energy lands in ``self.e_data``"""
         from . import fronthalf, hip_renderer
 
-        d, topo, n, V = self._direct, self.mesh.topology, self.n_views, self.mesh.nb_vertices
+        d, topo = self._direct, self.mesh.topology
         hip_renderer.camera_assemble(self.quaternions, self.translations, self.focal, self.center, self.distortion, shared=self.shared_intrinsics,
                                      out=(d.extrinsic, d.intrinsic, d.dist))  # fmt: skip
-        hip_renderer._launch(hip_renderer.lib().deodr_hip_project_points, self.device, hip_renderer._ptr(d.points), hip_renderer._ptr(d.extrinsic),
-                             hip_renderer._ptr(d.intrinsic), hip_renderer._ptr(d.dist), hip_renderer._ptr(d.ij), hip_renderer._ptr(d.depths), V, n)  # fmt: skip
+        fronthalf.project_points(d.points, d.extrinsic, d.intrinsic, d.dist, d.ij, d.depths)
         if self.scene.sigma > 0:
             fronthalf.silhouette_flags(d.ij, topo._faces_u32, topo._edge_faces, topo.clockwise, out=d.flags)
         d.ds.set_views(**d.views)  # (no copies: the tensors are used as they are; another render of the scene may have rebound them)
@@ -1375,28 +1378,16 @@ class CameraFitterMultiFrame:
     def step_device(self):
         """One iteration on the device -> (energy BEFORE the update [1], image [n,H,W,C]).  On the direct path the parameters and the momentum speeds are
         updated in place and the returned tensors are the same storage every step (clone what is to be kept); :meth:`step` converts at once."""
-        from . import fronthalf
-
         grads, image = self._data_gradients()
         e_prior, g_prior = self._prior()  # (of the parameters the gradients were taken at)
-        rows = [r for r in self._parameters() if r[1] in self.update]
-        if self._direct is not None:
-            entries = []
-            for name, _group, x, factor, step_max, normalize_rows in rows:
-                if name not in self.momentum.speed:
-                    self.momentum.speed[name] = torch.zeros_like(x)
-                entries.append((x, self.momentum.speed[name], grads[name], g_prior.get(name), factor, step_max, normalize_rows))
-            if entries:
-                fronthalf.momentum_update(entries, self.inertia, self.damping)
-        elif rows:
-            new = self.momentum.update_all([(name, x, grads[name], g_prior.get(name), factor, step_max, normalize_rows) for name, _g, x, factor, step_max, normalize_rows in rows])
-            for (name, *_), value in zip(rows, new):
+        entries = [(name, x, grads[name], g_prior.get(name), factor, step_max, normalize_rows)
+                   for name, group, x, factor, step_max, normalize_rows in self._parameters() if group in self.update]  # fmt: skip
+        if entries and self._direct is not None:
+            self.momentum.update_in_place(entries)
+        elif entries:
+            for (name, *_), value in zip(entries, self.momentum.update_all(entries)):
                 setattr(self, name, value)
         self.iter += 1
         return self._total_energy(e_prior), image
 
-    def step(self):
-        """-> (energy, images [n,H,W,C], squared difference per pixel [n,H,W]) as a float and NumPy arrays (synchronises)"""
-        energy, image = self.step_device()
-        image = image.to(torch.float64)
-        return float(energy[0]), image.cpu().numpy(), ((image - self.mesh_image) ** 2).sum(dim=-1).cpu().numpy()
+    step = _step_all_views
