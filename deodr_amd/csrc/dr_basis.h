@@ -9,8 +9,8 @@
 // in flight (a single dependent walk would be the kernel's duration: dr_fititer.h, GATHER_LANES); c[b][k] is the same in every lane.
 // Adjoint: a workgroup takes BASIS_ROW_TILE rows and one segment of j (basis_segments: the one place that rule is written); a piece of g is
 // loaded once and used for every row of the tile; per-thread sums -> wave_sum -> the wavefronts in order (LDS) -> one partial per (row,
-// segment, b); the last workgroup to arrive for a (chunk, row tile) -- a ticket on that tile's OWN counter word, the pattern of grid_sum in
-// dr_fronthalf.h -- adds the tile's partials in segment order and writes or accumulates coeffs_b.
+// segment, b); the last workgroup to arrive for a (chunk, row tile) -- last_to_arrive of dr_fronthalf.h on that tile's OWN counter word, as
+// grid_sum there -- adds the tile's partials in segment order and writes or accumulates coeffs_b.
 #pragma once
 
 namespace
@@ -149,7 +149,6 @@ __global__ __launch_bounds__(FH_BLOCK) void basis_apply_b_kernel(BasisArgs a)
 	using VB = typename BasisVec<BT, VEC>::type;
 	using VG = typename BasisVec<GT, VEC>::type;
 	__shared__ double s_wave[FH_BLOCK / 64][BASIS_ROW_TILE * NB];
-	__shared__ int s_last;
 	const BT *__restrict__ B = (const BT *)a.basis;
 	const int seg = (int)blockIdx.x, tile = (int)blockIdx.y, k0 = tile * BASIS_ROW_TILE, rows = a.K - k0 < BASIS_ROW_TILE ? a.K - k0 : BASIS_ROW_TILE;
 	const int b0 = (int)blockIdx.z * NB, nb = a.batch - b0 < NB ? a.batch - b0 : NB;
@@ -222,16 +221,8 @@ __global__ __launch_bounds__(FH_BLOCK) void basis_apply_b_kernel(BasisArgs a)
 			s += s_wave[w][threadIdx.x];
 		partials[(size_t)seg * SLOTS + threadIdx.x] = s;
 	}
-	__syncthreads();
-	if (threadIdx.x == 0)
-	{
-		__threadfence(); // release (after the barrier: the workgroup's partials are visible to the device before its ticket)
-		s_last = atomicAdd(a.counters + group, 1u) == (unsigned)a.S - 1;
-	}
-	__syncthreads();
-	if (!s_last)
+	if (!last_to_arrive(a.counters + group, (unsigned)a.S))
 		return;
-	__threadfence(); // acquire: the loads below see every workgroup's partial
 	if (threadIdx.x < BASIS_ROW_TILE * NB)
 	{
 		const int r = (int)threadIdx.x / NB, b = (int)threadIdx.x % NB;
@@ -239,13 +230,9 @@ __global__ __launch_bounds__(FH_BLOCK) void basis_apply_b_kernel(BasisArgs a)
 		for (int i = 0; i < a.S; i++)
 			s += partials[(size_t)i * SLOTS + threadIdx.x];
 		if (r < rows && b < nb)
-		{
-			double *out = a.coeffs_b + (size_t)(b0 + b) * a.K + (k0 + r);
-			*out = a.accumulate ? *out + s : s;
-		}
+			store_or_add(a.coeffs_b + (size_t)(b0 + b) * a.K + (k0 + r), s, a.accumulate);
 	}
-	if (threadIdx.x == 0)
-		atomicExch(a.counters + group, 0u);
+	reset_arrivals(a.counters + group);
 }
 
 } // namespace

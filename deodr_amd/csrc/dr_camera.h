@@ -3,7 +3,7 @@
 // parameters (quaternion + translation per view; focal, centre, distortion) to the per-view matrices the kernels index, with its adjoint.
 //
 // camera_project_b_kernel: grid (camera_blocks(V, n), n), the view's camera row uniform per workgroup (load_camera); a thread walks the vertices
-// 256 block + thread + 256 blocks i, recomputes the forward of each with the lines of project_points_b_kernel (points_b has the same bits), keeps the
+// 256 block + thread + 256 blocks i, recomputes the forward of each with project_point_b, the one copy of that adjoint (dr_fronthalf.h), keeps the
 // 23 sums in registers; per view one grid_sum<12> (extrinsic) and one grid_sum<11> (intrinsic, distortion), each on its own partial range and counter
 // word of that view; the last workgroup of a view to arrive at each writes (or adds to) those outputs, the second also the zero row of intrinsic_b.
 // 48 - 72 bytes per vertex and view: bound by launch latency at mesh sizes, not tuned further.
@@ -47,44 +47,26 @@ __global__ __launch_bounds__(FH_BLOCK) void camera_project_b_kernel(CameraProjec
 	for (int k = 0; k < CAMERA_SUMS; k++)
 		s[k] = 0;
 	for (int v = blockIdx.x * FH_BLOCK + threadIdx.x; v < V; v += gridDim.x * FH_BLOCK)
-	{ // (the same lines as project_points_b_kernel: points_b must have its bits)
+	{ // project_point_b (dr_fronthalf.h) gives points_b -- the bits of project_points_b_kernel, which calls it too -- and what the sums are made of
 		const size_t at = (size_t)b * V + v;
-		const double *pp = a.points + at * 3;
-		const double px = pp[0], py = pp[1], pz = pp[2];
-		const double cx = c.E[0] * px + c.E[1] * py + c.E[2] * pz + c.E[3], cy = c.E[4] * px + c.E[5] * py + c.E[6] * pz + c.E[7],
-					 cz = c.E[8] * px + c.E[9] * py + c.E[10] * pz + c.E[11];
-		const double x = cx / cz, y = cy / cz;
-		const double g0 = a.ij_b[2 * at], g1 = a.ij_b[2 * at + 1];
-		double xd_b = c.K[0] * g0 + c.K[3] * g1, yd_b = c.K[1] * g0 + c.K[4] * g1;
-		double x_b = xd_b, y_b = yd_b, xd = x, yd = y;
+		const Vec3 p = load3(a.points + at * 3);
+		const double px = p.x, py = p.y, pz = p.z, g0 = a.ij_b[2 * at], g1 = a.ij_b[2 * at + 1];
+		const ProjectB r = project_point_b(c, p, g0, g1, a.depths_b ? a.depths_b[at] : 0.0);
+		const double x = r.x, y = r.y, xd_b = r.xd_b, yd_b = r.yd_b, cx_b = r.camera_b.x, cy_b = r.camera_b.y, cz_b = r.camera_b.z;
+		double xd = x, yd = y;
 		if (c.distort)
-		{
-			const double k1 = c.d[0], k2 = c.d[1], p1 = c.d[2], p2 = c.d[3], k3 = c.d[4];
-			const double r2 = x * x + y * y, r4 = r2 * r2;
-			const double radial = 1 + k1 * r2 + k2 * r4 + k3 * (r2 * r4);
-			const double radial_b = x * xd_b + y * yd_b;
-			x_b = radial * xd_b + 2 * p1 * y * xd_b + 4 * p2 * x * xd_b + 2 * p2 * y * yd_b;
-			y_b = radial * yd_b + 2 * p1 * x * xd_b + 4 * p1 * y * yd_b + 2 * p2 * x * yd_b;
-			const double r2_b = p2 * xd_b + p1 * yd_b + radial_b * (k1 + 2 * k2 * r2 + 3 * k3 * r4);
-			x_b += 2 * x * r2_b;
-			y_b += 2 * y * r2_b;
-			// the forward's distorted point (project_points_kernel) and the adjoints of the five coefficients
+		{ // the forward's distorted point (project_point) and the adjoints of the five coefficients
+			const double p1 = c.d[2], p2 = c.d[3], r2 = r.r2, r4 = r.r4, radial_b = r.radial_b;
 			const double x2 = x * x, y2 = y * y;
-			xd = x * radial + (2 * p1 * x * y + p2 * (r2 + 2 * x2)), yd = y * radial + (p1 * (r2 + 2 * y2) + 2 * p2 * x * y);
+			xd = x * r.radial + (2 * p1 * x * y + p2 * (r2 + 2 * x2)), yd = y * r.radial + (p1 * (r2 + 2 * y2) + 2 * p2 * x * y);
 			s[18] += radial_b * r2;
 			s[19] += radial_b * r4;
 			s[20] += 2 * x * y * xd_b + (r2 + 2 * y2) * yd_b;
 			s[21] += (r2 + 2 * x2) * xd_b + 2 * x * y * yd_b;
 			s[22] += radial_b * (r2 * r4);
 		}
-		const double cx_b = x_b / cz, cy_b = y_b / cz, cz_b = (a.depths_b ? a.depths_b[at] : 0.0) - (x * x_b + y * y_b) / cz;
 		if (a.points_b)
-		{
-			double *o = a.points_b + at * 3;
-			o[0] = c.E[0] * cx_b + c.E[4] * cy_b + c.E[8] * cz_b;
-			o[1] = c.E[1] * cx_b + c.E[5] * cy_b + c.E[9] * cz_b;
-			o[2] = c.E[2] * cx_b + c.E[6] * cy_b + c.E[10] * cz_b;
-		}
+			store3(a.points_b + at * 3, r.point_b);
 		s[0] += cx_b * px, s[1] += cx_b * py, s[2] += cx_b * pz, s[3] += cx_b;
 		s[4] += cy_b * px, s[5] += cy_b * py, s[6] += cy_b * pz, s[7] += cy_b;
 		s[8] += cz_b * px, s[9] += cz_b * py, s[10] += cz_b * pz, s[11] += cz_b;
@@ -102,16 +84,10 @@ __global__ __launch_bounds__(FH_BLOCK) void camera_project_b_kernel(CameraProjec
 		for (int i = 0; i < CAMERA_SUMS_E; i++)
 			part[i] = s[i];
 		if (grid_sum<CAMERA_SUMS_E>(part, partials, a.counters + 2 * b, total, blockIdx.x, B))
-		{ // the last workgroup of the view: thread k < 12 has value k (a chain of compares, not an indexed register file)
-			double mine = 0;
-#pragma unroll
-			for (int i = 0; i < CAMERA_SUMS_E; i++)
-				mine = k == i ? total[i] : mine;
+		{ // the last workgroup of the view: thread k < 12 has value k
+			const double mine = total_of_thread(total, k);
 			if (k < CAMERA_SUMS_E)
-			{
-				double *out = a.extrinsic_b + 12 * b + k;
-				*out = a.accumulate ? *out + mine : mine;
-			}
+				store_or_add(a.extrinsic_b + 12 * b + k, mine, a.accumulate);
 		}
 	}
 	{
@@ -122,13 +98,10 @@ __global__ __launch_bounds__(FH_BLOCK) void camera_project_b_kernel(CameraProjec
 			part[i] = s[CAMERA_SUMS_E + i];
 		if (grid_sum<REST>(part, partials + (size_t)B * CAMERA_SUMS_E, a.counters + 2 * b + 1, total, blockIdx.x, B))
 		{ // threads 0 .. 5: the two rows of intrinsic_b, 6 .. 10: distortion_b, 11 .. 13: the zero row of intrinsic_b
-			double mine = 0;
-#pragma unroll
-			for (int i = 0; i < REST; i++)
-				mine = k == i ? total[i] : mine;
+			const double mine = total_of_thread(total, k);
 			double *out = k < 6 ? a.intrinsic_b + 9 * b + k : (k < REST && a.distortion_b) ? a.distortion_b + 5 * b + (k - 6) : nullptr;
 			if (out)
-				*out = a.accumulate ? *out + mine : mine;
+				store_or_add(out, mine, a.accumulate);
 			if (k >= REST && k < REST + 3 && !a.accumulate)
 				a.intrinsic_b[9 * b + 6 + (k - REST)] = 0;
 		}
@@ -149,8 +122,8 @@ __global__ __launch_bounds__(FIT_MAX_VIEWS) void camera_assemble_kernel(CameraAs
 	if (b >= a.n)
 		return;
 	const double *q = a.quaternions + 4 * b;
-	const double inv = 1 / sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-	const double x = q[0] * inv, y = q[1] * inv, z = q[2] * inv, w = q[3] * inv;
+	const double inv = 1 / sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]); // (MULTIPLIED by: load_unit_quaternion, dr_fititer.h, divides --
+	const double x = q[0] * inv, y = q[1] * inv, z = q[2] * inv, w = q[3] * inv;		// other bits, so not one function)
 	double *E = a.extrinsic + 12 * b, *K = a.intrinsic + 9 * b;
 	// R = I + 2 w [u]x + 2 [u]x^2, u = (x, y, z): qrot(q, p) = p + 2 (w u x p + u x (u x p)) as a matrix
 	E[0] = 1 - 2 * (y * y + z * z), E[1] = 2 * (x * y - w * z), E[2] = 2 * (x * z + w * y), E[3] = a.translations[3 * b];
@@ -186,7 +159,7 @@ __global__ __launch_bounds__(FIT_MAX_VIEWS) void camera_assemble_b_kernel(Camera
 	const double yn_b = -4 * y * (R[0] + R[10]) + 2 * x * s01 + 2 * z * s12 + 2 * w * a20;
 	const double zn_b = -4 * z * (R[0] + R[5]) + 2 * x * s02 + 2 * y * s12 + 2 * w * a01;
 	const double wn_b = 2 * (x * a12 + y * a20 + z * a01);
-	// through q / |q|: q_b = (qn_b - qn (qn . qn_b)) / |q|
+	// through q / |q|: q_b = (qn_b - qn (qn . qn_b)) / |q|, as a product with `inv` like the forward (fit_pose_project_b_kernel divides: other bits)
 	const double along = x * xn_b + y * yn_b + z * zn_b + w * wn_b;
 	double *qb = a.quaternions_b + 4 * b;
 	qb[0] = (xn_b - x * along) * inv, qb[1] = (yn_b - y * along) * inv, qb[2] = (zn_b - z * along) * inv, qb[3] = (wn_b - w * along) * inv;

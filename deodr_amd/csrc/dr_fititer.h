@@ -14,7 +14,8 @@
 //   momentum_update_kernel    (dr_fronthalf.h) all parameters, in place
 //
 // All sums over vertices are DETERMINISTIC: per-workgroup partials in a fixed order, added up by the last workgroup to arrive
-// (grid_sum below) -- the torch formulation of the same chain (deodr_amd/scene3d.py, mesh_fitter.py) is what these are tested against.
+// (grid_sum of dr_fronthalf.h, where the pose and camera algebra of these kernels lives too) -- the torch formulation of the same chain
+// (deodr_amd/scene3d.py, mesh_fitter.py) is what these are tested against.
 // The gathers use a vertex -> incident (face, corner) CSR built once per topology (MeshTopology), no atomics.
 #pragma once
 
@@ -22,58 +23,6 @@
 
 namespace
 {
-
-__device__ __forceinline__ Vec3 load3(const double *p) { return {p[0], p[1], p[2]}; }
-__device__ __forceinline__ Vec3 sub3(const Vec3 &a, const Vec3 &b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ void store3(double *p, const Vec3 &a) { p[0] = a.x, p[1] = a.y, p[2] = a.z; }
-
-// q = (x, y, z, w): p + 2 (w (u x p) + u x (u x p))   (deodr/tools.py:8-22)
-__device__ __forceinline__ Vec3 qrot_point(const Vec3 &u, double w, const Vec3 &p)
-{
-	const Vec3 a = cross3(u, p), bb = cross3(u, a);
-	return {p.x + 2 * (w * a.x + bb.x), p.y + 2 * (w * a.y + bb.y), p.z + 2 * (w * a.z + bb.z)};
-}
-
-__device__ __forceinline__ void project_point(const CameraRow &c, const Vec3 &p, double &i, double &j, double &depth)
-{
-	const double cx = c.E[0] * p.x + c.E[1] * p.y + c.E[2] * p.z + c.E[3], cy = c.E[4] * p.x + c.E[5] * p.y + c.E[6] * p.z + c.E[7],
-				 cz = c.E[8] * p.x + c.E[9] * p.y + c.E[10] * p.z + c.E[11];
-	double x = cx / cz, y = cy / cz;
-	if (c.distort)
-	{
-		const double k1 = c.d[0], k2 = c.d[1], p1 = c.d[2], p2 = c.d[3], k3 = c.d[4];
-		const double x2 = x * x, y2 = y * y, r2 = x2 + y2, r4 = r2 * r2;
-		const double radial = 1 + k1 * r2 + k2 * r4 + k3 * (r2 * r4);
-		const double xd = x * radial + (2 * p1 * x * y + p2 * (r2 + 2 * x2)), yd = y * radial + (p1 * (r2 + 2 * y2) + 2 * p2 * x * y);
-		x = xd, y = yd;
-	}
-	i = c.K[0] * x + c.K[1] * y + c.K[2];
-	j = c.K[3] * x + c.K[4] * y + c.K[5];
-	depth = cz;
-}
-
-__device__ __forceinline__ Vec3 project_point_b(const CameraRow &c, const Vec3 &p, double g0, double g1, double gd)
-{ // (the same lines as project_points_b_kernel)
-	const double cx = c.E[0] * p.x + c.E[1] * p.y + c.E[2] * p.z + c.E[3], cy = c.E[4] * p.x + c.E[5] * p.y + c.E[6] * p.z + c.E[7],
-				 cz = c.E[8] * p.x + c.E[9] * p.y + c.E[10] * p.z + c.E[11];
-	const double x = cx / cz, y = cy / cz;
-	const double xd_b = c.K[0] * g0 + c.K[3] * g1, yd_b = c.K[1] * g0 + c.K[4] * g1;
-	double x_b = xd_b, y_b = yd_b;
-	if (c.distort)
-	{
-		const double k1 = c.d[0], k2 = c.d[1], p1 = c.d[2], p2 = c.d[3], k3 = c.d[4];
-		const double r2 = x * x + y * y, r4 = r2 * r2;
-		const double radial = 1 + k1 * r2 + k2 * r4 + k3 * (r2 * r4);
-		const double radial_b = x * xd_b + y * yd_b;
-		x_b = radial * xd_b + 2 * p1 * y * xd_b + 4 * p2 * x * xd_b + 2 * p2 * y * yd_b;
-		y_b = radial * yd_b + 2 * p1 * x * xd_b + 4 * p1 * y * yd_b + 2 * p2 * x * yd_b;
-		const double r2_b = p2 * xd_b + p1 * yd_b + radial_b * (k1 + 2 * k2 * r2 + 3 * k3 * r4);
-		x_b += 2 * x * r2_b;
-		y_b += 2 * y * r2_b;
-	}
-	const double cx_b = x_b / cz, cy_b = y_b / cz, cz_b = gd - (x * x_b + y * y_b) / cz;
-	return {c.E[0] * cx_b + c.E[4] * cy_b + c.E[8] * cz_b, c.E[1] * cx_b + c.E[5] * cy_b + c.E[9] * cz_b, c.E[2] * cx_b + c.E[6] * cy_b + c.E[10] * cz_b};
-}
 
 constexpr int FIT_MAX_VIEWS = 64; // views (poses) of one fit_pose_project_b call
 
@@ -83,7 +32,7 @@ struct UnitQuaternion
 	double w, norm;
 };
 __device__ __forceinline__ UnitQuaternion load_unit_quaternion(const double *q, int b)
-{
+{ // DIVIDES by the norm; camera_assemble_kernel (dr_camera.h) multiplies by 1 / norm, which rounds differently: not one function
 	const double x = q[4 * b], y = q[4 * b + 1], z = q[4 * b + 2], w = q[4 * b + 3];
 	const double norm = sqrt(x * x + y * y + z * z + w * w);
 	return {{x / norm, y / norm, z / norm}, w / norm, norm};
@@ -92,16 +41,30 @@ __device__ __forceinline__ UnitQuaternion load_unit_quaternion(const double *q, 
 // The gathers of the shading and rigid-energy kernels give every list (the faces around a vertex, a row of L^T L) to GATHER_LANES adjacent lanes: one list entry is a
 // chain of dependent loads (slot -> vertex ids -> positions, ~1 us each on an idle chip), and a list of 6 - 20 entries walked by one
 // lane IS the kernel's duration (measured: 15 - 20 us per kernel, one lane per list).  Lane s takes the entries s, s + GATHER_LANES, ...
-// in order; the lanes' sums meet in a butterfly -- an order fixed by the list alone.
+// in order; the lanes' sums meet in a butterfly (lane_group_sum) -- an order fixed by the list alone.
 constexpr int GATHER_LANES = 8;
-__device__ __forceinline__ double lanes_sum(double v)
-{ // all lanes of the wavefront call it; -> the sum over each group of GATHER_LANES adjacent lanes, in every lane of the group
-	v += __shfl_xor(v, 1);
-	v += __shfl_xor(v, 2);
-	v += __shfl_xor(v, 4);
-	return v;
+
+// The colour adjoints of a vertex whose colours the views share, summed over its views: the lane of (vertex, view b) adds its view's ...
+__device__ __forceinline__ void add_view_colors(double (&col_sum)[4], const double *colors_b, int C)
+{
+#pragma unroll
+	for (int cc = 0; cc < 4; cc++)
+		if (cc < C)
+			col_sum[cc] += colors_b[cc];
 }
-__device__ __forceinline__ Vec3 lanes_sum3(const Vec3 &a) { return {lanes_sum(a.x), lanes_sum(a.y), lanes_sum(a.z)}; }
+// ... and the L lanes of the vertex meet; every lane of the wavefront calls it, `first`: the lane that stores
+template <int L>
+__device__ __forceinline__ void store_view_colors(const double (&col_sum)[4], double *colors_sum, int C, bool first)
+{
+#pragma unroll
+	for (int cc = 0; cc < 4; cc++)
+		if (cc < C)
+		{
+			const double t = lane_group_sum<1, L>(col_sum[cc]);
+			if (first)
+				colors_sum[cc] = t;
+		}
+}
 
 constexpr int POSE_B_BLOCKS = 64;		 // workgroups of fit_pose_project_b_kernel at most
 
@@ -151,12 +114,11 @@ __global__ __launch_bounds__(FH_BLOCK) void fit_pose_project_b_kernel(const doub
 {
 	__shared__ double s_wave[FH_BLOCK / 64][7 * FIT_MAX_VIEWS + 3];
 	__shared__ double s_quat[FIT_MAX_VIEWS][4];
-	__shared__ int s_last;
 	// The L (8; 1 for a single view: seven idle lanes per vertex cost the one-view fitters 2 us) adjacent lanes of a vertex take the views
 	// b = sub, sub + L, ...: one round trip for eight views (one thread per
 	// vertex walking the views: 19 us for the 8 views of the hand, 25 - 35 us for those of a 10 000-vertex mesh).  Sums over the views
-	// of a vertex: a butterfly over lane bits 0-2; sums over the vertices of a view: a butterfly over lane bits 3-5 (the eight vertices of
-	// the wavefront), then the wavefronts through LDS, the workgroups through `partials` -- orders fixed by the launch geometry alone.
+	// of a vertex: lane_group_sum<1, L>, lane bits 0-2; sums over the vertices of a view: lane_group_sum<L, 64>, lane bits 3-5 (the eight vertices of the
+	// wavefront; in every lane, for that lane's view), then the wavefronts through LDS, the workgroups through `partials` -- orders fixed by the geometry.
 	// At most POSE_B_BLOCKS workgroups, each walking the vertices in strides: with one workgroup per 32 vertices the 313 of a
 	// 10 000-vertex mesh cost a render loop that overlaps this kernel on a second stream 26 us per step instead of 15 (bench.py's
 	// shared-gradient reduction), and the last workgroup's sum over the workgroups grows with their number.
@@ -166,18 +128,6 @@ __global__ __launch_bounds__(FH_BLOCK) void fit_pose_project_b_kernel(const doub
 	for (int k = lane; k < K; k += 64)
 		s_wave[wave][k] = 0; // (a wavefront's own line: written and read by its lanes only until the sums below are gathered)
 	__syncthreads();
-	auto vertices_sum = [](double x) { // over the 64 / L vertices of the wavefront, for this lane's view; in every lane
-#pragma unroll
-		for (int d = L; d < 64; d <<= 1)
-			x += __shfl_xor(x, d);
-		return x;
-	};
-	auto views_sum = [](double x) { // over the L lanes (views) of a vertex; in every lane of the vertex
-#pragma unroll
-		for (int d = 1; d < L; d <<= 1)
-			x += __shfl_xor(x, d);
-		return x;
-	};
 	constexpr int PER_BLOCK = FH_BLOCK / L;
 	for (int base = blockIdx.x * PER_BLOCK; base < V; base += gridDim.x * PER_BLOCK) // (the same trips for every thread of the workgroup)
 	{
@@ -196,50 +146,34 @@ __global__ __launch_bounds__(FH_BLOCK) void fit_pose_project_b_kernel(const doub
 			{
 				const size_t at = (size_t)b * V + v;
 				if (colors_sum)
-#pragma unroll
-					for (int cc = 0; cc < 4; cc++)
-						if (cc < C)
-							col_sum[cc] += colors_b[at * C + cc];
+					add_view_colors(col_sum, colors_b + at * C, C);
 				const CameraRow cam = load_camera(extrinsic, intrinsic, distortion, b);
-				g = project_point_b(cam, load3(posed + 3 * at), ij_b[2 * at], ij_b[2 * at + 1], depths_b ? depths_b[at] * depths_b_scale : 0.0);
+				g = project_point_b(cam, load3(posed + 3 * at), ij_b[2 * at], ij_b[2 * at + 1], depths_b ? depths_b[at] * depths_b_scale : 0.0).point_b;
 				if (posed_b)
 					g = add3(g, load3(posed_b + 3 * at));
 			}
 			const UnitQuaternion uq = load_unit_quaternion(q, bq);
-			// r = c + 2 w a + 2 bb, a = u x c, bb = u x a   (deodr/tools.py:25-35)
-			const Vec3 &u = uq.u;
-			const Vec3 a = cross3(u, c);
-			const double w_b = 2 * dot3(g, a);
-			const Vec3 bb_b = scale3(2, g);
-			const Vec3 a_b = add3(scale3(2 * uq.w, g), cross3(bb_b, u));
-			const Vec3 u_b = add3(cross3(a, bb_b), cross3(c, a_b));
-			acc = add3(acc, add3(g, cross3(a_b, u))); // (g = 0 for a lane without a view: nothing added)
-			const double sums[7] = {u_b.x, u_b.y, u_b.z, w_b, g.x, g.y, g.z};
+			const QrotB r = qrot_point_b(uq.u, uq.w, c, g);
+			acc = add3(acc, r.p_b); // (g = 0 for a lane without a view: nothing added)
+			const double sums[7] = {r.u_b.x, r.u_b.y, r.u_b.z, r.w_b, g.x, g.y, g.z};
 #pragma unroll
 			for (int i = 0; i < 7; i++)
 			{
-				const double t = vertices_sum(sums[i]); // (every lane takes part: lanes beyond V or n hold zeros)
+				const double t = lane_group_sum<L, 64>(sums[i]); // (every lane takes part: lanes beyond V or n hold zeros)
 				if (lane < L && b < n)
 					s_wave[wave][7 * b + i] += t;
 			}
 		}
-		acc = {views_sum(acc.x), views_sum(acc.y), views_sum(acc.z)};
+		acc = lane_group_sum3<1, L>(acc);
 		if (on && sub == 0)
 			store3(vertices_b + 3 * v, acc);
-		if (colors_sum) // per-vertex colours shared by the views (a multi-view fit of a coloured mesh): their adjoints summed over the views
-#pragma unroll
-			for (int cc = 0; cc < 4; cc++)
-				if (cc < C)
-				{
-					const double t = views_sum(col_sum[cc]);
-					if (on && sub == 0)
-						colors_sum[(size_t)v * C + cc] = t;
-				}
+		if (colors_sum) // per-vertex colours shared by the views (a multi-view fit of a coloured mesh)
+			store_view_colors<L>(col_sum, colors_sum + (size_t)v * C, C, on && sub == 0);
 		const double sums[3] = {acc.x, acc.y, acc.z};
 #pragma unroll
 		for (int i = 0; i < 3; i++)
 		{
-			const double t = vertices_sum(sums[i]); // (the L lanes of a vertex hold the same sum: lane 0 = the wavefront's vertices)
+			const double t = lane_group_sum<L, 64>(sums[i]); // (the L lanes of a vertex hold the same sum: lane 0 = the wavefront's vertices)
 			if (lane == 0)
 				s_wave[wave][7 * n + i] += t;
 		}
@@ -252,16 +186,8 @@ __global__ __launch_bounds__(FH_BLOCK) void fit_pose_project_b_kernel(const doub
 			s += s_wave[w][k];
 		mine[k] = s;
 	}
-	__syncthreads();
-	if (threadIdx.x == 0)
-	{
-		__threadfence(); // release (one thread, after the barrier: the workgroup's partials are visible to the device before its ticket)
-		s_last = atomicAdd(counter, 1u) == gridDim.x - 1;
-	}
-	__syncthreads();
-	if (!s_last)
+	if (!last_to_arrive(counter, gridDim.x))
 		return;
-	__threadfence(); // acquire
 	double *pose_b = out + 3; // [n,4] then [n,3]
 	// lane k of every wavefront adds up output k (consecutive lanes read consecutive addresses) over the workgroups w, w + 4, ... of its
 	// wavefront w, eight independent partial sums at a time (a lane adding 400 partials one after the other waits 400 times: 142 us for
@@ -291,11 +217,10 @@ __global__ __launch_bounds__(FH_BLOCK) void fit_pose_project_b_kernel(const doub
 		else
 			s_quat[k / 7][k % 7] = s; // (the quaternion needs its four sums together: below)
 	}
-	if (threadIdx.x == 0)
-		atomicExch(counter, 0u);
+	reset_arrivals(counter);
 	__syncthreads();
 	for (int b = threadIdx.x; b < n; b += FH_BLOCK)
-	{ // q = raw / |raw|:  raw_b = (q_b - q (q . q_b)) / |raw|
+	{ // q = raw / |raw|:  raw_b = (q_b - q (q . q_b)) / |raw|  (DIVIDED, as load_unit_quaternion; camera_assemble_b_kernel multiplies by 1 / |raw|)
 		const UnitQuaternion uq = load_unit_quaternion(q, b);
 		const double g[4] = {s_quat[b][0], s_quat[b][1], s_quat[b][2], s_quat[b][3]};
 		const double qq[4] = {uq.u.x, uq.u.y, uq.u.z, uq.w};
@@ -323,31 +248,15 @@ __global__ __launch_bounds__(FH_BLOCK) void views_gradient_sum_kernel(const doub
 	{
 		const size_t at = (size_t)b * V + v;
 		if (colors_sum)
-#pragma unroll
-			for (int cc = 0; cc < 4; cc++)
-				if (cc < C)
-					col_sum[cc] += colors_b[at * C + cc];
+			add_view_colors(col_sum, colors_b + at * C, C);
 		const CameraRow cam = load_camera(extrinsic, intrinsic, distortion, b);
-		acc = add3(acc, project_point_b(cam, load3(posed + 3 * at), ij_b[2 * at], ij_b[2 * at + 1], depths_b ? depths_b[at] * depths_b_scale : 0.0));
+		acc = add3(acc, project_point_b(cam, load3(posed + 3 * at), ij_b[2 * at], ij_b[2 * at + 1], depths_b ? depths_b[at] * depths_b_scale : 0.0).point_b);
 	}
-	auto views_sum = [](double x) { // over the L lanes of a vertex (every lane of the wavefront takes part)
-#pragma unroll
-		for (int d = 1; d < L; d <<= 1)
-			x += __shfl_xor(x, d);
-		return x;
-	};
-	acc = {views_sum(acc.x), views_sum(acc.y), views_sum(acc.z)};
+	acc = lane_group_sum3<1, L>(acc); // over the L lanes of a vertex (every lane of the wavefront takes part)
 	if (on && sub == 0)
 		store3(vertices_b + 3 * v, acc);
 	if (colors_sum)
-#pragma unroll
-		for (int cc = 0; cc < 4; cc++)
-			if (cc < C)
-			{
-				const double t = views_sum(col_sum[cc]);
-				if (on && sub == 0)
-					colors_sum[(size_t)v * C + cc] = t;
-			}
+		store_view_colors<L>(col_sum, colors_sum + (size_t)v * C, C, on && sub == 0);
 }
 
 // ---- shading.  vf_offsets [V+1], vf_corners [3T]: for every vertex the (3 face + corner) slots it occupies (static per mesh)
@@ -363,9 +272,8 @@ __device__ __forceinline__ FaceNormal face_normal(const double *P, const uint32_
 	r.i0 = faces[3 * f], r.i1 = faces[3 * f + 1], r.i2 = faces[3 * f + 2];
 	const Vec3 p0 = load3(P + 3 * (size_t)r.i0);
 	r.e1 = sub3(load3(P + 3 * (size_t)r.i1), p0), r.e2 = sub3(load3(P + 3 * (size_t)r.i2), p0);
-	const Vec3 nn = cross3(r.e1, r.e2);
-	r.len = sqrt(dot3(nn, nn));
-	r.unit = {nn.x / r.len, nn.y / r.len, nn.z / r.len};
+	const Unit n = unit(cross3(r.e1, r.e2));
+	r.unit = n.N, r.len = n.len;
 	return r;
 }
 
@@ -389,7 +297,7 @@ __device__ __forceinline__ Vec3 accumulated_normal(const ShadeArgs &a, const dou
 	const uint32_t begin = on ? a.vf_offsets[v] : 0, end = on ? a.vf_offsets[v + 1] : 0;
 	for (uint32_t k = begin + sub; k < end; k += GATHER_LANES)
 		acc = add3(acc, face_normal(P, a.faces, a.vf_corners[k] / 3).unit);
-	return scale3(a.sign, lanes_sum3(acc));
+	return scale3(a.sign, lane_group_sum3<1, GATHER_LANES>(acc));
 }
 
 // grid: (V GATHER_LANES / FH_BLOCK, n)
@@ -400,8 +308,7 @@ __device__ __forceinline__ void vertex_shade_block(const ShadeArgs &a, double *l
 	const Vec3 acc = accumulated_normal(a, a.posed + (size_t)b * a.V * 3, v, sub, on);
 	if (!on || sub != 0)
 		return;
-	const double len = sqrt(dot3(acc, acc));
-	const Vec3 N = {acc.x / len, acc.y / len, acc.z / len};
+	const Vec3 N = unit(acc).N;
 	const double d = -dot3(N, load3(a.light));
 	const double lum = (d > 0 ? d : 0.0) + a.ambient[0];
 	const size_t at = (size_t)b * a.V + v;
@@ -429,8 +336,8 @@ __global__ __launch_bounds__(FH_BLOCK) void vertex_shade_b1_kernel(ShadeArgs a, 
 	double sums[7] = {0, 0, 0, 0, 0, 0, 0};
 	if (on && sub == 0)
 	{
-		const double len = sqrt(dot3(acc, acc));
-		const Vec3 N = {acc.x / len, acc.y / len, acc.z / len}, L = load3(a.light);
+		const Unit n = unit(acc);
+		const Vec3 N = n.N, L = load3(a.light);
 		const double d = -dot3(N, L);
 		const double lum = (d > 0 ? d : 0.0) + a.ambient[0];
 		double lum_b = lum_b_in ? lum_b_in[at] : 0.0;
@@ -443,9 +350,7 @@ __global__ __launch_bounds__(FH_BLOCK) void vertex_shade_b1_kernel(ShadeArgs a, 
 			}
 		const double d_b = d > 0 ? lum_b : 0.0;
 		sums[0] = -N.x * d_b, sums[1] = -N.y * d_b, sums[2] = -N.z * d_b, sums[3] = lum_b;
-		const Vec3 N_b = scale3(-d_b, L);
-		const double along = dot3(N, N_b);
-		store3(acc_b + 3 * at, {(N_b.x - N.x * along) / len, (N_b.y - N.y * along) / len, (N_b.z - N.z * along) / len});
+		store3(acc_b + 3 * at, unit_b(N, n.len, scale3(-d_b, L)));
 	}
 	double total[7];
 	if (grid_sum<7>(sums, partials, counter, total) && threadIdx.x < 4 + a.C)
@@ -465,13 +370,12 @@ __global__ __launch_bounds__(FH_BLOCK) void vertex_shade_b2_kernel(ShadeArgs a, 
 	{
 		const uint32_t slot = a.vf_corners[k], f = slot / 3, corner = slot % 3;
 		const FaceNormal fn = face_normal(P, a.faces, f);
-		const Vec3 unit_b = scale3(a.sign, add3(add3(load3(A + 3 * (size_t)fn.i0), load3(A + 3 * (size_t)fn.i1)), load3(A + 3 * (size_t)fn.i2)));
-		const double along = dot3(fn.unit, unit_b);
-		const Vec3 n_b = {(unit_b.x - fn.unit.x * along) / fn.len, (unit_b.y - fn.unit.y * along) / fn.len, (unit_b.z - fn.unit.z * along) / fn.len};
+		const Vec3 face_b = scale3(a.sign, add3(add3(load3(A + 3 * (size_t)fn.i0), load3(A + 3 * (size_t)fn.i1)), load3(A + 3 * (size_t)fn.i2)));
+		const Vec3 n_b = unit_b(fn.unit, fn.len, face_b);
 		const Vec3 e1_b = cross3(fn.e2, n_b), e2_b = cross3(n_b, fn.e1); // n = e1 x e2
 		g = add3(g, corner == 0 ? scale3(-1, add3(e1_b, e2_b)) : corner == 1 ? e1_b : e2_b);
 	}
-	g = lanes_sum3(g);
+	g = lane_group_sum3<1, GATHER_LANES>(g);
 	if (on && sub == 0)
 		store3(posed_b + ((size_t)b * a.V + v) * 3, g);
 }
@@ -502,7 +406,7 @@ __device__ __forceinline__ void rigid_energy_block(const RigidArgs &a, unsigned 
 		const size_t j = a.cols[k];
 		g = add3(g, scale3(a.vals[k], sub3(load3(a.x + 3 * j), load3(a.ref + 3 * j))));
 	}
-	g = scale3(a.cregu, lanes_sum3(g));
+	g = scale3(a.cregu, lane_group_sum3<1, GATHER_LANES>(g));
 	double e[1] = {0};
 	if (on && sub == 0)
 	{

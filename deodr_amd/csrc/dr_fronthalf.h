@@ -1,5 +1,7 @@
 // deodr_amd/csrc/dr_fronthalf.h -- part of the single translation unit dr_kernels.hip (device code, gfx950 / wave64).
-// The O(V) algebra either side of the rasterizer in a fit iteration, as a handful of kernels:
+// The O(V) algebra either side of the rasterizer in a fit iteration.  At the top of THIS file and nowhere else, what the kernels
+// of dr_fititer.h, dr_texfit.h, dr_subdiv.h, dr_basis.h, dr_camera.h and dr_lighting.h share with the ones here: Vec3, unit, qrot_point, CameraRow,
+// project_point and their adjoints; lane_group_sum, last_to_arrive (the arrival ticket), grid_sum, total_of_thread, store_or_add.  Then the kernels:
 //
 //   rigid_transform_kernel (+ _b)   centred vertices -> posed vertices of every view: qrot(q, v) + t
 //                                   (deodr/tools.py:8-35 qrot / qrot_backward; deodr/mesh_fitter.py:139-151)
@@ -21,146 +23,59 @@ using namespace dr;
 namespace
 {
 
+// ---- the small algebra of pose, camera and normals (no contraction, no fast-math: an inlined function gives every caller the bits of its text)
 struct Vec3
 {
 	double x, y, z;
 };
 __device__ __forceinline__ Vec3 cross3(const Vec3 &a, const Vec3 &b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
 __device__ __forceinline__ Vec3 add3(const Vec3 &a, const Vec3 &b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
+__device__ __forceinline__ Vec3 sub3(const Vec3 &a, const Vec3 &b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
 __device__ __forceinline__ Vec3 scale3(double s, const Vec3 &a) { return {s * a.x, s * a.y, s * a.z}; }
 __device__ __forceinline__ double dot3(const Vec3 &a, const Vec3 &b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+__device__ __forceinline__ Vec3 load3(const double *p) { return {p[0], p[1], p[2]}; }
+__device__ __forceinline__ void store3(double *p, const Vec3 &a) { p[0] = a.x, p[1] = a.y, p[2] = a.z; }
 
-constexpr int FH_BLOCK = 256;
-
-// ---- grid-wide sums without atomics on the values.  Every thread of every workgroup of a launch whose blockIdx.x runs over the
-// reduced range brings K values; `partials` holds K doubles per workgroup, `counter` one word that is zero between launches (the last
-// workgroup to arrive resets it).  -> true in ALL threads of the last workgroup, whose total[] then holds the sums (in workgroup order).
-// Deterministic grid-wide sums without atomics on the values.  Every thread of every workgroup of a launch (blockIdx.x over the reduced
-// range) brings K values; `partials` holds K doubles per workgroup, `counter` one word that is zero between launches (the last
-// workgroup to arrive resets it).  -> true in ALL threads of the last workgroup, whose total[] then holds the sums: the partial of
-// workgroup i is added by thread i mod FH_BLOCK in the order i, i + FH_BLOCK, ...; then the lanes of a wavefront (DPP tree), then
-// the wavefronts in order -- fixed by the launch geometry alone.
-template <int K>
-__device__ __forceinline__ bool grid_sum(const double (&v)[K], double *partials, unsigned *counter, double (&total)[K], unsigned block = blockIdx.x,
-										 unsigned nblocks = gridDim.x)
-{ // (block / nblocks: the position of this workgroup among the ones that take part, for kernels that are a part of a launch)
-	__shared__ double s_wave[FH_BLOCK / 64][K];
-	__shared__ int s_last;
-	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-	for (int k = 0; k < K; k++)
-	{
-		const double s = wave_sum(v[k]);
-		if (lane == 0)
-			s_wave[wave][k] = s;
-	}
-	__syncthreads();
-	if (threadIdx.x < K)
-	{
-		double s = 0;
-		for (int w = 0; w < FH_BLOCK / 64; w++)
-			s += s_wave[w][threadIdx.x];
-		partials[(size_t)block * K + threadIdx.x] = s;
-	}
-	__syncthreads();
-	if (threadIdx.x == 0)
-	{
-		__threadfence(); // release (after the barrier: the workgroup's partials are visible to the device before its ticket)
-		s_last = atomicAdd(counter, 1u) == nblocks - 1;
-	}
-	__syncthreads();
-	if (!s_last)
-		return false;
-	__threadfence(); // acquire: the loads below see every workgroup's partial
-	double mine[K];
-#pragma unroll
-	for (int k = 0; k < K; k++)
-		mine[k] = 0;
-	for (unsigned i = threadIdx.x; i < nblocks; i += FH_BLOCK)
-#pragma unroll
-		for (int k = 0; k < K; k++)
-			mine[k] += partials[(size_t)i * K + k];
-#pragma unroll
-	for (int k = 0; k < K; k++)
-	{
-		const double s = wave_sum(mine[k]);
-		if (lane == 0)
-			s_wave[wave][k] = s; // (every thread is past its reads of s_wave: the barriers above)
-	}
-	__syncthreads();
-#pragma unroll
-	for (int k = 0; k < K; k++)
-	{
-		total[k] = 0;
-		for (int w = 0; w < FH_BLOCK / 64; w++)
-			total[k] += s_wave[w][k];
-	}
-	if (threadIdx.x == 0)
-		atomicExch(counter, 0u);
-	return true;
+// a / |a| with the length it was divided by, and the adjoint through it: a_b = (N_b - N (N . N_b)) / |a|
+struct Unit
+{
+	Vec3 N;
+	double len;
+};
+__device__ __forceinline__ Unit unit(const Vec3 &a)
+{
+	const double len = sqrt(dot3(a, a));
+	return {{a.x / len, a.y / len, a.z / len}, len};
+}
+__device__ __forceinline__ Vec3 unit_b(const Vec3 &N, double len, const Vec3 &N_b)
+{
+	const double along = dot3(N, N_b);
+	return {(N_b.x - N.x * along) / len, (N_b.y - N.y * along) / len, (N_b.z - N.z * along) / len};
 }
 
-// ---- rigid transform: out[b][v] = qrot(q[b], v[v]) + t[b]   (q = (x, y, z, w), unit)
-__global__ __launch_bounds__(FH_BLOCK) void rigid_transform_kernel(const double *vc, const double *q, const double *t, double *out, int V, int n)
+// q = (x, y, z, w) = (u, w), unit: r = p + 2 (w a + bb), a = u x p, bb = u x a   (deodr/tools.py:8-22)
+__device__ __forceinline__ Vec3 qrot_point(const Vec3 &u, double w, const Vec3 &p)
 {
-	const int v = blockIdx.x * FH_BLOCK + threadIdx.x, b = blockIdx.y;
-	if (v >= V)
-		return;
-	const Vec3 p = {vc[3 * v], vc[3 * v + 1], vc[3 * v + 2]}, u = {q[4 * b], q[4 * b + 1], q[4 * b + 2]};
-	const double w = q[4 * b + 3];
 	const Vec3 a = cross3(u, p), bb = cross3(u, a);
-	double *o = out + ((size_t)b * V + v) * 3;
-	o[0] = p.x + 2 * (w * a.x + bb.x) + t[3 * b];
-	o[1] = p.y + 2 * (w * a.y + bb.y) + t[3 * b + 1];
-	o[2] = p.z + 2 * (w * a.z + bb.z) + t[3 * b + 2];
+	return {p.x + 2 * (w * a.x + bb.x), p.y + 2 * (w * a.y + bb.y), p.z + 2 * (w * a.z + bb.z)};
 }
-
-// adjoint: one thread per vertex walks the views (vc_b[v] = sum over views: no atomics, fixed order); the sums over the vertices --
-// q_b [n,4], t_b [n,3] -- are reduced per wavefront and leave with one atomic per value, wavefront and view (zeroed by the caller)
-__global__ __launch_bounds__(FH_BLOCK) void rigid_transform_b_kernel(const double *vc, const double *q, const double *out_b, double *vc_b, double *q_b,
-																	  double *t_b, int V, int n)
+// its adjoint for r_b = g   (deodr/tools.py:25-35)
+struct QrotB
 {
-	const int v = blockIdx.x * FH_BLOCK + threadIdx.x, lane = threadIdx.x & 63;
-	const bool on = v < V;
-	const Vec3 p = on ? Vec3{vc[3 * v], vc[3 * v + 1], vc[3 * v + 2]} : Vec3{0, 0, 0};
-	Vec3 acc = {0, 0, 0};
-	for (int b = 0; b < n; b++)
-	{
-		const Vec3 u = {q[4 * b], q[4 * b + 1], q[4 * b + 2]};
-		const double w = q[4 * b + 3];
-		Vec3 g = {0, 0, 0};
-		if (on)
-		{
-			const double *gb = out_b + ((size_t)b * V + v) * 3;
-			g = {gb[0], gb[1], gb[2]};
-		}
-		const Vec3 a = cross3(u, p);
-		// r = p + 2 w a + 2 bb, a = u x p, bb = u x a
-		const double w_b = 2 * dot3(g, a);
-		const Vec3 bb_b = scale3(2, g);
-		Vec3 a_b = add3(scale3(2 * w, g), cross3(bb_b, u)); // from 2 w a and from bb = u x a
-		Vec3 u_b = cross3(a, bb_b);							   // from bb = u x a
-		u_b = add3(u_b, cross3(p, a_b));					   // from a = u x p
-		const Vec3 p_b = add3(g, cross3(a_b, u));
-		acc = add3(acc, p_b);
-		const double sums[7] = {u_b.x, u_b.y, u_b.z, w_b, g.x, g.y, g.z};
-#pragma unroll
-		for (int i = 0; i < 7; i++)
-		{
-			const double s = wave_sum(sums[i]); // (every lane takes part: lanes beyond V hold zeros)
-			if (lane == 0 && s != 0)
-				atomic_add_f64(i < 4 ? q_b + 4 * b + i : t_b + 3 * b + (i - 4), s);
-		}
-	}
-	if (on)
-	{
-		vc_b[3 * v] = acc.x;
-		vc_b[3 * v + 1] = acc.y;
-		vc_b[3 * v + 2] = acc.z;
-	}
+	Vec3 p_b, u_b;
+	double w_b;
+};
+__device__ __forceinline__ QrotB qrot_point_b(const Vec3 &u, double w, const Vec3 &p, const Vec3 &g)
+{
+	const Vec3 a = cross3(u, p);
+	const double w_b = 2 * dot3(g, a);
+	const Vec3 bb_b = scale3(2, g);
+	const Vec3 a_b = add3(scale3(2 * w, g), cross3(bb_b, u)); // from 2 w a and from bb = u x a
+	const Vec3 u_b = add3(cross3(a, bb_b), cross3(p, a_b));	  // from bb = u x a and from a = u x p
+	return {add3(g, cross3(a_b, u)), u_b, w_b};
 }
 
-// ---- projection (dr.py:341-395): pc = R p + T; (x, y) = pc.xy / pc.z; distortion (k1, k2, p1, p2, k3); ij = K[:2,:2] (xd, yd) + K[:2,2]
+// projection (dr.py:341-395): pc = R p + T; (x, y) = pc.xy / pc.z; distortion (k1, k2, p1, p2, k3); ij = K[:2,:2] (xd, yd) + K[:2,2]
 struct CameraRow
 {
 	double E[12], K[6], d[5];
@@ -182,17 +97,10 @@ __device__ __forceinline__ CameraRow load_camera(const double *extrinsic, const 
 	return c;
 }
 
-__global__ __launch_bounds__(FH_BLOCK) void project_points_kernel(const double *points, const double *extrinsic, const double *intrinsic,
-																   const double *distortion, double *ij, double *depths, int V, int n)
+__device__ __forceinline__ void project_point(const CameraRow &c, const Vec3 &p, double &i, double &j, double &depth)
 {
-	const int v = blockIdx.x * FH_BLOCK + threadIdx.x, b = blockIdx.y;
-	if (v >= V)
-		return;
-	const CameraRow c = load_camera(extrinsic, intrinsic, distortion, b);
-	const double *pp = points + ((size_t)b * V + v) * 3;
-	const double px = pp[0], py = pp[1], pz = pp[2];
-	const double cx = c.E[0] * px + c.E[1] * py + c.E[2] * pz + c.E[3], cy = c.E[4] * px + c.E[5] * py + c.E[6] * pz + c.E[7],
-				 cz = c.E[8] * px + c.E[9] * py + c.E[10] * pz + c.E[11];
+	const double cx = c.E[0] * p.x + c.E[1] * p.y + c.E[2] * p.z + c.E[3], cy = c.E[4] * p.x + c.E[5] * p.y + c.E[6] * p.z + c.E[7],
+				 cz = c.E[8] * p.x + c.E[9] * p.y + c.E[10] * p.z + c.E[11];
 	double x = cx / cz, y = cy / cz;
 	if (c.distort)
 	{
@@ -202,29 +110,28 @@ __global__ __launch_bounds__(FH_BLOCK) void project_points_kernel(const double *
 		const double xd = x * radial + (2 * p1 * x * y + p2 * (r2 + 2 * x2)), yd = y * radial + (p1 * (r2 + 2 * y2) + 2 * p2 * x * y);
 		x = xd, y = yd;
 	}
-	const size_t at = (size_t)b * V + v;
-	ij[2 * at] = c.K[0] * x + c.K[1] * y + c.K[2];
-	ij[2 * at + 1] = c.K[3] * x + c.K[4] * y + c.K[5];
-	depths[at] = cz;
+	i = c.K[0] * x + c.K[1] * y + c.K[2];
+	j = c.K[3] * x + c.K[4] * y + c.K[5];
+	depth = cz;
 }
 
-__global__ __launch_bounds__(FH_BLOCK) void project_points_b_kernel(const double *points, const double *extrinsic, const double *intrinsic,
-																	 const double *distortion, const double *ij_b, const double *depths_b, double *points_b, int V,
-																	 int n)
-{ // adjoint of the above (Camera.project_points_backward, dr.py:397-438); depths_b may be NULL
-	const int v = blockIdx.x * FH_BLOCK + threadIdx.x, b = blockIdx.y;
-	if (v >= V)
-		return;
-	const CameraRow c = load_camera(extrinsic, intrinsic, distortion, b);
-	const size_t at = (size_t)b * V + v;
-	const double *pp = points + at * 3;
-	const double px = pp[0], py = pp[1], pz = pp[2];
-	const double cx = c.E[0] * px + c.E[1] * py + c.E[2] * pz + c.E[3], cy = c.E[4] * px + c.E[5] * py + c.E[6] * pz + c.E[7],
-				 cz = c.E[8] * px + c.E[9] * py + c.E[10] * pz + c.E[11];
+// adjoint of the above (Camera.project_points_backward, dr.py:397-438) for (i_b, j_b, depth_b) = (g0, g1, gd): the point's adjoint, and what the
+// adjoints of the camera's own entries are made of (camera_project_b_kernel, dr_camera.h; a caller that wants point_b alone computes nothing else)
+struct ProjectB
+{
+	Vec3 point_b, camera_b;					  // camera_b: the adjoint of pc = R p + T
+	double x, y, xd_b, yd_b;				  // pc.xy / pc.z; the adjoint of the distorted point
+	double r2, r4, radial, radial_b;		  // with distortion only
+};
+__device__ __forceinline__ ProjectB project_point_b(const CameraRow &c, const Vec3 &p, double g0, double g1, double gd)
+{
+	const double cx = c.E[0] * p.x + c.E[1] * p.y + c.E[2] * p.z + c.E[3], cy = c.E[4] * p.x + c.E[5] * p.y + c.E[6] * p.z + c.E[7],
+				 cz = c.E[8] * p.x + c.E[9] * p.y + c.E[10] * p.z + c.E[11];
+	ProjectB r;
 	const double x = cx / cz, y = cy / cz;
-	const double g0 = ij_b[2 * at], g1 = ij_b[2 * at + 1];
-	double xd_b = c.K[0] * g0 + c.K[3] * g1, yd_b = c.K[1] * g0 + c.K[4] * g1;
+	const double xd_b = c.K[0] * g0 + c.K[3] * g1, yd_b = c.K[1] * g0 + c.K[4] * g1;
 	double x_b = xd_b, y_b = yd_b;
+	r.r2 = r.r4 = r.radial_b = 0, r.radial = 1;
 	if (c.distort)
 	{
 		const double k1 = c.d[0], k2 = c.d[1], p1 = c.d[2], p2 = c.d[3], k3 = c.d[4];
@@ -236,12 +143,183 @@ __global__ __launch_bounds__(FH_BLOCK) void project_points_b_kernel(const double
 		const double r2_b = p2 * xd_b + p1 * yd_b + radial_b * (k1 + 2 * k2 * r2 + 3 * k3 * r4);
 		x_b += 2 * x * r2_b;
 		y_b += 2 * y * r2_b;
+		r.r2 = r2, r.r4 = r4, r.radial = radial, r.radial_b = radial_b;
 	}
-	const double cx_b = x_b / cz, cy_b = y_b / cz, cz_b = (depths_b ? depths_b[at] : 0.0) - (x * x_b + y * y_b) / cz;
-	double *o = points_b + at * 3;
-	o[0] = c.E[0] * cx_b + c.E[4] * cy_b + c.E[8] * cz_b;
-	o[1] = c.E[1] * cx_b + c.E[5] * cy_b + c.E[9] * cz_b;
-	o[2] = c.E[2] * cx_b + c.E[6] * cy_b + c.E[10] * cz_b;
+	const double cx_b = x_b / cz, cy_b = y_b / cz, cz_b = gd - (x * x_b + y * y_b) / cz;
+	r.point_b = {c.E[0] * cx_b + c.E[4] * cy_b + c.E[8] * cz_b, c.E[1] * cx_b + c.E[5] * cy_b + c.E[9] * cz_b, c.E[2] * cx_b + c.E[6] * cy_b + c.E[10] * cz_b};
+	r.camera_b = {cx_b, cy_b, cz_b};
+	r.x = x, r.y = y, r.xd_b = xd_b, r.yd_b = yd_b;
+	return r;
+}
+
+constexpr int FH_BLOCK = 256;
+
+// ---- the sum over each group of adjacent lanes whose lane numbers differ in the bits FIRST, 2 FIRST, ... < END (powers of two), in every lane of
+// the group: a butterfly, an order fixed by the lane numbers alone.  All lanes of the wavefront call it.
+template <int FIRST, int END>
+__device__ __forceinline__ double lane_group_sum(double v)
+{
+#pragma unroll
+	for (int d = FIRST; d < END; d <<= 1)
+		v += __shfl_xor(v, d);
+	return v;
+}
+template <int FIRST, int END>
+__device__ __forceinline__ Vec3 lane_group_sum3(const Vec3 &a)
+{
+	return {lane_group_sum<FIRST, END>(a.x), lane_group_sum<FIRST, END>(a.y), lane_group_sum<FIRST, END>(a.z)};
+}
+
+// ---- the arrival ticket: the one memory-ordering protocol of these headers.  Every thread of a workgroup calls it after that thread's partials
+// are stored; n workgroups draw on `counter`, a word that is zero between launches.  -> true in ALL threads of the last workgroup to arrive, whose
+// loads then see every workgroup's partials.  That workgroup calls reset_arrivals once it is done.
+__device__ __forceinline__ bool last_to_arrive(unsigned *counter, unsigned n)
+{
+	__shared__ int s_last;
+	__syncthreads();
+	if (threadIdx.x == 0)
+	{
+		__threadfence(); // release (one thread, after the barrier: the workgroup's partials are visible to the device before its ticket)
+		s_last = atomicAdd(counter, 1u) == n - 1;
+	}
+	__syncthreads();
+	if (!s_last)
+		return false;
+	__threadfence(); // acquire: the loads that follow see every workgroup's partials
+	return true;
+}
+__device__ __forceinline__ void reset_arrivals(unsigned *counter) { if (threadIdx.x == 0) atomicExch(counter, 0u); }
+
+// ---- deterministic grid-wide sums without atomics on the values.  Every thread of every workgroup of a launch (blockIdx.x over the reduced
+// range) brings K values; `partials` holds K doubles per workgroup, `counter` one word for last_to_arrive.  -> true in ALL threads of the last
+// workgroup, whose total[] then holds the sums: the partial of workgroup i is added by thread i mod FH_BLOCK in the order i, i + FH_BLOCK, ...;
+// then the lanes of a wavefront (DPP tree), then the wavefronts in order -- fixed by the launch geometry alone.
+template <int K>
+__device__ __forceinline__ bool grid_sum(const double (&v)[K], double *partials, unsigned *counter, double (&total)[K], unsigned block = blockIdx.x,
+										 unsigned nblocks = gridDim.x)
+{ // (block / nblocks: the position of this workgroup among the ones that take part, for kernels that are a part of a launch)
+	__shared__ double s_wave[FH_BLOCK / 64][K];
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+	for (int k = 0; k < K; k++)
+	{
+		const double s = wave_sum(v[k]);
+		if (lane == 0)
+			s_wave[wave][k] = s;
+	}
+	__syncthreads();
+	if (threadIdx.x < K)
+	{
+		double s = 0;
+		for (int w = 0; w < FH_BLOCK / 64; w++)
+			s += s_wave[w][threadIdx.x];
+		partials[(size_t)block * K + threadIdx.x] = s;
+	}
+	if (!last_to_arrive(counter, nblocks))
+		return false;
+	double mine[K];
+#pragma unroll
+	for (int k = 0; k < K; k++)
+		mine[k] = 0;
+	for (unsigned i = threadIdx.x; i < nblocks; i += FH_BLOCK)
+#pragma unroll
+		for (int k = 0; k < K; k++)
+			mine[k] += partials[(size_t)i * K + k];
+#pragma unroll
+	for (int k = 0; k < K; k++)
+	{
+		const double s = wave_sum(mine[k]);
+		if (lane == 0)
+			s_wave[wave][k] = s; // (every thread is past its reads of s_wave: the barriers of last_to_arrive)
+	}
+	__syncthreads();
+#pragma unroll
+	for (int k = 0; k < K; k++)
+	{
+		total[k] = 0;
+		for (int w = 0; w < FH_BLOCK / 64; w++)
+			total[k] += s_wave[w][k];
+	}
+	reset_arrivals(counter);
+	return true;
+}
+
+// What the last workgroup does with its totals.  Thread k's own: total[k] by a chain of compares (not an indexed register file: that is scratch);
+// 0 for k >= K.
+template <int K>
+__device__ __forceinline__ double total_of_thread(const double (&total)[K], int k)
+{
+	double mine = 0;
+#pragma unroll
+	for (int i = 0; i < K; i++)
+		mine = k == i ? total[i] : mine;
+	return mine;
+}
+// an output that a call either writes or adds to
+__device__ __forceinline__ void store_or_add(double *out, double v, int accumulate) { *out = accumulate ? *out + v : v; }
+
+// ---- rigid transform: out[b][v] = qrot(q[b], v[v]) + t[b]   (q = (x, y, z, w), unit)
+__global__ __launch_bounds__(FH_BLOCK) void rigid_transform_kernel(const double *vc, const double *q, const double *t, double *out, int V, int n)
+{
+	const int v = blockIdx.x * FH_BLOCK + threadIdx.x, b = blockIdx.y;
+	if (v >= V)
+		return;
+	const Vec3 r = qrot_point(load3(q + 4 * b), q[4 * b + 3], load3(vc + 3 * v));
+	double *o = out + ((size_t)b * V + v) * 3;
+	o[0] = r.x + t[3 * b], o[1] = r.y + t[3 * b + 1], o[2] = r.z + t[3 * b + 2]; // (not load3(t): three values read ahead of the stores are 6 VGPRs more)
+}
+
+// adjoint: one thread per vertex walks the views (vc_b[v] = sum over views: no atomics, fixed order); the sums over the vertices --
+// q_b [n,4], t_b [n,3] -- are reduced per wavefront and leave with one atomic per value, wavefront and view (zeroed by the caller)
+__global__ __launch_bounds__(FH_BLOCK) void rigid_transform_b_kernel(const double *vc, const double *q, const double *out_b, double *vc_b, double *q_b,
+																	  double *t_b, int V, int n)
+{
+	const int v = blockIdx.x * FH_BLOCK + threadIdx.x, lane = threadIdx.x & 63;
+	const bool on = v < V;
+	const Vec3 p = on ? load3(vc + 3 * v) : Vec3{0, 0, 0};
+	Vec3 acc = {0, 0, 0};
+	for (int b = 0; b < n; b++)
+	{
+		const Vec3 u = load3(q + 4 * b);
+		const double w = q[4 * b + 3];
+		const Vec3 g = on ? load3(out_b + ((size_t)b * V + v) * 3) : Vec3{0, 0, 0};
+		const QrotB r = qrot_point_b(u, w, p, g);
+		acc = add3(acc, r.p_b);
+		const double sums[7] = {r.u_b.x, r.u_b.y, r.u_b.z, r.w_b, g.x, g.y, g.z};
+#pragma unroll
+		for (int i = 0; i < 7; i++)
+		{
+			const double s = wave_sum(sums[i]); // (every lane takes part: lanes beyond V hold zeros)
+			if (lane == 0 && s != 0)
+				atomic_add_f64(i < 4 ? q_b + 4 * b + i : t_b + 3 * b + (i - 4), s);
+		}
+	}
+	if (on)
+		store3(vc_b + 3 * v, acc);
+}
+
+// ---- projection: project_point and its adjoint, one thread per (view, vertex)
+__global__ __launch_bounds__(FH_BLOCK) void project_points_kernel(const double *points, const double *extrinsic, const double *intrinsic,
+																   const double *distortion, double *ij, double *depths, int V, int n)
+{
+	const int v = blockIdx.x * FH_BLOCK + threadIdx.x, b = blockIdx.y;
+	if (v >= V)
+		return;
+	const CameraRow c = load_camera(extrinsic, intrinsic, distortion, b);
+	const size_t at = (size_t)b * V + v;
+	project_point(c, load3(points + at * 3), ij[2 * at], ij[2 * at + 1], depths[at]);
+}
+
+__global__ __launch_bounds__(FH_BLOCK) void project_points_b_kernel(const double *points, const double *extrinsic, const double *intrinsic,
+																	 const double *distortion, const double *ij_b, const double *depths_b, double *points_b, int V,
+																	 int n)
+{ // depths_b may be NULL
+	const int v = blockIdx.x * FH_BLOCK + threadIdx.x, b = blockIdx.y;
+	if (v >= V)
+		return;
+	const CameraRow c = load_camera(extrinsic, intrinsic, distortion, b);
+	const size_t at = (size_t)b * V + v;
+	store3(points_b + at * 3, project_point_b(c, load3(points + at * 3), ij_b[2 * at], ij_b[2 * at + 1], depths_b ? depths_b[at] : 0.0).point_b);
 }
 
 // ---- silhouette flags: flag[b][f][e] = 1 when exactly one face on edge e of face f is front-facing in view b.

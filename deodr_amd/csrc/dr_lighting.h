@@ -1,5 +1,5 @@
 // Spherical-harmonic lighting (bands 0 - 2) and per-vertex albedo (include/deodr_hip_lighting.h), beside vertex_shade_* of dr_fititer.h: the same
-// vertex normal (accumulated_normal: sign * the sum of the unit normals of the faces around a vertex, GATHER_LANES lanes per vertex), normalised;
+// vertex normal (accumulated_normal: sign * the sum of the unit normals of the faces around a vertex, GATHER_LANES lanes per vertex), normalised by unit() of dr_fronthalf.h;
 //
 //     E[b,v,c] = sum_k sh[k, min(c, S-1)] Y_k(N[b,v])          (not clamped)          colors[b,v,c] = albedo[v or 0, c] E[b,v,c]
 //
@@ -80,8 +80,7 @@ __global__ __launch_bounds__(FH_BLOCK) void sh_shade_kernel(SHArgs a, double *lu
 	const Vec3 acc = accumulated_normal(a.mesh, a.mesh.posed + (size_t)b * V * 3, v, sub, on);
 	if (!on || sub != 0)
 		return;
-	const double len = sqrt(dot3(acc, acc));
-	const Vec3 N = {acc.x / len, acc.y / len, acc.z / len};
+	const Vec3 N = unit(acc).N;
 	double Y[SH_COEFFS];
 	sh_basis(N, Y);
 	const size_t at = (size_t)b * V + v;
@@ -129,8 +128,8 @@ __global__ __launch_bounds__(FH_BLOCK) void sh_shade_b1_kernel(SHArgs a, SHBackA
 		const Vec3 acc = accumulated_normal(a.mesh, a.mesh.posed + (size_t)b * V * 3, v, sub, on);
 		if (on && sub == 0)
 		{ // (no `continue`: every lane is back for the next trip's shuffles)
-			const double len = sqrt(dot3(acc, acc));
-			const Vec3 N = {acc.x / len, acc.y / len, acc.z / len};
+			const Unit n = unit(acc);
+			const Vec3 N = n.N;
 			double Y[SH_COEFFS];
 			sh_basis(N, Y);
 			// E_b[c]: the adjoint of the irradiance of channel c
@@ -151,7 +150,7 @@ __global__ __launch_bounds__(FH_BLOCK) void sh_shade_b1_kernel(SHArgs a, SHBackA
 						else if (o.products)
 							o.products[at * C + c] = p;
 						else if (o.albedo_direct)
-							o.albedo_direct[at * C + c] = o.accumulate ? o.albedo_direct[at * C + c] + p : p; // (one view: at = v)
+							store_or_add(o.albedo_direct + at * C + c, p, o.accumulate); // (one view: at = v)
 					}
 			}
 			Vec3 N_b;
@@ -173,59 +172,36 @@ __global__ __launch_bounds__(FH_BLOCK) void sh_shade_b1_kernel(SHArgs a, SHBackA
 				if (S > 2)
 					N_b = add3(N_b, scale3(E_b[2], sh_dot_gradient(a.sh + 2, S, N)));
 			}
-			const double along = dot3(N, N_b);
-			store3(o.acc_b + 3 * at, {(N_b.x - N.x * along) / len, (N_b.y - N.y * along) / len, (N_b.z - N.z * along) / len});
+			store3(o.acc_b + 3 * at, unit_b(N, n.len, N_b));
 		}
 	}
 	// up to three sums of at most 12 values, each with its own partial range and counter word (one grid_sum of 30 values holds three arrays of 30
-	// doubles at its peak).  Thread k of the last workgroup to arrive has value k: a chain of compares, not an indexed register file.
+	// doubles at its peak).  Thread k of the last workgroup to arrive has value k (total_of_thread).
 	const unsigned B = gridDim.x;
 	const int k = threadIdx.x;
 	{
 		double total[SH_SUMS_FIRST];
 		if (grid_sum<SH_SUMS_FIRST>(s0, o.partials, o.counters, total))
 		{
-			double mine = 0;
-#pragma unroll
-			for (int i = 0; i < SH_SUMS_FIRST; i++)
-				mine = k == i ? total[i] : mine;
 			double *out = k < SH_COEFFS ? (o.sh_b ? o.sh_b + (size_t)k * S : nullptr) : (k < SH_COEFFS + C && o.albedo_b) ? o.albedo_b + (k - SH_COEFFS) : nullptr;
 			if (out)
-				*out = o.accumulate ? *out + mine : mine;
+				store_or_add(out, total_of_thread(total, k), o.accumulate);
 		}
 	}
 	if (S > 1)
 	{
 		double total[SH_COEFFS];
 		if (grid_sum<SH_COEFFS>(s1, o.partials + (size_t)B * SH_SUMS_FIRST, o.counters + 1, total))
-		{
-			double mine = 0;
-#pragma unroll
-			for (int i = 0; i < SH_COEFFS; i++)
-				mine = k == i ? total[i] : mine;
 			if (k < SH_COEFFS && o.sh_b)
-			{
-				double *out = o.sh_b + (size_t)k * S + 1;
-				*out = o.accumulate ? *out + mine : mine;
-			}
-		}
+				store_or_add(o.sh_b + (size_t)k * S + 1, total_of_thread(total, k), o.accumulate);
 	}
 	if (S > 2)
 	{
 		__syncthreads(); // (the same grid_sum<9> as above, the same LDS: its last workgroup may still be reading its totals)
 		double total[SH_COEFFS];
 		if (grid_sum<SH_COEFFS>(s2, o.partials + (size_t)B * (SH_SUMS_FIRST + SH_COEFFS), o.counters + 2, total))
-		{
-			double mine = 0;
-#pragma unroll
-			for (int i = 0; i < SH_COEFFS; i++)
-				mine = k == i ? total[i] : mine;
 			if (k < SH_COEFFS && o.sh_b)
-			{
-				double *out = o.sh_b + (size_t)k * S + 2;
-				*out = o.accumulate ? *out + mine : mine;
-			}
-		}
+				store_or_add(o.sh_b + (size_t)k * S + 2, total_of_thread(total, k), o.accumulate);
 	}
 }
 
@@ -238,7 +214,7 @@ __global__ __launch_bounds__(FH_BLOCK) void sh_albedo_sum_kernel(const double *p
 	double s = products[i];
 	for (int b = 1; b < n; b++)
 		s += products[(size_t)b * count + i];
-	albedo_b[i] = accumulate ? albedo_b[i] + s : s;
+	store_or_add(albedo_b + i, s, accumulate);
 }
 
 } // namespace

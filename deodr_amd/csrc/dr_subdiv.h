@@ -4,8 +4,8 @@
 //
 // One row entry is a chain of two dependent loads (column id -> the D values of that column), so a row walked by ONE lane is the kernel's
 // duration (dr_fititer.h, GATHER_LANES: measured there on rows of the same length).  Lane s of a row's group takes the entries s, s + LANES, ...
-// in order; the lanes' sums meet in a butterfly over the lane bits of the group.  Both orders are fixed by the row alone: no atomics on values,
-// results bit-identical from run to run.  LANES = 8: eight rows per wavefront, the butterfly of lanes_sum; LANES = 64: one row per wavefront, the
+// in order; the lanes' sums meet in a butterfly over the lane bits of the group (lane_group_sum, dr_fronthalf.h).  Both orders are fixed by the row alone: no atomics on values,
+// results bit-identical from run to run.  LANES = 8: eight rows per wavefront, lane_group_sum<1, LANES> of dr_fronthalf.h; LANES = 64: one row per wavefront, the
 // column ids and the values of a round are two coalesced loads.  Arithmetic in double, one rounding to the storage type per stored value.
 #pragma once
 
@@ -26,15 +26,6 @@ constexpr unsigned SUBDIV_LONG_ROW = 32; // nnz / n_rows from which a row gets a
 
 // the one rule both the launch and deodr_hip_subdiv_lanes() follow
 inline int subdiv_lanes(int n_rows, uint32_t nnz) { return nnz / (uint32_t)n_rows >= SUBDIV_LONG_ROW ? SUBDIV_LANES_LONG : SUBDIV_LANES_SHORT; }
-
-template <int LANES>
-__device__ __forceinline__ double subdiv_group_sum(double v)
-{ // all lanes of the wavefront call it; -> the sum over each group of LANES adjacent lanes, in every lane of the group
-#pragma unroll
-	for (int m = 1; m < LANES; m *= 2)
-		v += __shfl_xor(v, m);
-	return v;
-}
 
 // DC: the number of values per column at compile time (3: vertices), 0: a.D at run time, walked in pieces of 4 (the row is read again per piece)
 // grid: (ceil(n_rows LANES / FH_BLOCK), batch)
@@ -68,7 +59,7 @@ __global__ __launch_bounds__(FH_BLOCK) void subdiv_apply_kernel(SubdivArgs a)
 		}
 #pragma unroll
 		for (int c = 0; c < PIECE; c++)
-			acc[c] = subdiv_group_sum<LANES>(acc[c]);
+			acc[c] = lane_group_sum<1, LANES>(acc[c]); // (all lanes of the wavefront take part)
 		if (live && sub == 0)
 		{
 #pragma unroll

@@ -227,6 +227,46 @@ def test_autograd_ops_of_a_point_cloud(V, n):
         close_elem(got, ref[key], key)
 
 
+@pytest.mark.parametrize("distortion", [False, True], ids=["plain", "distorted"])
+@pytest.mark.parametrize("V,n", [(33, 9), (257, 1)])
+def test_fused_and_plain_kernels_share_their_algebra(V, n, distortion):
+    """The pose, the projection and its adjoint exist once in the device code (dr_fronthalf.h), so the fused kernels of a fit iteration and the
+    plain ones give the same BITS: (33, 9) has eight lanes per vertex, two trips over the views and a part-filled second workgroup, (257, 1)
+    the one-lane instances with one vertex past a workgroup."""
+    from deodr_amd import fronthalf
+    from deodr_amd.hip_renderer import _launch, _ptr, lib
+
+    assert_point_regime(V, n)
+    d = point_case(V, n)
+    cam = camera(d, n, distortion)
+    q, t, mean = dev(d["quaternions"]), dev(d["translations"]), dev(d["vertices"].mean(axis=0))
+    arena = Arena()
+    vertices = arena.out(V, 3)
+    posed, ij, depths = arena.out(n, V, 3), arena.out(n, V, 2), arena.out(n, V)
+    vertices.copy_(dev(d["vertices"]))  # (centred in place)
+    fronthalf.fit_pose_project(vertices, mean, q, t, cam, posed, ij, depths)
+    # the projection of the fused kernel = project_points_kernel on the posed vertices it wrote
+    ij_plain, depths_plain = arena.out(n, V, 2), arena.out(n, V)
+    fronthalf.project_points(posed, cam.extrinsic, cam.intrinsic, cam.distortion, ij_plain, depths_plain)
+    assert torch.equal(ij, ij_plain) and torch.equal(depths, depths_plain)
+    # its pose = rigid_transform_kernel with the quaternions normalised as load_unit_quaternion does: every component DIVIDED by the norm
+    x, y, z, w = (d["quaternions"][:, i] for i in range(4))
+    norm = np.sqrt(((x * x + y * y) + z * z) + w * w)
+    unit_q = dev(d["quaternions"] / norm[:, None])
+    posed_plain = arena.out(n, V, 3)
+    _launch(lib().deodr_hip_rigid_transform, posed.device, _ptr(vertices), _ptr(unit_q), _ptr(t), _ptr(posed_plain), V, n)
+    assert torch.equal(posed, posed_plain)
+    if n == 1:  # one view: the sum over the views of the camera adjoints is project_points_b_kernel's one
+        ij_b, depths_b = dev(d["ij_b"]), dev(d["depths_b"])
+        shared_b, points_b = arena.out(V, 3), arena.out(n, V, 3)
+        fronthalf.views_gradient_sum(posed, cam, ij_b, shared_b, depths_b=depths_b, depths_b_scale=fr.DEPTHS_B_SCALE)
+        scaled = depths_b * fr.DEPTHS_B_SCALE  # (one IEEE multiply, as in the kernel)
+        _launch(lib().deodr_hip_project_points_b, posed.device, _ptr(posed), _ptr(cam.extrinsic), _ptr(cam.intrinsic), _ptr(cam.distortion), _ptr(ij_b),
+                _ptr(scaled), _ptr(points_b), V, n)  # fmt: skip
+        assert torch.equal(shared_b, points_b[0])
+    arena.check()
+
+
 def test_more_views_than_fit_max_views_are_refused():
     from deodr_amd import fronthalf
 
