@@ -20,6 +20,7 @@ _COMPANIONS = (
     ("BASIS_HEADER", "deodr_hip_basis.h", False),  # linear bases: morphable models
     ("CAMERA_HEADER", "deodr_hip_camera.h", False),  # camera calibration
     ("LIGHTING_HEADER", "deodr_hip_lighting.h", False),  # spherical-harmonic lighting, per-vertex albedo
+    ("SKINNING_HEADER", "deodr_hip_skinning.h", False),  # linear blend skinning
 )
 
 # C type (without `const`, without spaces around the stars) -> ctypes.  Data pointers are c_void_p: callers pass device addresses (Python

@@ -65,12 +65,14 @@
 #include "../../include/deodr_hip_basis.h"
 #include "../../include/deodr_hip_camera.h"
 #include "../../include/deodr_hip_lighting.h"
+#include "../../include/deodr_hip_skinning.h"
 #include "dr_fititer.h" // <- dr_finalize.h <- dr_backward.h <- dr_backward_generic.h <- dr_forward.h <- dr_forward_generic.h <- dr_setup.h <- dr_workspace.h <- dr_prims.h
 #include "dr_texfit.h"  // texture smoothness + step (include/deodr_hip_texture.h); uses grid_sum of dr_fronthalf.h
 #include "dr_subdiv.h"  // rows of a sparse matrix applied to [batch, n, D] blocks (include/deodr_hip_subdiv.h): Loop subdivision and its adjoint
 #include "dr_basis.h"   // a dense [K, N] basis applied to coefficient vectors, and its adjoint (include/deodr_hip_basis.h): morphable models
 #include "dr_camera.h"  // the camera as a differentiable input: full adjoint of the projection, calibration parameters <-> matrices (include/deodr_hip_camera.h)
 #include "dr_lighting.h" // spherical-harmonic lighting and per-vertex albedo beside vertex_shade_* of dr_fititer.h (include/deodr_hip_lighting.h)
+#include "dr_skinning.h" // linear blend skinning: joint chain, blend of the influences of a vertex, their adjoints (include/deodr_hip_skinning.h)
 
 using namespace dr;
 using namespace dr::dispatch;
@@ -1690,6 +1692,91 @@ int deodr_hip_sh_shade_b(const double *posed, const uint32_t *faces, const uint3
 	if (posed_b)
 		hipLaunchKernelGGL(vertex_shade_b2_kernel, dim3(fh_blocks((long long)V * GATHER_LANES), n), dim3(FH_BLOCK), 0, st, a.mesh, (const double *)o.acc_b, posed_b);
 	return check_hip(hipGetLastError(), "sh_shade_b launch");
+}
+
+// ---- linear blend skinning (include/deodr_hip_skinning.h, kernels in dr_skinning.h)
+
+int deodr_hip_skinning_abi_version(void) { return DEODR_HIP_SKINNING_ABI_VERSION; }
+
+static const char *skin_dims(int V, int J, int K, int n)
+{ // -> NULL, or which limit of the header the dimensions break
+	if (n < 1 || n > FIT_MAX_VIEWS)
+		return "n must be in 1 .. 64";
+	if (J < 1 || J > SKIN_MAX_JOINTS)
+		return "J must be in 1 .. 256";
+	if (K < 1 || K > SKIN_MAX_INFLUENCES)
+		return "K must be in 1 .. 8";
+	if (V < 1 || V > SKIN_MAX_VERTICES)
+		return "V must be in 1 .. 2^24";
+	return NULL;
+}
+
+size_t deodr_hip_skin_scratch_bytes(int V, int J, int K, int n) { return skin_dims(V, J, K, n) ? 0 : scratch_need((size_t)n * J * SKIN_CHAIN_B); }
+
+int deodr_hip_skin_apply(const double *vertices, const double *joints, const uint32_t *parents, const double *quaternions, const uint32_t *indices,
+						 const double *weights, double *world, double *posed, int V, int J, int K, int n, void *stream)
+{
+	const char *what = "skin_apply";
+	if (!vertices || !joints || !parents || !quaternions || !indices || !weights || !world || !posed)
+		return fail(what, "vertices, joints, parents, quaternions, indices, weights, world or posed == NULL");
+	if (const char *why = skin_dims(V, J, K, n))
+		return fail(what, why);
+	const void *const doubles[] = {vertices, joints, quaternions, weights, world, posed};
+	const void *const words[] = {parents, indices};
+	if (any_misaligned(doubles, 8) || any_misaligned(words, 4))
+		return fail(what, "misaligned pointer");
+	const size_t v3 = 24 * (size_t)V, nj = (size_t)n * J, vk = (size_t)V * K;
+	const Range outputs[] = {{world, 8 * SKIN_WORLD * nj}, {posed, n * v3}};
+	const Range inputs[] = {{vertices, v3}, {joints, 24 * (size_t)J}, {parents, 4 * (size_t)J}, {quaternions, 32 * nj}, {indices, 4 * vk}, {weights, 8 * vk}};
+	if (any_overlap(outputs, inputs) || ranges_overlap(world, 8 * SKIN_WORLD * nj, posed, n * v3))
+		return fail(what, "an output must not overlap an input or the other output");
+	const SkinArgs a = {vertices, joints, quaternions, parents, indices, weights, V, J, K, n};
+	const hipStream_t st = (hipStream_t)stream;
+	hipLaunchKernelGGL(skin_chain_kernel, dim3(1), dim3(FIT_MAX_VIEWS), 0, st, a, world);
+	hipLaunchKernelGGL(skin_apply_kernel, dim3(fh_blocks((long long)V * GATHER_LANES), n), dim3(FH_BLOCK), 0, st, a, (const double *)world, posed);
+	return check_hip(hipGetLastError(), "skin_apply launch");
+}
+
+int deodr_hip_skin_apply_b(const double *vertices, const double *joints, const uint32_t *parents, const double *quaternions, const uint32_t *indices,
+						   const double *weights, const double *world, const double *posed_b, const uint32_t *joint_offsets,
+						   const uint32_t *joint_slots, int nnz, double *vertices_b, double *quaternions_b, double *joints_b, void *scratch,
+						   size_t scratch_bytes, int V, int J, int K, int n, void *stream)
+{
+	const char *what = "skin_apply_b";
+	if (!vertices || !joints || !parents || !quaternions || !indices || !weights || !world || !posed_b || !joint_offsets || !joint_slots || !scratch)
+		return fail(what, "vertices, joints, parents, quaternions, indices, weights, world, posed_b, joint_offsets, joint_slots or scratch == NULL");
+	if (!vertices_b && !quaternions_b && !joints_b)
+		return fail(what, "no output requested (vertices_b, quaternions_b, joints_b)");
+	if (const char *why = skin_dims(V, J, K, n))
+		return fail(what, why);
+	if (nnz < 0 || (long long)nnz > (long long)V * K)
+		return fail(what, "nnz must be in 0 .. V K");
+	const void *const doubles[] = {vertices, joints, quaternions, weights, world, posed_b, vertices_b, quaternions_b, joints_b, scratch};
+	const void *const words[] = {parents, indices, joint_offsets, joint_slots};
+	if (any_misaligned(doubles, 8) || any_misaligned(words, 4))
+		return fail(what, "misaligned pointer");
+	const Scratch sc = {scratch, scratch_bytes};
+	if (!sc.holds(deodr_hip_skin_scratch_bytes(V, J, K, n)))
+		return fail(what, "scratch too small (deodr_hip_skin_scratch_bytes)");
+	const size_t v3 = 24 * (size_t)V, nj = (size_t)n * J, vk = (size_t)V * K;
+	const Range outputs[] = {{vertices_b, v3}, {quaternions_b, 32 * nj}, {joints_b, 24 * (size_t)J}, {scratch, scratch_bytes}};
+	const Range inputs[] = {{vertices, v3}, {joints, 24 * (size_t)J}, {parents, 4 * (size_t)J}, {quaternions, 32 * nj}, {indices, 4 * vk}, {weights, 8 * vk},
+							{world, 8 * SKIN_WORLD * nj}, {posed_b, n * v3}, {joint_offsets, 4 * ((size_t)J + 1)}, {joint_slots, 4 * (size_t)nnz}};
+	const Range written[] = {{vertices_b, v3}, {quaternions_b, 32 * nj}, {joints_b, 24 * (size_t)J}};
+	const Range scratch_range[] = {{scratch, scratch_bytes}};
+	if (any_overlap(outputs, inputs) || any_overlap(written, scratch_range) || ranges_overlap(vertices_b, v3, quaternions_b, 32 * nj) ||
+		ranges_overlap(vertices_b, v3, joints_b, 24 * (size_t)J) || ranges_overlap(quaternions_b, 32 * nj, joints_b, 24 * (size_t)J))
+		return fail(what, "an output must not overlap an input, the scratch or another output");
+	const SkinArgs a = {vertices, joints, quaternions, parents, indices, weights, V, J, K, n};
+	const hipStream_t st = (hipStream_t)stream;
+	if (vertices_b)
+		hipLaunchKernelGGL(skin_apply_b_kernel, dim3(fh_blocks((long long)V * GATHER_LANES)), dim3(FH_BLOCK), 0, st, a, world, posed_b, vertices_b);
+	if (quaternions_b || joints_b)
+	{
+		hipLaunchKernelGGL(skin_joint_b_kernel, dim3(J, n), dim3(FH_BLOCK), 0, st, a, world, posed_b, joint_offsets, joint_slots, (uint32_t)nnz, sc.doubles());
+		hipLaunchKernelGGL(skin_chain_b_kernel, dim3(1), dim3(FH_BLOCK), 0, st, a, world, sc.doubles(), quaternions_b, joints_b);
+	}
+	return check_hip(hipGetLastError(), "skin_apply_b launch");
 }
 
 #ifdef DR_WAVE_TRACE

@@ -410,6 +410,35 @@ class SHShadeFunc(torch.autograd.Function):
         return posed_b, sh_b, albedo_b, None
 
 
+def _skin_scratch(skin, n):
+    """one scratch per (skin, number of poses), for the autograd wrapper (the kernels of one stream run one after the other)"""
+    cache = skin.__dict__.setdefault("_skin_scratch", {})
+    if n not in cache:
+        cache[n] = hr.skin_scratch(skin.V, skin.J, skin.K, n, skin.device)
+    return cache[n]
+
+
+class SkinFunc(torch.autograd.Function):
+    """(vertices [V,3], quaternions [n,J,4] raw, joints [J,3]; skin: a ``deodr_amd.skinning.Skin``) -> posed [n,V,3]: linear blend skinning
+    (``deodr_amd/skinning.py`` has the formulas) in two launches; the adjoint -- gradients to all three -- in up to three (``deodr_hip_skin_apply_b``)."""
+
+    @staticmethod
+    def forward(ctx, vertices, quaternions, joints, skin):
+        v, q, c = vertices.contiguous(), quaternions.contiguous(), joints.contiguous()
+        world, posed = hr.skin_apply(v, c, skin.parents, q, skin.indices, skin.weights)
+        ctx.save_for_backward(v, q, c, world)
+        ctx.skin = skin
+        return posed
+
+    @staticmethod
+    def backward(ctx, posed_b):
+        v, q, c, world = ctx.saved_tensors
+        skin = ctx.skin
+        v_b, q_b, c_b = hr.skin_apply_b(v, c, skin.parents, q, skin.indices, skin.weights, world, posed_b.contiguous(), skin.joint_offsets,
+                                        skin.joint_slots, scratch=_skin_scratch(skin, q.shape[0]), want=ctx.needs_input_grad[:3])  # fmt: skip
+        return v_b, q_b, c_b, None
+
+
 def sh_shade(posed, sh, albedo, topology):
     """-> luminosity [n,V] (``albedo`` None) or colors [n,V,C] of the posed vertices [n,V,3] (or [V,3]) under the SH lighting ``sh``, differentiable in
     all three: the kernels on float64 ROCm tensors, the same formulas as torch ops (``lighting.sh_shade_torch``) otherwise"""

@@ -36,8 +36,9 @@ _COMPANIONS = (
     (_abi.BASIS_HEADER, "basis", "linear-basis"),  # linear bases: morphable models
     (_abi.CAMERA_HEADER, "camera", "camera"),  # camera calibration
     (_abi.LIGHTING_HEADER, "lighting", "lighting"),  # spherical-harmonic lighting, per-vertex albedo
+    (_abi.SKINNING_HEADER, "skinning", "skinning"),  # linear blend skinning
 )
-TEXTURE_ABI_VERSION, SUBDIV_ABI_VERSION, RETAINED_ABI_VERSION, BASIS_ABI_VERSION, CAMERA_ABI_VERSION, LIGHTING_ABI_VERSION = (
+TEXTURE_ABI_VERSION, SUBDIV_ABI_VERSION, RETAINED_ABI_VERSION, BASIS_ABI_VERSION, CAMERA_ABI_VERSION, LIGHTING_ABI_VERSION, SKINNING_ABI_VERSION = (
     h.defines[f"DEODR_HIP_{key.upper()}_ABI_VERSION"] for h, key, _ in _COMPANIONS
 )
 # words of the 64-byte status block at the start of the workspace
@@ -1219,6 +1220,95 @@ def sh_shade_b(posed, faces, vf_offsets, vf_corners, sh, albedo=None, luminosity
         if t is not None:
             _touched(t)
     return posed_b, sh_b, albedo_b
+
+
+# ---- linear blend skinning (include/deodr_hip_skinning.h) ---------------------------------------------------------------------------------
+
+SKIN_MAX_VIEWS, SKIN_MAX_JOINTS, SKIN_MAX_INFLUENCES, SKIN_MAX_VERTICES = 64, 256, 8, 2**24  # the limits include/deodr_hip_skinning.h states
+
+
+def skin_scratch(V, J, K, n, device):
+    """the scratch of :func:`skin_apply_b` for V vertices, J joints, K influences per vertex and n poses (one per stream in use)"""
+    need = int(lib().deodr_hip_skin_scratch_bytes(int(V), int(J), int(K), int(n)))
+    if need == 0:
+        raise ValueError(f"skin_scratch: V = {V}, J = {J}, K = {K}, n = {n} is outside the limits of include/deodr_hip_skinning.h")
+    with torch.cuda.device(device):
+        return torch.zeros(need, dtype=torch.uint8, device=device)
+
+
+def _skin_args(what, vertices, joints, parents, quaternions, indices, weights):
+    """checks before the library is called -> (V, J, K, n, rows of :func:`_check_tensors` for the inputs)"""
+    _rocm_tensor(what, "vertices", vertices)
+    if vertices.dim() != 2 or int(vertices.shape[1]) != 3 or not 1 <= int(vertices.shape[0]) <= SKIN_MAX_VERTICES:
+        raise ValueError(f"{what}: vertices must have shape [1 <= V <= 2^24, 3], not {list(vertices.shape)}")
+    V = int(vertices.shape[0])
+    if not torch.is_tensor(quaternions) or quaternions.dim() != 3 or int(quaternions.shape[2]) != 4 or not 1 <= int(quaternions.shape[0]) <= SKIN_MAX_VIEWS \
+            or not 1 <= int(quaternions.shape[1]) <= SKIN_MAX_JOINTS:  # fmt: skip
+        raise ValueError(f"{what}: quaternions must have shape [1 <= n <= {SKIN_MAX_VIEWS}, 1 <= J <= {SKIN_MAX_JOINTS}, 4], not "
+                         f"{list(getattr(quaternions, 'shape', ()))}")  # fmt: skip
+    n, J = int(quaternions.shape[0]), int(quaternions.shape[1])
+    if not torch.is_tensor(indices) or indices.dim() != 2 or int(indices.shape[0]) != V or not 1 <= int(indices.shape[1]) <= SKIN_MAX_INFLUENCES:
+        raise ValueError(f"{what}: indices must have shape [{V}, 1 <= K <= {SKIN_MAX_INFLUENCES}], not {list(getattr(indices, 'shape', ()))}")
+    K = int(indices.shape[1])
+    rows = [("vertices", vertices, _F64_ONLY, (V, 3)), ("joints", joints, _F64_ONLY, (J, 3)), ("parents", parents, _I32_ONLY, (J,)),
+            ("quaternions", quaternions, _F64_ONLY, (n, J, 4)), ("indices", indices, _I32_ONLY, (V, K)), ("weights", weights, _F64_ONLY, (V, K))]  # fmt: skip
+    return V, J, K, n, rows
+
+
+def skin_apply(vertices, joints, parents, quaternions, indices, weights, world=None, posed=None):
+    """``deodr_hip_skin_apply``: linear blend skinning in two launches.  ``vertices`` [V,3], ``joints`` [J,3], ``quaternions`` [n,J,4] (raw), ``weights``
+    [V,K] float64 ROCm tensors; ``parents`` [J], ``indices`` [V,K] int32 (the uint32 tables of the header) -> (world [n,J,7], posed [n,V,3]).
+    The tables are NOT checked here (:class:`deodr_amd.skinning.Skin` does that on the host); the kernels skip what is out of range."""
+    what = "skin_apply"
+    V, J, K, n, rows = _skin_args(what, vertices, joints, parents, quaternions, indices, weights)
+    rows += [(name, t, _F64_ONLY, shape) for name, t, shape in (("world", world, (n, J, 7)), ("posed", posed, (n, V, 3))) if t is not None]
+    _check_tensors(what, "vertices", vertices.device, rows)
+    dev = vertices.device
+    with torch.cuda.device(dev):
+        world = torch.empty((n, J, 7), dtype=torch.float64, device=dev) if world is None else world
+        posed = torch.empty((n, V, 3), dtype=torch.float64, device=dev) if posed is None else posed
+    _launch(lib().deodr_hip_skin_apply, dev, _ptr(vertices), _ptr(joints), _ptr(parents), _ptr(quaternions), _ptr(indices), _ptr(weights), _ptr(world),
+            _ptr(posed), V, J, K, n)  # fmt: skip
+    _touched(world), _touched(posed)
+    return world, posed
+
+
+def skin_apply_b(vertices, joints, parents, quaternions, indices, weights, world, posed_b, joint_offsets, joint_slots, vertices_b=None,
+                 quaternions_b=None, joints_b=None, scratch=None, want=(True, True, True)):
+    """``deodr_hip_skin_apply_b``: the adjoint of :func:`skin_apply` -> (vertices_b [V,3] | None, quaternions_b [n,J,4] | None, joints_b [J,3] | None),
+    allocated where not given and ``want`` asks for them.  ``world`` [n,J,7] from the forward call; ``joint_offsets`` [J+1], ``joint_slots`` [nnz] the
+    transposed table (int32).  Deterministic; asynchronous on the current stream.  ``scratch``: a :func:`skin_scratch` of the caller's; None: one per
+    device and stream."""
+    what = "skin_apply_b"
+    V, J, K, n, rows = _skin_args(what, vertices, joints, parents, quaternions, indices, weights)
+    rows += [("world", world, _F64_ONLY, (n, J, 7)), ("posed_b", posed_b, _F64_ONLY, (n, V, 3)), ("joint_offsets", joint_offsets, _I32_ONLY, (J + 1,)),
+             ("joint_slots", joint_slots, _I32_ONLY, (None,))]  # fmt: skip
+    optional = (("vertices_b", vertices_b, (V, 3)), ("quaternions_b", quaternions_b, (n, J, 4)), ("joints_b", joints_b, (J, 3)))
+    rows += [(name, t, _F64_ONLY, shape) for name, t, shape in optional if t is not None]
+    if scratch is not None:
+        rows.append(("scratch", scratch, (torch.uint8,), (None,)))
+    _check_tensors(what, "vertices", vertices.device, rows)
+    nnz = int(joint_slots.shape[0])
+    if nnz > V * K:
+        raise ValueError(f"{what}: joint_slots must have at most V K = {V * K} entries, not {nnz}")
+    if not any(w or t is not None for w, t in zip(want, (vertices_b, quaternions_b, joints_b))):
+        raise ValueError(f"{what}: no output requested")
+    dev = vertices.device
+    with torch.cuda.device(dev):
+        vertices_b, quaternions_b, joints_b = (torch.empty(shape, dtype=torch.float64, device=dev) if t is None and w else t
+                                               for w, (_, t, shape) in zip(want, optional))  # fmt: skip
+        if scratch is None:
+            scratch = _cached_scratch("skin", dev, int(lib().deodr_hip_skin_scratch_bytes(V, J, K, n)), lambda: skin_scratch(V, J, K, n, dev),
+                                      f"{what}: pass scratch= (skin_scratch) when capturing a graph: none of this size exists for this stream yet")  # fmt: skip
+    # (a table without entries: torch gives an empty tensor no address, the library wants one it never reads)
+    slots = joint_slots if nnz else joint_offsets
+    _launch(lib().deodr_hip_skin_apply_b, dev, _ptr(vertices), _ptr(joints), _ptr(parents), _ptr(quaternions), _ptr(indices), _ptr(weights), _ptr(world),
+            _ptr(posed_b), _ptr(joint_offsets), _ptr(slots), nnz, _ptr(vertices_b), _ptr(quaternions_b), _ptr(joints_b), _ptr(scratch), scratch.numel(),
+            V, J, K, n)  # fmt: skip
+    for t in (vertices_b, quaternions_b, joints_b):
+        if t is not None:
+            _touched(t)
+    return vertices_b, quaternions_b, joints_b
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -314,15 +314,27 @@ class _PoseFitter:
     derived vertices against the mean (same ``cregu``) + ``coefficient_regu sum((c / sigmas)**2)`` (``sigmas`` [K], None: ones).  The coefficient
     gradient is the basis adjoint (one kernel, deodr_amd/basis.py) of the total vertex gradient plus the prior's; the update is the momentum rule with
     ``step_factor_coefficients`` and the fourth entry of ``step_max``.  With ``subdivisions`` the two compose: basis, then cage, then subdivision.
-    The iteration runs through autograd, as a subdivided fit does."""
+    The iteration runs through autograd, as a subdivided fit does.
+
+    ``skin`` (None: off, every path as it is without the keyword): a :class:`deodr_amd.skinning.Skin` of the mesh -- an articulated object.
+    ``self.joint_quaternions`` [J,4] is one more parameter (identity after ``reset()``, or ``joint_quaternions_init``), one pose of the skeleton shared
+    by all views.  What is rendered is ``qrot(q_view, skin.apply(vertices, joint_quaternions) - mean(vertices)) + t_view``: the skin acts in the frame
+    the vertices and the joints were given in, then the mean of the rest vertices is subtracted (the vertices are then NOT re-centred between steps:
+    they stay in the frame of the joints).  The rigid energy acts on the rest vertices as before; with ``shape_basis`` the basis comes first, the skin
+    second.  The update is one more momentum entry with ``step_factor_joints``, rows renormalised; ``joint_regu >= 0`` adds the prior
+    ``joint_regu sum |q - q_init|^2``.  The iteration runs through autograd; ``skin`` with ``subdivisions > 0`` is refused."""
 
     direct = True  # run an iteration as the fixed kernel sequence of _DirectIteration when the tensors allow it (False: always autograd)
 
     step_factor_vertices, step_factor_quaternion, step_factor_translation = 0.0005, 0.00006, 0.00005
     step_factor_coefficients = 0.0005  # (with an orthonormal basis a step of the coefficients moves the vertices as far as the same step of the vertices)
+    # What the depth fits of the four-joint hand at 64 x 64 pixels are run with (tests/test_skinning_fit_host.py, first energy 3.4); the rig whose
+    # first energy is 50 overshoots with it and converges with 1e-4.  The data gradient is a sum over the pixels: a step factor that suits one
+    # image size scales with the inverse of the number of pixels.
+    step_factor_joints = 0.0003
 
     def __init__(self, vertices, faces, euler_init, translation_init, cregu, inertia, damping, device, n_poses=1, clockwise=False, pixel_dtype=torch.float64,
-                 subdivisions=0, shape_basis=None, coefficient_regu=0.0, sigmas=None):  # fmt: skip
+                 subdivisions=0, shape_basis=None, coefficient_regu=0.0, sigmas=None, skin=None, joint_quaternions_init=None, joint_regu=0.0):  # fmt: skip
         self.device = torch.device(device)
         self.cregu, self.inertia, self.damping = cregu, inertia, damping
         v0 = np.asarray(vertices, dtype=np.float64)
@@ -353,6 +365,9 @@ class _PoseFitter:
             self.shape_basis = basis.with_mean(self.vertices_init)
             self.coefficient_regu = float(coefficient_regu)
             self._prior = _GaussianPrior(sigmas, self.shape_basis.K, self.coefficient_regu, self.device)
+        self.skin = skin
+        if skin is not None:
+            self._init_skin(v0, joint_quaternions_init, joint_regu)
         q0 = np.asarray([_quat_from_euler_zyx(e) for e in np.atleast_2d(euler_init)])
         t0 = np.atleast_2d(np.asarray(translation_init, dtype=np.float64))
         self.transform_quaternion_init = torch.as_tensor(np.broadcast_to(q0, (n_poses, 4)).copy(), device=self.device)
@@ -360,10 +375,28 @@ class _PoseFitter:
         self.object_center, self.object_radius = v0.mean(axis=0), float(np.max(np.std(v0, axis=0)))
         self.reset()
 
+    def _init_skin(self, v0, joint_quaternions_init, joint_regu):
+        skin = self.skin
+        if self.subdivisions:
+            raise ValueError("skin with subdivisions > 0 is not supported (the skin of a subdivided cage is out of scope)")
+        if skin.V != v0.shape[0]:
+            raise ValueError(f"skin: a Skin of {skin.V} vertices for a mesh of {v0.shape[0]}")
+        if skin.device != self.vertices_init.device:
+            raise ValueError(f"skin: the Skin lives on {skin.device}, the fitter on {self.vertices_init.device}")
+        if not joint_regu >= 0:
+            raise ValueError("joint_regu must be >= 0")
+        q = np.tile([0.0, 0.0, 0.0, 1.0], (skin.J, 1)) if joint_quaternions_init is None else np.array(joint_quaternions_init, dtype=np.float64)
+        if q.shape != (skin.J, 4):
+            raise ValueError(f"joint_quaternions_init must have shape [{skin.J}, 4], not {list(q.shape)}")
+        self.joint_regu = float(joint_regu)
+        self.joint_quaternions_init = torch.as_tensor(q / np.linalg.norm(q, axis=1, keepdims=True), device=self.device)
+
     def reset(self):
         self.vertices = self.vertices_init.clone()
         if self.shape_basis is not None:
             self.coefficients = torch.zeros(self.shape_basis.K, dtype=torch.float64, device=self.device)
+        if self.skin is not None:
+            self.joint_quaternions = self.joint_quaternions_init.clone()
         self.transform_quaternion = self.transform_quaternion_init.clone()
         self.transform_translation = self.transform_translation_init.clone()
         self.momentum = _Momentum(self.inertia, self.damping)
@@ -379,7 +412,10 @@ class _PoseFitter:
         from . import fronthalf
 
         q = self.transform_quaternion_leaf / self.transform_quaternion_leaf.norm(dim=-1, keepdim=True)
-        centred = vertices - vertices.mean(dim=0, keepdim=True)
+        if self.skin is not None:  # (skinned in the frame of the joints, then moved by the mean of the rest vertices: one articulated pose for all views)
+            centred = self.skin.apply(vertices, self.joint_quaternions_leaf) - vertices.mean(dim=0, keepdim=True)
+        else:
+            centred = vertices - vertices.mean(dim=0, keepdim=True)
         if self.subdivisions:  # (centring commutes with S: its rows sum to 1.  Centred first, the data gradient arrives on the cage projected on zero-mean displacements)
             control = centred
             centred = self.subdivision.apply(control)
@@ -391,12 +427,22 @@ class _PoseFitter:
     def _leaves(self, extra=()):
         if self.shape_basis is not None:  # the vertices are derived: mean + coefficients . basis (not centred: _transformed does that in the graph)
             self.vertices = self.shape_basis.apply(self.coefficients)
-        else:
+        elif self.skin is None:  # (with a skin the vertices stay in the frame of the joints: _transformed subtracts their mean in the graph)
             self.vertices = self.vertices - self.vertices.mean(dim=0, keepdim=True)
         self.vertices_leaf = self.vertices.detach().requires_grad_(True)
         self.transform_quaternion_leaf = self.transform_quaternion.detach().requires_grad_(True)
         self.transform_translation_leaf = self.transform_translation.detach().requires_grad_(True)
-        return [self.vertices_leaf, self.transform_quaternion_leaf, self.transform_translation_leaf] + list(extra)
+        leaves = [self.vertices_leaf, self.transform_quaternion_leaf, self.transform_translation_leaf] + list(extra)
+        if self.skin is not None:  # the last leaf: _without_joint_gradient takes its gradient off the list again
+            self.joint_quaternions_leaf = self.joint_quaternions.detach().requires_grad_(True)
+            leaves.append(self.joint_quaternions_leaf)
+        return leaves
+
+    def _without_joint_gradient(self, grads):
+        """the gradients of :meth:`_leaves` without that of the joint quaternions, which is kept for :meth:`_update_pose_and_shape`"""
+        grads = list(grads)
+        self._g_joints = grads.pop() if self.skin is not None else None
+        return grads
 
     def coefficients_gradient(self, g_vertices):
         """-> (basis adjoint of a vertex gradient [V,3], gradient of the prior ``coefficient_regu sum((c / sigmas)**2)``), both [K]"""
@@ -404,6 +450,8 @@ class _PoseFitter:
 
     def _energy_with_prior(self, energy):
         """``energy`` + the coefficient prior of a fit with ``shape_basis`` (of the parameters the gradients were taken at)"""
+        if self.skin is not None and self.joint_regu:
+            energy = energy + self.joint_regu * ((self.joint_quaternions - self.joint_quaternions_init) ** 2).sum()
         return energy if self.shape_basis is None else energy + self._prior.energy(self.coefficients)
 
     def _update_pose_and_shape(self, g_vertices, g_quaternion, g_translation, grad_rigidity, step_max, extra=()):
@@ -419,9 +467,14 @@ class _PoseFitter:
             ("quaternion", self.transform_quaternion, g_quaternion, None, self.step_factor_quaternion, step_max[1], 4),  # renormalised per view
             ("translation", self.transform_translation, g_translation, None, self.step_factor_translation, step_max[2], 0),
         ] + list(extra)
+        if self.skin is not None:  # one pose of the skeleton, rows renormalised as the view quaternions are
+            g_prior = _prior_gradient(self.joint_regu, 1.0, self.joint_quaternions - self.joint_quaternions_init) if self.joint_regu else None
+            entries.append(("joint_quaternions", self.joint_quaternions, self._g_joints, g_prior, self.step_factor_joints, None, 4))
         new = self.momentum.update_all(entries)
         setattr(self, shape[0], new[0])
         self.transform_quaternion, self.transform_translation = new[1:3]
+        if self.skin is not None:
+            self.joint_quaternions = new.pop()
         self.iter += 1
         return new[3:]
 
@@ -433,7 +486,7 @@ class _PoseFitter:
         sequence fold the centring and the gradient mean into passes keyed to the RENDERED vertex array, which is then not the parameter)"""
         from . import fronthalf
 
-        if self.subdivisions or self.shape_basis is not None:  # (with a basis the rendered vertex array is not the parameter either)
+        if self.subdivisions or self.shape_basis is not None or self.skin is not None:  # (with a basis or a skin the rendered vertex array is not the parameter either)
             return None
 
         topo = self.mesh.topology
@@ -507,9 +560,10 @@ class MeshDepthFitter(_PoseFitter):
     """Fit a deformable mesh to a depth image (reference deodr/mesh_fitter.py:20-196)."""
 
     def __init__(self, vertices, faces, euler_init, translation_init, cregu=2000, inertia=0.96, damping=0.05, device="cuda", pixel_dtype=torch.float64,
-                 subdivisions=0, shape_basis=None, coefficient_regu=0.0, sigmas=None):  # fmt: skip
+                 subdivisions=0, shape_basis=None, coefficient_regu=0.0, sigmas=None, skin=None, joint_quaternions_init=None, joint_regu=0.0):  # fmt: skip
         super().__init__(vertices, faces, euler_init, translation_init, cregu, inertia, damping, device, pixel_dtype=pixel_dtype, subdivisions=subdivisions,
-                         shape_basis=shape_basis, coefficient_regu=coefficient_regu, sigmas=sigmas)  # fmt: skip
+                         shape_basis=shape_basis, coefficient_regu=coefficient_regu, sigmas=sigmas, skin=skin,
+                         joint_quaternions_init=joint_quaternions_init, joint_regu=joint_regu)  # fmt: skip
         self.camera_center = self.object_center + np.array([-0.5, 0, 5]) * self.object_radius
 
     def set_max_depth(self, max_depth):
@@ -575,7 +629,7 @@ class MeshDepthFitter(_PoseFitter):
             return self._step_direct(d)
         leaves = self._leaves()
         e_data, e_rigid, g_rigid, depth, diff_image = self.energy()
-        g_v, g_q, g_t = torch.autograd.grad(e_data, leaves)
+        g_v, g_q, g_t = self._without_joint_gradient(torch.autograd.grad(e_data, leaves))
         energy = self._energy_with_prior(e_data + e_rigid)
         self._update_pose_and_shape(g_v, g_q, g_t, g_rigid, (1, 0.1, 0.1, 1))
         return energy, depth.detach(), diff_image.detach()
@@ -643,14 +697,16 @@ class MeshRGBFitterWithPose(_PoseFitter):
 
     def __init__(self, vertices, faces, euler_init, translation_init, default_color, default_light_directional, default_light_ambient, cregu=2000,
                  inertia=0.96, damping=0.05, update_lights=True, update_color=True, device="cuda", pixel_dtype=torch.float64, n_poses=1,
-                 subdivisions=0, shape_basis=None, coefficient_regu=0.0, sigmas=None, light_sh_init=None, vertex_albedo=False, albedo_regu=0.0):  # fmt: skip
+                 subdivisions=0, shape_basis=None, coefficient_regu=0.0, sigmas=None, light_sh_init=None, vertex_albedo=False, albedo_regu=0.0,
+                 skin=None, joint_quaternions_init=None, joint_regu=0.0):  # fmt: skip
         self.default_color = np.asarray(default_color, dtype=np.float64)
         self._init_lighting(light_sh_init, vertex_albedo, albedo_regu)
         self.default_light_directional = np.asarray(default_light_directional, dtype=np.float64)
         self.default_light_ambient = float(default_light_ambient)
         self.update_lights, self.update_color = update_lights, update_color
         super().__init__(vertices, faces, euler_init, translation_init, cregu, inertia, damping, device, n_poses=n_poses, pixel_dtype=pixel_dtype,
-                         subdivisions=subdivisions, shape_basis=shape_basis, coefficient_regu=coefficient_regu, sigmas=sigmas)  # fmt: skip
+                         subdivisions=subdivisions, shape_basis=shape_basis, coefficient_regu=coefficient_regu, sigmas=sigmas, skin=skin,
+                         joint_quaternions_init=joint_quaternions_init, joint_regu=joint_regu)  # fmt: skip
         self.camera_center = self.object_center + np.atleast_2d(np.asarray(translation_init, dtype=np.float64))[0] + np.array([0, 0, 9]) * self.object_radius
 
     step_factor_light_sh, step_factor_albedo = 0.0001, 0.00001  # (those of the directional light and of the single colour)
@@ -811,8 +867,11 @@ class MeshRGBFitterWithPose(_PoseFitter):
         e_data, image = self._data_energy()
         e_rigid, g_rigid = self.rigid_energy.evaluate(self.vertices_leaf.detach())
         e_albedo, g_albedo = self._albedo_smoothness() if sh else (None, None)
-        g_v, g_q, g_t, g_col, *g_lights = torch.autograd.grad(e_data, leaves)
-        g_v, g_col, *g_lights, e_data = self._reduce_shared([g_v, g_col, *g_lights, e_data.detach()])
+        g_v, g_q, g_t, g_col, *g_lights = self._without_joint_gradient(torch.autograd.grad(e_data, leaves))
+        if self.skin is None:
+            g_v, g_col, *g_lights, e_data = self._reduce_shared([g_v, g_col, *g_lights, e_data.detach()])
+        else:  # (the pose of the skeleton is shared by the views, as the vertices are)
+            g_v, g_col, *g_lights, self._g_joints, e_data = self._reduce_shared([g_v, g_col, *g_lights, self._g_joints, e_data.detach()])
         updates = self._appearance_updates(g_col, g_lights, g_albedo)
         energy = self._energy_with_prior(e_data + e_rigid + e_albedo if sh else e_data + e_rigid)
         flat = lambda t: t.reshape(1) if t.dim() == 0 else t  # (``light_ambient`` is a scalar tensor: one row of one element for the update, () again after it)
@@ -862,7 +921,8 @@ class MeshRGBFitterWithPoseMultiFrame(MeshRGBFitterWithPose):
 
     def __init__(self, vertices, faces, euler_init, translation_init, default_color, default_light_directional, default_light_ambient, cregu=2000,
                  cdata=1, inertia=0.97, damping=0.15, update_lights=True, update_color=True, device="cuda", pixel_dtype=torch.float64, group=None,
-                 subdivisions=0, shape_basis=None, coefficient_regu=0.0, sigmas=None, light_sh_init=None, vertex_albedo=False, albedo_regu=0.0):  # fmt: skip
+                 subdivisions=0, shape_basis=None, coefficient_regu=0.0, sigmas=None, light_sh_init=None, vertex_albedo=False, albedo_regu=0.0,
+                 skin=None, joint_quaternions_init=None, joint_regu=0.0):  # fmt: skip
         euler_init, translation_init = np.atleast_2d(euler_init), np.atleast_2d(translation_init)
         self.cdata = cdata
         self.n_views_total = max(len(euler_init), len(translation_init))
@@ -875,7 +935,8 @@ class MeshRGBFitterWithPoseMultiFrame(MeshRGBFitterWithPose):
         super().__init__(vertices, faces, pick(euler_init), pick(translation_init), default_color, default_light_directional, default_light_ambient,
                          cregu, inertia, damping, update_lights, update_color, device, pixel_dtype, n_poses=len(self.my_views), subdivisions=subdivisions,
                          shape_basis=shape_basis, coefficient_regu=coefficient_regu, sigmas=sigmas, light_sh_init=light_sh_init,
-                         vertex_albedo=vertex_albedo, albedo_regu=albedo_regu)  # fmt: skip
+                         vertex_albedo=vertex_albedo, albedo_regu=albedo_regu, skin=skin, joint_quaternions_init=joint_quaternions_init,
+                         joint_regu=joint_regu)  # fmt: skip
         self.camera_center = self.object_center + np.array([0, 0, 6]) * self.object_radius
         self._packed = None
 
