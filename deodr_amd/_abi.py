@@ -21,6 +21,7 @@ _COMPANIONS = (
     ("CAMERA_HEADER", "deodr_hip_camera.h", False),  # camera calibration
     ("LIGHTING_HEADER", "deodr_hip_lighting.h", False),  # spherical-harmonic lighting, per-vertex albedo
     ("SKINNING_HEADER", "deodr_hip_skinning.h", False),  # linear blend skinning
+    ("PYRAMID_HEADER", "deodr_hip_pyramid.h", False),  # multi-scale L2 data term
 )
 
 # C type (without `const`, without spaces around the stars) -> ctypes.  Data pointers are c_void_p: callers pass device addresses (Python

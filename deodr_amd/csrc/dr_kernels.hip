@@ -66,6 +66,7 @@
 #include "../../include/deodr_hip_camera.h"
 #include "../../include/deodr_hip_lighting.h"
 #include "../../include/deodr_hip_skinning.h"
+#include "../../include/deodr_hip_pyramid.h"
 #include "dr_fititer.h" // <- dr_finalize.h <- dr_backward.h <- dr_backward_generic.h <- dr_forward.h <- dr_forward_generic.h <- dr_setup.h <- dr_workspace.h <- dr_prims.h
 #include "dr_texfit.h"  // texture smoothness + step (include/deodr_hip_texture.h); uses grid_sum of dr_fronthalf.h
 #include "dr_subdiv.h"  // rows of a sparse matrix applied to [batch, n, D] blocks (include/deodr_hip_subdiv.h): Loop subdivision and its adjoint
@@ -73,6 +74,7 @@
 #include "dr_camera.h"  // the camera as a differentiable input: full adjoint of the projection, calibration parameters <-> matrices (include/deodr_hip_camera.h)
 #include "dr_lighting.h" // spherical-harmonic lighting and per-vertex albedo beside vertex_shade_* of dr_fititer.h (include/deodr_hip_lighting.h)
 #include "dr_skinning.h" // linear blend skinning: joint chain, blend of the influences of a vertex, their adjoints (include/deodr_hip_skinning.h)
+#include "dr_pyramid.h"	 // the multi-scale L2 data term and its adjoint: levels 0 .. 3 per 8 x 8 tile, the levels above on the tile grid (include/deodr_hip_pyramid.h)
 
 using namespace dr;
 using namespace dr::dispatch;
@@ -1777,6 +1779,100 @@ int deodr_hip_skin_apply_b(const double *vertices, const double *joints, const u
 		hipLaunchKernelGGL(skin_chain_b_kernel, dim3(1), dim3(FH_BLOCK), 0, st, a, world, sc.doubles(), quaternions_b, joints_b);
 	}
 	return check_hip(hipGetLastError(), "skin_apply_b launch");
+}
+
+// ---- the multi-scale L2 data term (include/deodr_hip_pyramid.h, kernels in dr_pyramid.h)
+
+int deodr_hip_pyramid_abi_version(void) { return DEODR_HIP_PYRAMID_ABI_VERSION; }
+
+namespace
+{
+struct PyramidLayout
+{ // the scratch after its counter words, in doubles
+	size_t tiles, regions, partials_tile, partials_coarse, tile_w, tile_q, gamma, doubles;
+	int TH, TW, RH, RW;
+};
+const char *pyramid_dims(int n, int H, int W, int C, int levels)
+{ // -> NULL, or which limit of the header the dimensions break
+	if (levels < 1 || levels > PYR_MAX_LEVELS)
+		return "levels must be in 1 .. 8";
+	if (C < 1)
+		return "C must be >= 1";
+	if (n < 1 || H < 1 || W < 1)
+		return "n, H and W must be >= 1";
+	if ((double)n * H * W * C >= 1099511627776.0)
+		return "n H W C must be below 2^40";
+	return NULL;
+}
+PyramidLayout pyramid_layout(int n, int H, int W, int C, int levels)
+{
+	PyramidLayout l = {};
+	l.TH = (H + PYR_TILE - 1) / PYR_TILE, l.TW = (W + PYR_TILE - 1) / PYR_TILE;
+	l.RH = (l.TH + PYR_REGION - 1) / PYR_REGION, l.RW = (l.TW + PYR_REGION - 1) / PYR_REGION;
+	l.tiles = (size_t)n * l.TH * l.TW, l.regions = (size_t)n * l.RH * l.RW;
+	const bool above = levels > PYR_TILE_LEVELS;
+	l.partials_tile = 0;
+	l.partials_coarse = l.partials_tile + (size_t)PYR_BLOCKS * (PYR_TILE_LEVELS + 1);
+	l.tile_w = l.partials_coarse + (above ? l.regions * PYR_COARSE_LEVELS : 0);
+	l.tile_q = l.tile_w + (above ? l.tiles : 0);
+	l.gamma = l.tile_q + (above ? l.tiles * C : 0);
+	l.doubles = l.gamma + (above ? l.tiles * C : 0);
+	return l;
+}
+} // namespace
+
+size_t deodr_hip_pyramid_scratch_bytes(int n, int H, int W, int C, int levels)
+{
+	return pyramid_dims(n, H, W, C, levels) ? 0 : scratch_need(pyramid_layout(n, H, W, C, levels).doubles);
+}
+
+int deodr_hip_pyramid_l2(const void *image, const void *obs, const void *weights, int n, int H, int W, int C, int pixel_dtype, int levels,
+						 const double *level_weights, double *terms, double *loss, void *image_b, void *scratch, size_t scratch_bytes, void *stream)
+{
+	const char *what = "pyramid_l2";
+	if (!image || !obs || !level_weights || !terms || !scratch)
+		return fail(what, "image, obs, level_weights, terms or scratch == NULL");
+	if (const char *why = pyramid_dims(n, H, W, C, levels))
+		return fail(what, why);
+	const size_t elem = elem_bytes(pixel_dtype);
+	if (!elem)
+		return fail(what, "pixel_dtype must be DEODR_HIP_F32 or DEODR_HIP_F64");
+	const void *const pixels[] = {image, obs, weights, image_b};
+	const void *const doubles[] = {level_weights, terms, loss, scratch};
+	if (any_misaligned(pixels, elem) || any_misaligned(doubles, 8))
+		return fail(what, "misaligned pointer");
+	const Scratch sc = {scratch, scratch_bytes};
+	if (!sc.holds(deodr_hip_pyramid_scratch_bytes(n, H, W, C, levels)))
+		return fail(what, "scratch too small (deodr_hip_pyramid_scratch_bytes)");
+	const size_t frame = (size_t)n * H * W * elem, lam = 8 * ((size_t)levels + 1);
+	const Range outputs[] = {{terms, lam}, {loss, 8}, {image_b, frame * C}, {scratch, scratch_bytes}};
+	const Range inputs[] = {{image, frame * C}, {obs, frame * C}, {weights, frame}, {level_weights, lam}};
+	if (any_overlap(outputs, inputs) || ranges_overlap(terms, lam, loss, 8) || ranges_overlap(terms, lam, image_b, frame * C) ||
+		ranges_overlap(loss, 8, image_b, frame * C) || ranges_overlap(scratch, scratch_bytes, terms, lam) || ranges_overlap(scratch, scratch_bytes, loss, 8) ||
+		ranges_overlap(scratch, scratch_bytes, image_b, frame * C))
+		return fail(what, "an output must not overlap an input, the scratch or another output");
+	const PyramidLayout l = pyramid_layout(n, H, W, C, levels);
+	double *const d = sc.doubles();
+	const PyramidArgs a = {image, obs, weights, image_b, level_weights, terms, loss, d + l.partials_tile, d + l.partials_coarse, d + l.tile_w,
+						   d + l.tile_q, d + l.gamma, sc.counter(0), n, H, W, C, levels, l.TH, l.TW, l.RH, l.RW};
+	const hipStream_t st = (hipStream_t)stream;
+	if (check_hip(hipMemsetAsync(scratch, 0, SCRATCH_COUNTER_BYTES, st), "pyramid_l2 counters"))
+		return 1;
+	const dim3 grid(capped_blocks(l.tiles, PYR_WAVES, PYR_BLOCKS)), block(FH_BLOCK);
+	const bool above = levels > PYR_TILE_LEVELS;
+	with_pixel_type(pixel_dtype == DEODR_HIP_F64, [&](auto pix) {
+		using PixT = decltype(pix);
+		if (!above && image_b)
+			hipLaunchKernelGGL((pyramid_tile_kernel<PixT, PYR_REDUCE | PYR_ADJOINT>), grid, block, 0, st, a);
+		else
+			hipLaunchKernelGGL((pyramid_tile_kernel<PixT, PYR_REDUCE>), grid, block, 0, st, a);
+		if (above)
+			hipLaunchKernelGGL(pyramid_coarse_kernel, dim3((unsigned)l.regions), block, 0, st, a);
+		if (above && image_b)
+			hipLaunchKernelGGL((pyramid_tile_kernel<PixT, PYR_ADJOINT>), grid, block, 0, st, a);
+		return 0;
+	});
+	return check_hip(hipGetLastError(), "pyramid_l2 launch");
 }
 
 #ifdef DR_WAVE_TRACE

@@ -439,6 +439,35 @@ class SkinFunc(torch.autograd.Function):
         return v_b, q_b, c_b, None
 
 
+_pyramid_scratches = {}  # (device, n, H, W, C, levels) -> the scratch of PyramidL2Func (the kernels of one stream run one after the other)
+
+
+def _pyramid_scratch(image, levels):
+    key = (image.device, *(int(v) for v in image.shape), levels)
+    if key not in _pyramid_scratches:
+        _pyramid_scratches[key] = hr.pyramid_scratch(*key[1:], image.device)
+    return _pyramid_scratches[key]
+
+
+class PyramidL2Func(torch.autograd.Function):
+    """(image [n,H,W,C]; obs, weights [n,H,W] | None, level_weights [levels+1] float64 on the device, levels: constants) -> the multi-scale L2 loss
+    (``deodr_amd/pyramid.py`` has the formulas), a float64 scalar.  The forward call computes d loss / d image as well and keeps it; the backward
+    multiplies it by the incoming scalar."""
+
+    @staticmethod
+    def forward(ctx, image, obs, weights, level_weights, levels):
+        want = ctx.needs_input_grad[0]
+        _terms, loss, image_b = hr.pyramid_l2(image, obs, weights, levels, level_weights, scratch=_pyramid_scratch(image, levels), want_gradient=want)
+        if want:
+            ctx.save_for_backward(image_b)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, loss_b):
+        (image_b,) = ctx.saved_tensors
+        return image_b * loss_b.to(image_b.dtype), None, None, None, None
+
+
 def sh_shade(posed, sh, albedo, topology):
     """-> luminosity [n,V] (``albedo`` None) or colors [n,V,C] of the posed vertices [n,V,3] (or [V,3]) under the SH lighting ``sh``, differentiable in
     all three: the kernels on float64 ROCm tensors, the same formulas as torch ops (``lighting.sh_shade_torch``) otherwise"""

@@ -52,6 +52,26 @@ def _pixel_weights(weights, shape, device, pixel_dtype):
     return None if w is None else torch.as_tensor(w, device=device).to(pixel_dtype).contiguous()
 
 
+def _pyramid_schedule(levels, weights, device):
+    """the ``pyramid_levels=`` / ``pyramid_weights=`` keywords of the colour and camera fitters -> (levels, the level weights as a float64 tensor
+    [levels+1] on ``device`` -- all ones when ``weights`` is None --, or None when ``levels`` is 0: the data term is the plain L2 of the fit step)"""
+    from . import pyramid
+
+    if isinstance(levels, bool) or int(levels) != levels or not 0 <= int(levels) <= pyramid.MAX_LEVELS:
+        raise ValueError(f"pyramid_levels must be an integer in 0 .. {pyramid.MAX_LEVELS}, not {levels!r}")
+    levels = int(levels)
+    if levels == 0:
+        if weights is not None:
+            raise ValueError("pyramid_weights needs pyramid_levels > 0")
+        return 0, None
+    w = np.ones(levels + 1) if weights is None else np.array(weights, dtype=np.float64)
+    if w.shape != (levels + 1,):
+        raise ValueError(f"pyramid_weights must have pyramid_levels + 1 = {levels + 1} entries, not shape {list(w.shape)}")
+    if not np.all(w >= 0):  # (a NaN is refused as well)
+        raise ValueError("pyramid_weights must be >= 0")
+    return levels, torch.as_tensor(w, device=device)
+
+
 def _kernel_clamp(step_max):
     """the kernels' convention for the clamp of a step: None or not positive means none"""
     return step_max if step_max is not None and step_max > 0 else None
@@ -488,6 +508,8 @@ class _PoseFitter:
 
         if self.subdivisions or self.shape_basis is not None or self.skin is not None:  # (with a basis or a skin the rendered vertex array is not the parameter either)
             return None
+        if self.pyramid_levels:  # (the multi-scale data term is not the fit step's: render, the term's image_b, render_backward under autograd)
+            return None
 
         topo = self.mesh.topology
         params = (self.vertices, self.transform_quaternion, self.transform_translation)
@@ -541,6 +563,7 @@ class _PoseFitter:
         pass  # single process, every view local
 
     weights = None  # per-pixel weights of the data term [n,H,W] (float64, this fitter's device), or None: set_image(s)(..., weights=...)
+    pyramid_levels, pyramid_weights = 0, None  # the colour fitters' multi-scale data term (their ``pyramid_levels=`` keyword); 0: off
 
     def _set_weights(self, w):
         """the :func:`_weights_nhw` of ``set_image`` / ``set_images`` (None: an unweighted fit), kept in float64: :meth:`_fit_weights` casts when a step needs them"""
@@ -693,12 +716,20 @@ class MeshDepthFitterPytorchOptim:
 
 
 class MeshRGBFitterWithPose(_PoseFitter):
-    """Fit a deformable mesh, its pose, a directional + ambient light and one colour to a colour image (mesh_fitter.py:199-376)."""
+    """Fit a deformable mesh, its pose, a directional + ambient light and one colour to a colour image (mesh_fitter.py:199-376).
+
+    ``pyramid_levels`` (0: off, every path as it is without the keyword) = L in 1 .. 8: the data term becomes the multi-scale L2 of
+    ``deodr_amd/pyramid.py``, ``data_weight * sum_l pyramid_weights[l] term_l`` -- the squared residual at full resolution and again after summing over
+    2 x 2, ..., 2^L x 2^L cells --, which still pulls when the start is several pixels off.  ``self.pyramid_weights`` is a float64 device tensor [L+1]
+    (from ``pyramid_weights``; None: all ones) that the kernels read when they run: ``copy_`` a new schedule into it between steps, also under a
+    ``GraphedStep``.  The ``weights=`` of ``set_image(s)`` feed the term.  The iteration then runs through autograd (render, the term's ``image_b``,
+    ``render_backward``): the one-call fit step cannot carry a term in which the gradient of a pixel depends on its neighbours."""
 
     def __init__(self, vertices, faces, euler_init, translation_init, default_color, default_light_directional, default_light_ambient, cregu=2000,
                  inertia=0.96, damping=0.05, update_lights=True, update_color=True, device="cuda", pixel_dtype=torch.float64, n_poses=1,
                  subdivisions=0, shape_basis=None, coefficient_regu=0.0, sigmas=None, light_sh_init=None, vertex_albedo=False, albedo_regu=0.0,
-                 skin=None, joint_quaternions_init=None, joint_regu=0.0):  # fmt: skip
+                 skin=None, joint_quaternions_init=None, joint_regu=0.0, pyramid_levels=0, pyramid_weights=None):  # fmt: skip
+        self.pyramid_levels, self.pyramid_weights = _pyramid_schedule(pyramid_levels, pyramid_weights, torch.device(device))
         self.default_color = np.asarray(default_color, dtype=np.float64)
         self._init_lighting(light_sh_init, vertex_albedo, albedo_regu)
         self.default_light_directional = np.asarray(default_light_directional, dtype=np.float64)
@@ -787,6 +818,10 @@ class MeshRGBFitterWithPose(_PoseFitter):
         """-> (data energy, image [n,H,W,C]).  The data term of the colour fitters is exactly sum (image - obs)^2
         (mesh_fitter.py:296-318): rendered AND back-propagated by the one-call fit step (Scene3DDevice.render_l2)."""
         self._pose_scene()
+        if self.pyramid_levels:
+            loss, image = self.scene.render_pyramid_l2(self.camera, self._observation(), self.pyramid_levels, weights=self._fit_weights(),
+                                                       level_weights=self.pyramid_weights)  # fmt: skip
+            return self.data_weight * loss, image
         loss, image = self.scene.render_l2(self.camera, self._observation(), weights=self._fit_weights())
         return self.data_weight * loss, image
 
@@ -922,7 +957,7 @@ class MeshRGBFitterWithPoseMultiFrame(MeshRGBFitterWithPose):
     def __init__(self, vertices, faces, euler_init, translation_init, default_color, default_light_directional, default_light_ambient, cregu=2000,
                  cdata=1, inertia=0.97, damping=0.15, update_lights=True, update_color=True, device="cuda", pixel_dtype=torch.float64, group=None,
                  subdivisions=0, shape_basis=None, coefficient_regu=0.0, sigmas=None, light_sh_init=None, vertex_albedo=False, albedo_regu=0.0,
-                 skin=None, joint_quaternions_init=None, joint_regu=0.0):  # fmt: skip
+                 skin=None, joint_quaternions_init=None, joint_regu=0.0, pyramid_levels=0, pyramid_weights=None):  # fmt: skip
         euler_init, translation_init = np.atleast_2d(euler_init), np.atleast_2d(translation_init)
         self.cdata = cdata
         self.n_views_total = max(len(euler_init), len(translation_init))
@@ -936,7 +971,7 @@ class MeshRGBFitterWithPoseMultiFrame(MeshRGBFitterWithPose):
                          cregu, inertia, damping, update_lights, update_color, device, pixel_dtype, n_poses=len(self.my_views), subdivisions=subdivisions,
                          shape_basis=shape_basis, coefficient_regu=coefficient_regu, sigmas=sigmas, light_sh_init=light_sh_init,
                          vertex_albedo=vertex_albedo, albedo_regu=albedo_regu, skin=skin, joint_quaternions_init=joint_quaternions_init,
-                         joint_regu=joint_regu)  # fmt: skip
+                         joint_regu=joint_regu, pyramid_levels=pyramid_levels, pyramid_weights=pyramid_weights)  # fmt: skip
         self.camera_center = self.object_center + np.array([0, 0, 6]) * self.object_radius
         self._packed = None
 
@@ -1232,7 +1267,10 @@ class CameraFitterMultiFrame:
     ROCm tensors is then a fixed kernel sequence over persistent buffers -- ``deodr_hip_camera_assemble``, ``deodr_hip_project_points``, silhouette
     flags, the rasterizer's one-call fit step, ``deodr_hip_camera_project_b`` (the 23 sums per view, deterministic), ``deodr_hip_camera_assemble_b``, one
     ``deodr_hip_momentum_update`` of all groups -- no autograd graph, no tensor rebound, so ``GraphedStep(fitter)`` replays it as it is.  On CPU
-    tensors, or with ``direct = False``, the same iteration runs as autograd through ``DeviceCamera.from_pose`` and ``Scene3DDevice.render_l2``."""
+    tensors, or with ``direct = False``, the same iteration runs as autograd through ``DeviceCamera.from_pose`` and ``Scene3DDevice.render_l2``.
+
+    ``pyramid_levels`` / ``pyramid_weights``: the multi-scale data term, as on :class:`MeshRGBFitterWithPose` (0: off, every path as it is without the
+    keyword); with it the iteration is the autograd one, through ``Scene3DDevice.render_pyramid_l2``."""
 
     direct = True
     GROUPS = ("extrinsic", "focal", "center", "distortion")
@@ -1243,7 +1281,9 @@ class CameraFitterMultiFrame:
 
     def __init__(self, vertices, faces, quaternions_init, translations_init, focal_init, center_init, distortion_init=None, colors=None, uv=None,
                  faces_uv=None, texture=None, light_directional=None, light_ambient=1.0, update=GROUPS, shared_intrinsics=True, sigmas=None, sigma=1.0,
-                 inertia=0.9, damping=0.05, step_scale=None, clockwise=False, device="cuda", pixel_dtype=torch.float64):  # fmt: skip
+                 inertia=0.9, damping=0.05, step_scale=None, clockwise=False, device="cuda", pixel_dtype=torch.float64, pyramid_levels=0,
+                 pyramid_weights=None):  # fmt: skip
+        self.pyramid_levels, self.pyramid_weights = _pyramid_schedule(pyramid_levels, pyramid_weights, torch.device(device))
         unknown = [g for g in update if g not in self.GROUPS]
         if unknown:
             raise ValueError(f"CameraFitterMultiFrame: update may list {self.GROUPS}, not {unknown}")
@@ -1337,7 +1377,8 @@ class CameraFitterMultiFrame:
         self._direct = None
         topo = mesh.topology
         params = [p[2] for p in self._parameters()]
-        if self.direct and fronthalf.usable(mesh.vertices, *params) and topo._edge_faces is not None and n <= hip_renderer.CAMERA_MAX_VIEWS:
+        if (self.direct and not self.pyramid_levels and fronthalf.usable(mesh.vertices, *params) and topo._edge_faces is not None
+                and n <= hip_renderer.CAMERA_MAX_VIEWS):  # (the multi-scale data term is not the fit step's: through autograd)
             self._direct = self._direct_buffers(n, height, width, nb_colors)
         self.iter = 0
 
@@ -1403,7 +1444,10 @@ class CameraFitterMultiFrame:
         leaves = {name: x.detach().requires_grad_(group in self.update) for name, group, x, *_ in rows}
         camera = DeviceCamera.from_pose(leaves["quaternions"], leaves["translations"], leaves["focal"], leaves["center"], self.height, self.width,
                                         leaves.get("distortion"), shared_intrinsics=self.shared_intrinsics, device=self.device)  # fmt: skip
-        loss, image = self.scene.render_l2(camera, self._obs, weights=self.weights)
+        if self.pyramid_levels:
+            loss, image = self.scene.render_pyramid_l2(camera, self._obs, self.pyramid_levels, weights=self.weights, level_weights=self.pyramid_weights)
+        else:
+            loss, image = self.scene.render_l2(camera, self._obs, weights=self.weights)
         wanted = [name for name, group, *_ in rows if group in self.update]
         grads = dict(zip(wanted, torch.autograd.grad(loss, [leaves[k] for k in wanted]))) if wanted else {}
         self.e_data.copy_(loss.detach().reshape(1))

@@ -429,6 +429,23 @@ class Scene3DDevice:
         extra.update(self._differentiated_shared())  # (the same convention)
         return self._rasterize_l2(camera, ij, depths, colors, shade, textured, backface_culling, obs.expand(n, -1, -1, -1).contiguous(), **extra)
 
+    def render_pyramid_l2(self, camera, obs, levels, weights=None, level_weights=None, backface_culling=True):
+        """-> (the multi-scale L2 loss of ``render(camera)`` against ``obs`` as a differentiable scalar, the rendered images [n,H,W,C]):
+        :meth:`render` followed by :func:`deodr_amd.pyramid.pyramid_l2` (``levels`` coarse levels, ``level_weights`` [levels+1], None: ones), so the
+        adjoint is that term's ``image_b`` through the rasterizer's ``render_backward``.  ``obs`` [n,H,W,C] and ``weights`` [n,H,W] or [H,W] (``>= 0``, or
+        None) in the scene's pixel dtype (anything else is converted at every call).  The one-call fit step cannot carry this term: the gradient of
+        a pixel depends on the residuals of its neighbours."""
+        from . import pyramid
+
+        image = self.render(camera, backface_culling=backface_culling)
+        n = image.shape[0]
+        obs = obs.to(device=image.device, dtype=image.dtype).expand(n, -1, -1, -1).contiguous()
+        if weights is not None:
+            if tuple(weights.shape) not in ((n, camera.height, camera.width), (camera.height, camera.width)):
+                raise ValueError(f"weights must have shape [{n}, {camera.height}, {camera.width}] or [{camera.height}, {camera.width}], not {list(weights.shape)}")
+            weights = weights.to(device=image.device, dtype=image.dtype).expand(n, -1, -1).contiguous()
+        return pyramid.pyramid_l2(image, obs, weights, levels, level_weights), image
+
     def _differentiated_shared(self):
         """{"texture": mesh.texture, "uv": mesh.uv}, each only when it requires grad: the keyword arguments a textured render passes on"""
         m = self.mesh
