@@ -67,6 +67,7 @@
 #include "../../include/deodr_hip_lighting.h"
 #include "../../include/deodr_hip_skinning.h"
 #include "../../include/deodr_hip_pyramid.h"
+#include "../../include/deodr_hip_ssim.h"
 #include "dr_fititer.h" // <- dr_finalize.h <- dr_backward.h <- dr_backward_generic.h <- dr_forward.h <- dr_forward_generic.h <- dr_setup.h <- dr_workspace.h <- dr_prims.h
 #include "dr_texfit.h"  // texture smoothness + step (include/deodr_hip_texture.h); uses grid_sum of dr_fronthalf.h
 #include "dr_subdiv.h"  // rows of a sparse matrix applied to [batch, n, D] blocks (include/deodr_hip_subdiv.h): Loop subdivision and its adjoint
@@ -75,6 +76,7 @@
 #include "dr_lighting.h" // spherical-harmonic lighting and per-vertex albedo beside vertex_shade_* of dr_fititer.h (include/deodr_hip_lighting.h)
 #include "dr_skinning.h" // linear blend skinning: joint chain, blend of the influences of a vertex, their adjoints (include/deodr_hip_skinning.h)
 #include "dr_pyramid.h"	 // the multi-scale L2 data term and its adjoint: levels 0 .. 3 per 8 x 8 tile, the levels above on the tile grid (include/deodr_hip_pyramid.h)
+#include "dr_ssim.h"	 // the structural (SSIM) data term and its adjoint: two stencil kernels over 16 x 32 tiles with a halo in LDS (include/deodr_hip_ssim.h)
 
 using namespace dr;
 using namespace dr::dispatch;
@@ -1873,6 +1875,76 @@ int deodr_hip_pyramid_l2(const void *image, const void *obs, const void *weights
 		return 0;
 	});
 	return check_hip(hipGetLastError(), "pyramid_l2 launch");
+}
+
+// ---- the structural (SSIM) data term (include/deodr_hip_ssim.h, kernels in dr_ssim.h)
+
+int deodr_hip_ssim_abi_version(void) { return DEODR_HIP_SSIM_ABI_VERSION; }
+
+namespace
+{
+const char *ssim_dims(int n, int H, int W, int C)
+{ // -> NULL, or which limit of the header the dimensions break
+	if (n < 1 || H < 1 || W < 1 || C < 1)
+		return "n, H, W and C must be >= 1";
+	if ((double)n * H * W * C >= 1099511627776.0)
+		return "n H W C must be below 2^40";
+	return NULL;
+}
+} // namespace
+
+size_t deodr_hip_ssim_scratch_bytes(int n, int H, int W, int C)
+{ // the partials of the stats kernel, then the three maps
+	return ssim_dims(n, H, W, C) ? 0 : scratch_need((size_t)SSIM_BLOCKS * 2 + 3 * ((size_t)n * H * W * C));
+}
+
+int deodr_hip_ssim_l2(const void *image, const void *obs, const void *weights, int n, int H, int W, int C, int pixel_dtype, double data_range,
+					  const double *mix, double *terms, double *loss, void *image_b, void *scratch, size_t scratch_bytes, void *stream)
+{
+	const char *what = "ssim_l2";
+	if (!image || !obs || !mix || !terms || !scratch)
+		return fail(what, "image, obs, mix, terms or scratch == NULL");
+	if (const char *why = ssim_dims(n, H, W, C))
+		return fail(what, why);
+	if (!(data_range > 0) || !__builtin_isfinite(data_range))
+		return fail(what, "data_range must be finite and > 0");
+	const size_t elem = elem_bytes(pixel_dtype);
+	if (!elem)
+		return fail(what, "pixel_dtype must be DEODR_HIP_F32 or DEODR_HIP_F64");
+	const void *const pixels[] = {image, obs, weights, image_b};
+	const void *const doubles[] = {mix, terms, loss, scratch};
+	if (any_misaligned(pixels, elem) || any_misaligned(doubles, 8))
+		return fail(what, "misaligned pointer");
+	const Scratch sc = {scratch, scratch_bytes};
+	if (!sc.holds(deodr_hip_ssim_scratch_bytes(n, H, W, C)))
+		return fail(what, "scratch too small (deodr_hip_ssim_scratch_bytes)");
+	const size_t frame = (size_t)n * H * W * elem;
+	const Range outputs[] = {{terms, 16}, {loss, 8}, {image_b, frame * C}, {scratch, scratch_bytes}};
+	const Range inputs[] = {{image, frame * C}, {obs, frame * C}, {weights, frame}, {mix, 16}};
+	if (any_overlap(outputs, inputs) || ranges_overlap(terms, 16, loss, 8) || ranges_overlap(terms, 16, image_b, frame * C) ||
+		ranges_overlap(loss, 8, image_b, frame * C) || ranges_overlap(scratch, scratch_bytes, terms, 16) || ranges_overlap(scratch, scratch_bytes, loss, 8) ||
+		ranges_overlap(scratch, scratch_bytes, image_b, frame * C))
+		return fail(what, "an output must not overlap an input, the scratch or another output");
+	double *const d = sc.doubles();
+	const int TY = (H + SSIM_TH - 1) / SSIM_TH, TX = (W + SSIM_TW - 1) / SSIM_TW;
+	const double c1 = 0.01 * data_range, c2 = 0.03 * data_range;
+	const SsimArgs a = {image, obs, weights, image_b, mix, terms, loss, d, d + (size_t)SSIM_BLOCKS * 2, sc.counter(0), c1 * c1, c2 * c2, n, H, W, C, TY, TX};
+	const hipStream_t st = (hipStream_t)stream;
+	if (check_hip(hipMemsetAsync(scratch, 0, SCRATCH_COUNTER_BYTES, st), "ssim_l2 counters"))
+		return 1;
+	const dim3 grid(capped_blocks((size_t)n * TY * TX, 1, SSIM_BLOCKS)), block(FH_BLOCK);
+	with_pixel_type(pixel_dtype == DEODR_HIP_F64, [&](auto pix) {
+		using PixT = decltype(pix);
+		if (image_b)
+		{
+			hipLaunchKernelGGL((ssim_stats_kernel<PixT, true>), grid, block, 0, st, a);
+			hipLaunchKernelGGL(ssim_adjoint_kernel<PixT>, grid, block, 0, st, a);
+		}
+		else
+			hipLaunchKernelGGL((ssim_stats_kernel<PixT, false>), grid, block, 0, st, a);
+		return 0;
+	});
+	return check_hip(hipGetLastError(), "ssim_l2 launch");
 }
 
 #ifdef DR_WAVE_TRACE

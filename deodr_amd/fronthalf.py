@@ -468,6 +468,35 @@ class PyramidL2Func(torch.autograd.Function):
         return image_b * loss_b.to(image_b.dtype), None, None, None, None
 
 
+_ssim_scratches = {}  # (device, n, H, W, C) -> the scratch of SSIML2Func (the kernels of one stream run one after the other)
+
+
+def _ssim_scratch(image):
+    key = (image.device, *(int(v) for v in image.shape))
+    if key not in _ssim_scratches:
+        _ssim_scratches[key] = hr.ssim_scratch(*key[1:], image.device)
+    return _ssim_scratches[key]
+
+
+class SSIML2Func(torch.autograd.Function):
+    """(image [n,H,W,C]; obs, weights [n,H,W] | None, mix [2] float64 on the device, data_range: constants) -> the mix of the pixel term and the
+    structural term (``deodr_amd/ssim.py`` has the formulas), a float64 scalar.  The forward call computes d loss / d image as well and keeps it; the
+    backward multiplies it by the incoming scalar."""
+
+    @staticmethod
+    def forward(ctx, image, obs, weights, mix, data_range):
+        want = ctx.needs_input_grad[0]
+        _terms, loss, image_b = hr.ssim_l2(image, obs, weights, mix, data_range, scratch=_ssim_scratch(image), want_gradient=want)
+        if want:
+            ctx.save_for_backward(image_b)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, loss_b):
+        (image_b,) = ctx.saved_tensors
+        return image_b * loss_b.to(image_b.dtype), None, None, None, None
+
+
 def sh_shade(posed, sh, albedo, topology):
     """-> luminosity [n,V] (``albedo`` None) or colors [n,V,C] of the posed vertices [n,V,3] (or [V,3]) under the SH lighting ``sh``, differentiable in
     all three: the kernels on float64 ROCm tensors, the same formulas as torch ops (``lighting.sh_shade_torch``) otherwise"""

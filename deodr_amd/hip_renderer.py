@@ -38,8 +38,9 @@ _COMPANIONS = (
     (_abi.LIGHTING_HEADER, "lighting", "lighting"),  # spherical-harmonic lighting, per-vertex albedo
     (_abi.SKINNING_HEADER, "skinning", "skinning"),  # linear blend skinning
     (_abi.PYRAMID_HEADER, "pyramid", "pyramid-loss"),  # multi-scale L2 data term
+    (_abi.SSIM_HEADER, "ssim", "ssim-loss"),  # structural (SSIM) data term
 )
-TEXTURE_ABI_VERSION, SUBDIV_ABI_VERSION, RETAINED_ABI_VERSION, BASIS_ABI_VERSION, CAMERA_ABI_VERSION, LIGHTING_ABI_VERSION, SKINNING_ABI_VERSION, PYRAMID_ABI_VERSION = (
+TEXTURE_ABI_VERSION, SUBDIV_ABI_VERSION, RETAINED_ABI_VERSION, BASIS_ABI_VERSION, CAMERA_ABI_VERSION, LIGHTING_ABI_VERSION, SKINNING_ABI_VERSION, PYRAMID_ABI_VERSION, SSIM_ABI_VERSION = (
     h.defines[f"DEODR_HIP_{key.upper()}_ABI_VERSION"] for h, key, _ in _COMPANIONS
 )
 # words of the 64-byte status block at the start of the workspace
@@ -1359,6 +1360,61 @@ def pyramid_l2(image, obs, weights, levels, level_weights, terms=None, loss=None
             scratch = _cached_scratch("pyramid", dev, need, lambda: pyramid_scratch(n, H, W, Cn, levels, dev),
                                       f"{what}: pass scratch= (pyramid_scratch) when capturing a graph: none of this size exists for this stream yet")  # fmt: skip
     _launch(lib().deodr_hip_pyramid_l2, dev, _ptr(image), _ptr(obs), _ptr(weights), n, H, W, Cn, _dtype_tag(image), levels, _ptr(level_weights),
+            _ptr(terms), _ptr(loss), _ptr(image_b), _ptr(scratch), scratch.numel())  # fmt: skip
+    for t in (terms, loss, image_b):
+        if t is not None:
+            _touched(t)
+    return terms, loss, image_b
+
+
+# ---- the structural (SSIM) data term (include/deodr_hip_ssim.h) ----------------------------------------------------------------------------
+
+SSIM_WINDOW = _abi.SSIM_HEADER.defines["DEODR_HIP_SSIM_WINDOW"]
+
+
+def ssim_scratch(n, H, W, C, device):
+    """the scratch of :func:`ssim_l2` for n frames of H x W x C (one per stream in use; it need not be zeroed)"""
+    need = int(lib().deodr_hip_ssim_scratch_bytes(int(n), int(H), int(W), int(C)))
+    if need == 0:
+        raise ValueError(f"ssim_scratch: n = {n}, H = {H}, W = {W}, C = {C} is outside the limits of include/deodr_hip_ssim.h")
+    with torch.cuda.device(device):
+        return torch.empty(need, dtype=torch.uint8, device=device)
+
+
+def ssim_l2(image, obs, weights, mix, data_range=1.0, terms=None, loss=None, image_b=None, scratch=None, want_gradient=True):
+    """``deodr_hip_ssim_l2``: ``loss = mix[0] sum w (image - obs)^2 + mix[1] sum w (1 - SSIM)`` under the 11 x 11 Gaussian window with zero padding
+    (the header has the formulas) -> (terms [2] float64: the two unweighted sums; loss [1] float64; image_b = d loss / d image, or None).  ``image``,
+    ``obs`` [n,H,W,C] float32 / float64 contiguous ROCm tensors, ``weights`` [n,H,W] of the same dtype or None -- they multiply the SSIM map and do
+    not enter the windows, so ``image_b`` is in general not 0 where a weight is --, ``mix`` [2] float64 ON THE DEVICE (read when the kernels run).
+    ``image_b`` is allocated when None and ``want_gradient``.  Deterministic; asynchronous on the current stream.  ``scratch``: a
+    :func:`ssim_scratch` of the caller's; None: one per device and stream."""
+    what = "ssim_l2"
+    _rocm_tensor(what, "image", image)
+    if image.dim() != 4 or min(image.shape) < 1:
+        raise ValueError(f"{what}: image must have shape [n >= 1, H >= 1, W >= 1, C >= 1], not {list(image.shape)}")
+    n, H, W, Cn = (int(v) for v in image.shape)
+    data_range = float(data_range)
+    if not (data_range > 0 and data_range < float("inf")):
+        raise ValueError(f"{what}: data_range must be finite and > 0, not {data_range}")
+    pix = (image.dtype,)
+    rows = [("image", image, _FLOATS, None), ("obs", obs, pix, (n, H, W, Cn)), ("mix", mix, _F64_ONLY, (2,))]
+    optional = (("weights", weights, pix, (n, H, W)), ("terms", terms, _F64_ONLY, (2,)), ("loss", loss, _F64_ONLY, (1,)),
+                ("image_b", image_b, pix, (n, H, W, Cn)), ("scratch", scratch, (torch.uint8,), (None,)))  # fmt: skip
+    rows += [row for row in optional if row[1] is not None]
+    _check_tensors(what, "image", image.device, rows)
+    dev = image.device
+    need = int(lib().deodr_hip_ssim_scratch_bytes(n, H, W, Cn))
+    if need == 0:
+        raise ValueError(f"{what}: image of shape {list(image.shape)} is outside the limits of include/deodr_hip_ssim.h")
+    with torch.cuda.device(dev):
+        terms = torch.empty(2, dtype=torch.float64, device=dev) if terms is None else terms
+        loss = torch.empty(1, dtype=torch.float64, device=dev) if loss is None else loss
+        if image_b is None and want_gradient:
+            image_b = torch.empty_like(image)
+        if scratch is None:
+            scratch = _cached_scratch("ssim", dev, need, lambda: ssim_scratch(n, H, W, Cn, dev),
+                                      f"{what}: pass scratch= (ssim_scratch) when capturing a graph: none of this size exists for this stream yet")  # fmt: skip
+    _launch(lib().deodr_hip_ssim_l2, dev, _ptr(image), _ptr(obs), _ptr(weights), n, H, W, Cn, _dtype_tag(image), data_range, _ptr(mix),
             _ptr(terms), _ptr(loss), _ptr(image_b), _ptr(scratch), scratch.numel())  # fmt: skip
     for t in (terms, loss, image_b):
         if t is not None:

@@ -72,6 +72,19 @@ def _pyramid_schedule(levels, weights, device):
     return levels, torch.as_tensor(w, device=device)
 
 
+def _ssim_mix(weight, data_range, pyramid_levels, device):
+    """the ``ssim_weight=`` / ``ssim_data_range=`` keywords of the colour and camera fitters -> (the float64 tensor [1 - weight, weight] on ``device``,
+    or None when ``weight`` is 0: the data term is the plain L2 of the fit step; the data range as a float)"""
+    if isinstance(weight, bool) or not isinstance(weight, (int, float, np.integer, np.floating)) or not 0 <= float(weight) <= 1:  # (a NaN is refused as well)
+        raise ValueError(f"ssim_weight must be a real number in 0 .. 1, not {weight!r}")
+    if isinstance(data_range, bool) or not isinstance(data_range, (int, float, np.integer, np.floating)) or not 0 < float(data_range) < np.inf:
+        raise ValueError(f"ssim_data_range must be a finite real number > 0, not {data_range!r}")
+    weight = float(weight)
+    if weight > 0 and pyramid_levels:
+        raise ValueError("ssim_weight > 0 and pyramid_levels > 0 cannot be combined: composing the two data terms is not supported")
+    return (torch.as_tensor([1.0 - weight, weight], dtype=torch.float64, device=device) if weight > 0 else None), float(data_range)
+
+
 def _kernel_clamp(step_max):
     """the kernels' convention for the clamp of a step: None or not positive means none"""
     return step_max if step_max is not None and step_max > 0 else None
@@ -508,7 +521,7 @@ class _PoseFitter:
 
         if self.subdivisions or self.shape_basis is not None or self.skin is not None:  # (with a basis or a skin the rendered vertex array is not the parameter either)
             return None
-        if self.pyramid_levels:  # (the multi-scale data term is not the fit step's: render, the term's image_b, render_backward under autograd)
+        if self.pyramid_levels or self.ssim_mix is not None:  # (the multi-scale and the structural data term are not the fit step's: render, the term's image_b, render_backward under autograd)
             return None
 
         topo = self.mesh.topology
@@ -564,6 +577,7 @@ class _PoseFitter:
 
     weights = None  # per-pixel weights of the data term [n,H,W] (float64, this fitter's device), or None: set_image(s)(..., weights=...)
     pyramid_levels, pyramid_weights = 0, None  # the colour fitters' multi-scale data term (their ``pyramid_levels=`` keyword); 0: off
+    ssim_mix, ssim_data_range = None, 1.0  # the colour fitters' structural data term (their ``ssim_weight=`` keyword); None: off
 
     def _set_weights(self, w):
         """the :func:`_weights_nhw` of ``set_image`` / ``set_images`` (None: an unweighted fit), kept in float64: :meth:`_fit_weights` casts when a step needs them"""
@@ -723,13 +737,23 @@ class MeshRGBFitterWithPose(_PoseFitter):
     2 x 2, ..., 2^L x 2^L cells --, which still pulls when the start is several pixels off.  ``self.pyramid_weights`` is a float64 device tensor [L+1]
     (from ``pyramid_weights``; None: all ones) that the kernels read when they run: ``copy_`` a new schedule into it between steps, also under a
     ``GraphedStep``.  The ``weights=`` of ``set_image(s)`` feed the term.  The iteration then runs through autograd (render, the term's ``image_b``,
-    ``render_backward``): the one-call fit step cannot carry a term in which the gradient of a pixel depends on its neighbours."""
+    ``render_backward``): the one-call fit step cannot carry a term in which the gradient of a pixel depends on its neighbours.
+
+    ``ssim_weight`` (0: off, every path as it is without the keyword) = lambda in (0, 1]: the data term becomes
+    ``data_weight * ((1 - lambda) sum w (image - obs)^2 + lambda sum w (1 - SSIM))`` of ``deodr_amd/ssim.py`` -- the structural dissimilarity under an
+    11 x 11 Gaussian window, which an exposure or shading the model does not explain moves far less than the pixel term --, with
+    ``ssim_data_range`` the span of the intensities.  ``self.ssim_mix`` is the float64 device tensor ``[1 - lambda, lambda]`` that the kernels read
+    when they run: ``copy_`` another mix into it between steps, also under a ``GraphedStep``.  The ``weights=`` of ``set_image(s)`` multiply the SSIM
+    map (they do not enter its windows: dilate a mask by 5 pixels where that matters).  The iteration runs through autograd as with
+    ``pyramid_levels``; the two keywords cannot be combined."""
 
     def __init__(self, vertices, faces, euler_init, translation_init, default_color, default_light_directional, default_light_ambient, cregu=2000,
                  inertia=0.96, damping=0.05, update_lights=True, update_color=True, device="cuda", pixel_dtype=torch.float64, n_poses=1,
                  subdivisions=0, shape_basis=None, coefficient_regu=0.0, sigmas=None, light_sh_init=None, vertex_albedo=False, albedo_regu=0.0,
-                 skin=None, joint_quaternions_init=None, joint_regu=0.0, pyramid_levels=0, pyramid_weights=None):  # fmt: skip
+                 skin=None, joint_quaternions_init=None, joint_regu=0.0, pyramid_levels=0, pyramid_weights=None, ssim_weight=0.0,
+                 ssim_data_range=1.0):  # fmt: skip
         self.pyramid_levels, self.pyramid_weights = _pyramid_schedule(pyramid_levels, pyramid_weights, torch.device(device))
+        self.ssim_mix, self.ssim_data_range = _ssim_mix(ssim_weight, ssim_data_range, self.pyramid_levels, torch.device(device))
         self.default_color = np.asarray(default_color, dtype=np.float64)
         self._init_lighting(light_sh_init, vertex_albedo, albedo_regu)
         self.default_light_directional = np.asarray(default_light_directional, dtype=np.float64)
@@ -821,6 +845,10 @@ class MeshRGBFitterWithPose(_PoseFitter):
         if self.pyramid_levels:
             loss, image = self.scene.render_pyramid_l2(self.camera, self._observation(), self.pyramid_levels, weights=self._fit_weights(),
                                                        level_weights=self.pyramid_weights)  # fmt: skip
+            return self.data_weight * loss, image
+        if self.ssim_mix is not None:
+            loss, image = self.scene.render_ssim_l2(self.camera, self._observation(), weights=self._fit_weights(), mix=self.ssim_mix,
+                                                    data_range=self.ssim_data_range)  # fmt: skip
             return self.data_weight * loss, image
         loss, image = self.scene.render_l2(self.camera, self._observation(), weights=self._fit_weights())
         return self.data_weight * loss, image
@@ -957,7 +985,8 @@ class MeshRGBFitterWithPoseMultiFrame(MeshRGBFitterWithPose):
     def __init__(self, vertices, faces, euler_init, translation_init, default_color, default_light_directional, default_light_ambient, cregu=2000,
                  cdata=1, inertia=0.97, damping=0.15, update_lights=True, update_color=True, device="cuda", pixel_dtype=torch.float64, group=None,
                  subdivisions=0, shape_basis=None, coefficient_regu=0.0, sigmas=None, light_sh_init=None, vertex_albedo=False, albedo_regu=0.0,
-                 skin=None, joint_quaternions_init=None, joint_regu=0.0, pyramid_levels=0, pyramid_weights=None):  # fmt: skip
+                 skin=None, joint_quaternions_init=None, joint_regu=0.0, pyramid_levels=0, pyramid_weights=None, ssim_weight=0.0,
+                 ssim_data_range=1.0):  # fmt: skip
         euler_init, translation_init = np.atleast_2d(euler_init), np.atleast_2d(translation_init)
         self.cdata = cdata
         self.n_views_total = max(len(euler_init), len(translation_init))
@@ -971,7 +1000,8 @@ class MeshRGBFitterWithPoseMultiFrame(MeshRGBFitterWithPose):
                          cregu, inertia, damping, update_lights, update_color, device, pixel_dtype, n_poses=len(self.my_views), subdivisions=subdivisions,
                          shape_basis=shape_basis, coefficient_regu=coefficient_regu, sigmas=sigmas, light_sh_init=light_sh_init,
                          vertex_albedo=vertex_albedo, albedo_regu=albedo_regu, skin=skin, joint_quaternions_init=joint_quaternions_init,
-                         joint_regu=joint_regu, pyramid_levels=pyramid_levels, pyramid_weights=pyramid_weights)  # fmt: skip
+                         joint_regu=joint_regu, pyramid_levels=pyramid_levels, pyramid_weights=pyramid_weights, ssim_weight=ssim_weight,
+                         ssim_data_range=ssim_data_range)  # fmt: skip
         self.camera_center = self.object_center + np.array([0, 0, 6]) * self.object_radius
         self._packed = None
 
@@ -1270,7 +1300,9 @@ class CameraFitterMultiFrame:
     tensors, or with ``direct = False``, the same iteration runs as autograd through ``DeviceCamera.from_pose`` and ``Scene3DDevice.render_l2``.
 
     ``pyramid_levels`` / ``pyramid_weights``: the multi-scale data term, as on :class:`MeshRGBFitterWithPose` (0: off, every path as it is without the
-    keyword); with it the iteration is the autograd one, through ``Scene3DDevice.render_pyramid_l2``."""
+    keyword); with it the iteration is the autograd one, through ``Scene3DDevice.render_pyramid_l2``.  ``ssim_weight`` / ``ssim_data_range``: the
+    structural data term, as on :class:`MeshRGBFitterWithPose` (0: off; ``self.ssim_mix`` the device tensor of the mix); the autograd iteration
+    through ``Scene3DDevice.render_ssim_l2``; not together with ``pyramid_levels``."""
 
     direct = True
     GROUPS = ("extrinsic", "focal", "center", "distortion")
@@ -1282,8 +1314,9 @@ class CameraFitterMultiFrame:
     def __init__(self, vertices, faces, quaternions_init, translations_init, focal_init, center_init, distortion_init=None, colors=None, uv=None,
                  faces_uv=None, texture=None, light_directional=None, light_ambient=1.0, update=GROUPS, shared_intrinsics=True, sigmas=None, sigma=1.0,
                  inertia=0.9, damping=0.05, step_scale=None, clockwise=False, device="cuda", pixel_dtype=torch.float64, pyramid_levels=0,
-                 pyramid_weights=None):  # fmt: skip
+                 pyramid_weights=None, ssim_weight=0.0, ssim_data_range=1.0):  # fmt: skip
         self.pyramid_levels, self.pyramid_weights = _pyramid_schedule(pyramid_levels, pyramid_weights, torch.device(device))
+        self.ssim_mix, self.ssim_data_range = _ssim_mix(ssim_weight, ssim_data_range, self.pyramid_levels, torch.device(device))
         unknown = [g for g in update if g not in self.GROUPS]
         if unknown:
             raise ValueError(f"CameraFitterMultiFrame: update may list {self.GROUPS}, not {unknown}")
@@ -1377,8 +1410,8 @@ class CameraFitterMultiFrame:
         self._direct = None
         topo = mesh.topology
         params = [p[2] for p in self._parameters()]
-        if (self.direct and not self.pyramid_levels and fronthalf.usable(mesh.vertices, *params) and topo._edge_faces is not None
-                and n <= hip_renderer.CAMERA_MAX_VIEWS):  # (the multi-scale data term is not the fit step's: through autograd)
+        if (self.direct and not self.pyramid_levels and self.ssim_mix is None and fronthalf.usable(mesh.vertices, *params) and topo._edge_faces is not None
+                and n <= hip_renderer.CAMERA_MAX_VIEWS):  # (the multi-scale and the structural data term are not the fit step's: through autograd)
             self._direct = self._direct_buffers(n, height, width, nb_colors)
         self.iter = 0
 
@@ -1446,6 +1479,8 @@ class CameraFitterMultiFrame:
                                         leaves.get("distortion"), shared_intrinsics=self.shared_intrinsics, device=self.device)  # fmt: skip
         if self.pyramid_levels:
             loss, image = self.scene.render_pyramid_l2(camera, self._obs, self.pyramid_levels, weights=self.weights, level_weights=self.pyramid_weights)
+        elif self.ssim_mix is not None:
+            loss, image = self.scene.render_ssim_l2(camera, self._obs, weights=self.weights, mix=self.ssim_mix, data_range=self.ssim_data_range)
         else:
             loss, image = self.scene.render_l2(camera, self._obs, weights=self.weights)
         wanted = [name for name, group, *_ in rows if group in self.update]

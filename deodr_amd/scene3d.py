@@ -446,6 +446,24 @@ class Scene3DDevice:
             weights = weights.to(device=image.device, dtype=image.dtype).expand(n, -1, -1).contiguous()
         return pyramid.pyramid_l2(image, obs, weights, levels, level_weights), image
 
+    def render_ssim_l2(self, camera, obs, weights=None, mix=None, data_range=1.0, backface_culling=True):
+        """-> (``mix[0] sum w (image - obs)^2 + mix[1] sum w (1 - SSIM)`` of ``render(camera)`` against ``obs`` as a differentiable scalar, the
+        rendered images [n,H,W,C]): :meth:`render` followed by :func:`deodr_amd.ssim.ssim_l2` (``mix`` [2], None: (0, 1); ``data_range``: the span of
+        the intensities), so the adjoint is that term's ``image_b`` through the rasterizer's ``render_backward``.  ``obs`` [n,H,W,C] and ``weights``
+        [n,H,W] or [H,W] (``>= 0``, or None) in the scene's pixel dtype (anything else is converted at every call); the weights multiply the SSIM
+        map and do not enter its windows.  The one-call fit step cannot carry this term: the gradient of a pixel depends on its 11 x 11
+        neighbourhood."""
+        from . import ssim
+
+        image = self.render(camera, backface_culling=backface_culling)
+        n = image.shape[0]
+        obs = obs.to(device=image.device, dtype=image.dtype).expand(n, -1, -1, -1).contiguous()
+        if weights is not None:
+            if tuple(weights.shape) not in ((n, camera.height, camera.width), (camera.height, camera.width)):
+                raise ValueError(f"weights must have shape [{n}, {camera.height}, {camera.width}] or [{camera.height}, {camera.width}], not {list(weights.shape)}")
+            weights = weights.to(device=image.device, dtype=image.dtype).expand(n, -1, -1).contiguous()
+        return ssim.ssim_l2(image, obs, weights, mix, data_range), image
+
     def _differentiated_shared(self):
         """{"texture": mesh.texture, "uv": mesh.uv}, each only when it requires grad: the keyword arguments a textured render passes on"""
         m = self.mesh
