@@ -68,6 +68,7 @@
 #include "../../include/deodr_hip_skinning.h"
 #include "../../include/deodr_hip_pyramid.h"
 #include "../../include/deodr_hip_ssim.h"
+#include "../../include/deodr_hip_solve.h"
 #include "dr_fititer.h" // <- dr_finalize.h <- dr_backward.h <- dr_backward_generic.h <- dr_forward.h <- dr_forward_generic.h <- dr_setup.h <- dr_workspace.h <- dr_prims.h
 #include "dr_texfit.h"  // texture smoothness + step (include/deodr_hip_texture.h); uses grid_sum of dr_fronthalf.h
 #include "dr_subdiv.h"  // rows of a sparse matrix applied to [batch, n, D] blocks (include/deodr_hip_subdiv.h): Loop subdivision and its adjoint
@@ -77,6 +78,7 @@
 #include "dr_skinning.h" // linear blend skinning: joint chain, blend of the influences of a vertex, their adjoints (include/deodr_hip_skinning.h)
 #include "dr_pyramid.h"	 // the multi-scale L2 data term and its adjoint: levels 0 .. 3 per 8 x 8 tile, the levels above on the tile grid (include/deodr_hip_pyramid.h)
 #include "dr_ssim.h"	 // the structural (SSIM) data term and its adjoint: two stencil kernels over 16 x 32 tiles with a halo in LDS (include/deodr_hip_ssim.h)
+#include "dr_solve.h"	 // sparse SPD solve by conjugate gradients: one workgroup per column for small systems, two launches per step above (include/deodr_hip_solve.h)
 
 using namespace dr;
 using namespace dr::dispatch;
@@ -1945,6 +1947,78 @@ int deodr_hip_ssim_l2(const void *image, const void *obs, const void *weights, i
 		return 0;
 	});
 	return check_hip(hipGetLastError(), "ssim_l2 launch");
+}
+
+// ---- sparse symmetric positive definite solve (include/deodr_hip_solve.h, kernels in dr_solve.h)
+
+int deodr_hip_solve_abi_version(void) { return DEODR_HIP_SOLVE_ABI_VERSION; }
+
+namespace
+{
+const char *solve_dims(int n, uint32_t nnz, int D, int iterations)
+{ // -> NULL, or which limit of the header the arguments break
+	if (n <= 0)
+		return "n must be positive";
+	if (nnz < (uint32_t)n)
+		return "nnz must be >= n (the diagonal is stored)";
+	if (D < 1 || D > SOLVE_MAX_D)
+		return "D must be in 1 .. 4";
+	if (iterations < 1)
+		return "iterations must be >= 1";
+	return NULL;
+}
+} // namespace
+
+size_t deodr_hip_spd_solve_scratch_bytes(int n, int D) { return solve_dims(n, (uint32_t)(n > 0 ? n : 0), D, 1) ? 0 : scratch_need(solve_scratch_doubles(n, D)); }
+
+int deodr_hip_spd_solve_launches(int n, uint32_t nnz, int D, int iterations)
+{
+	return solve_dims(n, nnz, D, iterations) ? 0 : solve_small(n) ? 1 : 2 + 2 * iterations;
+}
+
+int deodr_hip_spd_solve(const uint32_t *offsets, const uint32_t *cols, const double *vals, int n, uint32_t nnz, const double *b, double *x, int D,
+						int iterations, double rel_tol, double *residual, void *scratch, size_t scratch_bytes, void *stream)
+{
+	const char *what = "spd_solve";
+	if (!offsets || !cols || !vals || !b || !x || !residual || !scratch)
+		return fail(what, "offsets, cols, vals, b, x, residual or scratch == NULL");
+	if (const char *why = solve_dims(n, nnz, D, iterations))
+		return fail(what, why);
+	if (!(rel_tol >= 0)) // (a NaN is refused as well)
+		return fail(what, "rel_tol must be >= 0");
+	const void *const words[] = {offsets, cols};
+	const void *const doubles[] = {vals, b, x, residual, scratch};
+	if (any_misaligned(words, 4) || any_misaligned(doubles, 8))
+		return fail(what, "misaligned pointer");
+	const Scratch sc = {scratch, scratch_bytes};
+	if (!sc.holds(deodr_hip_spd_solve_scratch_bytes(n, D)))
+		return fail(what, "scratch too small (deodr_hip_spd_solve_scratch_bytes)");
+	const size_t nd = 8 * (size_t)n * (size_t)D;
+	if (ranges_overlap(x, nd, b, nd))
+		return fail(what, "x must not overlap b");
+	const Range outputs[] = {{x, nd}, {residual, 8 * (size_t)D}, {scratch, scratch_bytes}};
+	const Range inputs[] = {{offsets, 4 * ((size_t)n + 1)}, {cols, 4 * (size_t)nnz}, {vals, 8 * (size_t)nnz}, {b, nd}};
+	if (any_overlap(outputs, inputs) || ranges_overlap(x, nd, residual, 8 * (size_t)D) || ranges_overlap(scratch, scratch_bytes, x, nd) ||
+		ranges_overlap(scratch, scratch_bytes, residual, 8 * (size_t)D))
+		return fail(what, "an output must not overlap an input, the scratch or another output");
+	double *const d = sc.doubles(), *const arrays = d + SOLVE_SCALARS + (size_t)SOLVE_BLOCKS * SOLVE_MAX_D;
+	const size_t cells = (size_t)n * (size_t)D;
+	const SolveArgs a = {offsets, cols, vals, b, x, residual, d, d + SOLVE_SCALARS, arrays, arrays + 3 * cells, sc.counter(0), rel_tol * rel_tol, n, D, iterations};
+	const hipStream_t st = (hipStream_t)stream;
+	if (solve_small(n))
+		hipLaunchKernelGGL(solve_small_kernel, dim3(D), dim3(SOLVE_SMALL_THREADS), 0, st, a);
+	else
+	{
+		double *const p0 = arrays + cells, *const p1 = arrays + 2 * cells;
+		switch (D)
+		{
+		case 1: solve_launch_large<1>(a, p0, p1, st); break;
+		case 2: solve_launch_large<2>(a, p0, p1, st); break;
+		case 3: solve_launch_large<3>(a, p0, p1, st); break;
+		default: solve_launch_large<4>(a, p0, p1, st); break;
+		}
+	}
+	return check_hip(hipGetLastError(), "spd_solve launch");
 }
 
 #ifdef DR_WAVE_TRACE

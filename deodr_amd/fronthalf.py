@@ -497,6 +497,28 @@ class SSIML2Func(torch.autograd.Function):
         return image_b * loss_b.to(image_b.dtype), None, None, None, None
 
 
+class SpdSolveFunc(torch.autograd.Function):
+    """(b [n,D]; system: a :class:`deodr_amd.smoothing.SpdSystem`, iterations, rel_tol: constants) -> (x, residual [D]) of
+    ``deodr_amd.smoothing.spd_solve``, differentiable in ``b``.  ``A`` is symmetric, so the adjoint of ``b -> A^-1 b`` is the same solve of the
+    incoming gradient.  With a truncated recurrence that is the adjoint of the CONVERGED operator, not of the ``iterations`` steps themselves (which
+    are not linear in ``b``): exact only as far as the solve converges.  ``residual`` carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, b, system, iterations, rel_tol):
+        from . import smoothing
+
+        ctx.system, ctx.iterations, ctx.rel_tol = system, iterations, rel_tol
+        x, residual = smoothing.solve_no_grad(system, b, iterations, rel_tol)
+        ctx.mark_non_differentiable(residual)
+        return x, residual
+
+    @staticmethod
+    def backward(ctx, x_b, _residual_b):
+        from . import smoothing
+
+        return smoothing.spd_solve(ctx.system, x_b.contiguous(), ctx.iterations, ctx.rel_tol)[0], None, None, None
+
+
 def sh_shade(posed, sh, albedo, topology):
     """-> luminosity [n,V] (``albedo`` None) or colors [n,V,C] of the posed vertices [n,V,3] (or [V,3]) under the SH lighting ``sh``, differentiable in
     all three: the kernels on float64 ROCm tensors, the same formulas as torch ops (``lighting.sh_shade_torch``) otherwise"""

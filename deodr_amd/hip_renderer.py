@@ -39,8 +39,9 @@ _COMPANIONS = (
     (_abi.SKINNING_HEADER, "skinning", "skinning"),  # linear blend skinning
     (_abi.PYRAMID_HEADER, "pyramid", "pyramid-loss"),  # multi-scale L2 data term
     (_abi.SSIM_HEADER, "ssim", "ssim-loss"),  # structural (SSIM) data term
+    (_abi.SOLVE_HEADER, "solve", "sparse-solve"),  # sparse SPD solve: smoothed vertex steps
 )
-TEXTURE_ABI_VERSION, SUBDIV_ABI_VERSION, RETAINED_ABI_VERSION, BASIS_ABI_VERSION, CAMERA_ABI_VERSION, LIGHTING_ABI_VERSION, SKINNING_ABI_VERSION, PYRAMID_ABI_VERSION, SSIM_ABI_VERSION = (
+TEXTURE_ABI_VERSION, SUBDIV_ABI_VERSION, RETAINED_ABI_VERSION, BASIS_ABI_VERSION, CAMERA_ABI_VERSION, LIGHTING_ABI_VERSION, SKINNING_ABI_VERSION, PYRAMID_ABI_VERSION, SSIM_ABI_VERSION, SOLVE_ABI_VERSION = (
     h.defines[f"DEODR_HIP_{key.upper()}_ABI_VERSION"] for h, key, _ in _COMPANIONS
 )
 # words of the 64-byte status block at the start of the workspace
@@ -1420,6 +1421,67 @@ def ssim_l2(image, obs, weights, mix, data_range=1.0, terms=None, loss=None, ima
         if t is not None:
             _touched(t)
     return terms, loss, image_b
+
+
+# ---- sparse symmetric positive definite solve (include/deodr_hip_solve.h) -----------------------------------------------------------------
+
+SOLVE_N_SMALL = _abi.SOLVE_HEADER.defines["DEODR_HIP_SOLVE_N_SMALL"]
+SOLVE_MAX_D = 4  # (the limit include/deodr_hip_solve.h states)
+
+
+def spd_launches(n, nnz, D, iterations):
+    """``deodr_hip_spd_solve_launches``: the kernel launches of a :func:`spd_solve` call -- 1 up to ``SOLVE_N_SMALL`` rows, ``2 + 2 iterations`` above"""
+    return int(lib().deodr_hip_spd_solve_launches(int(n), int(nnz), int(D), int(iterations)))
+
+
+def spd_scratch(n, D, device):
+    """the scratch of :func:`spd_solve` for a system of n rows and D columns (one per stream in use; it need not be zeroed)"""
+    need = int(lib().deodr_hip_spd_solve_scratch_bytes(int(n), int(D)))
+    if need == 0:
+        raise ValueError(f"spd_scratch: n = {n}, D = {D} is outside the limits of include/deodr_hip_solve.h")
+    with torch.cuda.device(device):
+        return torch.empty(need, dtype=torch.uint8, device=device)
+
+
+def spd_solve(offsets, cols, vals, b, iterations, rel_tol=0.0, x=None, residual=None, scratch=None):
+    """``deodr_hip_spd_solve``: ``iterations`` steps of conjugate gradients from ``x = 0`` on ``A x = b``, the columns of ``b`` [n, D <= 4] (float64)
+    independently -> (x [n, D], residual [D]: the squared relative residual of the recurrence); the header has the recurrence.  ``A`` in compressed
+    rows: ``offsets`` [n + 1] and ``cols`` [nnz] as 4-byte integer tensors (uint32 bit patterns), ``vals`` [nnz] float64, read when the kernels run.
+    The tables are trusted (symmetric positive definite, ``offsets`` non-decreasing from 0 to nnz, ``cols`` < n): :mod:`deodr_amd.smoothing` checks
+    its own on the host.  Deterministic; asynchronous on the current stream.  ``scratch``: a :func:`spd_scratch` of the caller's; None: one per
+    device and stream."""
+    what = "spd_solve"
+    _rocm_tensor(what, "b", b)
+    if b.dim() != 2 or b.shape[0] < 1 or not 1 <= b.shape[1] <= SOLVE_MAX_D:
+        raise ValueError(f"{what}: b must have shape [n >= 1, 1 <= D <= {SOLVE_MAX_D}], not {list(b.shape)}")
+    n, D = (int(v) for v in b.shape)
+    iterations, rel_tol = int(iterations), float(rel_tol)
+    if iterations < 1:
+        raise ValueError(f"{what}: iterations must be >= 1, not {iterations}")
+    if not rel_tol >= 0:
+        raise ValueError(f"{what}: rel_tol must be >= 0, not {rel_tol}")
+    tables = "offsets and cols must be one-dimensional 4-byte integer tensors"
+    rows = [("b", b, _F64_ONLY, None), ("offsets", offsets, _INDICES, (n + 1,), f"offsets must be a 4-byte integer tensor of n + 1 = {n + 1} entries"),
+            ("cols", cols, _INDICES, (None,), tables)]  # fmt: skip
+    _check_tensors(what, "b", b.device, rows)
+    rows = [("vals", vals, _F64_ONLY, tuple(cols.shape), "vals must be a float64 tensor of the shape of cols")]
+    optional = (("x", x, _F64_ONLY, (n, D)), ("residual", residual, _F64_ONLY, (D,)), ("scratch", scratch, (torch.uint8,), (None,)))
+    rows += [row for row in optional if row[1] is not None]
+    _check_tensors(what, "b", b.device, rows)
+    nnz, dev = int(cols.numel()), b.device
+    if nnz < n:
+        raise ValueError(f"{what}: the matrix has {nnz} entries for {n} rows (the diagonal is stored)")
+    with torch.cuda.device(dev):
+        x = torch.empty_like(b) if x is None else x
+        residual = torch.empty(D, dtype=torch.float64, device=dev) if residual is None else residual
+        if scratch is None:
+            need = int(lib().deodr_hip_spd_solve_scratch_bytes(n, D))
+            scratch = _cached_scratch("solve", dev, need, lambda: spd_scratch(n, D, dev),
+                                      f"{what}: pass scratch= (spd_scratch) when capturing a graph: none of this size exists for this stream yet")  # fmt: skip
+    _launch(lib().deodr_hip_spd_solve, dev, _ptr(offsets), _ptr(cols), _ptr(vals), n, nnz, _ptr(b), _ptr(x), D, iterations, rel_tol, _ptr(residual),
+            _ptr(scratch), scratch.numel())  # fmt: skip
+    _touched(x), _touched(residual)
+    return x, residual
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -85,6 +85,18 @@ def _ssim_mix(weight, data_range, pyramid_levels, device):
     return (torch.as_tensor([1.0 - weight, weight], dtype=torch.float64, device=device) if weight > 0 else None), float(data_range)
 
 
+def _smoothing_keywords(smoothing, iterations):
+    """the ``smoothing=`` / ``smoothing_iterations=`` keywords of the pose fitters -> (lambda as a float, 0: off; the steps of the solve)"""
+    from . import smoothing as sm
+
+    if isinstance(smoothing, bool) or not isinstance(smoothing, (int, float, np.integer, np.floating)) or not 0 <= float(smoothing) < np.inf:  # (a NaN is refused as well)
+        raise ValueError(f"smoothing must be a finite real number >= 0, not {smoothing!r}")
+    iterations = sm.DEFAULT_ITERATIONS if iterations is None else iterations
+    if isinstance(iterations, bool) or int(iterations) != iterations or int(iterations) < 1:
+        raise ValueError(f"smoothing_iterations must be an integer >= 1, not {iterations!r}")
+    return float(smoothing), int(iterations)
+
+
 def _kernel_clamp(step_max):
     """the kernels' convention for the clamp of a step: None or not positive means none"""
     return step_max if step_max is not None and step_max > 0 else None
@@ -355,7 +367,18 @@ class _PoseFitter:
     the vertices and the joints were given in, then the mean of the rest vertices is subtracted (the vertices are then NOT re-centred between steps:
     they stay in the frame of the joints).  The rigid energy acts on the rest vertices as before; with ``shape_basis`` the basis comes first, the skin
     second.  The update is one more momentum entry with ``step_factor_joints``, rows renormalised; ``joint_regu >= 0`` adds the prior
-    ``joint_regu sum |q - q_init|^2``.  The iteration runs through autograd; ``skin`` with ``subdivisions > 0`` is refused."""
+    ``joint_regu sum |q - q_init|^2``.  The iteration runs through autograd; ``skin`` with ``subdivisions > 0`` is refused.
+
+    ``smoothing`` (0: off, nothing is built and every path is as it is without the keyword) = lambda > 0: the vertices step in the metric
+    ``I + lambda L`` of the graph Laplacian ``L`` (deodr_amd/smoothing.py).  The vertex entry of the momentum update receives
+    ``u = (I + lambda L)^-1 (g_data + g_rigid)`` -- ``smoothing_iterations`` steps of conjugate gradients (None: ``smoothing.DEFAULT_ITERATIONS``), one
+    launch on the device for a mesh of up to 1024 vertices -- in place of the sum of the two gradients (under ``torch.distributed`` after the
+    all-reduce); the clamp and the momentum act on ``u``, the poses, lights, colours and joints are untouched.  A rough, sparse gradient becomes a
+    smooth one of the same mean, so ``step_factor_vertices`` can be larger than without.  With ``subdivisions`` ``L`` is the cage's Laplacian and the
+    cage gradient is smoothed, with ``skin`` the gradient of the rest vertices; with ``shape_basis`` the keyword is refused (the parameter is the
+    coefficient vector).  ``self.smoothing_system`` is the :class:`deodr_amd.smoothing.SpdSystem` (``copy_`` the values of another lambda into its
+    ``vals`` between steps, also under a ``GraphedStep``), ``self.smoothing_residual`` [3] the squared relative residual the last solve ended with,
+    for display.  The iteration runs through autograd; ``GraphedStep`` replays it."""
 
     direct = True  # run an iteration as the fixed kernel sequence of _DirectIteration when the tensors allow it (False: always autograd)
 
@@ -367,7 +390,8 @@ class _PoseFitter:
     step_factor_joints = 0.0003
 
     def __init__(self, vertices, faces, euler_init, translation_init, cregu, inertia, damping, device, n_poses=1, clockwise=False, pixel_dtype=torch.float64,
-                 subdivisions=0, shape_basis=None, coefficient_regu=0.0, sigmas=None, skin=None, joint_quaternions_init=None, joint_regu=0.0):  # fmt: skip
+                 subdivisions=0, shape_basis=None, coefficient_regu=0.0, sigmas=None, skin=None, joint_quaternions_init=None, joint_regu=0.0,
+                 smoothing=0.0, smoothing_iterations=None):  # fmt: skip
         self.device = torch.device(device)
         self.cregu, self.inertia, self.damping = cregu, inertia, damping
         v0 = np.asarray(vertices, dtype=np.float64)
@@ -401,6 +425,14 @@ class _PoseFitter:
         self.skin = skin
         if skin is not None:
             self._init_skin(v0, joint_quaternions_init, joint_regu)
+        self.smoothing, self.smoothing_iterations = _smoothing_keywords(smoothing, smoothing_iterations)
+        self.smoothing_system = self.smoothing_residual = None
+        if self.smoothing > 0:
+            from .smoothing import laplacian_system
+
+            if self.shape_basis is not None:
+                raise ValueError("smoothing with shape_basis is not supported: the parameter is the coefficient vector, not the vertices")
+            self.smoothing_system = laplacian_system(self.control_mesh.topology, self.smoothing)  # (with subdivisions: of the cage, the parameter)
         q0 = np.asarray([_quat_from_euler_zyx(e) for e in np.atleast_2d(euler_init)])
         t0 = np.atleast_2d(np.asarray(translation_init, dtype=np.float64))
         self.transform_quaternion_init = torch.as_tensor(np.broadcast_to(q0, (n_poses, 4)).copy(), device=self.device)
@@ -490,7 +522,12 @@ class _PoseFitter:
     def _update_pose_and_shape(self, g_vertices, g_quaternion, g_translation, grad_rigidity, step_max, extra=()):
         """the rebinding momentum update of the shape (the vertices; with ``shape_basis`` the coefficients: the total vertex gradient goes through the
         basis adjoint), the poses and the ``extra`` entries -> the new values of the extras"""
-        if self.shape_basis is None:
+        if self.smoothing_system is not None:  # the step in the metric I + lambda L: one solve of the total vertex gradient, then the same rule
+            from .smoothing import spd_solve
+
+            u, self.smoothing_residual = spd_solve(self.smoothing_system, (g_vertices + grad_rigidity).detach(), self.smoothing_iterations)
+            shape = ("vertices", self.vertices, u, None, self.step_factor_vertices, step_max[0], 0)
+        elif self.shape_basis is None:
             shape = ("vertices", self.vertices, g_vertices, grad_rigidity, self.step_factor_vertices, step_max[0], 0)
         else:
             g_c, g_prior = self.coefficients_gradient(g_vertices + grad_rigidity)
@@ -522,6 +559,8 @@ class _PoseFitter:
         if self.subdivisions or self.shape_basis is not None or self.skin is not None:  # (with a basis or a skin the rendered vertex array is not the parameter either)
             return None
         if self.pyramid_levels or self.ssim_mix is not None:  # (the multi-scale and the structural data term are not the fit step's: render, the term's image_b, render_backward under autograd)
+            return None
+        if self.smoothing_system is not None:  # (the solve sits between the gradients and the momentum update, which the fixed sequence fuses with the energy)
             return None
 
         topo = self.mesh.topology
@@ -597,10 +636,12 @@ class MeshDepthFitter(_PoseFitter):
     """Fit a deformable mesh to a depth image (reference deodr/mesh_fitter.py:20-196)."""
 
     def __init__(self, vertices, faces, euler_init, translation_init, cregu=2000, inertia=0.96, damping=0.05, device="cuda", pixel_dtype=torch.float64,
-                 subdivisions=0, shape_basis=None, coefficient_regu=0.0, sigmas=None, skin=None, joint_quaternions_init=None, joint_regu=0.0):  # fmt: skip
+                 subdivisions=0, shape_basis=None, coefficient_regu=0.0, sigmas=None, skin=None, joint_quaternions_init=None, joint_regu=0.0,
+                 smoothing=0.0, smoothing_iterations=None):  # fmt: skip
         super().__init__(vertices, faces, euler_init, translation_init, cregu, inertia, damping, device, pixel_dtype=pixel_dtype, subdivisions=subdivisions,
                          shape_basis=shape_basis, coefficient_regu=coefficient_regu, sigmas=sigmas, skin=skin,
-                         joint_quaternions_init=joint_quaternions_init, joint_regu=joint_regu)  # fmt: skip
+                         joint_quaternions_init=joint_quaternions_init, joint_regu=joint_regu, smoothing=smoothing,
+                         smoothing_iterations=smoothing_iterations)  # fmt: skip
         self.camera_center = self.object_center + np.array([-0.5, 0, 5]) * self.object_radius
 
     def set_max_depth(self, max_depth):
@@ -751,7 +792,7 @@ class MeshRGBFitterWithPose(_PoseFitter):
                  inertia=0.96, damping=0.05, update_lights=True, update_color=True, device="cuda", pixel_dtype=torch.float64, n_poses=1,
                  subdivisions=0, shape_basis=None, coefficient_regu=0.0, sigmas=None, light_sh_init=None, vertex_albedo=False, albedo_regu=0.0,
                  skin=None, joint_quaternions_init=None, joint_regu=0.0, pyramid_levels=0, pyramid_weights=None, ssim_weight=0.0,
-                 ssim_data_range=1.0):  # fmt: skip
+                 ssim_data_range=1.0, smoothing=0.0, smoothing_iterations=None):  # fmt: skip
         self.pyramid_levels, self.pyramid_weights = _pyramid_schedule(pyramid_levels, pyramid_weights, torch.device(device))
         self.ssim_mix, self.ssim_data_range = _ssim_mix(ssim_weight, ssim_data_range, self.pyramid_levels, torch.device(device))
         self.default_color = np.asarray(default_color, dtype=np.float64)
@@ -761,7 +802,8 @@ class MeshRGBFitterWithPose(_PoseFitter):
         self.update_lights, self.update_color = update_lights, update_color
         super().__init__(vertices, faces, euler_init, translation_init, cregu, inertia, damping, device, n_poses=n_poses, pixel_dtype=pixel_dtype,
                          subdivisions=subdivisions, shape_basis=shape_basis, coefficient_regu=coefficient_regu, sigmas=sigmas, skin=skin,
-                         joint_quaternions_init=joint_quaternions_init, joint_regu=joint_regu)  # fmt: skip
+                         joint_quaternions_init=joint_quaternions_init, joint_regu=joint_regu, smoothing=smoothing,
+                         smoothing_iterations=smoothing_iterations)  # fmt: skip
         self.camera_center = self.object_center + np.atleast_2d(np.asarray(translation_init, dtype=np.float64))[0] + np.array([0, 0, 9]) * self.object_radius
 
     step_factor_light_sh, step_factor_albedo = 0.0001, 0.00001  # (those of the directional light and of the single colour)
@@ -986,7 +1028,7 @@ class MeshRGBFitterWithPoseMultiFrame(MeshRGBFitterWithPose):
                  cdata=1, inertia=0.97, damping=0.15, update_lights=True, update_color=True, device="cuda", pixel_dtype=torch.float64, group=None,
                  subdivisions=0, shape_basis=None, coefficient_regu=0.0, sigmas=None, light_sh_init=None, vertex_albedo=False, albedo_regu=0.0,
                  skin=None, joint_quaternions_init=None, joint_regu=0.0, pyramid_levels=0, pyramid_weights=None, ssim_weight=0.0,
-                 ssim_data_range=1.0):  # fmt: skip
+                 ssim_data_range=1.0, smoothing=0.0, smoothing_iterations=None):  # fmt: skip
         euler_init, translation_init = np.atleast_2d(euler_init), np.atleast_2d(translation_init)
         self.cdata = cdata
         self.n_views_total = max(len(euler_init), len(translation_init))
@@ -1001,7 +1043,7 @@ class MeshRGBFitterWithPoseMultiFrame(MeshRGBFitterWithPose):
                          shape_basis=shape_basis, coefficient_regu=coefficient_regu, sigmas=sigmas, light_sh_init=light_sh_init,
                          vertex_albedo=vertex_albedo, albedo_regu=albedo_regu, skin=skin, joint_quaternions_init=joint_quaternions_init,
                          joint_regu=joint_regu, pyramid_levels=pyramid_levels, pyramid_weights=pyramid_weights, ssim_weight=ssim_weight,
-                         ssim_data_range=ssim_data_range)  # fmt: skip
+                         ssim_data_range=ssim_data_range, smoothing=smoothing, smoothing_iterations=smoothing_iterations)  # fmt: skip
         self.camera_center = self.object_center + np.array([0, 0, 6]) * self.object_radius
         self._packed = None
 
