@@ -1,6 +1,6 @@
 // deodr_amd/csrc/dr_fronthalf.h -- part of the single translation unit dr_kernels.hip (device code, gfx950 / wave64).
 // The O(V) algebra either side of the rasterizer in a fit iteration.  At the top of THIS file and nowhere else, what the kernels
-// of dr_fititer.h, dr_texfit.h, dr_subdiv.h, dr_basis.h, dr_camera.h, dr_lighting.h, dr_skinning.h, dr_pyramid.h, dr_ssim.h and dr_solve.h share with the ones here: Vec3, unit, qrot_point, CameraRow,
+// of dr_fititer.h, dr_texfit.h, dr_subdiv.h, dr_basis.h, dr_camera.h, dr_lighting.h, dr_skinning.h, dr_pyramid.h, dr_ssim.h, dr_solve.h and dr_arap.h share with the ones here: Vec3, unit, qrot_point, CameraRow,
 // project_point and their adjoints; lane_group_sum, last_to_arrive (the arrival ticket), grid_sum, total_of_thread, store_or_add.  Then the kernels:
 //
 //   rigid_transform_kernel (+ _b)   centred vertices -> posed vertices of every view: qrot(q, v) + t

@@ -69,6 +69,7 @@
 #include "../../include/deodr_hip_pyramid.h"
 #include "../../include/deodr_hip_ssim.h"
 #include "../../include/deodr_hip_solve.h"
+#include "../../include/deodr_hip_arap.h"
 #include "dr_fititer.h" // <- dr_finalize.h <- dr_backward.h <- dr_backward_generic.h <- dr_forward.h <- dr_forward_generic.h <- dr_setup.h <- dr_workspace.h <- dr_prims.h
 #include "dr_texfit.h"  // texture smoothness + step (include/deodr_hip_texture.h); uses grid_sum of dr_fronthalf.h
 #include "dr_subdiv.h"  // rows of a sparse matrix applied to [batch, n, D] blocks (include/deodr_hip_subdiv.h): Loop subdivision and its adjoint
@@ -79,6 +80,7 @@
 #include "dr_pyramid.h"	 // the multi-scale L2 data term and its adjoint: levels 0 .. 3 per 8 x 8 tile, the levels above on the tile grid (include/deodr_hip_pyramid.h)
 #include "dr_ssim.h"	 // the structural (SSIM) data term and its adjoint: two stencil kernels over 16 x 32 tiles with a halo in LDS (include/deodr_hip_ssim.h)
 #include "dr_solve.h"	 // sparse SPD solve by conjugate gradients: one workgroup per column for small systems, two launches per step above (include/deodr_hip_solve.h)
+#include "dr_arap.h"	 // as-rigid-as-possible energy: a 3 x 3 polar decomposition per vertex by Jacobi on Horn's matrix, then the gradient (include/deodr_hip_arap.h)
 
 using namespace dr;
 using namespace dr::dispatch;
@@ -2019,6 +2021,70 @@ int deodr_hip_spd_solve(const uint32_t *offsets, const uint32_t *cols, const dou
 		}
 	}
 	return check_hip(hipGetLastError(), "spd_solve launch");
+}
+
+// ---- as-rigid-as-possible energy (include/deodr_hip_arap.h, kernels in dr_arap.h)
+
+int deodr_hip_arap_abi_version(void) { return DEODR_HIP_ARAP_ABI_VERSION; }
+
+namespace
+{
+const char *arap_dims(int V, int n)
+{ // -> NULL, or which limit of the header the arguments break
+	if (V <= 0)
+		return "V must be positive";
+	if (n <= 0 || n > ARAP_MAX_POSES)
+		return "n must be in 1 .. 65535";
+	return NULL;
+}
+} // namespace
+
+size_t deodr_hip_arap_scratch_bytes(int V, int n) { return arap_dims(V, n) ? 0 : scratch_need(arap_scratch_doubles(V, n)); }
+
+int deodr_hip_arap_blocks(int V) { return V <= 0 ? 0 : (int)arap_blocks(V); }
+
+int deodr_hip_arap_launches(int V, uint32_t nnz, int n)
+{
+	(void)nnz;
+	return arap_dims(V, n) ? 0 : 2;
+}
+
+int deodr_hip_arap_energy(const uint32_t *offsets, const uint32_t *cols, const double *weights, int V, uint32_t nnz, const double *vertices_ref,
+						  const double *vertices, int n, double cregu, double *energy, double *gradient, double *rotations, void *scratch,
+						  size_t scratch_bytes, void *stream)
+{
+	const char *what = "arap_energy";
+	if (!offsets || !vertices_ref || !vertices || !energy || !gradient || !scratch || (nnz && (!cols || !weights)))
+		return fail(what, "offsets, cols, weights, vertices_ref, vertices, energy, gradient or scratch == NULL");
+	if (const char *why = arap_dims(V, n))
+		return fail(what, why);
+	if (!(cregu >= 0)) // (a NaN is refused as well)
+		return fail(what, "cregu must be >= 0");
+	const void *const words[] = {offsets, cols};
+	const void *const doubles[] = {weights, vertices_ref, vertices, energy, gradient, rotations, scratch};
+	if (any_misaligned(words, 4) || any_misaligned(doubles, 8))
+		return fail(what, "misaligned pointer");
+	const Scratch sc = {scratch, scratch_bytes};
+	if (!sc.holds(deodr_hip_arap_scratch_bytes(V, n)))
+		return fail(what, "scratch too small (deodr_hip_arap_scratch_bytes)");
+	const size_t cells = (size_t)n * (size_t)V;
+	const Range outputs[] = {{energy, 8 * (size_t)n}, {gradient, 24 * cells}, {rotations, 32 * cells}, {scratch, scratch_bytes}};
+	const Range inputs[] = {{offsets, 4 * ((size_t)V + 1)}, {cols, 4 * (size_t)nnz}, {weights, 8 * (size_t)nnz}, {vertices_ref, 24 * (size_t)V}, {vertices, 24 * cells}};
+	bool clash = any_overlap(outputs, inputs);
+	for (size_t i = 0; i < 4; i++)
+		for (size_t j = i + 1; j < 4; j++)
+			clash = clash || ranges_overlap(outputs[i].p, outputs[i].bytes, outputs[j].p, outputs[j].bytes);
+	if (clash)
+		return fail(what, "an output must not overlap an input, the scratch or another output");
+	double *const d = sc.doubles();
+	double *const partials = d + 5 * cells;
+	const ArapArgs a = {offsets, cols, weights, vertices_ref, vertices, energy, gradient, rotations, d, d + 4 * cells, partials,
+						(unsigned *)(partials + (size_t)ARAP_MAX_BLOCKS * (size_t)n), cregu, V, n};
+	const hipStream_t st = (hipStream_t)stream;
+	const dim3 grid(arap_blocks(V), (unsigned)n), block(ARAP_BLOCK);
+	hipLaunchKernelGGL(arap_rotations_kernel, grid, block, 0, st, a);
+	hipLaunchKernelGGL(arap_gradient_kernel, grid, block, 0, st, a);
+	return check_hip(hipGetLastError(), "arap_energy launch");
 }
 
 #ifdef DR_WAVE_TRACE

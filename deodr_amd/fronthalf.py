@@ -338,7 +338,7 @@ class VertexLuminosityFunc(torch.autograd.Function):
 
 
 class RigidEnergyFunc(torch.autograd.Function):
-    """vertices [V,3] -> (energy, gradient [V,3]) of the as-rigid-as-possible energy (deodr/laplacian_rigid_energy.py:15-41) in one kernel;
+    """vertices [V,3] -> (energy, gradient [V,3]) of the Laplacian rigid energy (deodr/laplacian_rigid_energy.py:15-41) in one kernel;
     the energy is differentiable (its adjoint is the gradient the same launch produced)"""
 
     @staticmethod
@@ -517,6 +517,24 @@ class SpdSolveFunc(torch.autograd.Function):
         from . import smoothing
 
         return smoothing.spd_solve(ctx.system, x_b.contiguous(), ctx.iterations, ctx.rel_tol)[0], None, None, None
+
+
+class ArapEnergyFunc(torch.autograd.Function):
+    """(vertices [n,V,3]; energy: a :class:`deodr_amd.arap.ArapEnergyDevice`) -> (energy [n], gradient [n,V,3]) of the as-rigid-as-possible energy
+    (include/deodr_hip_arap.h) in two launches; the energy is differentiable (its adjoint is the gradient the same call produced, exact wherever
+    the rotations of the cells are unique), the gradient is not"""
+
+    @staticmethod
+    def forward(ctx, vertices, arap):
+        energy, grad, _ = arap.evaluate_no_grad(vertices)
+        ctx.save_for_backward(grad)
+        ctx.mark_non_differentiable(grad)
+        return energy, grad
+
+    @staticmethod
+    def backward(ctx, energy_b, _grad_b):
+        (grad,) = ctx.saved_tensors
+        return energy_b[:, None, None] * grad, None
 
 
 def sh_shade(posed, sh, albedo, topology):

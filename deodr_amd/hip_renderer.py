@@ -40,8 +40,9 @@ _COMPANIONS = (
     (_abi.PYRAMID_HEADER, "pyramid", "pyramid-loss"),  # multi-scale L2 data term
     (_abi.SSIM_HEADER, "ssim", "ssim-loss"),  # structural (SSIM) data term
     (_abi.SOLVE_HEADER, "solve", "sparse-solve"),  # sparse SPD solve: smoothed vertex steps
+    (_abi.ARAP_HEADER, "arap", "arap-energy"),  # as-rigid-as-possible energy
 )
-TEXTURE_ABI_VERSION, SUBDIV_ABI_VERSION, RETAINED_ABI_VERSION, BASIS_ABI_VERSION, CAMERA_ABI_VERSION, LIGHTING_ABI_VERSION, SKINNING_ABI_VERSION, PYRAMID_ABI_VERSION, SSIM_ABI_VERSION, SOLVE_ABI_VERSION = (
+TEXTURE_ABI_VERSION, SUBDIV_ABI_VERSION, RETAINED_ABI_VERSION, BASIS_ABI_VERSION, CAMERA_ABI_VERSION, LIGHTING_ABI_VERSION, SKINNING_ABI_VERSION, PYRAMID_ABI_VERSION, SSIM_ABI_VERSION, SOLVE_ABI_VERSION, ARAP_ABI_VERSION = (
     h.defines[f"DEODR_HIP_{key.upper()}_ABI_VERSION"] for h, key, _ in _COMPANIONS
 )
 # words of the 64-byte status block at the start of the workspace
@@ -1482,6 +1483,73 @@ def spd_solve(offsets, cols, vals, b, iterations, rel_tol=0.0, x=None, residual=
             _ptr(scratch), scratch.numel())  # fmt: skip
     _touched(x), _touched(residual)
     return x, residual
+
+
+# ---- as-rigid-as-possible energy (include/deodr_hip_arap.h) --------------------------------------------------------------------------------
+
+ARAP_SWEEPS, ARAP_BLOCK, ARAP_MAX_BLOCKS = (_abi.ARAP_HEADER.defines["DEODR_HIP_ARAP_" + n] for n in ("SWEEPS", "BLOCK", "MAX_BLOCKS"))
+
+
+def arap_launches(V, nnz, n):
+    """``deodr_hip_arap_launches``: the kernel launches of an :func:`arap_energy` call, 2 (0 for shapes the call refuses)"""
+    return int(lib().deodr_hip_arap_launches(int(V), int(nnz), int(n)))
+
+
+def arap_blocks(V):
+    """``deodr_hip_arap_blocks``: the workgroups per pose of both launches, ``min(ceil(V / ARAP_BLOCK), ARAP_MAX_BLOCKS)``; the grid is (blocks, n)"""
+    return int(lib().deodr_hip_arap_blocks(int(V)))
+
+
+def arap_scratch(V, n, device):
+    """the scratch of :func:`arap_energy` for n poses of V vertices (one per stream in use; it need not be zeroed)"""
+    need = int(lib().deodr_hip_arap_scratch_bytes(int(V), int(n)))
+    if need == 0:
+        raise ValueError(f"arap_scratch: V = {V}, n = {n} is outside the limits of include/deodr_hip_arap.h")
+    with torch.cuda.device(device):
+        return torch.empty(need, dtype=torch.uint8, device=device)
+
+
+def arap_energy(offsets, cols, weights, vertices_ref, vertices, cregu, energy=None, gradient=None, rotations=None, scratch=None, want_rotations=False):
+    """``deodr_hip_arap_energy``: the as-rigid-as-possible energy of ``vertices`` [n,V,3] against ``vertices_ref`` [V,3] (float64) over the vertex
+    adjacency in compressed rows -- ``offsets`` [V + 1] and ``cols`` [nnz] as 4-byte integer tensors (uint32 bit patterns), ``weights`` [nnz]
+    float64, read when the kernels run -> (energy [n], gradient [n,V,3], rotations [n,V,4] as (x, y, z, w) quaternions or None); the header has
+    the operation.  ``rotations`` is written when a tensor is given or ``want_rotations``.  The tables are trusted (:mod:`deodr_amd.arap` checks
+    its own on the host).  Deterministic; asynchronous on the current stream.  ``scratch``: an :func:`arap_scratch` of the caller's; None: one per
+    device and stream."""
+    what = "arap_energy"
+    _rocm_tensor(what, "vertices", vertices)
+    if vertices.dim() != 3 or vertices.shape[0] < 1 or vertices.shape[1] < 1 or vertices.shape[2] != 3:
+        raise ValueError(f"{what}: vertices must have shape [n >= 1, V >= 1, 3], not {list(vertices.shape)}")
+    n, V = int(vertices.shape[0]), int(vertices.shape[1])
+    cregu = float(cregu)
+    if not cregu >= 0:
+        raise ValueError(f"{what}: cregu must be >= 0, not {cregu}")
+    tables = "offsets and cols must be one-dimensional 4-byte integer tensors"
+    rows = [("vertices", vertices, _F64_ONLY, None), ("vertices_ref", vertices_ref, _F64_ONLY, (V, 3)),
+            ("offsets", offsets, _INDICES, (V + 1,), f"offsets must be a 4-byte integer tensor of V + 1 = {V + 1} entries"),
+            ("cols", cols, _INDICES, (None,), tables)]  # fmt: skip
+    _check_tensors(what, "vertices", vertices.device, rows)
+    rows = [("weights", weights, _F64_ONLY, tuple(cols.shape), "weights must be a float64 tensor of the shape of cols")]
+    optional = (("energy", energy, _F64_ONLY, (n,)), ("gradient", gradient, _F64_ONLY, (n, V, 3)), ("rotations", rotations, _F64_ONLY, (n, V, 4)),
+                ("scratch", scratch, (torch.uint8,), (None,)))  # fmt: skip
+    rows += [row for row in optional if row[1] is not None]
+    _check_tensors(what, "vertices", vertices.device, rows)
+    nnz, dev = int(cols.numel()), vertices.device
+    with torch.cuda.device(dev):
+        energy = torch.empty(n, dtype=torch.float64, device=dev) if energy is None else energy
+        gradient = torch.empty_like(vertices) if gradient is None else gradient
+        if rotations is None and want_rotations:
+            rotations = torch.empty((n, V, 4), dtype=torch.float64, device=dev)
+        if scratch is None:
+            need = int(lib().deodr_hip_arap_scratch_bytes(V, n))
+            scratch = _cached_scratch("arap", dev, need, lambda: arap_scratch(V, n, dev),
+                                      f"{what}: pass scratch= (arap_scratch) when capturing a graph: none of this size exists for this stream yet")  # fmt: skip
+    _launch(lib().deodr_hip_arap_energy, dev, _ptr(offsets), _ptr(cols), _ptr(weights), V, nnz, _ptr(vertices_ref), _ptr(vertices), n, cregu,
+            _ptr(energy), _ptr(gradient), _ptr(rotations), _ptr(scratch), scratch.numel())  # fmt: skip
+    _touched(energy), _touched(gradient)
+    if rotations is not None:
+        _touched(rotations)
+    return energy, gradient, rotations
 
 
 # ---------------------------------------------------------------------------------------------------------------------

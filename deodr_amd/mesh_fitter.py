@@ -378,7 +378,16 @@ class _PoseFitter:
     cage gradient is smoothed, with ``skin`` the gradient of the rest vertices; with ``shape_basis`` the keyword is refused (the parameter is the
     coefficient vector).  ``self.smoothing_system`` is the :class:`deodr_amd.smoothing.SpdSystem` (``copy_`` the values of another lambda into its
     ``vals`` between steps, also under a ``GraphedStep``), ``self.smoothing_residual`` [3] the squared relative residual the last solve ended with,
-    for display.  The iteration runs through autograd; ``GraphedStep`` replays it."""
+    for display.  The iteration runs through autograd; ``GraphedStep`` replays it.
+
+    ``rigidity``: "laplacian" (the default: the reference's ``0.5 cregu d^T (L^T L) d`` of the displacement ``d``, nothing else is built and every
+    path is as it is without the keyword) or "arap": ``self.rigid_energy`` is a :class:`deodr_amd.arap.ArapEnergyDevice` -- the
+    as-rigid-as-possible energy of Sorkine and Alexa, which does not charge a rotation of a part of the mesh (a finger that bends) as stretch --
+    on the same vertices the Laplacian energy acts on (the cage with ``subdivisions``, the rest vertices with ``skin``, the derived vertices with
+    ``shape_basis``), with ``arap_weights`` "uniform", "cotangent" (of the rest mesh, negative values clamped to 0) or an array per adjacency
+    entry.  ``cregu`` keeps its name but NOT its scale: ``L^T L`` is a squared Laplacian (entries of order valence^2), the ARAP energy is first
+    order in the edges, so the same ``cregu`` is a much softer regulariser under "arap" (examples/arap_hand_fitting.py says how one was chosen).
+    ``smoothing`` composes unchanged.  The iteration runs through autograd; ``GraphedStep`` replays it."""
 
     direct = True  # run an iteration as the fixed kernel sequence of _DirectIteration when the tensors allow it (False: always autograd)
 
@@ -391,7 +400,7 @@ class _PoseFitter:
 
     def __init__(self, vertices, faces, euler_init, translation_init, cregu, inertia, damping, device, n_poses=1, clockwise=False, pixel_dtype=torch.float64,
                  subdivisions=0, shape_basis=None, coefficient_regu=0.0, sigmas=None, skin=None, joint_quaternions_init=None, joint_regu=0.0,
-                 smoothing=0.0, smoothing_iterations=None):  # fmt: skip
+                 smoothing=0.0, smoothing_iterations=None, rigidity="laplacian", arap_weights="uniform"):  # fmt: skip
         self.device = torch.device(device)
         self.cregu, self.inertia, self.damping = cregu, inertia, damping
         v0 = np.asarray(vertices, dtype=np.float64)
@@ -408,7 +417,15 @@ class _PoseFitter:
         self.last_vertices = {}  # with subdivisions: the centred control vertices and S of them, as the last _transformed built them (in the graph)
         self.scene = Scene3DDevice(pixel_dtype=pixel_dtype)
         self.scene.set_mesh(self.mesh)
-        self.rigid_energy = LaplacianRigidEnergyDevice(self.control_mesh.topology, v0, cregu)
+        if rigidity not in ("laplacian", "arap"):
+            raise ValueError(f'rigidity must be "laplacian" or "arap", not {rigidity!r}')
+        self.rigidity = rigidity
+        if rigidity == "arap":
+            from .arap import ArapEnergyDevice
+
+            self.rigid_energy = ArapEnergyDevice(self.control_mesh.topology, v0, cregu, arap_weights)
+        else:
+            self.rigid_energy = LaplacianRigidEnergyDevice(self.control_mesh.topology, v0, cregu)
         self.vertices_init = torch.as_tensor(v0, device=self.device)
         self.shape_basis = None
         if shape_basis is not None:
@@ -562,6 +579,8 @@ class _PoseFitter:
             return None
         if self.smoothing_system is not None:  # (the solve sits between the gradients and the momentum update, which the fixed sequence fuses with the energy)
             return None
+        if self.rigidity != "laplacian":  # (the fixed sequence fuses the Laplacian energy into its first launch; the two launches of ARAP go through autograd)
+            return None
 
         topo = self.mesh.topology
         params = (self.vertices, self.transform_quaternion, self.transform_translation)
@@ -637,11 +656,11 @@ class MeshDepthFitter(_PoseFitter):
 
     def __init__(self, vertices, faces, euler_init, translation_init, cregu=2000, inertia=0.96, damping=0.05, device="cuda", pixel_dtype=torch.float64,
                  subdivisions=0, shape_basis=None, coefficient_regu=0.0, sigmas=None, skin=None, joint_quaternions_init=None, joint_regu=0.0,
-                 smoothing=0.0, smoothing_iterations=None):  # fmt: skip
+                 smoothing=0.0, smoothing_iterations=None, rigidity="laplacian", arap_weights="uniform"):  # fmt: skip
         super().__init__(vertices, faces, euler_init, translation_init, cregu, inertia, damping, device, pixel_dtype=pixel_dtype, subdivisions=subdivisions,
                          shape_basis=shape_basis, coefficient_regu=coefficient_regu, sigmas=sigmas, skin=skin,
                          joint_quaternions_init=joint_quaternions_init, joint_regu=joint_regu, smoothing=smoothing,
-                         smoothing_iterations=smoothing_iterations)  # fmt: skip
+                         smoothing_iterations=smoothing_iterations, rigidity=rigidity, arap_weights=arap_weights)  # fmt: skip
         self.camera_center = self.object_center + np.array([-0.5, 0, 5]) * self.object_radius
 
     def set_max_depth(self, max_depth):
@@ -792,7 +811,7 @@ class MeshRGBFitterWithPose(_PoseFitter):
                  inertia=0.96, damping=0.05, update_lights=True, update_color=True, device="cuda", pixel_dtype=torch.float64, n_poses=1,
                  subdivisions=0, shape_basis=None, coefficient_regu=0.0, sigmas=None, light_sh_init=None, vertex_albedo=False, albedo_regu=0.0,
                  skin=None, joint_quaternions_init=None, joint_regu=0.0, pyramid_levels=0, pyramid_weights=None, ssim_weight=0.0,
-                 ssim_data_range=1.0, smoothing=0.0, smoothing_iterations=None):  # fmt: skip
+                 ssim_data_range=1.0, smoothing=0.0, smoothing_iterations=None, rigidity="laplacian", arap_weights="uniform"):  # fmt: skip
         self.pyramid_levels, self.pyramid_weights = _pyramid_schedule(pyramid_levels, pyramid_weights, torch.device(device))
         self.ssim_mix, self.ssim_data_range = _ssim_mix(ssim_weight, ssim_data_range, self.pyramid_levels, torch.device(device))
         self.default_color = np.asarray(default_color, dtype=np.float64)
@@ -803,7 +822,7 @@ class MeshRGBFitterWithPose(_PoseFitter):
         super().__init__(vertices, faces, euler_init, translation_init, cregu, inertia, damping, device, n_poses=n_poses, pixel_dtype=pixel_dtype,
                          subdivisions=subdivisions, shape_basis=shape_basis, coefficient_regu=coefficient_regu, sigmas=sigmas, skin=skin,
                          joint_quaternions_init=joint_quaternions_init, joint_regu=joint_regu, smoothing=smoothing,
-                         smoothing_iterations=smoothing_iterations)  # fmt: skip
+                         smoothing_iterations=smoothing_iterations, rigidity=rigidity, arap_weights=arap_weights)  # fmt: skip
         self.camera_center = self.object_center + np.atleast_2d(np.asarray(translation_init, dtype=np.float64))[0] + np.array([0, 0, 9]) * self.object_radius
 
     step_factor_light_sh, step_factor_albedo = 0.0001, 0.00001  # (those of the directional light and of the single colour)
@@ -1028,7 +1047,7 @@ class MeshRGBFitterWithPoseMultiFrame(MeshRGBFitterWithPose):
                  cdata=1, inertia=0.97, damping=0.15, update_lights=True, update_color=True, device="cuda", pixel_dtype=torch.float64, group=None,
                  subdivisions=0, shape_basis=None, coefficient_regu=0.0, sigmas=None, light_sh_init=None, vertex_albedo=False, albedo_regu=0.0,
                  skin=None, joint_quaternions_init=None, joint_regu=0.0, pyramid_levels=0, pyramid_weights=None, ssim_weight=0.0,
-                 ssim_data_range=1.0, smoothing=0.0, smoothing_iterations=None):  # fmt: skip
+                 ssim_data_range=1.0, smoothing=0.0, smoothing_iterations=None, rigidity="laplacian", arap_weights="uniform"):  # fmt: skip
         euler_init, translation_init = np.atleast_2d(euler_init), np.atleast_2d(translation_init)
         self.cdata = cdata
         self.n_views_total = max(len(euler_init), len(translation_init))
@@ -1043,7 +1062,8 @@ class MeshRGBFitterWithPoseMultiFrame(MeshRGBFitterWithPose):
                          shape_basis=shape_basis, coefficient_regu=coefficient_regu, sigmas=sigmas, light_sh_init=light_sh_init,
                          vertex_albedo=vertex_albedo, albedo_regu=albedo_regu, skin=skin, joint_quaternions_init=joint_quaternions_init,
                          joint_regu=joint_regu, pyramid_levels=pyramid_levels, pyramid_weights=pyramid_weights, ssim_weight=ssim_weight,
-                         ssim_data_range=ssim_data_range, smoothing=smoothing, smoothing_iterations=smoothing_iterations)  # fmt: skip
+                         ssim_data_range=ssim_data_range, smoothing=smoothing, smoothing_iterations=smoothing_iterations, rigidity=rigidity,
+                         arap_weights=arap_weights)  # fmt: skip
         self.camera_center = self.object_center + np.array([0, 0, 6]) * self.object_radius
         self._packed = None
 

@@ -204,8 +204,9 @@ class MeshTopology:
 
 
 class LaplacianRigidEnergyDevice:
-    """As-rigid-as-possible energy 0.5 c (V - V_ref)^T (L^T L x I3) (V - V_ref) and its gradient, on the device
-    (reference deodr/laplacian_rigid_energy.py:15-41; its PyTorch twin falls back to SciPy on the host, :38-46)."""
+    """Laplacian rigid energy 0.5 c (V - V_ref)^T (L^T L x I3) (V - V_ref) and its gradient, on the device
+    (reference deodr/laplacian_rigid_energy.py:15-41; its PyTorch twin falls back to SciPy on the host, :38-46).  A quadratic in the
+    displacement: not invariant to rotations of a part of the mesh (``deodr_amd.arap.ArapEnergyDevice`` is)."""
 
     def __init__(self, topology, vertices_ref, cregu):
         if topology.n_components > 1:
