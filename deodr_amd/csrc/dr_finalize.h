@@ -16,8 +16,16 @@ namespace
 // arrays, every contribution is one memory-side atomic, and an atomic INSTRUCTION whose 64 lanes name 64 different vertices touches
 // 64 cache lines (tools/probes/order_atomic_probe.hip: 160 000 triangles x 18 adds take 117 us that way, 14 us through a table like
 // this one -- 38 us even when no two triangles share a vertex, because the table is flushed vertex-major: the lanes of one
-// instruction add to consecutive addresses).  Open addressing on the vertex index; a corner that finds no slot after VT_PROBES
-// steps falls back to the direct atomics.  Only KIND_INTERP triangles with nb_colors <= 4 (row: ij 2 + colours 4).
+// instruction add to consecutive addresses).  Only KIND_INTERP triangles with nb_colors <= 4 (row: ij 2 + colours 4).
+// Two ways to a row, chosen per workgroup:
+// * window: the ids of a block's vertices are usually close together (bumpy_sphere(100, 100): 77 of 79 blocks span fewer than 512 ids).  The
+//   workgroup reduces {min, max} of the ids of its live table triangles (a DPP reduction per wavefront, one LDS pair per wavefront, written
+//   in front of the barrier that decides `merge`); with base = min & ~7, a block whose max - base < VT_SLOTS uses row id - base: no key, no
+//   CAS, no probing, and the flush walks rows 0 ... max - base array by array, so the lanes of one atomic instruction add to consecutive
+//   elements of ij_b (eight vertices: one 128-byte line), then of colors_b.  The benchmark's finalize: 152 k -> 78 k atomic requests per
+//   launch (the rest are the edge blocks'), 17.4 -> 14.8 us.
+// * hash (the block does not fit: pole fans, meshes without index locality): open addressing on the vertex index; a corner that finds no
+//   slot after VT_PROBES steps falls back to the direct atomics.  Flushed vertex-major: a row's 16 + 32 bytes per eight lanes.
 constexpr int VT_SLOTS = 512, VT_ROW = 6, VT_PROBES = 8;
 struct VertexTable
 {
@@ -177,12 +185,41 @@ __device__ __forceinline__ void finalize_body(KParams &p)
 		// (the table's 26 KB are only touched by a block that has a triangle for it: half the blocks of a closed mesh are all back-facing)
 		__shared__ __attribute__((aligned(16))) char s_vt_storage[TABLE ? sizeof(VertexTable) : 16]; // (no table, no LDS for it)
 		VertexTable &s_vt = *(VertexTable *)s_vt_storage;
-		const bool merge = TABLE && p.prim_tables && P <= 4 && __syncthreads_or(live && (flag & 3u) == KIND_INTERP);
+		// the id range of the block's table triangles, one {max id, max ~id} pair per wavefront: written in front of the barrier that
+		// decides `merge` and read behind it (no barrier of its own).  A wavefront without such a triangle -- every wavefront of a
+		// textured launch -- stores the empty pair and does not reduce.
+		__shared__ uint32_t s_vt_range[TABLE ? PRIM_BLOCK / 64 : 1][2];
+		const bool to_table = live && (flag & 3u) == KIND_INTERP;
+		if (TABLE && p.prim_tables && P <= 4)
+		{
+			uint32_t hi = 0, nlo = 0;
+			if (__ballot(to_table))
+			{
+				hi = wave_max_u32(to_table ? max(f0, max(f1, f2)) : 0u);
+				nlo = wave_max_u32(to_table ? max(~f0, max(~f1, ~f2)) : 0u);
+			}
+			if ((threadIdx.x & 63) == 0)
+				s_vt_range[threadIdx.x >> 6][0] = hi, s_vt_range[threadIdx.x >> 6][1] = nlo;
+		}
+		const bool merge = TABLE && p.prim_tables && P <= 4 && __syncthreads_or(to_table);
+		bool window = false; // (all three uniform over the workgroup)
+		uint32_t vt_base = 0;
+		int vt_rows = VT_SLOTS;
 		if (merge)
 		{
-			for (int i = threadIdx.x; i < VT_SLOTS; i += PRIM_BLOCK)
-				s_vt.key[i] = 0xffffffffu;
-			for (int i = threadIdx.x; i < VT_SLOTS * VT_ROW; i += PRIM_BLOCK)
+			uint32_t hi = 0, nlo = 0;
+#pragma unroll
+			for (int i = 0; i < PRIM_BLOCK / 64; i++)
+				hi = max(hi, s_vt_range[i][0]), nlo = max(nlo, s_vt_range[i][1]);
+			vt_base = (uint32_t)uniform((int)(~nlo & ~7u));
+			const uint32_t span = (uint32_t)uniform((int)hi) - vt_base;
+			window = span < (uint32_t)VT_SLOTS;
+			if (window) // rows 0 ... span, and none at or beyond the view's last vertex
+				vt_rows = (int)min(span + 1u, (uint32_t)p.V - vt_base);
+			else
+				for (int i = threadIdx.x; i < VT_SLOTS; i += PRIM_BLOCK)
+					s_vt.key[i] = 0xffffffffu;
+			for (int i = threadIdx.x; i < vt_rows * VT_ROW; i += PRIM_BLOCK)
 				(&s_vt.val[0][0])[i] = 0;
 			__syncthreads();
 		}
@@ -199,7 +236,12 @@ __device__ __forceinline__ void finalize_body(KParams &p)
 					la[i] = i < 3 * P ? acc[i] : 0.0;
 				if (merge && (flag & 3u) == KIND_INTERP)
 				{
-					MergeSink sink = {s, g, s_vt, {f0, f1, f2}, {vertex_slot(s_vt, f0), vertex_slot(s_vt, f1), vertex_slot(s_vt, f2)}};
+					int s0, s1, s2;
+					if (window)
+						s0 = (int)(f0 - vt_base), s1 = (int)(f1 - vt_base), s2 = (int)(f2 - vt_base);
+					else
+						s0 = vertex_slot(s_vt, f0), s1 = vertex_slot(s_vt, f1), s2 = vertex_slot(s_vt, f2);
+					MergeSink sink = {s, g, s_vt, {f0, f1, f2}, {s0, s1, s2}};
 					finalize_triangle<true>(s, k, KIND_INTERP, la, sink);
 				}
 				else
@@ -218,8 +260,18 @@ __device__ __forceinline__ void finalize_body(KParams &p)
 				acc[i] = 0; // self-cleaning accumulators
 			DR_WAVE_PHASE_T(3);
 		}
-		if (merge)
-		{ // flush, vertex-major: eight lanes per row (six used), i.e. one instruction adds to the 16 + 32 contiguous bytes of eight vertices
+		if (merge && window)
+		{ // flush of a window, array by array: the lanes of one instruction add to consecutive elements of ij_b, then of colors_b, from vertex
+		  // vt_base on (a multiple of 8: whole lines); an element nobody added to stays zero and is skipped
+			__syncthreads();
+			for (int i = threadIdx.x; i < vt_rows * 2; i += PRIM_BLOCK)
+				DeviceAdd()(g.ij_b, 2 * (size_t)vt_base + i, p.vtx_f64, s_vt.val[i >> 1][i & 1]);
+			const int C = p.C;
+			for (int i = threadIdx.x; i < vt_rows * C; i += PRIM_BLOCK)
+				DeviceAdd()(g.colors_b, (size_t)vt_base * C + i, p.vtx_f64, s_vt.val[i / C][2 + i % C]);
+		}
+		else if (merge)
+		{ // flush of the hashed table, vertex-major: eight lanes per row (six used), i.e. one instruction adds to the 16 + 32 contiguous bytes of eight vertices
 			__syncthreads();
 			for (int i = threadIdx.x; i < VT_SLOTS * 8; i += PRIM_BLOCK)
 			{

@@ -495,6 +495,18 @@ __device__ __forceinline__ double wave_sum_dpp(double v)
 // NOTE: must be called with all 64 lanes enabled (a DPP move reads 0 from a disabled lane)
 __device__ __forceinline__ double wave_sum(double v) { return wave_sum_dpp(v); }
 
+// largest value over the 64 lanes, returned to every lane (as wave_sum_dpp: a lane without a source reads 0, the identity here).  All 64 lanes enabled.
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v)
+{
+	v = max(v, (uint32_t)dpp_i<0x111>((int)v));
+	v = max(v, (uint32_t)dpp_i<0x112>((int)v));
+	v = max(v, (uint32_t)dpp_i<0x114>((int)v));
+	v = max(v, (uint32_t)dpp_i<0x118>((int)v));
+	const uint32_t a = (uint32_t)__builtin_amdgcn_readlane((int)v, 15), b = (uint32_t)__builtin_amdgcn_readlane((int)v, 31);
+	const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)v, 47), d = (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+	return max(max(a, b), max(c, d));
+}
+
 // Sixteen wave sums for the price of about three: a transposing butterfly.  At step b the lanes whose bit b is clear keep the
 // even member of every pair of values and receive it from a lane whose bit b is set, and vice versa, so the number of live
 // values halves at each step while the number of lanes that share a value halves too (15 exchanges instead of 16 x 6).

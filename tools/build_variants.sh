@@ -31,6 +31,8 @@
 #    that has since been removed -- they fit the sources of commit 8cd22f9: `git worktree add /tmp/r6 8cd22f9` and apply them there)
 #   (tools/variants/head_neighbours.patch: four one-line neighbours of the forward's walker divisor and head share against the sources that carry
 #    HEAD_TRIS -- one hunk per variant, measured and not adopted, profiles/r09a_ab_neighbours.txt)
+#   (tools/variants/acc_rows_128.patch: the moment accumulators' rows on 128-byte lines of their own, a `diff -u` of deodr_amd/csrc against the sources that
+#    first carry the windowed vertex table -- `patch -p1` inside deodr_amd/csrc; measured and not adopted, profiles/r10a_b_rows.txt)
 #   <name>     EXTRA="-D..."    anything else: the product sources with the flags of $EXTRA
 ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 OUT=$ROOT/tools/variants

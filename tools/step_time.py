@@ -12,6 +12,16 @@ if "--lib" in sys.argv:
 B, S, steps = arg("--views", 8), arg("--size", 1024), arg("--steps", 40)
 dev = torch.device("cuda:0")
 views = [scenes.sphere_scene(size=S, angle=float(a)) for a in np.linspace(-0.5, 0.5, B)]
+if "--permute-ids" in sys.argv:  # the same scene with its vertex ids randomly permuted: no block of triangles has index locality (finalize hashes every block)
+    perm = np.random.RandomState(0).permutation(len(views[0].ij))
+    for v in views:
+        for name in ("ij", "depths", "colors", "shade", "uv"):
+            a = np.asarray(getattr(v, name))
+            b = np.empty_like(a)
+            b[perm] = a
+            setattr(v, name, b)
+        v.faces = perm[np.asarray(v.faces, dtype=np.int64)].astype(np.uint32)
+        v.faces_uv = v.faces.copy()
 s0 = views[0]
 stack = lambda n: np.stack([np.asarray(getattr(v, n)) for v in views])
 ds = DeviceScene(s0.faces, s0.faces_uv, s0.textured, s0.shaded, s0.uv, stack("ij"), stack("depths"), stack("colors"), stack("shade"),
