@@ -25,6 +25,7 @@ _COMPANIONS = (
     ("SSIM_HEADER", "deodr_hip_ssim.h", False),  # structural (SSIM) data term
     ("SOLVE_HEADER", "deodr_hip_solve.h", False),  # sparse SPD solve: smoothed vertex steps
     ("ARAP_HEADER", "deodr_hip_arap.h", False),  # as-rigid-as-possible energy
+    ("CHAMFER_HEADER", "deodr_hip_chamfer.h", False),  # closest-point (Chamfer) data term
 )
 
 # C type (without `const`, without spaces around the stars) -> ctypes.  Data pointers are c_void_p: callers pass device addresses (Python

@@ -70,6 +70,7 @@
 #include "../../include/deodr_hip_ssim.h"
 #include "../../include/deodr_hip_solve.h"
 #include "../../include/deodr_hip_arap.h"
+#include "../../include/deodr_hip_chamfer.h"
 #include "dr_fititer.h" // <- dr_finalize.h <- dr_backward.h <- dr_backward_generic.h <- dr_forward.h <- dr_forward_generic.h <- dr_setup.h <- dr_workspace.h <- dr_prims.h
 #include "dr_texfit.h"  // texture smoothness + step (include/deodr_hip_texture.h); uses grid_sum of dr_fronthalf.h
 #include "dr_subdiv.h"  // rows of a sparse matrix applied to [batch, n, D] blocks (include/deodr_hip_subdiv.h): Loop subdivision and its adjoint
@@ -81,6 +82,7 @@
 #include "dr_ssim.h"	 // the structural (SSIM) data term and its adjoint: two stencil kernels over 16 x 32 tiles with a halo in LDS (include/deodr_hip_ssim.h)
 #include "dr_solve.h"	 // sparse SPD solve by conjugate gradients: one workgroup per column for small systems, two launches per step above (include/deodr_hip_solve.h)
 #include "dr_arap.h"	 // as-rigid-as-possible energy: a 3 x 3 polar decomposition per vertex by Jacobi on Horn's matrix, then the gradient (include/deodr_hip_arap.h)
+#include "dr_chamfer.h" // closest-point (Chamfer) energy: a brute-force tiled nearest-neighbour search both ways, the gradient gathered in the same walk (include/deodr_hip_chamfer.h)
 
 using namespace dr;
 using namespace dr::dispatch;
@@ -2085,6 +2087,87 @@ int deodr_hip_arap_energy(const uint32_t *offsets, const uint32_t *cols, const d
 	hipLaunchKernelGGL(arap_rotations_kernel, grid, block, 0, st, a);
 	hipLaunchKernelGGL(arap_gradient_kernel, grid, block, 0, st, a);
 	return check_hip(hipGetLastError(), "arap_energy launch");
+}
+
+// ---- closest-point (Chamfer) energy (include/deodr_hip_chamfer.h, kernels in dr_chamfer.h)
+
+int deodr_hip_chamfer_abi_version(void) { return DEODR_HIP_CHAMFER_ABI_VERSION; }
+
+namespace
+{
+const char *chamfer_dims(int V, int P, int n)
+{ // -> NULL, or which limit of the header the arguments break
+	if (V <= 0)
+		return "V must be positive";
+	if (P <= 0)
+		return "P must be positive";
+	if (n <= 0 || n > CHAMFER_MAX_POSES)
+		return "n must be in 1 .. 65535";
+	if ((unsigned long long)V * (unsigned long long)P > DEODR_HIP_CHAMFER_MAX_PAIRS)
+		return "V * P is above DEODR_HIP_CHAMFER_MAX_PAIRS (the search is brute force)";
+	return NULL;
+}
+bool chamfer_directions(int directions) { return directions >= 1 && directions <= 3; }
+} // namespace
+
+size_t deodr_hip_chamfer_scratch_bytes(int V, int P, int n) { return chamfer_dims(V, P, n) ? 0 : scratch_need(chamfer_scratch_doubles(V, P, n)); }
+
+int deodr_hip_chamfer_segments(int queries, int references) { return chamfer_segments(queries, references); }
+
+int deodr_hip_chamfer_launches(int V, int P, int n, int directions)
+{
+	return chamfer_dims(V, P, n) || !chamfer_directions(directions) ? 0 : directions & DEODR_HIP_CHAMFER_POINTS_TO_MESH ? 4 : 2;
+}
+
+int deodr_hip_chamfer(const double *vertices, int V, const double *points, int P, const double *point_weights, const double *vertex_weights,
+					  const double *params, int n, int directions, double *terms, double *loss, double *vertices_b, uint32_t *nearest_vertex,
+					  uint32_t *nearest_point, void *scratch, size_t scratch_bytes, void *stream)
+{
+	const char *what = "chamfer";
+	if (!vertices || !points || !params || !terms || !loss || !vertices_b || !scratch)
+		return fail(what, "vertices, points, params, terms, loss, vertices_b or scratch == NULL");
+	if (const char *why = chamfer_dims(V, P, n))
+		return fail(what, why);
+	if (!chamfer_directions(directions))
+		return fail(what, "directions must be in 1 .. 3");
+	const void *const words[] = {nearest_vertex, nearest_point};
+	const void *const doubles[] = {vertices, points, point_weights, vertex_weights, params, terms, loss, vertices_b, scratch};
+	if (any_misaligned(words, 4) || any_misaligned(doubles, 8))
+		return fail(what, "misaligned pointer");
+	const Scratch sc = {scratch, scratch_bytes};
+	if (!sc.holds(deodr_hip_chamfer_scratch_bytes(V, P, n)))
+		return fail(what, "scratch too small (deodr_hip_chamfer_scratch_bytes)");
+	const size_t N = (size_t)n, nv = N * (size_t)V, np = N * (size_t)P;
+	const Range outputs[] = {{terms, 16 * N}, {loss, 8 * N}, {vertices_b, 24 * nv}, {nearest_vertex, 4 * np}, {nearest_point, 4 * nv}, {scratch, scratch_bytes}};
+	const Range inputs[] = {{vertices, 24 * nv}, {points, 24 * np}, {point_weights, 8 * np}, {vertex_weights, 8 * (size_t)V}, {params, 24}};
+	bool clash = any_overlap(outputs, inputs);
+	for (size_t i = 0; i < 6; i++)
+		for (size_t j = i + 1; j < 6; j++)
+			clash = clash || ranges_overlap(outputs[i].p, outputs[i].bytes, outputs[j].p, outputs[j].bytes);
+	if (clash)
+		return fail(what, "an output must not overlap an input, the scratch or another output");
+	const int Sp = chamfer_segments(P, V), Sv = chamfer_segments(V, P);
+	const size_t sp = (size_t)Sp * np, sv = (size_t)Sv * nv;
+	double *const pd2 = sc.doubles(), *const vd2 = pd2 + sp, *const vg = vd2 + sv, *const partials = vg + 3 * sv;
+	uint32_t *const pidx = (uint32_t *)(partials + 2 * N * (size_t)CHAMFER_MAX_BLOCKS), *const vidx = pidx + sp, *const assign = vidx + sv;
+	ChamferArgs a = {vertices, points, point_weights, vertex_weights, params, terms, loss, vertices_b, nearest_vertex, nearest_point, pd2, vd2, vg,
+					 partials, pidx, vidx, assign, (unsigned *)(assign + np), V, P, n, Sp, Sv, directions, 1};
+	const hipStream_t st = (hipStream_t)stream;
+	const dim3 block(CHAMFER_BLOCK), walk_v(((unsigned)V - 1) / CHAMFER_BLOCK + 1, (unsigned)Sv, (unsigned)n);
+	if (directions & DEODR_HIP_CHAMFER_POINTS_TO_MESH)
+	{
+		hipLaunchKernelGGL((chamfer_walk_kernel<true, false>), dim3(((unsigned)P - 1) / CHAMFER_BLOCK + 1, (unsigned)Sp, (unsigned)n), block, 0, st, a, 1);
+		a.clear_tickets = 0;
+		hipLaunchKernelGGL(chamfer_points_kernel, dim3(chamfer_blocks(P), (unsigned)n), block, 0, st, a);
+		if (directions & DEODR_HIP_CHAMFER_MESH_TO_POINTS)
+			hipLaunchKernelGGL((chamfer_walk_kernel<true, true>), walk_v, block, 0, st, a, 0);
+		else
+			hipLaunchKernelGGL((chamfer_walk_kernel<false, true>), walk_v, block, 0, st, a, 0);
+	}
+	else
+		hipLaunchKernelGGL((chamfer_walk_kernel<true, false>), walk_v, block, 0, st, a, 0);
+	hipLaunchKernelGGL(chamfer_vertices_kernel, dim3(chamfer_blocks(V), (unsigned)n), block, 0, st, a);
+	return check_hip(hipGetLastError(), "chamfer launch");
 }
 
 #ifdef DR_WAVE_TRACE

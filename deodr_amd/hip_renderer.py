@@ -41,8 +41,9 @@ _COMPANIONS = (
     (_abi.SSIM_HEADER, "ssim", "ssim-loss"),  # structural (SSIM) data term
     (_abi.SOLVE_HEADER, "solve", "sparse-solve"),  # sparse SPD solve: smoothed vertex steps
     (_abi.ARAP_HEADER, "arap", "arap-energy"),  # as-rigid-as-possible energy
+    (_abi.CHAMFER_HEADER, "chamfer", "chamfer-term"),  # closest-point (Chamfer) data term
 )
-TEXTURE_ABI_VERSION, SUBDIV_ABI_VERSION, RETAINED_ABI_VERSION, BASIS_ABI_VERSION, CAMERA_ABI_VERSION, LIGHTING_ABI_VERSION, SKINNING_ABI_VERSION, PYRAMID_ABI_VERSION, SSIM_ABI_VERSION, SOLVE_ABI_VERSION, ARAP_ABI_VERSION = (
+TEXTURE_ABI_VERSION, SUBDIV_ABI_VERSION, RETAINED_ABI_VERSION, BASIS_ABI_VERSION, CAMERA_ABI_VERSION, LIGHTING_ABI_VERSION, SKINNING_ABI_VERSION, PYRAMID_ABI_VERSION, SSIM_ABI_VERSION, SOLVE_ABI_VERSION, ARAP_ABI_VERSION, CHAMFER_ABI_VERSION = (
     h.defines[f"DEODR_HIP_{key.upper()}_ABI_VERSION"] for h, key, _ in _COMPANIONS
 )
 # words of the 64-byte status block at the start of the workspace
@@ -1550,6 +1551,82 @@ def arap_energy(offsets, cols, weights, vertices_ref, vertices, cregu, energy=No
     if rotations is not None:
         _touched(rotations)
     return energy, gradient, rotations
+
+
+# ---- closest-point (Chamfer) energy (include/deodr_hip_chamfer.h) ---------------------------------------------------------------------------
+
+CHAMFER_POINTS_TO_MESH, CHAMFER_MESH_TO_POINTS, CHAMFER_BLOCK, CHAMFER_TILE, CHAMFER_MAX_BLOCKS, CHAMFER_TARGET_BLOCKS, CHAMFER_MAX_SEGMENTS, CHAMFER_MAX_PAIRS = (
+    _abi.CHAMFER_HEADER.defines["DEODR_HIP_CHAMFER_" + n] for n in ("POINTS_TO_MESH", "MESH_TO_POINTS", "BLOCK", "TILE", "MAX_BLOCKS", "TARGET_BLOCKS", "MAX_SEGMENTS", "MAX_PAIRS")
+)
+
+
+def chamfer_launches(V, P, n, directions=3):
+    """``deodr_hip_chamfer_launches``: the kernel launches of a :func:`chamfer` call -- 4 with points -> mesh, 2 with mesh -> points alone (0 for
+    arguments the call refuses)"""
+    return int(lib().deodr_hip_chamfer_launches(int(V), int(P), int(n), int(directions)))
+
+
+def chamfer_segments(queries, references):
+    """``deodr_hip_chamfer_segments``: into how many contiguous parts the references of a search are cut (the second dimension of its grid)"""
+    return int(lib().deodr_hip_chamfer_segments(int(queries), int(references)))
+
+
+def chamfer_scratch(V, P, n, device):
+    """the scratch of :func:`chamfer` for n poses of V vertices against P points (one per stream in use; it need not be zeroed)"""
+    need = int(lib().deodr_hip_chamfer_scratch_bytes(int(V), int(P), int(n)))
+    if need == 0:
+        raise ValueError(f"chamfer_scratch: V = {V}, P = {P}, n = {n} is outside the limits of include/deodr_hip_chamfer.h")
+    with torch.cuda.device(device):
+        return torch.empty(need, dtype=torch.uint8, device=device)
+
+
+def chamfer(vertices, points, params, point_weights=None, vertex_weights=None, directions=3, terms=None, loss=None, vertices_b=None,
+            nearest_vertex=None, nearest_point=None, scratch=None, want_nearest=False):  # fmt: skip
+    """``deodr_hip_chamfer``: the closest-point energy of ``vertices`` [n,V,3] against ``points`` [n,P,3] (float64) -> (terms [n,2], loss [n],
+    vertices_b [n,V,3], nearest_vertex [n,P] | None, nearest_point [n,V] | None as int32 tensors holding uint32 bit patterns); the header has the
+    operation.  ``params`` [3] float64 ON THE DEVICE = (mix_0, mix_1, max_distance), read when the kernels run; ``point_weights`` [n,P] and
+    ``vertex_weights`` [V] float64 or None (ones); ``directions``: bit 1 points -> mesh, bit 2 mesh -> points.  The nearest_* arrays are written when
+    a tensor is given or ``want_nearest``, for the directions that are on.  The values are trusted (:mod:`deodr_amd.chamfer` checks its own on the
+    host).  Deterministic; asynchronous on the current stream.  ``scratch``: a :func:`chamfer_scratch` of the caller's; None: one per device and
+    stream."""
+    what = "chamfer"
+    _rocm_tensor(what, "vertices", vertices)
+    if vertices.dim() != 3 or vertices.shape[0] < 1 or vertices.shape[1] < 1 or vertices.shape[2] != 3:
+        raise ValueError(f"{what}: vertices must have shape [n >= 1, V >= 1, 3], not {list(vertices.shape)}")
+    n, V = int(vertices.shape[0]), int(vertices.shape[1])
+    if not torch.is_tensor(points) or points.dim() != 3 or int(points.shape[0]) != n or points.shape[1] < 1 or points.shape[2] != 3:
+        raise ValueError(f"{what}: points must have shape [{n}, P >= 1, 3], not {list(getattr(points, 'shape', ()))}")
+    P, directions = int(points.shape[1]), int(directions)
+    if not 1 <= directions <= 3:
+        raise ValueError(f"{what}: directions must be in 1 .. 3, not {directions}")
+    rows = [("vertices", vertices, _F64_ONLY, None), ("points", points, _F64_ONLY, (n, P, 3)), ("params", params, _F64_ONLY, (3,))]
+    optional = (("point_weights", point_weights, _F64_ONLY, (n, P)), ("vertex_weights", vertex_weights, _F64_ONLY, (V,)),
+                ("terms", terms, _F64_ONLY, (n, 2)), ("loss", loss, _F64_ONLY, (n,)), ("vertices_b", vertices_b, _F64_ONLY, (n, V, 3)),
+                ("nearest_vertex", nearest_vertex, _INDICES, (n, P)), ("nearest_point", nearest_point, _INDICES, (n, V)),
+                ("scratch", scratch, (torch.uint8,), (None,)))  # fmt: skip
+    rows += [row for row in optional if row[1] is not None]
+    _check_tensors(what, "vertices", vertices.device, rows)
+    dev = vertices.device
+    need = int(lib().deodr_hip_chamfer_scratch_bytes(V, P, n))
+    if need == 0:
+        raise ValueError(f"{what}: V = {V}, P = {P}, n = {n} is outside the limits of include/deodr_hip_chamfer.h (V * P <= {CHAMFER_MAX_PAIRS}, n <= 65535)")
+    with torch.cuda.device(dev):
+        terms = torch.empty((n, 2), dtype=torch.float64, device=dev) if terms is None else terms
+        loss = torch.empty(n, dtype=torch.float64, device=dev) if loss is None else loss
+        vertices_b = torch.empty_like(vertices) if vertices_b is None else vertices_b
+        if want_nearest and nearest_vertex is None and directions & CHAMFER_POINTS_TO_MESH:
+            nearest_vertex = torch.empty((n, P), dtype=torch.int32, device=dev)
+        if want_nearest and nearest_point is None and directions & CHAMFER_MESH_TO_POINTS:
+            nearest_point = torch.empty((n, V), dtype=torch.int32, device=dev)
+        if scratch is None:
+            scratch = _cached_scratch("chamfer", dev, need, lambda: chamfer_scratch(V, P, n, dev),
+                                      f"{what}: pass scratch= (chamfer_scratch) when capturing a graph: none of this size exists for this stream yet")  # fmt: skip
+    _launch(lib().deodr_hip_chamfer, dev, _ptr(vertices), V, _ptr(points), P, _ptr(point_weights), _ptr(vertex_weights), _ptr(params), n, directions,
+            _ptr(terms), _ptr(loss), _ptr(vertices_b), _ptr(nearest_vertex), _ptr(nearest_point), _ptr(scratch), scratch.numel())  # fmt: skip
+    for t in (terms, loss, vertices_b, nearest_vertex, nearest_point):
+        if t is not None:
+            _touched(t)
+    return terms, loss, vertices_b, nearest_vertex, nearest_point
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -390,6 +390,9 @@ class _PoseFitter:
     ``smoothing`` composes unchanged.  The iteration runs through autograd; ``GraphedStep`` replays it."""
 
     direct = True  # run an iteration as the fixed kernel sequence of _DirectIteration when the tensors allow it (False: always autograd)
+    # pose the vertices with the one kernel of fronthalf.RigidTransformFunc when the tensors allow it.  Its adjoint adds the pose gradients of the
+    # wavefronts with double atomics, in no fixed order; False: the same formula as torch ops, whose reductions have one (MeshPointCloudFitter)
+    fused_pose = True
 
     step_factor_vertices, step_factor_quaternion, step_factor_translation = 0.0005, 0.00006, 0.00005
     step_factor_coefficients = 0.0005  # (with an orthonormal basis a step of the coefficients moves the vertices as far as the same step of the vertices)
@@ -502,7 +505,7 @@ class _PoseFitter:
             control = centred
             centred = self.subdivision.apply(control)
             self.last_vertices = {"control": control, "fine": centred}
-        if fronthalf.usable(centred, q, self.transform_translation_leaf):  # one kernel (two with its adjoint) instead of ~12 + ~25
+        if self.fused_pose and fronthalf.usable(centred, q, self.transform_translation_leaf):  # one kernel (two with its adjoint) instead of ~12 + ~25
             return fronthalf.RigidTransformFunc.apply(centred, q, self.transform_translation_leaf)
         return qrot(q, centred[None].expand(q.shape[0], -1, -1)) + self.transform_translation_leaf[:, None, :]
 
@@ -733,6 +736,82 @@ class MeshDepthFitter(_PoseFitter):
 
     def step(self):
         """-> (energy, synthetic depth [H,W], squared difference [H,W]) as a float and NumPy arrays, like the reference"""
+        return _to_host(*self.step_device())
+
+
+class MeshPointCloudFitter(_PoseFitter):
+    """Fit a deformable mesh and one rigid pose per cloud to unorganised 3-D point sets: scans, LiDAR sweeps, back-projected depth images
+    (:func:`deodr_amd.chamfer.depth_to_points`), the vertices of another mesh.  No camera and no render are involved.
+
+    The energy is the closest-point term (:class:`deodr_amd.chamfer.PointCloudTerm`, include/deodr_hip_chamfer.h) of ``_transformed(vertices)``
+    [n_poses,V,3] against one cloud per pose, summed over the poses, plus the rigid energy, plus the priors.  The iteration goes through autograd
+    (the term is one op: :class:`deodr_amd.fronthalf.ChamferFunc`); ``GraphedStep`` replays it.  ``subdivisions``, ``shape_basis``, ``skin``,
+    ``smoothing`` and ``rigidity`` compose through the shared machinery of :class:`_PoseFitter` (with ``subdivisions`` the fine vertices meet the
+    cloud).  ``directions``, ``max_distance``, ``mix``, ``normalise``: the term's; ``self.term.params`` may be ``copy_``-ed into between steps, also
+    under a ``GraphedStep`` (a ``max_distance`` that shrinks as the fit closes in).
+
+    The step factors are this fitter's own, chosen on examples/point_cloud_hand_fitting.py with ``normalise=True`` (both terms are then mean squared
+    distances, so the translation gradient is of the order of the offset whatever V and P are, and a vertex gradient of the order of offset / V):
+    the largest powers of ten (times 1, 2 or 5) at which the hand's 60 iterations against 400 of its own posed vertices lower the energy
+    monotonically after the first ten; ``step_factor_vertices`` is per vertex, multiplied by V here.  ``cregu`` is on the scale of the normalised
+    term (a mean squared distance, not a sum over pixels): the default is the one value those fits were run with, not the result of a sweep."""
+
+    step_factor_vertices, step_factor_quaternion, step_factor_translation = 0.2, 0.5, 1.0  # (vertices: times V, see above)
+    step_factor_coefficients, step_factor_joints = 0.2, 0.5
+    step_max = (None, None, None, None)  # no clamp: the gradients are bounded by the distances themselves
+    # every other launch of this iteration adds in a fixed order (the term, the rigid energies, the momentum update): with the pose as torch ops an
+    # iteration gives the same bits from run to run, and a GraphedStep the bits of the eager steps (tests/test_chamfer_gpu.py)
+    fused_pose = False
+
+    def __init__(self, vertices, faces, euler_init, translation_init, cregu=0.002, inertia=0.9, damping=0.05, device="cuda", n_poses=1,
+                 directions="both", max_distance=float("inf"), mix=(1.0, 1.0), normalise=True, subdivisions=0, shape_basis=None, coefficient_regu=0.0,
+                 sigmas=None, skin=None, joint_quaternions_init=None, joint_regu=0.0, smoothing=0.0, smoothing_iterations=None, rigidity="laplacian",
+                 arap_weights="uniform"):  # fmt: skip
+        super().__init__(vertices, faces, euler_init, translation_init, cregu, inertia, damping, device, n_poses=n_poses, subdivisions=subdivisions,
+                         shape_basis=shape_basis, coefficient_regu=coefficient_regu, sigmas=sigmas, skin=skin,
+                         joint_quaternions_init=joint_quaternions_init, joint_regu=joint_regu, smoothing=smoothing,
+                         smoothing_iterations=smoothing_iterations, rigidity=rigidity, arap_weights=arap_weights)  # fmt: skip
+        self.n_poses = int(n_poses)
+        self.step_factor_vertices = type(self).step_factor_vertices * self.control_mesh.nb_vertices
+        self._term_keywords = dict(directions=directions, max_distance=max_distance, mix=mix, normalise=normalise)
+        self.term = None
+
+    def set_point_clouds(self, points, weights=None, vertex_weights=None):
+        """one cloud per pose: a list of [P_i,3] clouds (padded at weight 0) or [n_poses,P,3]; ``weights``: per point, ``>= 0``, of the same layout
+        (None: ones); ``vertex_weights`` [V] of the vertices that meet the cloud (None: ones)"""
+        from .chamfer import PointCloudTerm
+
+        term = PointCloudTerm(points, weights, vertex_weights, device=self.device, **self._term_keywords)
+        if term.n != self.n_poses:
+            raise ValueError(f"set_point_clouds: {term.n} clouds for a fitter of {self.n_poses} poses")
+        self.term, self.iter = term, 0
+
+    def set_point_cloud(self, points, weights=None, vertex_weights=None):
+        """the cloud [P,3] of a fitter of one pose"""
+        if np.ndim(points) != 2:
+            raise ValueError(f"set_point_cloud: points must be [P, 3], not {list(np.shape(points))}")
+        self.set_point_clouds([points], None if weights is None else [weights], vertex_weights)
+
+    def energy(self):
+        """-> (data energy, rigid energy, rigid gradient, terms [n_poses,2], posed vertices [n_poses,V,3]) as device tensors"""
+        if self.term is None:
+            raise RuntimeError("MeshPointCloudFitter: set_point_cloud(s) first")
+        posed = self._transformed(self.vertices_leaf)
+        loss, terms = self.term.evaluate(posed)
+        e_rigid, g_rigid = self.rigid_energy.evaluate(self.vertices_leaf.detach())
+        return loss.sum(), e_rigid, g_rigid, terms, posed
+
+    def step_device(self):
+        """One iteration on the device -> (energy, terms [n_poses,2], posed vertices [n_poses,V,3]) as device tensors"""
+        leaves = self._leaves()
+        e_data, e_rigid, g_rigid, terms, posed = self.energy()
+        g_v, g_q, g_t = self._without_joint_gradient(torch.autograd.grad(e_data, leaves))
+        energy = self._energy_with_prior(e_data + e_rigid)
+        self._update_pose_and_shape(g_v, g_q, g_t, g_rigid, self.step_max)
+        return energy.detach(), terms.detach(), posed.detach()
+
+    def step(self):
+        """-> (energy, terms [n_poses,2], posed vertices [n_poses,V,3]) as a float and NumPy arrays"""
         return _to_host(*self.step_device())
 
 

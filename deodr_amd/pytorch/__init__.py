@@ -10,6 +10,7 @@ from ..mesh_fitter import (  # noqa: F401
     MeshDepthFitter,
     MeshDepthFitterEnergy,
     MeshDepthFitterPytorchOptim,
+    MeshPointCloudFitter,
     MeshRGBFitterWithPose,
     MeshRGBFitterWithPoseMultiFrame,
     MeshTextureFitterMultiFrame,
