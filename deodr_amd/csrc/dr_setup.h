@@ -3,6 +3,7 @@
 #pragma once
 
 #include "dr_workspace.h"
+#include "dr_binning.h" // the rule: which tiles of a box are requested (shared with tests/sim/tile_sim.cpp)
 
 using namespace dr;
 
@@ -24,61 +25,12 @@ __device__ __forceinline__ void place_in_tile(uint32_t *list, int cap_inline, ui
 	}
 }
 
-// The same rejection for the 3 x 3 block of tiles whose first tile is (tx0, ty0): bit 3 dy + dx of the result is set when tile
-// (tx0 + dx, ty0 + dy) is clearly outside one of the N half-planes.  The corner where a half-plane function is largest
-// is the same in every tile, so a x and b y are formed once per column / row of tiles (the per-tile form above costs
-// ~20 operations per half-plane and tile, and binning was half of the arithmetic of the set-up kernel).  The slack uses the
-// largest scale of the block, i.e. it is at least as cautious as the per-tile test.
-template <int N>
-__device__ __forceinline__ uint32_t tiles3x3_outside_halfplanes(const double *eq, int tx0, int ty0)
-{
-	uint32_t out = 0;
-	const double xmax = (tx0 + 2) * TILE + (TILE - 1), ymax = (ty0 + 2) * TILE + (TILE - 1);
-#pragma unroll
-	for (int k = 0; k < N; k++)
-	{
-		const double a = eq[3 * k], b = eq[3 * k + 1], c = eq[3 * k + 2];
-		const double limit = -1e-9 * (fabs(a) * xmax + fabs(b) * ymax + fabs(c)) - 1e-12;
-		const double cx = tx0 * TILE + (a > 0 ? TILE - 1 : 0), cy = ty0 * TILE + (b > 0 ? TILE - 1 : 0);
-		double ax[3], by[3];
-#pragma unroll
-		for (int d = 0; d < 3; d++)
-		{
-			ax[d] = a * (cx + d * TILE);
-			by[d] = b * (cy + d * TILE) + c;
-		}
-#pragma unroll
-		for (int q = 0; q < 9; q++)
-			out |= (ax[q % 3] + by[q / 3] < limit) ? (1u << q) : 0u;
-	}
-	return out;
-}
-
 __device__ __forceinline__ uint32_t push_tile(uint32_t *cnt, uint32_t *list, int cap_inline, uint2 *pool, uint32_t pool_cap, uint32_t *spill,
 											  int tile, uint32_t prim)
 {
 	const uint32_t slot = atomicAdd(&cnt[tile], 1u);
 	place_in_tile(list, cap_inline, pool, pool_cap, spill, tile, prim, slot);
 	return slot; // 0: first primitive of the tile
-}
-
-// Conservative rejection for binning: a primitive covers a pixel only where every one of its half-plane functions
-// E = a x + b y + c is >= 0 (or > 0); if some E is clearly negative on all four corner pixels of the tile, no pixel of the
-// tile can be covered.  The slack keeps the test safe against the rounding of the exact span arithmetic used later.
-template <int N>
-__device__ __forceinline__ bool tile_outside_halfplanes(const double *eq, int tx, int ty)
-{
-	const double xa = tx * TILE, xb = tx * TILE + (TILE - 1), ya = ty * TILE, yb = ty * TILE + (TILE - 1);
-#pragma unroll
-	for (int k = 0; k < N; k++)
-	{
-		const double a = eq[3 * k], b = eq[3 * k + 1], c = eq[3 * k + 2];
-		const double emax = a * (a > 0 ? xb : xa) + b * (b > 0 ? yb : ya) + c;
-		const double scale = fabs(a) * xb + fabs(b) * yb + fabs(c);
-		if (emax < -1e-9 * scale - 1e-12)
-			return true;
-	}
-	return false;
 }
 
 // Work split of the per-primitive kernels (set-up, finalize).  Triangle blocks take PRIM_BLOCK triangles each.  The
@@ -358,7 +310,8 @@ __global__ __launch_bounds__(PRIM_BLOCK, PRIM_WAVES) void setup_bin_kernel(KPara
 #pragma unroll
 				for (int i = 0; i < 12; i++)
 					q[i] = (tri_block && i >= 9) ? 0.0 : __shfl(hp[i], owner, 64);
-				const int tx0 = __shfl(btx0, owner, 64), ty0 = __shfl(bty0, owner, 64), ntx = __shfl(bntx, owner, 64), nty = __shfl(bnty, owner, 64);
+				const int tx0 = __shfl(btx0, owner, 64), ty0 = __shfl(bty0, owner, 64), ntx = __shfl(bntx, owner, 64), nty_s = __shfl(bnty, owner, 64);
+				const int nty = nty_s < 0 ? -nty_s : nty_s; // (a triangle whose first and last rows of tiles are kept hands in -nty: see the first block below)
 				prim[u] = (uint32_t)__shfl(bprim, owner, 64);
 				use[u] = 0;
 				tile0[u] = 0;
@@ -374,7 +327,7 @@ __global__ __launch_bounds__(PRIM_BLOCK, PRIM_WAVES) void setup_bin_kernel(KPara
 					for (int c = 0; c < 9; c++)
 					{
 						const int dx = bx + c % 3, dy = by + c / 3;
-						if (dx < ntx && dy < nty && (!((outside >> c) & 1u) || dx == keep_dx))
+						if (dx < ntx && dy < nty && (!((outside >> c) & 1u) || dx == keep_dx || (nty_s < 0 && (dy == 0 || dy == nty - 1))))
 							use[u] |= 1u << c;
 					}
 				}
@@ -436,6 +389,11 @@ __global__ __launch_bounds__(PRIM_BLOCK, PRIM_WAVES) void setup_bin_kernel(KPara
 			// column x_max although that pixel is outside the left edge.  tri_half_span reproduces it; the half-plane test must
 			// then not drop the tiles of that column.
 			const int keep_dx = s.strict ? -1 : ntx - 1;
+			// The same rule draws the pixel row that an exactly horizontal edge lies on from the triangle's other edge out to x_min or x_max: the
+			// edge is the left or right one of a half of that single row, its a is 0 and so is the numerator on that row, and floor_div / ceil_div
+			// then leave the bound of the row unclipped (H.h:440-519).  That row is the first or the last of the triangle: the half-plane test must
+			// not drop the tiles of the box's first and last rows of tiles.
+			const bool keep_rows = !s.strict && (eq[0] == 0 || eq[3] == 0 || eq[6] == 0);
 			// The slot requests of the first 3 x 3 block of tiles (for the usual small triangle: all of them) leave NOW, before the
 			// attribute planes are formed and the record is stored: that arithmetic and those stores then overlap the round trip
 			// of the requests (5.5 of the 12.6 us of a triangle wavefront, tools/wave_trace.py) instead of preceding it.
@@ -451,7 +409,7 @@ __global__ __launch_bounds__(PRIM_BLOCK, PRIM_WAVES) void setup_bin_kernel(KPara
 				for (int q = 0; q < 9; q++)
 				{
 					const int dx = q % 3, dy = q / 3;
-					use0[q] = dx < ntx && dy < nty && (!((outside >> q) & 1u) || dx == keep_dx);
+					use0[q] = dx < ntx && dy < nty && (!((outside >> q) & 1u) || dx == keep_dx || (keep_rows && (dy == 0 || dy == nty - 1)));
 					if (use0[q])
 						slot0[q] = atomicAdd(&w.tri_cnt[(ty0 + dy) * p.L.tiles_x + tx0 + dx], 1u);
 				}
@@ -475,7 +433,7 @@ __global__ __launch_bounds__(PRIM_BLOCK, PRIM_WAVES) void setup_bin_kernel(KPara
 #pragma unroll
 			for (int i = 0; i < 9; i++)
 				hp[i] = eq[i];
-			btx0 = tx0, bty0 = ty0, bntx = ntx, bnty = nty, bprim = k;
+			btx0 = tx0, bty0 = ty0, bntx = ntx, bnty = keep_rows ? -nty : nty, bprim = k;
 		} while (false);
 		DR_WAVE_PHASE_T(4);
 		bin_rest(extra, true, hp, btx0, bty0, bntx, bnty, bprim);

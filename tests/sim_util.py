@@ -21,16 +21,26 @@ class SimScene(C.Structure):
     )
 
 
-def _built(src, out, headers):
+def _built(src, out, headers, defines=()):
     deps = [src] + [os.path.join(HERE, "..", "deodr_amd", "csrc", h) for h in headers]
     if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", out, src], check=True)
+        subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", *defines, "-o", out, src], check=True)
     return C.CDLL(out)
 
 
+def kernel_tile():
+    """TILE of deodr_amd/csrc/dr_workspace.h: the simulator is compiled for the kernels' tile size"""
+    with open(os.path.join(HERE, "..", "deodr_amd", "csrc", "dr_workspace.h")) as f:
+        return int(re.search(r"constexpr\s+int\s+TILE\s*=\s*(\d+)\s*;", f.read()).group(1))
+
+
 def lib():
-    L = _built(SRC, LIB, ("dr_math.h", "dr_prims.h"))
+    L = _built(SRC, LIB, ("dr_math.h", "dr_prims.h", "dr_binning.h", "dr_workspace.h"), (f"-DDR_SIM_TILE={kernel_tile()}",))
     L.sim_bin_counts.argtypes = [C.POINTER(SimScene), C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.sim_bin_counts.restype = C.c_int
+    L.sim_prim_boxes.argtypes = [C.POINTER(SimScene), C.c_void_p, C.c_void_p]
+    L.sim_set_fault.argtypes = [C.c_int]
+    L.sim_tile.restype = C.c_int
     L.sim_tri_coverage.argtypes = [C.POINTER(SimScene), C.c_int, C.c_void_p]
     L.sim_edge_coverage.argtypes = [C.POINTER(SimScene), C.c_int, C.c_int, C.c_void_p]
     return L
@@ -117,5 +127,15 @@ def bin_counts(s, sigma=1.0, tile=8, exact=True):
     c, keep = sim_scene(s, sigma)
     nt = ((s.width + tile - 1) // tile) * ((s.height + tile - 1) // tile)
     tc, ec = np.zeros(nt, np.uint32), np.zeros(nt, np.uint32)
-    lib().sim_bin_counts(C.byref(c), tile, int(exact), tc.ctypes.data, ec.ctypes.data)
+    if lib().sim_bin_counts(C.byref(c), tile, int(exact), tc.ctypes.data, ec.ctypes.data) != 0:
+        raise ValueError(f"the simulator bins into the kernels' tiles of {lib().sim_tile()} pixels, not {tile}")
     return tc, ec
+
+
+def prim_boxes(s, sigma=1.0):
+    """-> (tri [T, 6], edge [T, 3, 6]) int32 rows (drawn, on_screen, tx0, ty0, ntx, nty): the box of tiles setup_bin_kernel walks for every
+    triangle and for the band of every edge slot (drawn: the slot gets a record)"""
+    c, keep = sim_scene(s, sigma)
+    tri, edge = np.zeros((c.T, 6), np.int32), np.zeros((c.T, 3, 6), np.int32)
+    lib().sim_prim_boxes(C.byref(c), tri.ctypes.data, edge.ctypes.data)
+    return tri, edge
