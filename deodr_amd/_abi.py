@@ -26,6 +26,7 @@ _COMPANIONS = (
     ("SOLVE_HEADER", "deodr_hip_solve.h", False),  # sparse SPD solve: smoothed vertex steps
     ("ARAP_HEADER", "deodr_hip_arap.h", False),  # as-rigid-as-possible energy
     ("CHAMFER_HEADER", "deodr_hip_chamfer.h", False),  # closest-point (Chamfer) data term
+    ("SURFACE_HEADER", "deodr_hip_surface.h", False),  # point-to-surface distance
 )
 
 # C type (without `const`, without spaces around the stars) -> ctypes.  Data pointers are c_void_p: callers pass device addresses (Python
@@ -34,7 +35,7 @@ _COMPANIONS = (
 # caller: those are typed.  Pointers to the header's own structs are added as the structs are met.
 _CTYPES = {
     "int": C.c_int, "double": C.c_double, "size_t": C.c_size_t, "uint32_t": C.c_uint32, "char*": C.c_char_p,
-    "void*": C.c_void_p, "double*": C.c_void_p, "uint32_t*": C.c_void_p, "uint8_t*": C.c_void_p, "double**": C.c_void_p,
+    "void*": C.c_void_p, "double*": C.c_void_p, "uint32_t*": C.c_void_p, "int32_t*": C.c_void_p, "uint8_t*": C.c_void_p, "double**": C.c_void_p,
     "int*": C.POINTER(C.c_int), "unsigned long long*": C.POINTER(C.c_ulonglong),
 }  # fmt: skip
 

@@ -71,6 +71,7 @@
 #include "../../include/deodr_hip_solve.h"
 #include "../../include/deodr_hip_arap.h"
 #include "../../include/deodr_hip_chamfer.h"
+#include "../../include/deodr_hip_surface.h"
 #include "dr_fititer.h" // <- dr_finalize.h <- dr_backward.h <- dr_backward_generic.h <- dr_forward.h <- dr_forward_generic.h <- dr_setup.h <- dr_workspace.h <- dr_prims.h
 #include "dr_texfit.h"  // texture smoothness + step (include/deodr_hip_texture.h); uses grid_sum of dr_fronthalf.h
 #include "dr_subdiv.h"  // rows of a sparse matrix applied to [batch, n, D] blocks (include/deodr_hip_subdiv.h): Loop subdivision and its adjoint
@@ -83,6 +84,7 @@
 #include "dr_solve.h"	 // sparse SPD solve by conjugate gradients: one workgroup per column for small systems, two launches per step above (include/deodr_hip_solve.h)
 #include "dr_arap.h"	 // as-rigid-as-possible energy: a 3 x 3 polar decomposition per vertex by Jacobi on Horn's matrix, then the gradient (include/deodr_hip_arap.h)
 #include "dr_chamfer.h" // closest-point (Chamfer) energy: a brute-force tiled nearest-neighbour search both ways, the gradient gathered in the same walk (include/deodr_hip_chamfer.h)
+#include "dr_surface.h" // point-to-surface distance: the closest point of the closest triangle by a brute-force tiled search over face records, on the machinery of dr_chamfer.h (include/deodr_hip_surface.h)
 
 using namespace dr;
 using namespace dr::dispatch;
@@ -2168,6 +2170,105 @@ int deodr_hip_chamfer(const double *vertices, int V, const double *points, int P
 		hipLaunchKernelGGL((chamfer_walk_kernel<true, false>), walk_v, block, 0, st, a, 0);
 	hipLaunchKernelGGL(chamfer_vertices_kernel, dim3(chamfer_blocks(V), (unsigned)n), block, 0, st, a);
 	return check_hip(hipGetLastError(), "chamfer launch");
+}
+
+// ---- point-to-surface distance (include/deodr_hip_surface.h, kernels in dr_surface.h)
+
+int deodr_hip_surface_abi_version(void) { return DEODR_HIP_SURFACE_ABI_VERSION; }
+
+namespace
+{
+const char *surface_dims(int V, int F, int P, int n)
+{ // -> NULL, or which limit of the header the arguments break whatever the directions
+	if (V <= 0)
+		return "V must be positive";
+	if (F <= 0 || F > SURFACE_MAX_FACES)
+		return "F must be in 1 .. 715827882";
+	if (P <= 0)
+		return "P must be positive";
+	if (n <= 0 || n > CHAMFER_MAX_POSES)
+		return "n must be in 1 .. 65535";
+	if ((unsigned long long)F * (unsigned long long)P > DEODR_HIP_SURFACE_MAX_PAIRS)
+		return "F * P is above DEODR_HIP_SURFACE_MAX_PAIRS (the search is brute force)";
+	return NULL;
+}
+const char *surface_vertex_pairs(int V, int P, int directions)
+{
+	if ((directions & DEODR_HIP_CHAMFER_MESH_TO_POINTS) && (unsigned long long)V * (unsigned long long)P > DEODR_HIP_CHAMFER_MAX_PAIRS)
+		return "V * P is above DEODR_HIP_CHAMFER_MAX_PAIRS with mesh -> points on (the search is brute force)";
+	return NULL;
+}
+} // namespace
+
+size_t deodr_hip_surface_distance_scratch_bytes(int V, int F, int P, int n)
+{
+	return surface_dims(V, F, P, n) ? 0 : scratch_need(surface_scratch_doubles(V, F, P, n));
+}
+
+int deodr_hip_surface_distance_launches(int V, int F, int P, int n, int directions)
+{
+	if (surface_dims(V, F, P, n) || !chamfer_directions(directions) || surface_vertex_pairs(V, P, directions))
+		return 0;
+	return directions == 3 ? 6 : directions == 1 ? 5 : 2;
+}
+
+int deodr_hip_surface_distance(const double *vertices, int V, const int32_t *faces, int F, const int32_t *corner_offsets, const int32_t *corners,
+							   const double *points, int P, const double *point_weights, const double *vertex_weights, const double *params, int n,
+							   int directions, double *terms, double *loss, double *vertices_b, uint32_t *nearest_face, double *barycentric,
+							   uint32_t *nearest_point, void *scratch, size_t scratch_bytes, void *stream)
+{
+	const char *what = "surface_distance";
+	if (!vertices || !faces || !corner_offsets || !corners || !points || !params || !terms || !loss || !vertices_b || !scratch)
+		return fail(what, "vertices, faces, corner_offsets, corners, points, params, terms, loss, vertices_b or scratch == NULL");
+	if (const char *why = surface_dims(V, F, P, n))
+		return fail(what, why);
+	if (!chamfer_directions(directions))
+		return fail(what, "directions must be in 1 .. 3");
+	if (const char *why = surface_vertex_pairs(V, P, directions))
+		return fail(what, why);
+	const void *const words[] = {faces, corner_offsets, corners, nearest_face, nearest_point};
+	const void *const doubles[] = {vertices, points, point_weights, vertex_weights, params, terms, loss, vertices_b, barycentric, scratch};
+	if (any_misaligned(words, 4) || any_misaligned(doubles, 8))
+		return fail(what, "misaligned pointer");
+	const Scratch sc = {scratch, scratch_bytes};
+	if (!sc.holds(deodr_hip_surface_distance_scratch_bytes(V, F, P, n)))
+		return fail(what, "scratch too small (deodr_hip_surface_distance_scratch_bytes)");
+	const size_t N = (size_t)n, nv = N * (size_t)V, np = N * (size_t)P, nf = N * (size_t)F;
+	const Range outputs[] = {{terms, 16 * N}, {loss, 8 * N}, {vertices_b, 24 * nv}, {nearest_face, 4 * np}, {barycentric, 24 * np}, {nearest_point, 4 * nv}, {scratch, scratch_bytes}};
+	const Range inputs[] = {{vertices, 24 * nv}, {faces, 12 * (size_t)F}, {corner_offsets, 4 * ((size_t)V + 1)}, {corners, 12 * (size_t)F}, {points, 24 * np},
+							{point_weights, 8 * np}, {vertex_weights, 8 * (size_t)V}, {params, 24}};
+	bool clash = any_overlap(outputs, inputs);
+	for (size_t i = 0; i < 7; i++)
+		for (size_t j = i + 1; j < 7; j++)
+			clash = clash || ranges_overlap(outputs[i].p, outputs[i].bytes, outputs[j].p, outputs[j].bytes);
+	if (clash)
+		return fail(what, "an output must not overlap an input, the scratch or another output");
+	const int Sp = chamfer_segments(P, F), Sg = chamfer_segments(F, P), Sv = chamfer_segments(V, P);
+	const size_t sp = (size_t)Sp * np, sg = (size_t)Sg * nf, sv = (size_t)Sv * nv;
+	double *const rec = sc.doubles(), *const pd2 = rec + (size_t)SURFACE_REC * nf, *const pull = pd2 + sp, *const fg = pull + 6 * np, *const vd2 = fg + 9 * sg;
+	double *const partials = vd2 + sv;
+	uint32_t *const pidx = (uint32_t *)(partials + 2 * N * (size_t)CHAMFER_MAX_BLOCKS), *const vidx = pidx + sp, *const assign = vidx + sv;
+	unsigned *const tickets = (unsigned *)(assign + np);
+	const SurfaceArgs a = {vertices, faces, corner_offsets, corners, points, point_weights, vertex_weights, params, terms, loss, vertices_b, nearest_face,
+						   barycentric, nearest_point, rec, pd2, pull, fg, vd2, partials, pidx, vidx, assign, tickets, V, F, P, n, Sp, Sg, Sv, directions};
+	const hipStream_t st = (hipStream_t)stream;
+	const dim3 block(CHAMFER_BLOCK);
+	if (directions & DEODR_HIP_CHAMFER_POINTS_TO_MESH)
+	{
+		hipLaunchKernelGGL(surface_prep_kernel, dim3(chamfer_blocks(F), (unsigned)n), block, 0, st, a);
+		hipLaunchKernelGGL(surface_search_kernel, dim3(((unsigned)P - 1) / CHAMFER_BLOCK + 1, (unsigned)Sp, (unsigned)n), block, 0, st, a);
+		hipLaunchKernelGGL(surface_points_kernel, dim3(chamfer_blocks(P), (unsigned)n), block, 0, st, a);
+		hipLaunchKernelGGL(surface_gather_kernel, dim3(((unsigned)F - 1) / CHAMFER_BLOCK + 1, (unsigned)Sg, (unsigned)n), block, 0, st, a);
+	}
+	if (directions & DEODR_HIP_CHAMFER_MESH_TO_POINTS)
+	{ // the vertex-major search of the Chamfer operator itself, into this call's scratch; alone, it is the first launch and clears the tickets
+		ChamferArgs c = {};
+		c.vertices = vertices, c.points = points, c.vd2 = vd2, c.vidx = vidx, c.tickets = tickets;
+		c.V = V, c.P = P, c.n = n, c.Sv = Sv, c.directions = directions, c.clear_tickets = !(directions & DEODR_HIP_CHAMFER_POINTS_TO_MESH);
+		hipLaunchKernelGGL((chamfer_walk_kernel<true, false>), dim3(((unsigned)V - 1) / CHAMFER_BLOCK + 1, (unsigned)Sv, (unsigned)n), block, 0, st, c, 0);
+	}
+	hipLaunchKernelGGL(surface_vertices_kernel, dim3(chamfer_blocks(V), (unsigned)n), block, 0, st, a);
+	return check_hip(hipGetLastError(), "surface_distance launch");
 }
 
 #ifdef DR_WAVE_TRACE

@@ -555,6 +555,25 @@ class ChamferFunc(torch.autograd.Function):
         return loss_b[:, None, None] * vertices_b, None
 
 
+class SurfaceDistanceFunc(torch.autograd.Function):
+    """(vertices [n,V,3]; term: a :class:`deodr_amd.surface.PointSurfaceTerm`) -> (loss [n], terms [n,2]) of the point-to-surface energy
+    (include/deodr_hip_surface.h); the loss is differentiable (its adjoint is the ``vertices_b`` the same call produced: the envelope theorem, exact
+    wherever every closest point is unique), the terms are not: they are marked so, and torch refuses a gradient asked of them ("does not require
+    grad")"""
+
+    @staticmethod
+    def forward(ctx, vertices, term):
+        terms, loss, vertices_b = term.evaluate_no_grad(vertices)[:3]
+        ctx.save_for_backward(vertices_b)
+        ctx.mark_non_differentiable(terms)
+        return loss, terms
+
+    @staticmethod
+    def backward(ctx, loss_b, _terms_b):
+        (vertices_b,) = ctx.saved_tensors
+        return loss_b[:, None, None] * vertices_b, None
+
+
 def sh_shade(posed, sh, albedo, topology):
     """-> luminosity [n,V] (``albedo`` None) or colors [n,V,C] of the posed vertices [n,V,3] (or [V,3]) under the SH lighting ``sh``, differentiable in
     all three: the kernels on float64 ROCm tensors, the same formulas as torch ops (``lighting.sh_shade_torch``) otherwise"""

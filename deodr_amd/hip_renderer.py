@@ -42,8 +42,9 @@ _COMPANIONS = (
     (_abi.SOLVE_HEADER, "solve", "sparse-solve"),  # sparse SPD solve: smoothed vertex steps
     (_abi.ARAP_HEADER, "arap", "arap-energy"),  # as-rigid-as-possible energy
     (_abi.CHAMFER_HEADER, "chamfer", "chamfer-term"),  # closest-point (Chamfer) data term
+    (_abi.SURFACE_HEADER, "surface", "surface-distance"),  # point-to-surface distance
 )
-TEXTURE_ABI_VERSION, SUBDIV_ABI_VERSION, RETAINED_ABI_VERSION, BASIS_ABI_VERSION, CAMERA_ABI_VERSION, LIGHTING_ABI_VERSION, SKINNING_ABI_VERSION, PYRAMID_ABI_VERSION, SSIM_ABI_VERSION, SOLVE_ABI_VERSION, ARAP_ABI_VERSION, CHAMFER_ABI_VERSION = (
+TEXTURE_ABI_VERSION, SUBDIV_ABI_VERSION, RETAINED_ABI_VERSION, BASIS_ABI_VERSION, CAMERA_ABI_VERSION, LIGHTING_ABI_VERSION, SKINNING_ABI_VERSION, PYRAMID_ABI_VERSION, SSIM_ABI_VERSION, SOLVE_ABI_VERSION, ARAP_ABI_VERSION, CHAMFER_ABI_VERSION, SURFACE_ABI_VERSION = (
     h.defines[f"DEODR_HIP_{key.upper()}_ABI_VERSION"] for h, key, _ in _COMPANIONS
 )
 # words of the 64-byte status block at the start of the workspace
@@ -1627,6 +1628,82 @@ def chamfer(vertices, points, params, point_weights=None, vertex_weights=None, d
         if t is not None:
             _touched(t)
     return terms, loss, vertices_b, nearest_vertex, nearest_point
+
+
+# ---- point-to-surface distance (include/deodr_hip_surface.h) --------------------------------------------------------------------------------
+
+SURFACE_MAX_PAIRS = _abi.SURFACE_HEADER.defines["DEODR_HIP_SURFACE_MAX_PAIRS"]
+
+
+def surface_launches(V, F, P, n, directions=3):
+    """``deodr_hip_surface_distance_launches``: the kernel launches of a :func:`surface_distance` call -- 5 with points -> mesh alone, 6 with both
+    directions, 2 with mesh -> points alone (0 for arguments the call refuses)"""
+    return int(lib().deodr_hip_surface_distance_launches(int(V), int(F), int(P), int(n), int(directions)))
+
+
+def surface_scratch(V, F, P, n, device):
+    """the scratch of :func:`surface_distance` for n poses of V vertices and F faces against P points (one per stream in use; it need not be zeroed)"""
+    need = int(lib().deodr_hip_surface_distance_scratch_bytes(int(V), int(F), int(P), int(n)))
+    if need == 0:
+        raise ValueError(f"surface_scratch: V = {V}, F = {F}, P = {P}, n = {n} is outside the limits of include/deodr_hip_surface.h")
+    with torch.cuda.device(device):
+        return torch.empty(need, dtype=torch.uint8, device=device)
+
+
+def surface_distance(vertices, faces, corner_offsets, corners, points, params, point_weights=None, vertex_weights=None, directions=3, terms=None,
+                     loss=None, vertices_b=None, nearest_face=None, barycentric=None, nearest_point=None, scratch=None, want_nearest=False):  # fmt: skip
+    """``deodr_hip_surface_distance``: the point-to-surface distance of ``points`` [n,P,3] to the triangles ``faces`` [F,3] (int32) of ``vertices``
+    [n,V,3] (float64) -> (terms [n,2], loss [n], vertices_b [n,V,3], nearest_face [n,P] | None, barycentric [n,P,3] | None, nearest_point [n,V] |
+    None; the indices as int32 tensors holding uint32 bit patterns); the header has the operation.  ``corner_offsets`` [V + 1] and ``corners``
+    [3 F] (int32): the transposed table of ``faces`` (:func:`deodr_amd.surface.corner_table`).  ``params`` [3] float64 ON THE DEVICE = (mix_0,
+    mix_1, max_distance), read when the kernels run; ``point_weights`` [n,P] and ``vertex_weights`` [V] float64 or None (ones); ``directions``: bit
+    1 points -> mesh, bit 2 mesh -> points.  The nearest_* and barycentric arrays are written when a tensor is given or ``want_nearest``, for the
+    directions that are on.  The values and the tables are trusted (:mod:`deodr_amd.surface` checks its own on the host).  Deterministic;
+    asynchronous on the current stream.  ``scratch``: a :func:`surface_scratch` of the caller's; None: one per device and stream."""
+    what = "surface_distance"
+    _rocm_tensor(what, "vertices", vertices)
+    if vertices.dim() != 3 or vertices.shape[0] < 1 or vertices.shape[1] < 1 or vertices.shape[2] != 3:
+        raise ValueError(f"{what}: vertices must have shape [n >= 1, V >= 1, 3], not {list(vertices.shape)}")
+    n, V = int(vertices.shape[0]), int(vertices.shape[1])
+    if not torch.is_tensor(faces) or faces.dim() != 2 or faces.shape[0] < 1 or faces.shape[1] != 3:
+        raise ValueError(f"{what}: faces must have shape [F >= 1, 3], not {list(getattr(faces, 'shape', ()))}")
+    if not torch.is_tensor(points) or points.dim() != 3 or int(points.shape[0]) != n or points.shape[1] < 1 or points.shape[2] != 3:
+        raise ValueError(f"{what}: points must have shape [{n}, P >= 1, 3], not {list(getattr(points, 'shape', ()))}")
+    F, P, directions = int(faces.shape[0]), int(points.shape[1]), int(directions)
+    if not 1 <= directions <= 3:
+        raise ValueError(f"{what}: directions must be in 1 .. 3, not {directions}")
+    rows = [("vertices", vertices, _F64_ONLY, None), ("faces", faces, (torch.int32,), (F, 3)), ("corner_offsets", corner_offsets, (torch.int32,), (V + 1,)),
+            ("corners", corners, (torch.int32,), (3 * F,)), ("points", points, _F64_ONLY, (n, P, 3)), ("params", params, _F64_ONLY, (3,))]  # fmt: skip
+    optional = (("point_weights", point_weights, _F64_ONLY, (n, P)), ("vertex_weights", vertex_weights, _F64_ONLY, (V,)),
+                ("terms", terms, _F64_ONLY, (n, 2)), ("loss", loss, _F64_ONLY, (n,)), ("vertices_b", vertices_b, _F64_ONLY, (n, V, 3)),
+                ("nearest_face", nearest_face, _INDICES, (n, P)), ("barycentric", barycentric, _F64_ONLY, (n, P, 3)),
+                ("nearest_point", nearest_point, _INDICES, (n, V)), ("scratch", scratch, (torch.uint8,), (None,)))  # fmt: skip
+    rows += [row for row in optional if row[1] is not None]
+    _check_tensors(what, "vertices", vertices.device, rows)
+    dev = vertices.device
+    need = int(lib().deodr_hip_surface_distance_scratch_bytes(V, F, P, n))
+    if need == 0 or not lib().deodr_hip_surface_distance_launches(V, F, P, n, directions):
+        raise ValueError(f"{what}: V = {V}, F = {F}, P = {P}, n = {n} is outside the limits of include/deodr_hip_surface.h (F * P <= {SURFACE_MAX_PAIRS}, "
+                         f"V * P <= {CHAMFER_MAX_PAIRS} with mesh -> points, n <= 65535)")  # fmt: skip
+    with torch.cuda.device(dev):
+        terms = torch.empty((n, 2), dtype=torch.float64, device=dev) if terms is None else terms
+        loss = torch.empty(n, dtype=torch.float64, device=dev) if loss is None else loss
+        vertices_b = torch.empty_like(vertices) if vertices_b is None else vertices_b
+        if want_nearest and directions & CHAMFER_POINTS_TO_MESH:
+            nearest_face = torch.empty((n, P), dtype=torch.int32, device=dev) if nearest_face is None else nearest_face
+            barycentric = torch.empty((n, P, 3), dtype=torch.float64, device=dev) if barycentric is None else barycentric
+        if want_nearest and nearest_point is None and directions & CHAMFER_MESH_TO_POINTS:
+            nearest_point = torch.empty((n, V), dtype=torch.int32, device=dev)
+        if scratch is None:
+            scratch = _cached_scratch("surface", dev, need, lambda: surface_scratch(V, F, P, n, dev),
+                                      f"{what}: pass scratch= (surface_scratch) when capturing a graph: none of this size exists for this stream yet")  # fmt: skip
+    _launch(lib().deodr_hip_surface_distance, dev, _ptr(vertices), V, _ptr(faces), F, _ptr(corner_offsets), _ptr(corners), _ptr(points), P,
+            _ptr(point_weights), _ptr(vertex_weights), _ptr(params), n, directions, _ptr(terms), _ptr(loss), _ptr(vertices_b), _ptr(nearest_face),
+            _ptr(barycentric), _ptr(nearest_point), _ptr(scratch), scratch.numel())  # fmt: skip
+    for t in (terms, loss, vertices_b, nearest_face, barycentric, nearest_point):
+        if t is not None:
+            _touched(t)
+    return terms, loss, vertices_b, nearest_face, barycentric, nearest_point
 
 
 # ---------------------------------------------------------------------------------------------------------------------

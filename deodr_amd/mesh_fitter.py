@@ -750,6 +750,12 @@ class MeshPointCloudFitter(_PoseFitter):
     cloud).  ``directions``, ``max_distance``, ``mix``, ``normalise``: the term's; ``self.term.params`` may be ``copy_``-ed into between steps, also
     under a ``GraphedStep`` (a ``max_distance`` that shrinks as the fit closes in).
 
+    ``metric``: "vertex" (the default: the term above, every point against the VERTICES) or "surface": points -> mesh measures every point against
+    the closest point of the closest TRIANGLE (:class:`deodr_amd.surface.PointSurfaceTerm`, include/deodr_hip_surface.h) of the mesh that meets the
+    cloud -- what a cloud denser than the mesh needs: points that lie on a face then cost nothing and pull nothing.  mesh -> points is the same
+    either way.  The step factors are the ones below for both metrics: a point's pull is spread over the three corners of its face with weights
+    that sum to 1, so the gradients have the scale they have against the vertices (examples/point_surface_hand_fitting.py runs with them).
+
     The step factors are this fitter's own, chosen on examples/point_cloud_hand_fitting.py with ``normalise=True`` (both terms are then mean squared
     distances, so the translation gradient is of the order of the offset whatever V and P are, and a vertex gradient of the order of offset / V):
     the largest powers of ten (times 1, 2 or 5) at which the hand's 60 iterations against 400 of its own posed vertices lower the energy
@@ -766,7 +772,10 @@ class MeshPointCloudFitter(_PoseFitter):
     def __init__(self, vertices, faces, euler_init, translation_init, cregu=0.002, inertia=0.9, damping=0.05, device="cuda", n_poses=1,
                  directions="both", max_distance=float("inf"), mix=(1.0, 1.0), normalise=True, subdivisions=0, shape_basis=None, coefficient_regu=0.0,
                  sigmas=None, skin=None, joint_quaternions_init=None, joint_regu=0.0, smoothing=0.0, smoothing_iterations=None, rigidity="laplacian",
-                 arap_weights="uniform"):  # fmt: skip
+                 arap_weights="uniform", metric="vertex"):  # fmt: skip
+        if metric not in ("vertex", "surface"):
+            raise ValueError(f'metric must be "vertex" or "surface", not {metric!r}')
+        self.metric = metric
         super().__init__(vertices, faces, euler_init, translation_init, cregu, inertia, damping, device, n_poses=n_poses, subdivisions=subdivisions,
                          shape_basis=shape_basis, coefficient_regu=coefficient_regu, sigmas=sigmas, skin=skin,
                          joint_quaternions_init=joint_quaternions_init, joint_regu=joint_regu, smoothing=smoothing,
@@ -779,9 +788,14 @@ class MeshPointCloudFitter(_PoseFitter):
     def set_point_clouds(self, points, weights=None, vertex_weights=None):
         """one cloud per pose: a list of [P_i,3] clouds (padded at weight 0) or [n_poses,P,3]; ``weights``: per point, ``>= 0``, of the same layout
         (None: ones); ``vertex_weights`` [V] of the vertices that meet the cloud (None: ones)"""
-        from .chamfer import PointCloudTerm
+        if self.metric == "surface":  # the faces of the mesh that meets the cloud: the subdivided ones with subdivisions
+            from .surface import PointSurfaceTerm
 
-        term = PointCloudTerm(points, weights, vertex_weights, device=self.device, **self._term_keywords)
+            term = PointSurfaceTerm(self.mesh.topology.faces, self.mesh.nb_vertices, points, weights, vertex_weights, device=self.device, **self._term_keywords)
+        else:
+            from .chamfer import PointCloudTerm
+
+            term = PointCloudTerm(points, weights, vertex_weights, device=self.device, **self._term_keywords)
         if term.n != self.n_poses:
             raise ValueError(f"set_point_clouds: {term.n} clouds for a fitter of {self.n_poses} poses")
         self.term, self.iter = term, 0
