@@ -27,6 +27,7 @@ _COMPANIONS = (
     ("ARAP_HEADER", "deodr_hip_arap.h", False),  # as-rigid-as-possible energy
     ("CHAMFER_HEADER", "deodr_hip_chamfer.h", False),  # closest-point (Chamfer) data term
     ("SURFACE_HEADER", "deodr_hip_surface.h", False),  # point-to-surface distance
+    ("CHAMFER_GRID_HEADER", "deodr_hip_chamfer_grid.h", False),  # closest-point term over a uniform grid, stable sort by key
 )
 
 # C type (without `const`, without spaces around the stars) -> ctypes.  Data pointers are c_void_p: callers pass device addresses (Python

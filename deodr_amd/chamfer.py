@@ -10,7 +10,11 @@ inside a captured graph.
 
 :class:`PointCloudTerm` holds the clouds, the weights and the device-resident ``params`` and evaluates, differentiably; :func:`chamfer_torch` is
 the same definition as torch ops, chunked over the queries -- what runs on tensors the kernels do not take (CPU tensors, other dtypes) and what
-the kernels are timed against; :func:`depth_to_points` back-projects a depth image.  ``deodr_amd.pytorch.MeshPointCloudFitter`` fits with it."""
+the kernels are timed against; :func:`depth_to_points` back-projects a depth image.  ``deodr_amd.pytorch.MeshPointCloudFitter`` fits with it.
+
+``PointCloudTerm(search="grid")`` finds the same neighbours over a uniform grid of hashed cells (``include/deodr_hip_chamfer_grid.h``,
+``deodr_amd/csrc/dr_chamfer_grid.h``): the cost grows with V + P instead of V * P and there is no cap on V * P; it needs a finite
+``max_distance``, and a query with nothing within it has no correspondence (-1)."""
 
 import math
 
@@ -18,6 +22,7 @@ import numpy as np
 import torch
 
 DIRECTIONS = {"points_to_mesh": 1, "mesh_to_points": 2, "both": 3}
+SEARCHES = ("brute", "grid")
 CHUNK_BYTES = 64 << 20  # of distances that exist at once in chamfer_torch
 
 
@@ -66,6 +71,28 @@ def chamfer_torch(vertices, points, params, point_weights=None, vertex_weights=N
         return terms, loss, g, nearest_vertex, nearest_point
 
 
+def mask_beyond(queries, refs, nearest, params):
+    """``nearest`` [n,Q] (int64, into ``refs`` [n,R,3]) with -1 where the header's d2 of the pair is above ``params[2] ** 2``: what the grid search
+    reports for a query with no neighbour within ``max_distance``"""
+    tau2 = params[2].to(queries.dtype) * params[2].to(queries.dtype)
+    d = queries - torch.gather(refs, 1, nearest[..., None].expand(-1, -1, 3))
+    d2 = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+    return torch.where(d2 <= tau2, nearest, torch.full_like(nearest, -1))
+
+
+def default_cell_size(clouds):
+    """the cell size of ``search="grid"`` when none is given, from the clouds alone (nothing that moves): twice the spacing the points of a cloud
+    would have if they covered half the surface of its bounding box evenly, ``2 sqrt((e0 e1 + e1 e2 + e0 e2) / P)`` with e the extents of the box
+    -- a cell then holds a handful of the points of a scanned surface --, the largest over the clouds; 1 for clouds without extent.  Reasoned,
+    not swept; the kernels never use a cell below ``max_distance / 4`` whatever this gives."""
+    sizes = []
+    for c in clouds:
+        e = c.max(axis=0) - c.min(axis=0)
+        sizes.append(2.0 * math.sqrt(float(e[0] * e[1] + e[1] * e[2] + e[0] * e[2]) / len(c)))
+    size = max(sizes)
+    return size if size > 0 and math.isfinite(size) else 1.0
+
+
 def _array(a):
     return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
 
@@ -80,16 +107,32 @@ class PointCloudTerm:
     ``mix`` = (mix_0, mix_1).  ``normalise``: every weight vector is divided by its sum, so both terms are weighted mean squared distances.
     Checked here, on the host, because the kernels cannot: finite coordinates, finite weights ``>= 0`` with a positive sum, ``max_distance``,
     ``mix``.  ``self.params`` [3] = (mix_0, mix_1, max_distance), ``self.points`` and the weights are device tensors read when the kernels run:
-    ``copy_`` other values into them between calls, also between replays of a captured graph (they are not checked again)."""
+    ``copy_`` other values into them between calls, also between replays of a captured graph (they are not checked again).
 
-    def __init__(self, points, point_weights=None, vertex_weights=None, directions="both", max_distance=math.inf, mix=(1.0, 1.0), normalise=True, device="cuda"):
+    ``search``: "brute" (the default: every pair is visited, V * P is capped) or "grid": the same neighbours over a uniform grid of cells
+    (``deodr_hip_chamfer_grid``); the same loss, terms and gradient up to the order of the sums (on CPU tensors: the same bits), no cap on V * P.
+    The grid needs a finite ``max_distance`` -- an infinite one is refused here, and at a call when it was ``copy_``-ed into ``params`` where the
+    host can see it (CPU tensors) --, and :meth:`correspondences` gives -1 for a query with nothing within ``max_distance``.  ``cell_size`` > 0:
+    the cells' edge (the kernels use ``max(cell_size, max_distance / 4)``); None: :func:`default_cell_size` of the clouds, evaluated once here."""
+
+    def __init__(self, points, point_weights=None, vertex_weights=None, directions="both", max_distance=math.inf, mix=(1.0, 1.0), normalise=True, device="cuda",
+                 search="brute", cell_size=None):  # fmt: skip
         what = "PointCloudTerm"
         if directions not in DIRECTIONS:
             raise ValueError(f'{what}: directions must be "both", "points_to_mesh" or "mesh_to_points", not {directions!r}')
+        if search not in SEARCHES:
+            raise ValueError(f'{what}: search must be "brute" or "grid", not {search!r}')
+        if cell_size is not None and search != "grid":
+            raise ValueError(f'{what}: cell_size belongs to search="grid"')
+        if cell_size is not None and not (float(cell_size) > 0 and math.isfinite(float(cell_size))):
+            raise ValueError(f"{what}: cell_size must be finite and > 0, not {cell_size}")
+        self.search = search
         self.device, self.directions, self.normalise = torch.device(device), DIRECTIONS[directions], bool(normalise)
         max_distance, mix = float(max_distance), tuple(float(m) for m in mix)
         if not max_distance > 0:  # (a NaN is refused as well)
             raise ValueError(f"{what}: max_distance must be > 0 (inf: no truncation), not {max_distance}")
+        if search == "grid" and not math.isfinite(max_distance):
+            raise ValueError(f'{what}: search="grid" needs a finite max_distance (only neighbours within it are looked for), not {max_distance}')
         if len(mix) != 2 or not all(math.isfinite(m) for m in mix):
             raise ValueError(f"{what}: mix must be two finite values, not {mix}")
         if isinstance(points, (list, tuple)):
@@ -118,6 +161,7 @@ class PointCloudTerm:
             w[b, : len(c)] = self._weights(cw, "point_weights")
             pts[b, : len(c)], pts[b, len(c) :] = c, c[0]
         self.nb_points = P
+        self.cell_size = None if search != "grid" else float(cell_size) if cell_size is not None else default_cell_size(clouds)
         self.points, self.point_weights = torch.as_tensor(pts, device=self.device), torch.as_tensor(w, device=self.device)
         self.vertex_weights = None
         if vertex_weights is not None:
@@ -162,12 +206,27 @@ class PointCloudTerm:
         v = self._posed(vertices).detach().contiguous()
         V = int(v.shape[1])
         u = self._vertex_weights(V)
+        grid = self.search == "grid"
+        if grid and not self.params.is_cuda and not math.isfinite(float(self.params[2])):
+            raise ValueError('PointCloudTerm: search="grid" needs a finite max_distance, params[2] is not')
         if not self.uses_kernel(v):
             to = lambda t: None if t is None else t.to(v.device)
-            out = chamfer_torch(v, to(self.points), to(self.params), to(self.point_weights), to(u), self.directions)
-            return out if want_nearest else out[:3] + (None, None)
+            points, params = to(self.points), to(self.params)
+            out = chamfer_torch(v, points, params, to(self.point_weights), to(u), self.directions)
+            if not want_nearest:
+                return out[:3] + (None, None)
+            if grid:  # the same values; the correspondences beyond max_distance are none
+                p = points.to(v.dtype)
+                out = out[:3] + (None if out[3] is None else mask_beyond(p, v, out[3], params), None if out[4] is None else mask_beyond(v, p, out[4], params))
+            return out
         from . import hip_renderer as hr
 
+        if grid:
+            if ("grid", self.n, V) not in self._scratch:
+                self._scratch[("grid", self.n, V)] = hr.chamfer_grid_scratch(V, self.nb_points, self.n, v.device)
+            terms, loss, g, nv, npt = hr.chamfer_grid(v, self.points, self.params, self.cell_size, self.point_weights, u, self.directions,
+                                                      scratch=self._scratch[("grid", self.n, V)], want_nearest=want_nearest)  # fmt: skip
+            return terms, loss, g, (None if nv is None else nv.long()), (None if npt is None else npt.long())  # (NONE, all bits set, is -1)
         if (self.n, V) not in self._scratch:
             self._scratch[(self.n, V)] = hr.chamfer_scratch(V, self.nb_points, self.n, v.device)
         terms, loss, g, nv, npt = hr.chamfer(v, self.points, self.params, self.point_weights, u, self.directions, scratch=self._scratch[(self.n, V)],
@@ -185,7 +244,8 @@ class PointCloudTerm:
 
     def correspondences(self, vertices):
         """-> (nearest_vertex [n,P] | None, nearest_point [n,V] | None), int64: the index of the nearest vertex of every point (None without points ->
-        mesh; a padded point has the one of its cloud's first point) and of the nearest point of every vertex (None without mesh -> points)"""
+        mesh; a padded point has the one of its cloud's first point) and of the nearest point of every vertex (None without mesh -> points); with
+        ``search="grid"`` -1 where nothing lies within ``max_distance``"""
         return self.evaluate_no_grad(vertices, want_nearest=True)[3:]
 
 

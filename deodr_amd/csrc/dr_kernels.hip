@@ -72,6 +72,7 @@
 #include "../../include/deodr_hip_arap.h"
 #include "../../include/deodr_hip_chamfer.h"
 #include "../../include/deodr_hip_surface.h"
+#include "../../include/deodr_hip_chamfer_grid.h"
 #include "dr_fititer.h" // <- dr_finalize.h <- dr_backward.h <- dr_backward_generic.h <- dr_forward.h <- dr_forward_generic.h <- dr_setup.h <- dr_workspace.h <- dr_prims.h
 #include "dr_texfit.h"  // texture smoothness + step (include/deodr_hip_texture.h); uses grid_sum of dr_fronthalf.h
 #include "dr_subdiv.h"  // rows of a sparse matrix applied to [batch, n, D] blocks (include/deodr_hip_subdiv.h): Loop subdivision and its adjoint
@@ -85,6 +86,8 @@
 #include "dr_arap.h"	 // as-rigid-as-possible energy: a 3 x 3 polar decomposition per vertex by Jacobi on Horn's matrix, then the gradient (include/deodr_hip_arap.h)
 #include "dr_chamfer.h" // closest-point (Chamfer) energy: a brute-force tiled nearest-neighbour search both ways, the gradient gathered in the same walk (include/deodr_hip_chamfer.h)
 #include "dr_surface.h" // point-to-surface distance: the closest point of the closest triangle by a brute-force tiled search over face records, on the machinery of dr_chamfer.h (include/deodr_hip_surface.h)
+#include "dr_sort.h"	// a stable LSD radix sort by key: histograms, a scan over (digit, workgroup), a scatter ranked by ballots (include/deodr_hip_chamfer_grid.h)
+#include "dr_chamfer_grid.h" // the closest-point energy over a uniform grid of hashed cells: keys, sort, build, ring search, gather; the combine steps of dr_chamfer.h (include/deodr_hip_chamfer_grid.h)
 
 using namespace dr;
 using namespace dr::dispatch;
@@ -2269,6 +2272,147 @@ int deodr_hip_surface_distance(const double *vertices, int V, const int32_t *fac
 	}
 	hipLaunchKernelGGL(surface_vertices_kernel, dim3(chamfer_blocks(V), (unsigned)n), block, 0, st, a);
 	return check_hip(hipGetLastError(), "surface_distance launch");
+}
+
+// ---- stable sort by key, closest-point energy over a uniform grid (include/deodr_hip_chamfer_grid.h, kernels in dr_sort.h and dr_chamfer_grid.h)
+
+int deodr_hip_chamfer_grid_abi_version(void) { return DEODR_HIP_CHAMFER_GRID_ABI_VERSION; }
+
+size_t deodr_hip_sort_keys_scratch_bytes(int N, int n, int bits) { return sort_dims(N, n, bits) ? 0 : 4 * sort_scratch_words(N, n); }
+
+int deodr_hip_sort_keys_launches(int N, int n, int bits) { return sort_dims(N, n, bits) ? 0 : 3 * sort_passes(bits); }
+
+int deodr_hip_sort_keys(const uint32_t *keys, int N, int n, int bits, uint32_t *sorted_keys, uint32_t *order, void *scratch, size_t scratch_bytes,
+						void *stream)
+{
+	const char *what = "sort_keys";
+	if (!keys || !order || !scratch)
+		return fail(what, "keys, order or scratch == NULL");
+	if (const char *why = sort_dims(N, n, bits))
+		return fail(what, why);
+	const void *const words[] = {keys, sorted_keys, order, scratch};
+	if (any_misaligned(words, 4))
+		return fail(what, "misaligned pointer");
+	if (scratch_bytes < deodr_hip_sort_keys_scratch_bytes(N, n, bits))
+		return fail(what, "scratch too small (deodr_hip_sort_keys_scratch_bytes)");
+	const size_t row_bytes = 4 * (size_t)n * (size_t)N;
+	const Range buffers[] = {{keys, row_bytes}, {sorted_keys, row_bytes}, {order, row_bytes}, {scratch, scratch_bytes}};
+	for (size_t i = 0; i < 4; i++)
+		for (size_t j = i + 1; j < 4; j++)
+			if (ranges_overlap(buffers[i].p, buffers[i].bytes, buffers[j].p, buffers[j].bytes))
+				return fail(what, "keys, sorted_keys, order and scratch must not overlap");
+	sort_launch(keys, N, n, bits, sorted_keys, order, (uint32_t *)scratch, (hipStream_t)stream);
+	return check_hip(hipGetLastError(), "sort_keys launch");
+}
+
+namespace
+{
+const char *chamfer_grid_dims(int V, int P, int n)
+{ // -> NULL, or which limit of the header the arguments break
+	if (V <= 0 || V > CG_MAX_ITEMS)
+		return "V must be in 1 .. DEODR_HIP_CHAMFER_GRID_MAX_ITEMS";
+	if (P <= 0 || P > CG_MAX_ITEMS)
+		return "P must be in 1 .. DEODR_HIP_CHAMFER_GRID_MAX_ITEMS";
+	if (n <= 0 || n > CHAMFER_MAX_POSES)
+		return "n must be in 1 .. 65535";
+	return NULL;
+}
+// the scratch: doubles after the counter bytes, then 4-byte words, then the scratch of the sorts
+size_t chamfer_grid_doubles(int V, int P, int n) { return (size_t)n * (8 * (size_t)V + 5 * (size_t)P + 2 * (size_t)CHAMFER_MAX_BLOCKS); }
+size_t chamfer_grid_words(int V, int P, int n)
+{
+	const size_t Tv = (size_t)1 << chamfer_grid_table_bits(V), Tp = (size_t)1 << chamfer_grid_table_bits(P);
+	return (size_t)n * (7 * (size_t)P + 4 * (size_t)V + 2 * Tv + 2 * Tp + 2);
+}
+} // namespace
+
+int deodr_hip_chamfer_grid_table_bits(int references) { return chamfer_grid_table_bits(references); }
+
+size_t deodr_hip_chamfer_grid_scratch_bytes(int V, int P, int n)
+{
+	if (chamfer_grid_dims(V, P, n))
+		return 0;
+	return scratch_need(chamfer_grid_doubles(V, P, n)) + 4 * (chamfer_grid_words(V, P, n) + sort_scratch_words(V > P ? V : P, n));
+}
+
+int deodr_hip_chamfer_grid_launches(int V, int P, int n, int directions)
+{
+	if (chamfer_grid_dims(V, P, n) || !chamfer_directions(directions))
+		return 0;
+	int launches = 1; // the vertices' combine step
+	if (directions & DEODR_HIP_CHAMFER_POINTS_TO_MESH) // keys, sort, build of the vertices; search, combine, sort of the assignment, gather
+		launches += 2 + 3 * sort_passes(chamfer_grid_table_bits(V)) + 3 + 3 * sort_passes(chamfer_grid_assign_bits(V));
+	if (directions & DEODR_HIP_CHAMFER_MESH_TO_POINTS) // keys, sort, build of the points; search
+		launches += 2 + 3 * sort_passes(chamfer_grid_table_bits(P)) + 1;
+	return launches;
+}
+
+int deodr_hip_chamfer_grid(const double *vertices, int V, const double *points, int P, const double *point_weights, const double *vertex_weights,
+						   const double *params, double cell_size, int n, int directions, double *terms, double *loss, double *vertices_b,
+						   uint32_t *nearest_vertex, uint32_t *nearest_point, void *scratch, size_t scratch_bytes, void *stream)
+{
+	const char *what = "chamfer_grid";
+	if (!vertices || !points || !params || !terms || !loss || !vertices_b || !scratch)
+		return fail(what, "vertices, points, params, terms, loss, vertices_b or scratch == NULL");
+	if (const char *why = chamfer_grid_dims(V, P, n))
+		return fail(what, why);
+	if (!chamfer_directions(directions))
+		return fail(what, "directions must be in 1 .. 3");
+	if (!(cell_size > 0) || !(cell_size < __builtin_inf()))
+		return fail(what, "cell_size must be finite and > 0");
+	const void *const words[] = {nearest_vertex, nearest_point};
+	const void *const doubles[] = {vertices, points, point_weights, vertex_weights, params, terms, loss, vertices_b, scratch};
+	if (any_misaligned(words, 4) || any_misaligned(doubles, 8))
+		return fail(what, "misaligned pointer");
+	const Scratch sc = {scratch, scratch_bytes};
+	if (!sc.holds(deodr_hip_chamfer_grid_scratch_bytes(V, P, n)))
+		return fail(what, "scratch too small (deodr_hip_chamfer_grid_scratch_bytes)");
+	const size_t N = (size_t)n, nv = N * (size_t)V, np = N * (size_t)P;
+	const Range outputs[] = {{terms, 16 * N}, {loss, 8 * N}, {vertices_b, 24 * nv}, {nearest_vertex, 4 * np}, {nearest_point, 4 * nv}, {scratch, scratch_bytes}};
+	const Range inputs[] = {{vertices, 24 * nv}, {points, 24 * np}, {point_weights, 8 * np}, {vertex_weights, 8 * (size_t)V}, {params, 24}};
+	bool clash = any_overlap(outputs, inputs);
+	for (size_t i = 0; i < 6; i++)
+		for (size_t j = i + 1; j < 6; j++)
+			clash = clash || ranges_overlap(outputs[i].p, outputs[i].bytes, outputs[j].p, outputs[j].bytes);
+	if (clash)
+		return fail(what, "an output must not overlap an input, the scratch or another output");
+	const int tv = chamfer_grid_table_bits(V), tp = chamfer_grid_table_bits(P);
+	const size_t Tv = (size_t)1 << tv, Tp = (size_t)1 << tp;
+	double *const records_v = sc.doubles(), *const records_p = records_v + 4 * nv, *const pd2 = records_p + 4 * np, *const vd2 = pd2 + np;
+	double *const vg = vd2 + nv, *const partials = vg + 3 * nv;
+	uint32_t *const table_v = (uint32_t *)(partials + 2 * N * (size_t)CHAMFER_MAX_BLOCKS), *const table_p = table_v + 2 * N * Tv; // (pairs: 8-byte aligned)
+	uint32_t *const pidx = table_p + 2 * N * Tp, *const vidx = pidx + np, *const assign = vidx + nv;
+	uint32_t *const keys_v = assign + np, *const keys_p = keys_v + 3 * nv, *const sorted_assign = keys_p + 3 * np, *const assign_order = sorted_assign + np;
+	uint32_t *const tickets = assign_order + np, *const sort_words = tickets + 2 * N;
+	ChamferGridArgs g = {{{vertices, records_v, keys_v, keys_v + nv, keys_v + 2 * nv, table_v, V, tv}, {points, records_p, keys_p, keys_p + np, keys_p + 2 * np, table_p, P, tp}},
+						 params, point_weights, pd2, vd2, vg, pidx, vidx, sorted_assign, assign_order, (unsigned *)tickets, cell_size, V, P, n, 1};
+	// the combine steps of dr_chamfer.h, with one segment per search
+	const ChamferArgs a = {vertices, points, point_weights, vertex_weights, params, terms, loss, vertices_b, nearest_vertex, nearest_point, pd2, vd2, vg,
+						   partials, pidx, vidx, assign, (unsigned *)tickets, V, P, n, 1, 1, directions, 0};
+	const hipStream_t st = (hipStream_t)stream;
+	const dim3 block(CHAMFER_BLOCK);
+	const bool to_mesh = directions & DEODR_HIP_CHAMFER_POINTS_TO_MESH, to_points = directions & DEODR_HIP_CHAMFER_MESH_TO_POINTS;
+	for (int which = 0; which < 2; which++)
+		if (which == 0 ? to_mesh : to_points)
+		{
+			const ChamferGridSet &s = g.set[which];
+			const size_t T = (size_t)1 << s.table_bits;
+			hipLaunchKernelGGL(chamfer_grid_keys_kernel, dim3(chamfer_blocks(T > (size_t)s.R ? (int)T : s.R), (unsigned)n), block, 0, st, g, which);
+			g.clear_tickets = 0;
+			sort_launch(s.keys, s.R, n, s.table_bits, s.sorted_keys, s.order, sort_words, st);
+			hipLaunchKernelGGL(chamfer_grid_build_kernel, dim3(chamfer_blocks(s.R), (unsigned)n), block, 0, st, g, which);
+		}
+	if (to_mesh)
+	{
+		hipLaunchKernelGGL(chamfer_grid_search_kernel, dim3(((unsigned)P - 1) / CHAMFER_BLOCK + 1, (unsigned)n), block, 0, st, g, 1, (int)to_points);
+		hipLaunchKernelGGL(chamfer_points_kernel, dim3(chamfer_blocks(P), (unsigned)n), block, 0, st, a);
+		sort_launch(assign, P, n, chamfer_grid_assign_bits(V), sorted_assign, assign_order, sort_words, st);
+		hipLaunchKernelGGL(chamfer_grid_gather_kernel, dim3(((unsigned)V - 1) / CG_GATHER_VERTICES + 1, (unsigned)n), block, 0, st, g);
+	}
+	if (to_points)
+		hipLaunchKernelGGL(chamfer_grid_search_kernel, dim3(((unsigned)V - 1) / CHAMFER_BLOCK + 1, (unsigned)n), block, 0, st, g, 0, (int)to_mesh);
+	hipLaunchKernelGGL(chamfer_vertices_kernel, dim3(chamfer_blocks(V), (unsigned)n), block, 0, st, a);
+	return check_hip(hipGetLastError(), "chamfer_grid launch");
 }
 
 #ifdef DR_WAVE_TRACE

@@ -540,7 +540,8 @@ class ArapEnergyFunc(torch.autograd.Function):
 class ChamferFunc(torch.autograd.Function):
     """(vertices [n,V,3]; term: a :class:`deodr_amd.chamfer.PointCloudTerm`) -> (loss [n], terms [n,2]) of the closest-point energy
     (include/deodr_hip_chamfer.h); the loss is differentiable (its adjoint is the ``vertices_b`` the same call produced, exact wherever every nearest
-    neighbour is unique), the terms are not: they are marked so, and torch refuses a gradient asked of them ("does not require grad")"""
+    neighbour is unique), the terms are not: they are marked so, and torch refuses a gradient asked of them ("does not require grad").  The term
+    chooses the search: with ``search="grid"`` the call is ``deodr_hip_chamfer_grid`` (include/deodr_hip_chamfer_grid.h), the same op otherwise"""
 
     @staticmethod
     def forward(ctx, vertices, term):

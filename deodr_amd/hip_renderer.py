@@ -43,8 +43,9 @@ _COMPANIONS = (
     (_abi.ARAP_HEADER, "arap", "arap-energy"),  # as-rigid-as-possible energy
     (_abi.CHAMFER_HEADER, "chamfer", "chamfer-term"),  # closest-point (Chamfer) data term
     (_abi.SURFACE_HEADER, "surface", "surface-distance"),  # point-to-surface distance
+    (_abi.CHAMFER_GRID_HEADER, "chamfer_grid", "chamfer-grid"),  # closest-point term over a uniform grid, stable sort by key
 )
-TEXTURE_ABI_VERSION, SUBDIV_ABI_VERSION, RETAINED_ABI_VERSION, BASIS_ABI_VERSION, CAMERA_ABI_VERSION, LIGHTING_ABI_VERSION, SKINNING_ABI_VERSION, PYRAMID_ABI_VERSION, SSIM_ABI_VERSION, SOLVE_ABI_VERSION, ARAP_ABI_VERSION, CHAMFER_ABI_VERSION, SURFACE_ABI_VERSION = (
+TEXTURE_ABI_VERSION, SUBDIV_ABI_VERSION, RETAINED_ABI_VERSION, BASIS_ABI_VERSION, CAMERA_ABI_VERSION, LIGHTING_ABI_VERSION, SKINNING_ABI_VERSION, PYRAMID_ABI_VERSION, SSIM_ABI_VERSION, SOLVE_ABI_VERSION, ARAP_ABI_VERSION, CHAMFER_ABI_VERSION, SURFACE_ABI_VERSION, CHAMFER_GRID_ABI_VERSION = (
     h.defines[f"DEODR_HIP_{key.upper()}_ABI_VERSION"] for h, key, _ in _COMPANIONS
 )
 # words of the 64-byte status block at the start of the workspace
@@ -1624,6 +1625,129 @@ def chamfer(vertices, points, params, point_weights=None, vertex_weights=None, d
                                       f"{what}: pass scratch= (chamfer_scratch) when capturing a graph: none of this size exists for this stream yet")  # fmt: skip
     _launch(lib().deodr_hip_chamfer, dev, _ptr(vertices), V, _ptr(points), P, _ptr(point_weights), _ptr(vertex_weights), _ptr(params), n, directions,
             _ptr(terms), _ptr(loss), _ptr(vertices_b), _ptr(nearest_vertex), _ptr(nearest_point), _ptr(scratch), scratch.numel())  # fmt: skip
+    for t in (terms, loss, vertices_b, nearest_vertex, nearest_point):
+        if t is not None:
+            _touched(t)
+    return terms, loss, vertices_b, nearest_vertex, nearest_point
+
+
+# ---- stable sort by key, closest-point energy over a uniform grid (include/deodr_hip_chamfer_grid.h) ----------------------------------------
+
+_G = _abi.CHAMFER_GRID_HEADER.defines
+SORT_DIGIT_BITS, SORT_BLOCK, SORT_ITEMS, SORT_MAX_ITEMS = (_G["DEODR_HIP_SORT_" + n] for n in ("DIGIT_BITS", "BLOCK", "ITEMS", "MAX_ITEMS"))
+CHAMFER_GRID_NONE, CHAMFER_GRID_RINGS, CHAMFER_GRID_CELL_LIMIT, CHAMFER_GRID_MAX_ITEMS, CHAMFER_GRID_MIN_TABLE_BITS, CHAMFER_GRID_MAX_TABLE_BITS = (
+    _G["DEODR_HIP_CHAMFER_GRID_" + n] for n in ("NONE", "RINGS", "CELL_LIMIT", "MAX_ITEMS", "MIN_TABLE_BITS", "MAX_TABLE_BITS")
+)
+
+
+def sort_keys_launches(N, n, bits):
+    """``deodr_hip_sort_keys_launches``: three per pass of ``SORT_DIGIT_BITS`` bits (0 for arguments the call refuses)"""
+    return int(lib().deodr_hip_sort_keys_launches(int(N), int(n), int(bits)))
+
+
+def sort_keys_scratch(N, n, bits, device):
+    """the scratch of :func:`sort_keys` for n rows of N keys (it need not be zeroed)"""
+    need = int(lib().deodr_hip_sort_keys_scratch_bytes(int(N), int(n), int(bits)))
+    if need == 0:
+        raise ValueError(f"sort_keys_scratch: N = {N}, n = {n}, bits = {bits} is outside the limits of include/deodr_hip_chamfer_grid.h")
+    with torch.cuda.device(device):
+        return torch.empty(need, dtype=torch.uint8, device=device)
+
+
+def sort_keys(keys, bits=32, sorted_keys=None, order=None, scratch=None, want_sorted=True):
+    """``deodr_hip_sort_keys``: ``keys`` [n,N] (int32 or uint32 tensors holding uint32 bit patterns) -> (sorted_keys [n,N] | None, order [n,N] int32):
+    per row the stable permutation that sorts the low ``bits`` bits of the keys, and ``keys[order]``.  Deterministic; asynchronous on the current
+    stream; nothing is read back.  ``scratch``: a :func:`sort_keys_scratch` of the caller's; None: one per device and stream."""
+    what = "sort_keys"
+    _rocm_tensor(what, "keys", keys)
+    if keys.dim() != 2 or keys.shape[0] < 1 or keys.shape[1] < 1:
+        raise ValueError(f"{what}: keys must have shape [n >= 1, N >= 1], not {list(keys.shape)}")
+    n, N, bits = int(keys.shape[0]), int(keys.shape[1]), int(bits)
+    if not 1 <= bits <= 32:
+        raise ValueError(f"{what}: bits must be in 1 .. 32, not {bits}")
+    rows = [("keys", keys, _INDICES, None)]
+    rows += [row for row in (("sorted_keys", sorted_keys, _INDICES, (n, N)), ("order", order, _INDICES, (n, N)), ("scratch", scratch, (torch.uint8,), (None,)))
+             if row[1] is not None]  # fmt: skip
+    _check_tensors(what, "keys", keys.device, rows)
+    dev = keys.device
+    need = int(lib().deodr_hip_sort_keys_scratch_bytes(N, n, bits))
+    if need == 0:
+        raise ValueError(f"{what}: N = {N}, n = {n} is outside the limits of include/deodr_hip_chamfer_grid.h (N <= {SORT_MAX_ITEMS}, n <= 65535)")
+    with torch.cuda.device(dev):
+        if want_sorted and sorted_keys is None:
+            sorted_keys = torch.empty_like(keys)
+        order = torch.empty((n, N), dtype=torch.int32, device=dev) if order is None else order
+        if scratch is None:
+            scratch = _cached_scratch("sort_keys", dev, need, lambda: sort_keys_scratch(N, n, bits, dev),
+                                      f"{what}: pass scratch= (sort_keys_scratch) when capturing a graph: none of this size exists for this stream yet")  # fmt: skip
+    _launch(lib().deodr_hip_sort_keys, dev, _ptr(keys), N, n, bits, _ptr(sorted_keys), _ptr(order), _ptr(scratch), scratch.numel())
+    for t in (sorted_keys, order):
+        if t is not None:
+            _touched(t)
+    return sorted_keys, order
+
+
+def chamfer_grid_table_bits(references):
+    """``deodr_hip_chamfer_grid_table_bits``: log2 of the buckets of the hash table of a grid over ``references`` references (0: outside the limits)"""
+    return int(lib().deodr_hip_chamfer_grid_table_bits(int(references)))
+
+
+def chamfer_grid_launches(V, P, n, directions=3):
+    """``deodr_hip_chamfer_grid_launches``: the kernel launches of a :func:`chamfer_grid` call (0 for arguments the call refuses)"""
+    return int(lib().deodr_hip_chamfer_grid_launches(int(V), int(P), int(n), int(directions)))
+
+
+def chamfer_grid_scratch(V, P, n, device):
+    """the scratch of :func:`chamfer_grid` for n poses of V vertices against P points (one per stream in use; it need not be zeroed)"""
+    need = int(lib().deodr_hip_chamfer_grid_scratch_bytes(int(V), int(P), int(n)))
+    if need == 0:
+        raise ValueError(f"chamfer_grid_scratch: V = {V}, P = {P}, n = {n} is outside the limits of include/deodr_hip_chamfer_grid.h")
+    with torch.cuda.device(device):
+        return torch.empty(need, dtype=torch.uint8, device=device)
+
+
+def chamfer_grid(vertices, points, params, cell_size, point_weights=None, vertex_weights=None, directions=3, terms=None, loss=None, vertices_b=None,
+                 nearest_vertex=None, nearest_point=None, scratch=None, want_nearest=False):  # fmt: skip
+    """``deodr_hip_chamfer_grid``: :func:`chamfer` with the nearest neighbours found over a uniform grid of cells of size ``max(cell_size,
+    max_distance / CHAMFER_GRID_RINGS)`` -- the same arguments and results, the same indices; a query with no neighbour within ``max_distance``
+    (``params[2]``, which must be FINITE: trusted here, :mod:`deodr_amd.chamfer` checks its own) reports ``CHAMFER_GRID_NONE``.  No cap on V * P.
+    ``scratch``: a :func:`chamfer_grid_scratch` of the caller's; None: one per device and stream."""
+    what = "chamfer_grid"
+    _rocm_tensor(what, "vertices", vertices)
+    if vertices.dim() != 3 or vertices.shape[0] < 1 or vertices.shape[1] < 1 or vertices.shape[2] != 3:
+        raise ValueError(f"{what}: vertices must have shape [n >= 1, V >= 1, 3], not {list(vertices.shape)}")
+    n, V = int(vertices.shape[0]), int(vertices.shape[1])
+    if not torch.is_tensor(points) or points.dim() != 3 or int(points.shape[0]) != n or points.shape[1] < 1 or points.shape[2] != 3:
+        raise ValueError(f"{what}: points must have shape [{n}, P >= 1, 3], not {list(getattr(points, 'shape', ()))}")
+    P, directions, cell_size = int(points.shape[1]), int(directions), float(cell_size)
+    if not 1 <= directions <= 3:
+        raise ValueError(f"{what}: directions must be in 1 .. 3, not {directions}")
+    if not (cell_size > 0 and cell_size < float("inf")):
+        raise ValueError(f"{what}: cell_size must be finite and > 0, not {cell_size}")
+    rows = [("vertices", vertices, _F64_ONLY, None), ("points", points, _F64_ONLY, (n, P, 3)), ("params", params, _F64_ONLY, (3,))]
+    optional = (("point_weights", point_weights, _F64_ONLY, (n, P)), ("vertex_weights", vertex_weights, _F64_ONLY, (V,)),
+                ("terms", terms, _F64_ONLY, (n, 2)), ("loss", loss, _F64_ONLY, (n,)), ("vertices_b", vertices_b, _F64_ONLY, (n, V, 3)),
+                ("nearest_vertex", nearest_vertex, _INDICES, (n, P)), ("nearest_point", nearest_point, _INDICES, (n, V)),
+                ("scratch", scratch, (torch.uint8,), (None,)))  # fmt: skip
+    rows += [row for row in optional if row[1] is not None]
+    _check_tensors(what, "vertices", vertices.device, rows)
+    dev = vertices.device
+    need = int(lib().deodr_hip_chamfer_grid_scratch_bytes(V, P, n))
+    if need == 0:
+        raise ValueError(f"{what}: V = {V}, P = {P}, n = {n} is outside the limits of include/deodr_hip_chamfer_grid.h (V, P <= {CHAMFER_GRID_MAX_ITEMS}, n <= 65535)")
+    with torch.cuda.device(dev):
+        terms = torch.empty((n, 2), dtype=torch.float64, device=dev) if terms is None else terms
+        loss = torch.empty(n, dtype=torch.float64, device=dev) if loss is None else loss
+        vertices_b = torch.empty_like(vertices) if vertices_b is None else vertices_b
+        if want_nearest and nearest_vertex is None and directions & CHAMFER_POINTS_TO_MESH:
+            nearest_vertex = torch.empty((n, P), dtype=torch.int32, device=dev)
+        if want_nearest and nearest_point is None and directions & CHAMFER_MESH_TO_POINTS:
+            nearest_point = torch.empty((n, V), dtype=torch.int32, device=dev)
+        if scratch is None:
+            scratch = _cached_scratch("chamfer_grid", dev, need, lambda: chamfer_grid_scratch(V, P, n, dev),
+                                      f"{what}: pass scratch= (chamfer_grid_scratch) when capturing a graph: none of this size exists for this stream yet")  # fmt: skip
+    _launch(lib().deodr_hip_chamfer_grid, dev, _ptr(vertices), V, _ptr(points), P, _ptr(point_weights), _ptr(vertex_weights), _ptr(params), cell_size, n,
+            directions, _ptr(terms), _ptr(loss), _ptr(vertices_b), _ptr(nearest_vertex), _ptr(nearest_point), _ptr(scratch), scratch.numel())  # fmt: skip
     for t in (terms, loss, vertices_b, nearest_vertex, nearest_point):
         if t is not None:
             _touched(t)

@@ -756,6 +756,10 @@ class MeshPointCloudFitter(_PoseFitter):
     either way.  The step factors are the ones below for both metrics: a point's pull is spread over the three corners of its face with weights
     that sum to 1, so the gradients have the scale they have against the vertices (examples/point_surface_hand_fitting.py runs with them).
 
+    ``search``: "brute" (the default) or "grid", ``cell_size``: the term's (``PointCloudTerm(search="grid")``, include/deodr_hip_chamfer_grid.h):
+    the same neighbours found over a uniform grid, for clouds of 10^5 points and more; it needs a finite ``max_distance``, composes with every
+    keyword the brute search composes with, and is refused together with ``metric="surface"``.
+
     The step factors are this fitter's own, chosen on examples/point_cloud_hand_fitting.py with ``normalise=True`` (both terms are then mean squared
     distances, so the translation gradient is of the order of the offset whatever V and P are, and a vertex gradient of the order of offset / V):
     the largest powers of ten (times 1, 2 or 5) at which the hand's 60 iterations against 400 of its own posed vertices lower the energy
@@ -772,10 +776,16 @@ class MeshPointCloudFitter(_PoseFitter):
     def __init__(self, vertices, faces, euler_init, translation_init, cregu=0.002, inertia=0.9, damping=0.05, device="cuda", n_poses=1,
                  directions="both", max_distance=float("inf"), mix=(1.0, 1.0), normalise=True, subdivisions=0, shape_basis=None, coefficient_regu=0.0,
                  sigmas=None, skin=None, joint_quaternions_init=None, joint_regu=0.0, smoothing=0.0, smoothing_iterations=None, rigidity="laplacian",
-                 arap_weights="uniform", metric="vertex"):  # fmt: skip
+                 arap_weights="uniform", metric="vertex", search="brute", cell_size=None):  # fmt: skip
         if metric not in ("vertex", "surface"):
             raise ValueError(f'metric must be "vertex" or "surface", not {metric!r}')
-        self.metric = metric
+        if search not in ("brute", "grid"):
+            raise ValueError(f'search must be "brute" or "grid", not {search!r}')
+        if search == "grid" and metric == "surface":
+            raise ValueError('search="grid" finds nearest VERTICES: it does not go with metric="surface" (a grid over the triangles does not exist yet)')
+        if cell_size is not None and search != "grid":
+            raise ValueError('cell_size belongs to search="grid"')
+        self.metric, self.search = metric, search
         super().__init__(vertices, faces, euler_init, translation_init, cregu, inertia, damping, device, n_poses=n_poses, subdivisions=subdivisions,
                          shape_basis=shape_basis, coefficient_regu=coefficient_regu, sigmas=sigmas, skin=skin,
                          joint_quaternions_init=joint_quaternions_init, joint_regu=joint_regu, smoothing=smoothing,
@@ -783,6 +793,8 @@ class MeshPointCloudFitter(_PoseFitter):
         self.n_poses = int(n_poses)
         self.step_factor_vertices = type(self).step_factor_vertices * self.control_mesh.nb_vertices
         self._term_keywords = dict(directions=directions, max_distance=max_distance, mix=mix, normalise=normalise)
+        if search == "grid":  # (its own refusals -- an infinite max_distance, a bad cell_size -- come from the term, in set_point_clouds)
+            self._term_keywords.update(search=search, cell_size=cell_size)
         self.term = None
 
     def set_point_clouds(self, points, weights=None, vertex_weights=None):
