@@ -43,13 +43,24 @@ def _nearest(queries, refs, chunk_bytes):
     return torch.cat(best, dim=1), torch.cat(arg, dim=1)
 
 
+def _mesh_to_points(v, p, vertex_weights, mix1, tau2, terms, g, chunk_bytes):
+    """mesh -> points of :func:`chamfer_torch` and :func:`deodr_amd.surface.surface_distance_torch`: term_1 -> ``terms[:, 1]``, its gradient added
+    to ``g``; -> nearest_point [n,V]"""
+    u = torch.ones(int(v.shape[1]), dtype=v.dtype, device=v.device) if vertex_weights is None else vertex_weights.to(v.dtype)
+    d2, nearest_point = _nearest(v, p, chunk_bytes)
+    near = d2 <= tau2
+    terms[:, 1] = (u[None] * torch.where(near, d2, tau2)).sum(dim=1)
+    g += mix1 * ((2 * u[None] * near)[..., None] * (v - torch.gather(p, 1, nearest_point[..., None].expand(-1, -1, 3))))
+    return nearest_point
+
+
 def chamfer_torch(vertices, points, params, point_weights=None, vertex_weights=None, directions=3, chunk_bytes=CHUNK_BYTES):
     """the operation of ``include/deodr_hip_chamfer.h`` as torch ops, in the dtype of ``vertices`` [n,V,3] -> (terms [n,2], loss [n], vertices_b
     [n,V,3], nearest_vertex [n,P] | None, nearest_point [n,V] | None, int64).  ``params`` [3] = (mix_0, mix_1, max_distance), a tensor; no more
     than about ``chunk_bytes`` of distances exist at once.  No autograd: see :class:`deodr_amd.fronthalf.ChamferFunc`."""
     with torch.no_grad():
         v, p = vertices, points.to(vertices.dtype)
-        n, V, P = int(v.shape[0]), int(v.shape[1]), int(p.shape[1])
+        n, P = int(v.shape[0]), int(p.shape[1])
         params = params.to(v.dtype)
         mix0, mix1, tau2 = params[0], params[1], params[2] * params[2]
         terms, g = torch.zeros((n, 2), dtype=v.dtype, device=v.device), torch.zeros_like(v)
@@ -62,11 +73,7 @@ def chamfer_torch(vertices, points, params, point_weights=None, vertex_weights=N
             pull = (2 * w * near)[..., None] * (torch.gather(v, 1, nearest_vertex[..., None].expand(-1, -1, 3)) - p)
             g += mix0 * torch.zeros_like(v).scatter_add_(1, nearest_vertex[..., None].expand(-1, -1, 3), pull)
         if directions & 2:
-            u = torch.ones(V, dtype=v.dtype, device=v.device) if vertex_weights is None else vertex_weights.to(v.dtype)
-            d2, nearest_point = _nearest(v, p, chunk_bytes)
-            near = d2 <= tau2
-            terms[:, 1] = (u[None] * torch.where(near, d2, tau2)).sum(dim=1)
-            g += mix1 * ((2 * u[None] * near)[..., None] * (v - torch.gather(p, 1, nearest_point[..., None].expand(-1, -1, 3))))
+            nearest_point = _mesh_to_points(v, p, vertex_weights, mix1, tau2, terms, g, chunk_bytes)
         loss = (mix0 * terms[:, 0] if directions & 1 else 0) + (mix1 * terms[:, 1] if directions & 2 else 0)
         return terms, loss, g, nearest_vertex, nearest_point
 
@@ -200,6 +207,24 @@ class PointCloudTerm:
             raise ValueError(f"PointCloudTerm: vertices must be [V, 3] or [{self.n}, V, 3] (one pose per cloud), not {list(vertices.shape)}")
         return vertices
 
+    def _torch(self, v, u, want_nearest):
+        """:meth:`evaluate_no_grad` on tensors the kernels do not take"""
+        to = lambda t: None if t is None else t.to(v.device)
+        points, params = to(self.points), to(self.params)
+        out = chamfer_torch(v, points, params, to(self.point_weights), to(u), self.directions)
+        if not want_nearest:
+            return out[:3] + (None, None)
+        if self.search == "grid":  # the same values; the correspondences beyond max_distance are none
+            p = points.to(v.dtype)
+            out = out[:3] + (None if out[3] is None else mask_beyond(p, v, out[3], params), None if out[4] is None else mask_beyond(v, p, out[4], params))
+        return out
+
+    def _kernel(self, hr, V):
+        """-> (the function that makes the scratch, its dimensions, the operator, its arguments between the vertices and the weights)"""
+        if self.search == "grid":
+            return hr.chamfer_grid_scratch, (V, self.nb_points, self.n), hr.chamfer_grid, (self.points, self.params, self.cell_size)
+        return hr.chamfer_scratch, (V, self.nb_points, self.n), hr.chamfer, (self.points, self.params)
+
     def evaluate_no_grad(self, vertices, want_nearest=False):
         """(terms [n,2], loss [n], vertices_b [n,V,3], nearest_vertex [n,P] | None, nearest_point [n,V] | None) without autograd:
         ``deodr_hip_chamfer`` on float64 ROCm tensors, :func:`chamfer_torch` elsewhere (the indices int64 either way)"""
@@ -210,28 +235,16 @@ class PointCloudTerm:
         if grid and not self.params.is_cuda and not math.isfinite(float(self.params[2])):
             raise ValueError('PointCloudTerm: search="grid" needs a finite max_distance, params[2] is not')
         if not self.uses_kernel(v):
-            to = lambda t: None if t is None else t.to(v.device)
-            points, params = to(self.points), to(self.params)
-            out = chamfer_torch(v, points, params, to(self.point_weights), to(u), self.directions)
-            if not want_nearest:
-                return out[:3] + (None, None)
-            if grid:  # the same values; the correspondences beyond max_distance are none
-                p = points.to(v.dtype)
-                out = out[:3] + (None if out[3] is None else mask_beyond(p, v, out[3], params), None if out[4] is None else mask_beyond(v, p, out[4], params))
-            return out
+            return self._torch(v, u, want_nearest)
         from . import hip_renderer as hr
 
-        if grid:
-            if ("grid", self.n, V) not in self._scratch:
-                self._scratch[("grid", self.n, V)] = hr.chamfer_grid_scratch(V, self.nb_points, self.n, v.device)
-            terms, loss, g, nv, npt = hr.chamfer_grid(v, self.points, self.params, self.cell_size, self.point_weights, u, self.directions,
-                                                      scratch=self._scratch[("grid", self.n, V)], want_nearest=want_nearest)  # fmt: skip
-            return terms, loss, g, (None if nv is None else nv.long()), (None if npt is None else npt.long())  # (NONE, all bits set, is -1)
-        if (self.n, V) not in self._scratch:
-            self._scratch[(self.n, V)] = hr.chamfer_scratch(V, self.nb_points, self.n, v.device)
-        terms, loss, g, nv, npt = hr.chamfer(v, self.points, self.params, self.point_weights, u, self.directions, scratch=self._scratch[(self.n, V)],
-                                             want_nearest=want_nearest)  # fmt: skip
-        return terms, loss, g, (None if nv is None else nv.long()), (None if npt is None else npt.long())  # (V, P < 2^31: the bit patterns are the values)
+        key = ("grid", self.n, V) if grid else (self.n, V)
+        make_scratch, dims, operator, args = self._kernel(hr, V)
+        if key not in self._scratch:
+            self._scratch[key] = make_scratch(*dims, v.device)
+        out = operator(v, *args, self.point_weights, u, self.directions, scratch=self._scratch[key], want_nearest=want_nearest)
+        # the indices: below 2^31, the bit patterns are the values; NONE of the grid, all bits set, is -1
+        return tuple(t.long() if t is not None and t.dtype == torch.int32 else t for t in out)
 
     def evaluate(self, vertices):
         """-> (loss [n], terms [n,2]) of ``vertices`` [n,V,3] (or [V,3]: the same mesh against every cloud).  The loss is differentiable in the

@@ -1,6 +1,6 @@
 // The closest-point (Chamfer) energy with the nearest neighbours found over a uniform grid of hashed cells (include/deodr_hip_chamfer_grid.h has
-// the operation and the contract, DESIGN.md 4o the exactness argument).  On the machinery of dr_chamfer.h -- its combine steps, with one segment --
-// and of dr_sort.h:
+// the operation and the contract, DESIGN.md 4o the exactness argument).  On the machinery of dr_chamfer.h -- its ticket clear and its combine
+// steps, with one segment -- and of dr_sort.h:
 //
 // chamfer_grid_keys_kernel    a thread per reference: cell = clamp(floor(x / h)) per axis -> bucket = hash(cell) & (T - 1) -> keys; the same
 //                             threads clear the bucket table (start = end = 0: empty).  The first one of a call clears the arrival tickets.
@@ -22,7 +22,8 @@
 // No floating-point atomics, no integer atomics but the tickets of grid_sum.  Scratch after its 64 counter bytes (unused), doubles first:
 // records_v [n][V][4], records_p [n][P][4], pd2 [n][P], vd2 [n][V], vg [n][V][3], partials [2][n][CHAMFER_MAX_BLOCKS]; then 4-byte words:
 // table_v [n][Tv][2], table_p [n][Tp][2] (read as pairs: 8-byte aligned), pidx [n][P], vidx [n][V], assign [n][P], keys / sorted keys / order of
-// the vertices [3][n][V] and of the points [3][n][P], the sorted assignment and its order [2][n][P], tickets [2][n]; then the scratch of the sorts.
+// the vertices [3][n][V] and of the points [3][n][P], the sorted assignment and its order [2][n][P], tickets [2][n]; then the scratch of the sorts
+// (chamfer_grid_carve).
 #pragma once
 
 namespace
@@ -74,6 +75,38 @@ struct ChamferGridArgs
 	int V, P, n, clear_tickets;
 };
 
+// What a call launches with: the grids' kernels take g, the combine steps of dr_chamfer.h a (one segment per search), the sorts sort_words
+struct ChamferGridCall
+{
+	ChamferGridArgs g;
+	ChamferArgs a;
+	uint32_t *sort_words;
+};
+
+// The scratch layout of the overview, stated once: the dimensions (checked) of a call -> g and a, and the bytes of its scratch; with a base, its
+// arrays -> g, a (the ones both read: the same) and sort_words.
+inline size_t chamfer_grid_carve(ChamferGridCall &call, int V, int P, int n, void *base)
+{
+	ChamferGridArgs &g = call.g;
+	ChamferArgs &a = call.a;
+	g.V = a.V = V, g.P = a.P = P, g.n = a.n = n, a.Sp = a.Sv = 1;
+	g.set[0].R = V, g.set[0].table_bits = chamfer_grid_table_bits(V), g.set[1].R = P, g.set[1].table_bits = chamfer_grid_table_bits(P);
+	const size_t N = (size_t)n, nv = N * (size_t)V, np = N * (size_t)P;
+	dr::host::ScratchCarver c = {(char *)base};
+	g.set[0].records = c.take<double>(4 * nv), g.set[1].records = c.take<double>(4 * np);
+	a.pd2 = g.pd2 = c.take<double>(np), a.vd2 = g.vd2 = c.take<double>(nv), a.vg = g.vg = c.take<double>(3 * nv);
+	a.partials = c.take<double>(2 * N * (size_t)CHAMFER_MAX_BLOCKS);
+	for (ChamferGridSet &s : g.set)
+		s.table = c.take<uint32_t>(2 * N * ((size_t)1 << s.table_bits)); // (pairs: 8-byte aligned)
+	a.pidx = g.pidx = c.take<uint32_t>(np), a.vidx = g.vidx = c.take<uint32_t>(nv), a.assign = c.take<uint32_t>(np);
+	for (ChamferGridSet &s : g.set)
+		s.keys = c.take<uint32_t>(N * (size_t)s.R), s.sorted_keys = c.take<uint32_t>(N * (size_t)s.R), s.order = c.take<uint32_t>(N * (size_t)s.R);
+	g.sorted_assign = c.take<uint32_t>(np), g.assign_order = c.take<uint32_t>(np);
+	a.tickets = g.tickets = c.take<unsigned>(2 * N);
+	call.sort_words = c.take<uint32_t>(sort_scratch_words(V > P ? V : P, n));
+	return c.used;
+}
+
 struct ChamferGridRecord
 {
 	double x, y, z;
@@ -103,8 +136,7 @@ __global__ __launch_bounds__(CHAMFER_BLOCK) void chamfer_grid_keys_kernel(Chamfe
 {
 	const ChamferGridSet &s = a.set[which];
 	const size_t pose = blockIdx.y, R = (size_t)s.R, T = (size_t)1 << s.table_bits;
-	if (a.clear_tickets && blockIdx.x == 0 && threadIdx.x == 0)
-		a.tickets[pose] = 0, a.tickets[(size_t)a.n + pose] = 0; // (what the combine steps draw on: the launch boundaries order them)
+	chamfer_clear_tickets(a, pose, a.clear_tickets && blockIdx.x == 0);
 	const double h = chamfer_grid_h(a.params, a.cell_size);
 	const uint32_t mask = (uint32_t)(T - 1);
 	for (size_t i = (size_t)blockIdx.x * CHAMFER_BLOCK + threadIdx.x; i < R || i < T; i += (size_t)gridDim.x * CHAMFER_BLOCK)

@@ -1,6 +1,6 @@
 // deodr_amd/csrc/dr_host.h -- what every entry point of the C ABI asks of its arguments before it launches: the size of a dtype tag's elements,
 // whether two buffers overlap, the grid of a kernel that strides beyond a capped number of workgroups, and the layout of the scratch buffers
-// (counter words, then doubles).  Host only, plain C++17, nothing of HIP in it: dr_kernels.hip calls these from its entry points,
+// (counter words, then doubles; ScratchCarver hands out the arrays of an operator in order).  Host only, plain C++17, nothing of HIP in it: dr_kernels.hip calls these from its entry points,
 // tests/sim/host_sim.cpp compiles the same header for the CPU and tests/test_host_helpers.py pins the edge cases.
 #pragma once
 
@@ -23,8 +23,8 @@ inline bool ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t 
 	return x <= y ? y - x < a_bytes : x - y < b_bytes;
 }
 
-// The same for entry points with many arrays: does any of `outputs` share a byte with any of `inputs`; is any of `pointers` (NULL: not given) not
-// a multiple of `alignment` (a power of two).
+// The same for entry points with many arrays: does any of `outputs` share a byte with any of `inputs`; do any two of `ranges` share one; is any
+// of `pointers` (NULL: not given) not a multiple of `alignment` (a power of two).
 struct Range
 {
 	const void *p;
@@ -38,6 +38,19 @@ inline bool any_overlap(const Range (&outputs)[NO], const Range (&inputs)[NI])
 			if (ranges_overlap(o.p, o.bytes, i.p, i.bytes))
 				return true;
 	return false;
+}
+inline bool any_overlap(const Range *ranges, size_t count)
+{
+	for (size_t i = 0; i < count; i++)
+		for (size_t j = i + 1; j < count; j++)
+			if (ranges_overlap(ranges[i].p, ranges[i].bytes, ranges[j].p, ranges[j].bytes))
+				return true;
+	return false;
+}
+template <size_t N>
+inline bool any_overlap(const Range (&ranges)[N])
+{
+	return any_overlap(ranges, N);
 }
 template <size_t N>
 inline bool any_misaligned(const void *const (&pointers)[N], size_t alignment)
@@ -68,6 +81,23 @@ struct Scratch
 	bool holds(size_t need) const { return base && bytes >= need; }
 	unsigned *counter(int word) const { return (unsigned *)base + word; }
 	double *doubles() const { return (double *)((char *)base + SCRATCH_COUNTER_BYTES); }
+};
+
+// The arrays of an operator's scratch, handed out in the order they are asked for, from behind the counter bytes: the doubles first, then the 4-byte
+// words, so every array is aligned as its elements are.  One layout function per operator takes its arrays from a carver: without a base
+// (NULL: nothing is handed out) it states the size, with one the pointers -- the two cannot disagree.
+struct ScratchCarver
+{
+	char *base;
+	size_t used = SCRATCH_COUNTER_BYTES;
+	template <class T>
+	T *take(size_t count)
+	{
+		T *const p = base ? (T *)(base + used) : nullptr;
+		used += sizeof(T) * count;
+		return p;
+	}
+	size_t whole_doubles() const { return (used + sizeof(double) - 1) / sizeof(double) * sizeof(double); } // (an odd number of words: one more)
 };
 
 } // namespace dr::host

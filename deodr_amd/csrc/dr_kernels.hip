@@ -1649,7 +1649,7 @@ int deodr_hip_sh_shade(const double *posed, const uint32_t *faces, const uint32_
 	const Range outputs[] = {{luminosity, nv}, {colors, nv * C}};
 	const Range inputs[] = {{posed, 3 * nv}, {faces, 12}, {vf_offsets, 4 * ((size_t)V + 1)}, {vf_corners, 12}, {sh, 72 * (size_t)S},
 							{albedo, 8 * (size_t)C * (a.per_vertex ? (size_t)V : 1)}};
-	if (any_overlap(outputs, inputs) || ranges_overlap(luminosity, nv, colors, nv * C))
+	if (any_overlap(outputs, inputs) || any_overlap(outputs))
 		return fail(what, "an output must not overlap an input or the other output");
 	hipLaunchKernelGGL(sh_shade_kernel, dim3(fh_blocks((long long)V * GATHER_LANES), n), dim3(FH_BLOCK), 0, (hipStream_t)stream, a, luminosity, colors);
 	return check_hip(hipGetLastError(), "sh_shade launch");
@@ -1680,10 +1680,7 @@ int deodr_hip_sh_shade_b(const double *posed, const uint32_t *faces, const uint3
 	const Range outputs[] = {{posed_b, 3 * nv}, {sh_b, 72 * (size_t)S}, {albedo_b, alb}, {scratch, scratch_bytes}};
 	const Range inputs[] = {{posed, 3 * nv}, {faces, 12}, {vf_offsets, 4 * ((size_t)V + 1)}, {vf_corners, 12}, {sh, 72 * (size_t)S}, {albedo, alb},
 							{luminosity_b, nv}, {colors_b, nv * C}};
-	const Range written[] = {{posed_b, 3 * nv}, {sh_b, 72 * (size_t)S}, {albedo_b, alb}};
-	const Range scratch_range[] = {{scratch, scratch_bytes}};
-	if (any_overlap(outputs, inputs) || any_overlap(written, scratch_range) || ranges_overlap(posed_b, 3 * nv, sh_b, 72 * (size_t)S) ||
-		ranges_overlap(posed_b, 3 * nv, albedo_b, alb) || ranges_overlap(sh_b, 72 * (size_t)S, albedo_b, alb))
+	if (any_overlap(outputs, inputs) || any_overlap(outputs))
 		return fail(what, "an output must not overlap an input, the scratch or another output");
 	hipStream_t st = (hipStream_t)stream;
 	const unsigned blocks = (unsigned)sh_blocks(V, n);
@@ -1743,7 +1740,7 @@ int deodr_hip_skin_apply(const double *vertices, const double *joints, const uin
 	const size_t v3 = 24 * (size_t)V, nj = (size_t)n * J, vk = (size_t)V * K;
 	const Range outputs[] = {{world, 8 * SKIN_WORLD * nj}, {posed, n * v3}};
 	const Range inputs[] = {{vertices, v3}, {joints, 24 * (size_t)J}, {parents, 4 * (size_t)J}, {quaternions, 32 * nj}, {indices, 4 * vk}, {weights, 8 * vk}};
-	if (any_overlap(outputs, inputs) || ranges_overlap(world, 8 * SKIN_WORLD * nj, posed, n * v3))
+	if (any_overlap(outputs, inputs) || any_overlap(outputs))
 		return fail(what, "an output must not overlap an input or the other output");
 	const SkinArgs a = {vertices, joints, quaternions, parents, indices, weights, V, J, K, n};
 	const hipStream_t st = (hipStream_t)stream;
@@ -1777,10 +1774,7 @@ int deodr_hip_skin_apply_b(const double *vertices, const double *joints, const u
 	const Range outputs[] = {{vertices_b, v3}, {quaternions_b, 32 * nj}, {joints_b, 24 * (size_t)J}, {scratch, scratch_bytes}};
 	const Range inputs[] = {{vertices, v3}, {joints, 24 * (size_t)J}, {parents, 4 * (size_t)J}, {quaternions, 32 * nj}, {indices, 4 * vk}, {weights, 8 * vk},
 							{world, 8 * SKIN_WORLD * nj}, {posed_b, n * v3}, {joint_offsets, 4 * ((size_t)J + 1)}, {joint_slots, 4 * (size_t)nnz}};
-	const Range written[] = {{vertices_b, v3}, {quaternions_b, 32 * nj}, {joints_b, 24 * (size_t)J}};
-	const Range scratch_range[] = {{scratch, scratch_bytes}};
-	if (any_overlap(outputs, inputs) || any_overlap(written, scratch_range) || ranges_overlap(vertices_b, v3, quaternions_b, 32 * nj) ||
-		ranges_overlap(vertices_b, v3, joints_b, 24 * (size_t)J) || ranges_overlap(quaternions_b, 32 * nj, joints_b, 24 * (size_t)J))
+	if (any_overlap(outputs, inputs) || any_overlap(outputs))
 		return fail(what, "an output must not overlap an input, the scratch or another output");
 	const SkinArgs a = {vertices, joints, quaternions, parents, indices, weights, V, J, K, n};
 	const hipStream_t st = (hipStream_t)stream;
@@ -1860,9 +1854,7 @@ int deodr_hip_pyramid_l2(const void *image, const void *obs, const void *weights
 	const size_t frame = (size_t)n * H * W * elem, lam = 8 * ((size_t)levels + 1);
 	const Range outputs[] = {{terms, lam}, {loss, 8}, {image_b, frame * C}, {scratch, scratch_bytes}};
 	const Range inputs[] = {{image, frame * C}, {obs, frame * C}, {weights, frame}, {level_weights, lam}};
-	if (any_overlap(outputs, inputs) || ranges_overlap(terms, lam, loss, 8) || ranges_overlap(terms, lam, image_b, frame * C) ||
-		ranges_overlap(loss, 8, image_b, frame * C) || ranges_overlap(scratch, scratch_bytes, terms, lam) || ranges_overlap(scratch, scratch_bytes, loss, 8) ||
-		ranges_overlap(scratch, scratch_bytes, image_b, frame * C))
+	if (any_overlap(outputs, inputs) || any_overlap(outputs))
 		return fail(what, "an output must not overlap an input, the scratch or another output");
 	const PyramidLayout l = pyramid_layout(n, H, W, C, levels);
 	double *const d = sc.doubles();
@@ -1932,9 +1924,7 @@ int deodr_hip_ssim_l2(const void *image, const void *obs, const void *weights, i
 	const size_t frame = (size_t)n * H * W * elem;
 	const Range outputs[] = {{terms, 16}, {loss, 8}, {image_b, frame * C}, {scratch, scratch_bytes}};
 	const Range inputs[] = {{image, frame * C}, {obs, frame * C}, {weights, frame}, {mix, 16}};
-	if (any_overlap(outputs, inputs) || ranges_overlap(terms, 16, loss, 8) || ranges_overlap(terms, 16, image_b, frame * C) ||
-		ranges_overlap(loss, 8, image_b, frame * C) || ranges_overlap(scratch, scratch_bytes, terms, 16) || ranges_overlap(scratch, scratch_bytes, loss, 8) ||
-		ranges_overlap(scratch, scratch_bytes, image_b, frame * C))
+	if (any_overlap(outputs, inputs) || any_overlap(outputs))
 		return fail(what, "an output must not overlap an input, the scratch or another output");
 	double *const d = sc.doubles();
 	const int TY = (H + SSIM_TH - 1) / SSIM_TH, TX = (W + SSIM_TW - 1) / SSIM_TW;
@@ -2007,8 +1997,7 @@ int deodr_hip_spd_solve(const uint32_t *offsets, const uint32_t *cols, const dou
 		return fail(what, "x must not overlap b");
 	const Range outputs[] = {{x, nd}, {residual, 8 * (size_t)D}, {scratch, scratch_bytes}};
 	const Range inputs[] = {{offsets, 4 * ((size_t)n + 1)}, {cols, 4 * (size_t)nnz}, {vals, 8 * (size_t)nnz}, {b, nd}};
-	if (any_overlap(outputs, inputs) || ranges_overlap(x, nd, residual, 8 * (size_t)D) || ranges_overlap(scratch, scratch_bytes, x, nd) ||
-		ranges_overlap(scratch, scratch_bytes, residual, 8 * (size_t)D))
+	if (any_overlap(outputs, inputs) || any_overlap(outputs))
 		return fail(what, "an output must not overlap an input, the scratch or another output");
 	double *const d = sc.doubles(), *const arrays = d + SOLVE_SCALARS + (size_t)SOLVE_BLOCKS * SOLVE_MAX_D;
 	const size_t cells = (size_t)n * (size_t)D;
@@ -2077,11 +2066,7 @@ int deodr_hip_arap_energy(const uint32_t *offsets, const uint32_t *cols, const d
 	const size_t cells = (size_t)n * (size_t)V;
 	const Range outputs[] = {{energy, 8 * (size_t)n}, {gradient, 24 * cells}, {rotations, 32 * cells}, {scratch, scratch_bytes}};
 	const Range inputs[] = {{offsets, 4 * ((size_t)V + 1)}, {cols, 4 * (size_t)nnz}, {weights, 8 * (size_t)nnz}, {vertices_ref, 24 * (size_t)V}, {vertices, 24 * cells}};
-	bool clash = any_overlap(outputs, inputs);
-	for (size_t i = 0; i < 4; i++)
-		for (size_t j = i + 1; j < 4; j++)
-			clash = clash || ranges_overlap(outputs[i].p, outputs[i].bytes, outputs[j].p, outputs[j].bytes);
-	if (clash)
+	if (any_overlap(outputs, inputs) || any_overlap(outputs))
 		return fail(what, "an output must not overlap an input, the scratch or another output");
 	double *const d = sc.doubles();
 	double *const partials = d + 5 * cells;
@@ -2100,22 +2085,46 @@ int deodr_hip_chamfer_abi_version(void) { return DEODR_HIP_CHAMFER_ABI_VERSION; 
 
 namespace
 {
+const char *chamfer_poses(int n) { return n <= 0 || n > CHAMFER_MAX_POSES ? "n must be in 1 .. 65535" : NULL; } // (of the three closest-point operators)
 const char *chamfer_dims(int V, int P, int n)
 { // -> NULL, or which limit of the header the arguments break
 	if (V <= 0)
 		return "V must be positive";
 	if (P <= 0)
 		return "P must be positive";
-	if (n <= 0 || n > CHAMFER_MAX_POSES)
-		return "n must be in 1 .. 65535";
+	if (const char *why = chamfer_poses(n))
+		return why;
 	if ((unsigned long long)V * (unsigned long long)P > DEODR_HIP_CHAMFER_MAX_PAIRS)
 		return "V * P is above DEODR_HIP_CHAMFER_MAX_PAIRS (the search is brute force)";
 	return NULL;
 }
 bool chamfer_directions(int directions) { return directions >= 1 && directions <= 3; }
+
+// What deodr_hip_chamfer, deodr_hip_surface_distance and deodr_hip_chamfer_grid check alike once their own NULL sentence and dims have passed, in
+// the order their messages are documented in: the directions, `own` (the operator's own refusal, NULL: none), `misaligned` (any of its arrays),
+// the scratch against `need`, `clash` (an output overlaps an input or another output).  -> 1 with the message set, or 0.
+int closest_point_refused(const char *what, int directions, const char *own, bool misaligned, void *scratch, size_t scratch_bytes, size_t need,
+						  const char *too_small, bool clash)
+{
+	if (!chamfer_directions(directions))
+		return fail(what, "directions must be in 1 .. 3");
+	if (own)
+		return fail(what, own);
+	if (misaligned)
+		return fail(what, "misaligned pointer");
+	if (!Scratch{scratch, scratch_bytes}.holds(need))
+		return fail(what, too_small);
+	if (clash)
+		return fail(what, "an output must not overlap an input, the scratch or another output");
+	return 0;
+}
 } // namespace
 
-size_t deodr_hip_chamfer_scratch_bytes(int V, int P, int n) { return chamfer_dims(V, P, n) ? 0 : scratch_need(chamfer_scratch_doubles(V, P, n)); }
+size_t deodr_hip_chamfer_scratch_bytes(int V, int P, int n)
+{
+	ChamferArgs a;
+	return chamfer_dims(V, P, n) ? 0 : chamfer_carve(a, V, P, n, NULL);
+}
 
 int deodr_hip_chamfer_segments(int queries, int references) { return chamfer_segments(queries, references); }
 
@@ -2133,35 +2142,22 @@ int deodr_hip_chamfer(const double *vertices, int V, const double *points, int P
 		return fail(what, "vertices, points, params, terms, loss, vertices_b or scratch == NULL");
 	if (const char *why = chamfer_dims(V, P, n))
 		return fail(what, why);
-	if (!chamfer_directions(directions))
-		return fail(what, "directions must be in 1 .. 3");
 	const void *const words[] = {nearest_vertex, nearest_point};
 	const void *const doubles[] = {vertices, points, point_weights, vertex_weights, params, terms, loss, vertices_b, scratch};
-	if (any_misaligned(words, 4) || any_misaligned(doubles, 8))
-		return fail(what, "misaligned pointer");
-	const Scratch sc = {scratch, scratch_bytes};
-	if (!sc.holds(deodr_hip_chamfer_scratch_bytes(V, P, n)))
-		return fail(what, "scratch too small (deodr_hip_chamfer_scratch_bytes)");
 	const size_t N = (size_t)n, nv = N * (size_t)V, np = N * (size_t)P;
 	const Range outputs[] = {{terms, 16 * N}, {loss, 8 * N}, {vertices_b, 24 * nv}, {nearest_vertex, 4 * np}, {nearest_point, 4 * nv}, {scratch, scratch_bytes}};
 	const Range inputs[] = {{vertices, 24 * nv}, {points, 24 * np}, {point_weights, 8 * np}, {vertex_weights, 8 * (size_t)V}, {params, 24}};
-	bool clash = any_overlap(outputs, inputs);
-	for (size_t i = 0; i < 6; i++)
-		for (size_t j = i + 1; j < 6; j++)
-			clash = clash || ranges_overlap(outputs[i].p, outputs[i].bytes, outputs[j].p, outputs[j].bytes);
-	if (clash)
-		return fail(what, "an output must not overlap an input, the scratch or another output");
-	const int Sp = chamfer_segments(P, V), Sv = chamfer_segments(V, P);
-	const size_t sp = (size_t)Sp * np, sv = (size_t)Sv * nv;
-	double *const pd2 = sc.doubles(), *const vd2 = pd2 + sp, *const vg = vd2 + sv, *const partials = vg + 3 * sv;
-	uint32_t *const pidx = (uint32_t *)(partials + 2 * N * (size_t)CHAMFER_MAX_BLOCKS), *const vidx = pidx + sp, *const assign = vidx + sv;
-	ChamferArgs a = {vertices, points, point_weights, vertex_weights, params, terms, loss, vertices_b, nearest_vertex, nearest_point, pd2, vd2, vg,
-					 partials, pidx, vidx, assign, (unsigned *)(assign + np), V, P, n, Sp, Sv, directions, 1};
+	ChamferArgs a = {vertices, points, point_weights, vertex_weights, params, terms, loss, vertices_b, nearest_vertex, nearest_point};
+	if (closest_point_refused(what, directions, NULL, any_misaligned(words, 4) || any_misaligned(doubles, 8), scratch, scratch_bytes, chamfer_carve(a, V, P, n, NULL),
+							  "scratch too small (deodr_hip_chamfer_scratch_bytes)", any_overlap(outputs, inputs) || any_overlap(outputs)))
+		return 1;
+	chamfer_carve(a, V, P, n, scratch);
+	a.directions = directions, a.clear_tickets = 1;
 	const hipStream_t st = (hipStream_t)stream;
-	const dim3 block(CHAMFER_BLOCK), walk_v(((unsigned)V - 1) / CHAMFER_BLOCK + 1, (unsigned)Sv, (unsigned)n);
+	const dim3 block(CHAMFER_BLOCK), walk_v(((unsigned)V - 1) / CHAMFER_BLOCK + 1, (unsigned)a.Sv, (unsigned)n);
 	if (directions & DEODR_HIP_CHAMFER_POINTS_TO_MESH)
 	{
-		hipLaunchKernelGGL((chamfer_walk_kernel<true, false>), dim3(((unsigned)P - 1) / CHAMFER_BLOCK + 1, (unsigned)Sp, (unsigned)n), block, 0, st, a, 1);
+		hipLaunchKernelGGL((chamfer_walk_kernel<true, false>), dim3(((unsigned)P - 1) / CHAMFER_BLOCK + 1, (unsigned)a.Sp, (unsigned)n), block, 0, st, a, 1);
 		a.clear_tickets = 0;
 		hipLaunchKernelGGL(chamfer_points_kernel, dim3(chamfer_blocks(P), (unsigned)n), block, 0, st, a);
 		if (directions & DEODR_HIP_CHAMFER_MESH_TO_POINTS)
@@ -2189,8 +2185,8 @@ const char *surface_dims(int V, int F, int P, int n)
 		return "F must be in 1 .. 715827882";
 	if (P <= 0)
 		return "P must be positive";
-	if (n <= 0 || n > CHAMFER_MAX_POSES)
-		return "n must be in 1 .. 65535";
+	if (const char *why = chamfer_poses(n))
+		return why;
 	if ((unsigned long long)F * (unsigned long long)P > DEODR_HIP_SURFACE_MAX_PAIRS)
 		return "F * P is above DEODR_HIP_SURFACE_MAX_PAIRS (the search is brute force)";
 	return NULL;
@@ -2205,7 +2201,8 @@ const char *surface_vertex_pairs(int V, int P, int directions)
 
 size_t deodr_hip_surface_distance_scratch_bytes(int V, int F, int P, int n)
 {
-	return surface_dims(V, F, P, n) ? 0 : scratch_need(surface_scratch_doubles(V, F, P, n));
+	SurfaceArgs a;
+	return surface_dims(V, F, P, n) ? 0 : surface_carve(a, V, F, P, n, NULL);
 }
 
 int deodr_hip_surface_distance_launches(int V, int F, int P, int n, int directions)
@@ -2225,50 +2222,33 @@ int deodr_hip_surface_distance(const double *vertices, int V, const int32_t *fac
 		return fail(what, "vertices, faces, corner_offsets, corners, points, params, terms, loss, vertices_b or scratch == NULL");
 	if (const char *why = surface_dims(V, F, P, n))
 		return fail(what, why);
-	if (!chamfer_directions(directions))
-		return fail(what, "directions must be in 1 .. 3");
-	if (const char *why = surface_vertex_pairs(V, P, directions))
-		return fail(what, why);
 	const void *const words[] = {faces, corner_offsets, corners, nearest_face, nearest_point};
 	const void *const doubles[] = {vertices, points, point_weights, vertex_weights, params, terms, loss, vertices_b, barycentric, scratch};
-	if (any_misaligned(words, 4) || any_misaligned(doubles, 8))
-		return fail(what, "misaligned pointer");
-	const Scratch sc = {scratch, scratch_bytes};
-	if (!sc.holds(deodr_hip_surface_distance_scratch_bytes(V, F, P, n)))
-		return fail(what, "scratch too small (deodr_hip_surface_distance_scratch_bytes)");
-	const size_t N = (size_t)n, nv = N * (size_t)V, np = N * (size_t)P, nf = N * (size_t)F;
+	const size_t N = (size_t)n, nv = N * (size_t)V, np = N * (size_t)P;
 	const Range outputs[] = {{terms, 16 * N}, {loss, 8 * N}, {vertices_b, 24 * nv}, {nearest_face, 4 * np}, {barycentric, 24 * np}, {nearest_point, 4 * nv}, {scratch, scratch_bytes}};
 	const Range inputs[] = {{vertices, 24 * nv}, {faces, 12 * (size_t)F}, {corner_offsets, 4 * ((size_t)V + 1)}, {corners, 12 * (size_t)F}, {points, 24 * np},
 							{point_weights, 8 * np}, {vertex_weights, 8 * (size_t)V}, {params, 24}};
-	bool clash = any_overlap(outputs, inputs);
-	for (size_t i = 0; i < 7; i++)
-		for (size_t j = i + 1; j < 7; j++)
-			clash = clash || ranges_overlap(outputs[i].p, outputs[i].bytes, outputs[j].p, outputs[j].bytes);
-	if (clash)
-		return fail(what, "an output must not overlap an input, the scratch or another output");
-	const int Sp = chamfer_segments(P, F), Sg = chamfer_segments(F, P), Sv = chamfer_segments(V, P);
-	const size_t sp = (size_t)Sp * np, sg = (size_t)Sg * nf, sv = (size_t)Sv * nv;
-	double *const rec = sc.doubles(), *const pd2 = rec + (size_t)SURFACE_REC * nf, *const pull = pd2 + sp, *const fg = pull + 6 * np, *const vd2 = fg + 9 * sg;
-	double *const partials = vd2 + sv;
-	uint32_t *const pidx = (uint32_t *)(partials + 2 * N * (size_t)CHAMFER_MAX_BLOCKS), *const vidx = pidx + sp, *const assign = vidx + sv;
-	unsigned *const tickets = (unsigned *)(assign + np);
-	const SurfaceArgs a = {vertices, faces, corner_offsets, corners, points, point_weights, vertex_weights, params, terms, loss, vertices_b, nearest_face,
-						   barycentric, nearest_point, rec, pd2, pull, fg, vd2, partials, pidx, vidx, assign, tickets, V, F, P, n, Sp, Sg, Sv, directions};
+	SurfaceArgs a = {vertices, faces, corner_offsets, corners, points, point_weights, vertex_weights, params, terms, loss, vertices_b, nearest_face, barycentric, nearest_point};
+	if (closest_point_refused(what, directions, surface_vertex_pairs(V, P, directions), any_misaligned(words, 4) || any_misaligned(doubles, 8), scratch, scratch_bytes,
+							  surface_carve(a, V, F, P, n, NULL), "scratch too small (deodr_hip_surface_distance_scratch_bytes)", any_overlap(outputs, inputs) || any_overlap(outputs)))
+		return 1;
+	surface_carve(a, V, F, P, n, scratch);
+	a.directions = directions;
 	const hipStream_t st = (hipStream_t)stream;
 	const dim3 block(CHAMFER_BLOCK);
 	if (directions & DEODR_HIP_CHAMFER_POINTS_TO_MESH)
 	{
 		hipLaunchKernelGGL(surface_prep_kernel, dim3(chamfer_blocks(F), (unsigned)n), block, 0, st, a);
-		hipLaunchKernelGGL(surface_search_kernel, dim3(((unsigned)P - 1) / CHAMFER_BLOCK + 1, (unsigned)Sp, (unsigned)n), block, 0, st, a);
+		hipLaunchKernelGGL(surface_search_kernel, dim3(((unsigned)P - 1) / CHAMFER_BLOCK + 1, (unsigned)a.Sp, (unsigned)n), block, 0, st, a);
 		hipLaunchKernelGGL(surface_points_kernel, dim3(chamfer_blocks(P), (unsigned)n), block, 0, st, a);
-		hipLaunchKernelGGL(surface_gather_kernel, dim3(((unsigned)F - 1) / CHAMFER_BLOCK + 1, (unsigned)Sg, (unsigned)n), block, 0, st, a);
+		hipLaunchKernelGGL(surface_gather_kernel, dim3(((unsigned)F - 1) / CHAMFER_BLOCK + 1, (unsigned)a.Sg, (unsigned)n), block, 0, st, a);
 	}
 	if (directions & DEODR_HIP_CHAMFER_MESH_TO_POINTS)
 	{ // the vertex-major search of the Chamfer operator itself, into this call's scratch; alone, it is the first launch and clears the tickets
 		ChamferArgs c = {};
-		c.vertices = vertices, c.points = points, c.vd2 = vd2, c.vidx = vidx, c.tickets = tickets;
-		c.V = V, c.P = P, c.n = n, c.Sv = Sv, c.directions = directions, c.clear_tickets = !(directions & DEODR_HIP_CHAMFER_POINTS_TO_MESH);
-		hipLaunchKernelGGL((chamfer_walk_kernel<true, false>), dim3(((unsigned)V - 1) / CHAMFER_BLOCK + 1, (unsigned)Sv, (unsigned)n), block, 0, st, c, 0);
+		c.vertices = vertices, c.points = points, c.vd2 = a.vd2, c.vidx = a.vidx, c.tickets = a.tickets;
+		c.V = V, c.P = P, c.n = n, c.Sv = a.Sv, c.directions = directions, c.clear_tickets = !(directions & DEODR_HIP_CHAMFER_POINTS_TO_MESH);
+		hipLaunchKernelGGL((chamfer_walk_kernel<true, false>), dim3(((unsigned)V - 1) / CHAMFER_BLOCK + 1, (unsigned)a.Sv, (unsigned)n), block, 0, st, c, 0);
 	}
 	hipLaunchKernelGGL(surface_vertices_kernel, dim3(chamfer_blocks(V), (unsigned)n), block, 0, st, a);
 	return check_hip(hipGetLastError(), "surface_distance launch");
@@ -2297,10 +2277,8 @@ int deodr_hip_sort_keys(const uint32_t *keys, int N, int n, int bits, uint32_t *
 		return fail(what, "scratch too small (deodr_hip_sort_keys_scratch_bytes)");
 	const size_t row_bytes = 4 * (size_t)n * (size_t)N;
 	const Range buffers[] = {{keys, row_bytes}, {sorted_keys, row_bytes}, {order, row_bytes}, {scratch, scratch_bytes}};
-	for (size_t i = 0; i < 4; i++)
-		for (size_t j = i + 1; j < 4; j++)
-			if (ranges_overlap(buffers[i].p, buffers[i].bytes, buffers[j].p, buffers[j].bytes))
-				return fail(what, "keys, sorted_keys, order and scratch must not overlap");
+	if (any_overlap(buffers))
+		return fail(what, "keys, sorted_keys, order and scratch must not overlap");
 	sort_launch(keys, N, n, bits, sorted_keys, order, (uint32_t *)scratch, (hipStream_t)stream);
 	return check_hip(hipGetLastError(), "sort_keys launch");
 }
@@ -2313,16 +2291,7 @@ const char *chamfer_grid_dims(int V, int P, int n)
 		return "V must be in 1 .. DEODR_HIP_CHAMFER_GRID_MAX_ITEMS";
 	if (P <= 0 || P > CG_MAX_ITEMS)
 		return "P must be in 1 .. DEODR_HIP_CHAMFER_GRID_MAX_ITEMS";
-	if (n <= 0 || n > CHAMFER_MAX_POSES)
-		return "n must be in 1 .. 65535";
-	return NULL;
-}
-// the scratch: doubles after the counter bytes, then 4-byte words, then the scratch of the sorts
-size_t chamfer_grid_doubles(int V, int P, int n) { return (size_t)n * (8 * (size_t)V + 5 * (size_t)P + 2 * (size_t)CHAMFER_MAX_BLOCKS); }
-size_t chamfer_grid_words(int V, int P, int n)
-{
-	const size_t Tv = (size_t)1 << chamfer_grid_table_bits(V), Tp = (size_t)1 << chamfer_grid_table_bits(P);
-	return (size_t)n * (7 * (size_t)P + 4 * (size_t)V + 2 * Tv + 2 * Tp + 2);
+	return chamfer_poses(n);
 }
 } // namespace
 
@@ -2330,9 +2299,8 @@ int deodr_hip_chamfer_grid_table_bits(int references) { return chamfer_grid_tabl
 
 size_t deodr_hip_chamfer_grid_scratch_bytes(int V, int P, int n)
 {
-	if (chamfer_grid_dims(V, P, n))
-		return 0;
-	return scratch_need(chamfer_grid_doubles(V, P, n)) + 4 * (chamfer_grid_words(V, P, n) + sort_scratch_words(V > P ? V : P, n));
+	ChamferGridCall c;
+	return chamfer_grid_dims(V, P, n) ? 0 : chamfer_grid_carve(c, V, P, n, NULL);
 }
 
 int deodr_hip_chamfer_grid_launches(int V, int P, int n, int directions)
@@ -2356,39 +2324,21 @@ int deodr_hip_chamfer_grid(const double *vertices, int V, const double *points, 
 		return fail(what, "vertices, points, params, terms, loss, vertices_b or scratch == NULL");
 	if (const char *why = chamfer_grid_dims(V, P, n))
 		return fail(what, why);
-	if (!chamfer_directions(directions))
-		return fail(what, "directions must be in 1 .. 3");
-	if (!(cell_size > 0) || !(cell_size < __builtin_inf()))
-		return fail(what, "cell_size must be finite and > 0");
 	const void *const words[] = {nearest_vertex, nearest_point};
 	const void *const doubles[] = {vertices, points, point_weights, vertex_weights, params, terms, loss, vertices_b, scratch};
-	if (any_misaligned(words, 4) || any_misaligned(doubles, 8))
-		return fail(what, "misaligned pointer");
-	const Scratch sc = {scratch, scratch_bytes};
-	if (!sc.holds(deodr_hip_chamfer_grid_scratch_bytes(V, P, n)))
-		return fail(what, "scratch too small (deodr_hip_chamfer_grid_scratch_bytes)");
 	const size_t N = (size_t)n, nv = N * (size_t)V, np = N * (size_t)P;
 	const Range outputs[] = {{terms, 16 * N}, {loss, 8 * N}, {vertices_b, 24 * nv}, {nearest_vertex, 4 * np}, {nearest_point, 4 * nv}, {scratch, scratch_bytes}};
 	const Range inputs[] = {{vertices, 24 * nv}, {points, 24 * np}, {point_weights, 8 * np}, {vertex_weights, 8 * (size_t)V}, {params, 24}};
-	bool clash = any_overlap(outputs, inputs);
-	for (size_t i = 0; i < 6; i++)
-		for (size_t j = i + 1; j < 6; j++)
-			clash = clash || ranges_overlap(outputs[i].p, outputs[i].bytes, outputs[j].p, outputs[j].bytes);
-	if (clash)
-		return fail(what, "an output must not overlap an input, the scratch or another output");
-	const int tv = chamfer_grid_table_bits(V), tp = chamfer_grid_table_bits(P);
-	const size_t Tv = (size_t)1 << tv, Tp = (size_t)1 << tp;
-	double *const records_v = sc.doubles(), *const records_p = records_v + 4 * nv, *const pd2 = records_p + 4 * np, *const vd2 = pd2 + np;
-	double *const vg = vd2 + nv, *const partials = vg + 3 * nv;
-	uint32_t *const table_v = (uint32_t *)(partials + 2 * N * (size_t)CHAMFER_MAX_BLOCKS), *const table_p = table_v + 2 * N * Tv; // (pairs: 8-byte aligned)
-	uint32_t *const pidx = table_p + 2 * N * Tp, *const vidx = pidx + np, *const assign = vidx + nv;
-	uint32_t *const keys_v = assign + np, *const keys_p = keys_v + 3 * nv, *const sorted_assign = keys_p + 3 * np, *const assign_order = sorted_assign + np;
-	uint32_t *const tickets = assign_order + np, *const sort_words = tickets + 2 * N;
-	ChamferGridArgs g = {{{vertices, records_v, keys_v, keys_v + nv, keys_v + 2 * nv, table_v, V, tv}, {points, records_p, keys_p, keys_p + np, keys_p + 2 * np, table_p, P, tp}},
-						 params, point_weights, pd2, vd2, vg, pidx, vidx, sorted_assign, assign_order, (unsigned *)tickets, cell_size, V, P, n, 1};
-	// the combine steps of dr_chamfer.h, with one segment per search
-	const ChamferArgs a = {vertices, points, point_weights, vertex_weights, params, terms, loss, vertices_b, nearest_vertex, nearest_point, pd2, vd2, vg,
-						   partials, pidx, vidx, assign, (unsigned *)tickets, V, P, n, 1, 1, directions, 0};
+	ChamferGridCall call = {{}, {vertices, points, point_weights, vertex_weights, params, terms, loss, vertices_b, nearest_vertex, nearest_point}};
+	if (closest_point_refused(what, directions, cell_size > 0 && cell_size < __builtin_inf() ? NULL : "cell_size must be finite and > 0", any_misaligned(words, 4) || any_misaligned(doubles, 8), scratch,
+							  scratch_bytes, chamfer_grid_carve(call, V, P, n, NULL), "scratch too small (deodr_hip_chamfer_grid_scratch_bytes)", any_overlap(outputs, inputs) || any_overlap(outputs)))
+		return 1;
+	chamfer_grid_carve(call, V, P, n, scratch);
+	ChamferGridArgs &g = call.g;
+	g.set[0].coords = vertices, g.set[1].coords = points, g.params = params, g.point_weights = point_weights, g.cell_size = cell_size, g.clear_tickets = 1;
+	ChamferArgs &a = call.a; // the combine steps of dr_chamfer.h, with one segment per search
+	a.directions = directions;
+	uint32_t *const sort_words = call.sort_words;
 	const hipStream_t st = (hipStream_t)stream;
 	const dim3 block(CHAMFER_BLOCK);
 	const bool to_mesh = directions & DEODR_HIP_CHAMFER_POINTS_TO_MESH, to_points = directions & DEODR_HIP_CHAMFER_MESH_TO_POINTS;
@@ -2406,7 +2356,7 @@ int deodr_hip_chamfer_grid(const double *vertices, int V, const double *points, 
 	{
 		hipLaunchKernelGGL(chamfer_grid_search_kernel, dim3(((unsigned)P - 1) / CHAMFER_BLOCK + 1, (unsigned)n), block, 0, st, g, 1, (int)to_points);
 		hipLaunchKernelGGL(chamfer_points_kernel, dim3(chamfer_blocks(P), (unsigned)n), block, 0, st, a);
-		sort_launch(assign, P, n, chamfer_grid_assign_bits(V), sorted_assign, assign_order, sort_words, st);
+		sort_launch(a.assign, P, n, chamfer_grid_assign_bits(V), g.sorted_assign, g.assign_order, sort_words, st);
 		hipLaunchKernelGGL(chamfer_grid_gather_kernel, dim3(((unsigned)V - 1) / CG_GATHER_VERTICES + 1, (unsigned)n), block, 0, st, g);
 	}
 	if (to_points)

@@ -1,8 +1,10 @@
 // The point-to-surface distance between a point set and the triangles of a mesh, its gradient to the vertices and the correspondences
 // (include/deodr_hip_surface.h has the operation, operation by operation, and the contract).  Brute force, built on dr_chamfer.h: the same split
-// rule (chamfer_segments), the same tickets, grid_sum, and for mesh -> points the same search kernel.
+// rule (chamfer_segments, chamfer_segment_range), the same tickets (chamfer_clear_tickets), for mesh -> points the same search kernel, and in the
+// vertices' combine step the same mesh -> points half (chamfer_vertex_to_points) and tail (chamfer_write_terms).
 //
-// surface_prep_kernel    a thread per (pose, face): the record (a, b, c, ab, ac) of the posed triangle -> scratch; clears the arrival tickets.
+// surface_prep_kernel    a thread per (pose, face): the record (a, b, c, ab, ac) of the posed triangle -> scratch; with points -> mesh on it is
+//                        the first launch and clears the arrival tickets.
 // surface_search_kernel  a thread per point, grid (ceil(P / BLOCK), Sp, n): the face records of segment blockIdx.y are staged in LDS SURFACE_TILE at
 //                        a time, 128 bytes each, and every lane reads the same address at the same time (a broadcast).  surface_closest() is the
 //                        header's sequence with the seven regions as selects (the lanes hold different points against one triangle: branches
@@ -14,12 +16,12 @@
 //                        a segment of the points; where assign[k] == f the pull is fetched and its nine products added, in increasing k -> scratch.
 // chamfer_walk_kernel<true, false>   mesh -> points: the vertex-major search of dr_chamfer.h, unchanged.
 // surface_vertices_kernel  a thread per (pose, vertex): its corners in table order, per corner the segments' sums in order, one chain; plus the
-//                        mesh -> points part (chamfer_combine) -> vertices_b, nearest_point, term_1 through grid_sum; the last workgroup of a pose
+//                        mesh -> points half of dr_chamfer.h -> vertices_b, nearest_point, term_1 through grid_sum; the last workgroup of a pose
 //                        writes terms and loss.
 //
 // No floating-point atomics.  The scratch after its 64 bytes of counter words (unused here), doubles first: rec [n][F][16], pd2 [n][Sp][P],
 // pull [n][P][6], fg [n][Sg][F][9], vd2 [n][Sv][V], partials [2][n][CHAMFER_MAX_BLOCKS]; then 4-byte words: pidx [n][Sp][P], vidx [n][Sv][V],
-// assign [n][P], tickets [2][n].
+// assign [n][P], tickets [2][n] (surface_carve).
 #pragma once
 
 namespace
@@ -28,13 +30,6 @@ namespace
 constexpr int SURFACE_TILE = CHAMFER_TILE, SURFACE_REC = 16; // (a record: 15 doubles and one of padding, 128 bytes)
 constexpr int SURFACE_MAX_FACES = 715827882;				  // 3 F + 2 is an int32
 static_assert(SURFACE_TILE == CHAMFER_BLOCK, "a thread stages one record of a tile");
-
-inline size_t surface_scratch_doubles(int V, int F, int P, int n)
-{
-	const size_t sp = (size_t)chamfer_segments(P, F) * (size_t)P, sg = (size_t)chamfer_segments(F, P) * (size_t)F;
-	const size_t sv = (size_t)chamfer_segments(V, P) * (size_t)V, N = (size_t)n;
-	return N * ((size_t)SURFACE_REC * (size_t)F + sp + 6 * (size_t)P + 9 * sg + sv + 2 * (size_t)CHAMFER_MAX_BLOCKS) + (N * (sp + sv + (size_t)P + 2) + 1) / 2;
-}
 
 struct SurfaceArgs
 {
@@ -50,6 +45,19 @@ struct SurfaceArgs
 	unsigned *tickets;
 	int V, F, P, n, Sp, Sg, Sv, directions;
 };
+
+// The scratch layout of the overview, stated once: the dimensions (checked) and the splits of a call -> a, and the bytes of its scratch; with a
+// base, its arrays -> a.
+inline size_t surface_carve(SurfaceArgs &a, int V, int F, int P, int n, void *base)
+{
+	a.V = V, a.F = F, a.P = P, a.n = n, a.Sp = chamfer_segments(P, F), a.Sg = chamfer_segments(F, P), a.Sv = chamfer_segments(V, P);
+	const size_t N = (size_t)n, np = N * (size_t)P, nf = N * (size_t)F, sp = (size_t)a.Sp * np, sv = (size_t)a.Sv * N * (size_t)V;
+	dr::host::ScratchCarver c = {(char *)base};
+	a.rec = c.take<double>((size_t)SURFACE_REC * nf), a.pd2 = c.take<double>(sp), a.pull = c.take<double>(6 * np), a.fg = c.take<double>(9 * (size_t)a.Sg * nf);
+	a.vd2 = c.take<double>(sv), a.partials = c.take<double>(2 * N * (size_t)CHAMFER_MAX_BLOCKS);
+	a.pidx = c.take<uint32_t>(sp), a.vidx = c.take<uint32_t>(sv), a.assign = c.take<uint32_t>(np), a.tickets = c.take<unsigned>(2 * N);
+	return c.whole_doubles();
+}
 
 struct alignas(16) SurfaceRec
 {
@@ -113,8 +121,7 @@ __device__ __forceinline__ SurfaceRec surface_record(const double *vertices, con
 __global__ __launch_bounds__(CHAMFER_BLOCK) void surface_prep_kernel(SurfaceArgs a)
 {
 	const size_t pose = blockIdx.y, F = (size_t)a.F;
-	if (blockIdx.x == 0 && threadIdx.x == 0)
-		a.tickets[pose] = 0, a.tickets[(size_t)a.n + pose] = 0; // (what the combine steps draw on: the launch boundaries order them)
+	chamfer_clear_tickets(a, pose, blockIdx.x == 0);
 	const double *const vertices = a.vertices + pose * (size_t)a.V * 3;
 	double *const rec = a.rec + (size_t)SURFACE_REC * pose * F;
 	for (size_t f = (size_t)blockIdx.x * CHAMFER_BLOCK + threadIdx.x; f < F; f += (size_t)gridDim.x * CHAMFER_BLOCK)
@@ -131,10 +138,8 @@ __global__ __launch_bounds__(CHAMFER_BLOCK) void surface_search_kernel(SurfaceAr
 	const size_t pose = blockIdx.z;
 	const int P = a.P, F = a.F, S = (int)gridDim.y, seg = (int)blockIdx.y;
 	const double *const rec = a.rec + (size_t)SURFACE_REC * pose * (size_t)F;
-	const int tiles = (F - 1) / SURFACE_TILE + 1;
-	const int first = (int)((long long)seg * tiles / S) * SURFACE_TILE;
-	const long long last_tile = ((long long)(seg + 1) * tiles / S) * SURFACE_TILE;
-	const int end = last_tile < F ? (int)last_tile : F;
+	const ChamferRange range = chamfer_segment_range(seg, S, F);
+	const int first = range.first, end = range.end;
 	const int k = (int)blockIdx.x * CHAMFER_BLOCK + (int)threadIdx.x;
 	const bool active = k < P;
 	const double *const p = a.points + 3 * (pose * (size_t)P + (size_t)(active ? k : 0));
@@ -206,10 +211,8 @@ __global__ __launch_bounds__(CHAMFER_BLOCK) void surface_gather_kernel(SurfaceAr
 	const int P = a.P, F = a.F, S = (int)gridDim.y, seg = (int)blockIdx.y;
 	const uint32_t *const assign = a.assign + pose * (size_t)P;
 	const double *const pull = a.pull + 6 * pose * (size_t)P;
-	const int tiles = (P - 1) / CHAMFER_TILE + 1;
-	const int first = (int)((long long)seg * tiles / S) * CHAMFER_TILE;
-	const long long last_tile = ((long long)(seg + 1) * tiles / S) * CHAMFER_TILE;
-	const int end = last_tile < P ? (int)last_tile : P;
+	const ChamferRange range = chamfer_segment_range(seg, S, P);
+	const int first = range.first, end = range.end;
 	const int f = (int)blockIdx.x * CHAMFER_BLOCK + (int)threadIdx.x;
 	const bool active = f < F;
 	const uint32_t me = active ? (uint32_t)f : CHAMFER_NO_QUERY;
@@ -241,14 +244,13 @@ __global__ __launch_bounds__(CHAMFER_BLOCK) void surface_gather_kernel(SurfaceAr
 // grid: (chamfer_blocks(V), n)
 __global__ __launch_bounds__(CHAMFER_BLOCK) void surface_vertices_kernel(SurfaceArgs a)
 {
-	const size_t pose = blockIdx.y, V = (size_t)a.V, P = (size_t)a.P, F = (size_t)a.F;
-	const bool to_mesh = a.directions & DEODR_HIP_CHAMFER_POINTS_TO_MESH, to_points = a.directions & DEODR_HIP_CHAMFER_MESH_TO_POINTS;
-	const double mix0 = a.params[0], mix1 = a.params[1], tau = a.params[2], tau2 = tau * tau;
+	const size_t pose = blockIdx.y, V = (size_t)a.V, F = (size_t)a.F;
+	const ChamferMix m = chamfer_mix(a);
 	double s[1] = {0};
 	for (size_t i = (size_t)blockIdx.x * CHAMFER_BLOCK + threadIdx.x; i < V; i += (size_t)gridDim.x * CHAMFER_BLOCK)
 	{
 		double bx = 0, by = 0, bz = 0;
-		if (to_mesh)
+		if (m.to_mesh)
 		{
 			double gx = 0, gy = 0, gz = 0;
 			for (int32_t at = a.corner_offsets[i], stop = a.corner_offsets[i + 1]; at < stop; at++)
@@ -261,34 +263,14 @@ __global__ __launch_bounds__(CHAMFER_BLOCK) void surface_vertices_kernel(Surface
 					gx += g[0], gy += g[1], gz += g[2];
 				}
 			}
-			bx = mix0 * gx, by = mix0 * gy, bz = mix0 * gz;
+			bx = m.mix0 * gx, by = m.mix0 * gy, bz = m.mix0 * gz;
 		}
-		if (to_points)
-		{
-			double best;
-			uint32_t arg;
-			chamfer_combine(a.vd2, a.vidx, pose, a.Sv, V, i, best, arg);
-			if (a.nearest_point)
-				a.nearest_point[pose * V + i] = arg;
-			const bool near = best <= tau2;
-			const double u = a.vertex_weights ? a.vertex_weights[i] : 1.0;
-			s[0] += u * (near ? best : tau2);
-			if (near)
-			{
-				const double *const v = a.vertices + 3 * (pose * V + i), *const p = a.points + 3 * (pose * P + arg);
-				bx += mix1 * ((2 * u) * (v[0] - p[0])), by += mix1 * ((2 * u) * (v[1] - p[1])), bz += mix1 * ((2 * u) * (v[2] - p[2]));
-			}
-		}
+		if (m.to_points)
+			chamfer_vertex_to_points(a, m, pose, i, s[0], bx, by, bz);
 		double *const out = a.vertices_b + 3 * (pose * V + i);
 		out[0] = bx, out[1] = by, out[2] = bz;
 	}
-	double total[1];
-	if (grid_sum<1>(s, a.partials + ((size_t)a.n + pose) * CHAMFER_MAX_BLOCKS, a.tickets + (size_t)a.n + pose, total, blockIdx.x, gridDim.x) && threadIdx.x == 0)
-	{
-		const double term0 = to_mesh ? a.terms[2 * pose] : 0.0, term1 = to_points ? total[0] : 0.0; // (term_0: surface_points_kernel, launches before)
-		a.terms[2 * pose] = term0, a.terms[2 * pose + 1] = term1;
-		a.loss[pose] = (to_mesh ? mix0 * term0 : 0.0) + (to_points ? mix1 * term1 : 0.0);
-	}
+	chamfer_write_terms(a, m, pose, s);
 }
 
 } // namespace

@@ -541,7 +541,9 @@ class ChamferFunc(torch.autograd.Function):
     """(vertices [n,V,3]; term: a :class:`deodr_amd.chamfer.PointCloudTerm`) -> (loss [n], terms [n,2]) of the closest-point energy
     (include/deodr_hip_chamfer.h); the loss is differentiable (its adjoint is the ``vertices_b`` the same call produced, exact wherever every nearest
     neighbour is unique), the terms are not: they are marked so, and torch refuses a gradient asked of them ("does not require grad").  The term
-    chooses the search: with ``search="grid"`` the call is ``deodr_hip_chamfer_grid`` (include/deodr_hip_chamfer_grid.h), the same op otherwise"""
+    chooses what runs: with ``search="grid"`` the call is ``deodr_hip_chamfer_grid`` (include/deodr_hip_chamfer_grid.h), and a
+    :class:`deodr_amd.surface.PointSurfaceTerm` evaluates the point-to-surface energy (include/deodr_hip_surface.h: the envelope theorem, exact
+    wherever every closest point is unique) -- ``SurfaceDistanceFunc`` is this class"""
 
     @staticmethod
     def forward(ctx, vertices, term):
@@ -556,23 +558,7 @@ class ChamferFunc(torch.autograd.Function):
         return loss_b[:, None, None] * vertices_b, None
 
 
-class SurfaceDistanceFunc(torch.autograd.Function):
-    """(vertices [n,V,3]; term: a :class:`deodr_amd.surface.PointSurfaceTerm`) -> (loss [n], terms [n,2]) of the point-to-surface energy
-    (include/deodr_hip_surface.h); the loss is differentiable (its adjoint is the ``vertices_b`` the same call produced: the envelope theorem, exact
-    wherever every closest point is unique), the terms are not: they are marked so, and torch refuses a gradient asked of them ("does not require
-    grad")"""
-
-    @staticmethod
-    def forward(ctx, vertices, term):
-        terms, loss, vertices_b = term.evaluate_no_grad(vertices)[:3]
-        ctx.save_for_backward(vertices_b)
-        ctx.mark_non_differentiable(terms)
-        return loss, terms
-
-    @staticmethod
-    def backward(ctx, loss_b, _terms_b):
-        (vertices_b,) = ctx.saved_tensors
-        return loss_b[:, None, None] * vertices_b, None
+SurfaceDistanceFunc = ChamferFunc
 
 
 def sh_shade(posed, sh, albedo, topology):

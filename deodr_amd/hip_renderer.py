@@ -1573,13 +1573,76 @@ def chamfer_segments(queries, references):
     return int(lib().deodr_hip_chamfer_segments(int(queries), int(references)))
 
 
+def _byte_scratch(what, dims, need, header, device):
+    """``need`` bytes (what the library's ``*_scratch_bytes`` gave for ``dims``; 0: refused) of uninitialised scratch on ``device``"""
+    if need == 0:
+        raise ValueError(f"{what}: {dims} is outside the limits of include/{header}")
+    with torch.cuda.device(device):
+        return torch.empty(int(need), dtype=torch.uint8, device=device)
+
+
 def chamfer_scratch(V, P, n, device):
     """the scratch of :func:`chamfer` for n poses of V vertices against P points (one per stream in use; it need not be zeroed)"""
-    need = int(lib().deodr_hip_chamfer_scratch_bytes(int(V), int(P), int(n)))
-    if need == 0:
-        raise ValueError(f"chamfer_scratch: V = {V}, P = {P}, n = {n} is outside the limits of include/deodr_hip_chamfer.h")
-    with torch.cuda.device(device):
-        return torch.empty(need, dtype=torch.uint8, device=device)
+    need = lib().deodr_hip_chamfer_scratch_bytes(int(V), int(P), int(n))
+    return _byte_scratch("chamfer_scratch", f"V = {V}, P = {P}, n = {n}", need, "deodr_hip_chamfer.h", device)
+
+
+def _closest_point(what, header, limits, make_scratch, vertices, points, params, point_weights, vertex_weights, directions, terms, loss, vertices_b, found,
+                   nearest_point, scratch, want_nearest, mesh=None, cell_size=()):  # fmt: skip
+    """What :func:`chamfer`, :func:`chamfer_grid` and :func:`surface_distance` share: the checks of their tensors, the results and the scratch where
+    none were given, the call ``deodr_hip_<what>``.  ``found``: the results per point of points -> mesh as (name, tensor | None, dtypes, trailing
+    shape); ``mesh``: (faces, corner_offsets, corners) of the surface operator; ``cell_size``: (the cell size,) of the grid.  -> (terms, loss,
+    vertices_b, *found, nearest_point)"""
+    _rocm_tensor(what, "vertices", vertices)
+    if vertices.dim() != 3 or vertices.shape[0] < 1 or vertices.shape[1] < 1 or vertices.shape[2] != 3:
+        raise ValueError(f"{what}: vertices must have shape [n >= 1, V >= 1, 3], not {list(vertices.shape)}")
+    n, V = int(vertices.shape[0]), int(vertices.shape[1])
+    if mesh is not None and (not torch.is_tensor(mesh[0]) or mesh[0].dim() != 2 or mesh[0].shape[0] < 1 or mesh[0].shape[1] != 3):
+        raise ValueError(f"{what}: faces must have shape [F >= 1, 3], not {list(getattr(mesh[0], 'shape', ()))}")
+    if not torch.is_tensor(points) or points.dim() != 3 or int(points.shape[0]) != n or points.shape[1] < 1 or points.shape[2] != 3:
+        raise ValueError(f"{what}: points must have shape [{n}, P >= 1, 3], not {list(getattr(points, 'shape', ()))}")
+    P, directions, cell_size = int(points.shape[1]), int(directions), tuple(float(c) for c in cell_size)
+    if not 1 <= directions <= 3:
+        raise ValueError(f"{what}: directions must be in 1 .. 3, not {directions}")
+    if not all(c > 0 and c < float("inf") for c in cell_size):
+        raise ValueError(f"{what}: cell_size must be finite and > 0, not {cell_size[0]}")
+    rows, dims, said = [("vertices", vertices, _F64_ONLY, None)], (V, P, n), f"V = {V}, P = {P}, n = {n}"
+    if mesh is not None:
+        F = int(mesh[0].shape[0])
+        rows += [("faces", mesh[0], (torch.int32,), (F, 3)), ("corner_offsets", mesh[1], (torch.int32,), (V + 1,)), ("corners", mesh[2], (torch.int32,), (3 * F,))]
+        dims, said = (V, F, P, n), f"V = {V}, F = {F}, P = {P}, n = {n}"
+    rows += [("points", points, _F64_ONLY, (n, P, 3)), ("params", params, _F64_ONLY, (3,))]
+    optional = [("point_weights", point_weights, _F64_ONLY, (n, P)), ("vertex_weights", vertex_weights, _F64_ONLY, (V,)),
+                ("terms", terms, _F64_ONLY, (n, 2)), ("loss", loss, _F64_ONLY, (n,)), ("vertices_b", vertices_b, _F64_ONLY, (n, V, 3))]  # fmt: skip
+    optional += [(name, t, dtypes, (n, P) + tail) for name, t, dtypes, tail in found]
+    optional += [("nearest_point", nearest_point, _INDICES, (n, V)), ("scratch", scratch, (torch.uint8,), (None,))]
+    rows += [row for row in optional if row[1] is not None]
+    _check_tensors(what, "vertices", vertices.device, rows)
+    dev = vertices.device
+    need = int(getattr(lib(), f"deodr_hip_{what}_scratch_bytes")(*dims))
+    if need == 0 or not getattr(lib(), f"deodr_hip_{what}_launches")(*dims, directions):  # (the launches: a limit that depends on the directions)
+        raise ValueError(f"{what}: {said} is outside the limits of include/{header} ({limits})")
+    results = [t for _, t, _, _ in found]
+    with torch.cuda.device(dev):
+        terms = torch.empty((n, 2), dtype=torch.float64, device=dev) if terms is None else terms
+        loss = torch.empty(n, dtype=torch.float64, device=dev) if loss is None else loss
+        vertices_b = torch.empty_like(vertices) if vertices_b is None else vertices_b
+        if want_nearest and directions & CHAMFER_POINTS_TO_MESH:
+            results = [torch.empty((n, P) + tail, dtype=torch.int32 if dtypes is _INDICES else torch.float64, device=dev) if t is None else t
+                       for _, t, dtypes, tail in found]  # fmt: skip
+        if want_nearest and nearest_point is None and directions & CHAMFER_MESH_TO_POINTS:
+            nearest_point = torch.empty((n, V), dtype=torch.int32, device=dev)
+        if scratch is None:
+            scratch = _cached_scratch(make_scratch.__name__[: -len("_scratch")], dev, need, lambda: make_scratch(*dims, dev),
+                                      f"{what}: pass scratch= ({make_scratch.__name__}) when capturing a graph: none of this size exists for this stream yet")  # fmt: skip
+    out = (terms, loss, vertices_b, *results, nearest_point)
+    of_mesh = () if mesh is None else (_ptr(mesh[0]), dims[1], _ptr(mesh[1]), _ptr(mesh[2]))
+    _launch(getattr(lib(), f"deodr_hip_{what}"), dev, _ptr(vertices), V, *of_mesh, _ptr(points), P, _ptr(point_weights), _ptr(vertex_weights), _ptr(params),
+            *cell_size, n, directions, *(_ptr(t) for t in out), _ptr(scratch), scratch.numel())  # fmt: skip
+    for t in out:
+        if t is not None:
+            _touched(t)
+    return out
 
 
 def chamfer(vertices, points, params, point_weights=None, vertex_weights=None, directions=3, terms=None, loss=None, vertices_b=None,
@@ -1591,44 +1654,8 @@ def chamfer(vertices, points, params, point_weights=None, vertex_weights=None, d
     a tensor is given or ``want_nearest``, for the directions that are on.  The values are trusted (:mod:`deodr_amd.chamfer` checks its own on the
     host).  Deterministic; asynchronous on the current stream.  ``scratch``: a :func:`chamfer_scratch` of the caller's; None: one per device and
     stream."""
-    what = "chamfer"
-    _rocm_tensor(what, "vertices", vertices)
-    if vertices.dim() != 3 or vertices.shape[0] < 1 or vertices.shape[1] < 1 or vertices.shape[2] != 3:
-        raise ValueError(f"{what}: vertices must have shape [n >= 1, V >= 1, 3], not {list(vertices.shape)}")
-    n, V = int(vertices.shape[0]), int(vertices.shape[1])
-    if not torch.is_tensor(points) or points.dim() != 3 or int(points.shape[0]) != n or points.shape[1] < 1 or points.shape[2] != 3:
-        raise ValueError(f"{what}: points must have shape [{n}, P >= 1, 3], not {list(getattr(points, 'shape', ()))}")
-    P, directions = int(points.shape[1]), int(directions)
-    if not 1 <= directions <= 3:
-        raise ValueError(f"{what}: directions must be in 1 .. 3, not {directions}")
-    rows = [("vertices", vertices, _F64_ONLY, None), ("points", points, _F64_ONLY, (n, P, 3)), ("params", params, _F64_ONLY, (3,))]
-    optional = (("point_weights", point_weights, _F64_ONLY, (n, P)), ("vertex_weights", vertex_weights, _F64_ONLY, (V,)),
-                ("terms", terms, _F64_ONLY, (n, 2)), ("loss", loss, _F64_ONLY, (n,)), ("vertices_b", vertices_b, _F64_ONLY, (n, V, 3)),
-                ("nearest_vertex", nearest_vertex, _INDICES, (n, P)), ("nearest_point", nearest_point, _INDICES, (n, V)),
-                ("scratch", scratch, (torch.uint8,), (None,)))  # fmt: skip
-    rows += [row for row in optional if row[1] is not None]
-    _check_tensors(what, "vertices", vertices.device, rows)
-    dev = vertices.device
-    need = int(lib().deodr_hip_chamfer_scratch_bytes(V, P, n))
-    if need == 0:
-        raise ValueError(f"{what}: V = {V}, P = {P}, n = {n} is outside the limits of include/deodr_hip_chamfer.h (V * P <= {CHAMFER_MAX_PAIRS}, n <= 65535)")
-    with torch.cuda.device(dev):
-        terms = torch.empty((n, 2), dtype=torch.float64, device=dev) if terms is None else terms
-        loss = torch.empty(n, dtype=torch.float64, device=dev) if loss is None else loss
-        vertices_b = torch.empty_like(vertices) if vertices_b is None else vertices_b
-        if want_nearest and nearest_vertex is None and directions & CHAMFER_POINTS_TO_MESH:
-            nearest_vertex = torch.empty((n, P), dtype=torch.int32, device=dev)
-        if want_nearest and nearest_point is None and directions & CHAMFER_MESH_TO_POINTS:
-            nearest_point = torch.empty((n, V), dtype=torch.int32, device=dev)
-        if scratch is None:
-            scratch = _cached_scratch("chamfer", dev, need, lambda: chamfer_scratch(V, P, n, dev),
-                                      f"{what}: pass scratch= (chamfer_scratch) when capturing a graph: none of this size exists for this stream yet")  # fmt: skip
-    _launch(lib().deodr_hip_chamfer, dev, _ptr(vertices), V, _ptr(points), P, _ptr(point_weights), _ptr(vertex_weights), _ptr(params), n, directions,
-            _ptr(terms), _ptr(loss), _ptr(vertices_b), _ptr(nearest_vertex), _ptr(nearest_point), _ptr(scratch), scratch.numel())  # fmt: skip
-    for t in (terms, loss, vertices_b, nearest_vertex, nearest_point):
-        if t is not None:
-            _touched(t)
-    return terms, loss, vertices_b, nearest_vertex, nearest_point
+    return _closest_point("chamfer", "deodr_hip_chamfer.h", f"V * P <= {CHAMFER_MAX_PAIRS}, n <= 65535", chamfer_scratch, vertices, points, params, point_weights,
+                          vertex_weights, directions, terms, loss, vertices_b, [("nearest_vertex", nearest_vertex, _INDICES, ())], nearest_point, scratch, want_nearest)  # fmt: skip
 
 
 # ---- stable sort by key, closest-point energy over a uniform grid (include/deodr_hip_chamfer_grid.h) ----------------------------------------
@@ -1647,11 +1674,8 @@ def sort_keys_launches(N, n, bits):
 
 def sort_keys_scratch(N, n, bits, device):
     """the scratch of :func:`sort_keys` for n rows of N keys (it need not be zeroed)"""
-    need = int(lib().deodr_hip_sort_keys_scratch_bytes(int(N), int(n), int(bits)))
-    if need == 0:
-        raise ValueError(f"sort_keys_scratch: N = {N}, n = {n}, bits = {bits} is outside the limits of include/deodr_hip_chamfer_grid.h")
-    with torch.cuda.device(device):
-        return torch.empty(need, dtype=torch.uint8, device=device)
+    need = lib().deodr_hip_sort_keys_scratch_bytes(int(N), int(n), int(bits))
+    return _byte_scratch("sort_keys_scratch", f"N = {N}, n = {n}, bits = {bits}", need, "deodr_hip_chamfer_grid.h", device)
 
 
 def sort_keys(keys, bits=32, sorted_keys=None, order=None, scratch=None, want_sorted=True):
@@ -1699,11 +1723,8 @@ def chamfer_grid_launches(V, P, n, directions=3):
 
 def chamfer_grid_scratch(V, P, n, device):
     """the scratch of :func:`chamfer_grid` for n poses of V vertices against P points (one per stream in use; it need not be zeroed)"""
-    need = int(lib().deodr_hip_chamfer_grid_scratch_bytes(int(V), int(P), int(n)))
-    if need == 0:
-        raise ValueError(f"chamfer_grid_scratch: V = {V}, P = {P}, n = {n} is outside the limits of include/deodr_hip_chamfer_grid.h")
-    with torch.cuda.device(device):
-        return torch.empty(need, dtype=torch.uint8, device=device)
+    need = lib().deodr_hip_chamfer_grid_scratch_bytes(int(V), int(P), int(n))
+    return _byte_scratch("chamfer_grid_scratch", f"V = {V}, P = {P}, n = {n}", need, "deodr_hip_chamfer_grid.h", device)
 
 
 def chamfer_grid(vertices, points, params, cell_size, point_weights=None, vertex_weights=None, directions=3, terms=None, loss=None, vertices_b=None,
@@ -1712,46 +1733,9 @@ def chamfer_grid(vertices, points, params, cell_size, point_weights=None, vertex
     max_distance / CHAMFER_GRID_RINGS)`` -- the same arguments and results, the same indices; a query with no neighbour within ``max_distance``
     (``params[2]``, which must be FINITE: trusted here, :mod:`deodr_amd.chamfer` checks its own) reports ``CHAMFER_GRID_NONE``.  No cap on V * P.
     ``scratch``: a :func:`chamfer_grid_scratch` of the caller's; None: one per device and stream."""
-    what = "chamfer_grid"
-    _rocm_tensor(what, "vertices", vertices)
-    if vertices.dim() != 3 or vertices.shape[0] < 1 or vertices.shape[1] < 1 or vertices.shape[2] != 3:
-        raise ValueError(f"{what}: vertices must have shape [n >= 1, V >= 1, 3], not {list(vertices.shape)}")
-    n, V = int(vertices.shape[0]), int(vertices.shape[1])
-    if not torch.is_tensor(points) or points.dim() != 3 or int(points.shape[0]) != n or points.shape[1] < 1 or points.shape[2] != 3:
-        raise ValueError(f"{what}: points must have shape [{n}, P >= 1, 3], not {list(getattr(points, 'shape', ()))}")
-    P, directions, cell_size = int(points.shape[1]), int(directions), float(cell_size)
-    if not 1 <= directions <= 3:
-        raise ValueError(f"{what}: directions must be in 1 .. 3, not {directions}")
-    if not (cell_size > 0 and cell_size < float("inf")):
-        raise ValueError(f"{what}: cell_size must be finite and > 0, not {cell_size}")
-    rows = [("vertices", vertices, _F64_ONLY, None), ("points", points, _F64_ONLY, (n, P, 3)), ("params", params, _F64_ONLY, (3,))]
-    optional = (("point_weights", point_weights, _F64_ONLY, (n, P)), ("vertex_weights", vertex_weights, _F64_ONLY, (V,)),
-                ("terms", terms, _F64_ONLY, (n, 2)), ("loss", loss, _F64_ONLY, (n,)), ("vertices_b", vertices_b, _F64_ONLY, (n, V, 3)),
-                ("nearest_vertex", nearest_vertex, _INDICES, (n, P)), ("nearest_point", nearest_point, _INDICES, (n, V)),
-                ("scratch", scratch, (torch.uint8,), (None,)))  # fmt: skip
-    rows += [row for row in optional if row[1] is not None]
-    _check_tensors(what, "vertices", vertices.device, rows)
-    dev = vertices.device
-    need = int(lib().deodr_hip_chamfer_grid_scratch_bytes(V, P, n))
-    if need == 0:
-        raise ValueError(f"{what}: V = {V}, P = {P}, n = {n} is outside the limits of include/deodr_hip_chamfer_grid.h (V, P <= {CHAMFER_GRID_MAX_ITEMS}, n <= 65535)")
-    with torch.cuda.device(dev):
-        terms = torch.empty((n, 2), dtype=torch.float64, device=dev) if terms is None else terms
-        loss = torch.empty(n, dtype=torch.float64, device=dev) if loss is None else loss
-        vertices_b = torch.empty_like(vertices) if vertices_b is None else vertices_b
-        if want_nearest and nearest_vertex is None and directions & CHAMFER_POINTS_TO_MESH:
-            nearest_vertex = torch.empty((n, P), dtype=torch.int32, device=dev)
-        if want_nearest and nearest_point is None and directions & CHAMFER_MESH_TO_POINTS:
-            nearest_point = torch.empty((n, V), dtype=torch.int32, device=dev)
-        if scratch is None:
-            scratch = _cached_scratch("chamfer_grid", dev, need, lambda: chamfer_grid_scratch(V, P, n, dev),
-                                      f"{what}: pass scratch= (chamfer_grid_scratch) when capturing a graph: none of this size exists for this stream yet")  # fmt: skip
-    _launch(lib().deodr_hip_chamfer_grid, dev, _ptr(vertices), V, _ptr(points), P, _ptr(point_weights), _ptr(vertex_weights), _ptr(params), cell_size, n,
-            directions, _ptr(terms), _ptr(loss), _ptr(vertices_b), _ptr(nearest_vertex), _ptr(nearest_point), _ptr(scratch), scratch.numel())  # fmt: skip
-    for t in (terms, loss, vertices_b, nearest_vertex, nearest_point):
-        if t is not None:
-            _touched(t)
-    return terms, loss, vertices_b, nearest_vertex, nearest_point
+    return _closest_point("chamfer_grid", "deodr_hip_chamfer_grid.h", f"V, P <= {CHAMFER_GRID_MAX_ITEMS}, n <= 65535", chamfer_grid_scratch, vertices, points, params,
+                          point_weights, vertex_weights, directions, terms, loss, vertices_b, [("nearest_vertex", nearest_vertex, _INDICES, ())], nearest_point, scratch,
+                          want_nearest, cell_size=(cell_size,))  # fmt: skip
 
 
 # ---- point-to-surface distance (include/deodr_hip_surface.h) --------------------------------------------------------------------------------
@@ -1767,11 +1751,8 @@ def surface_launches(V, F, P, n, directions=3):
 
 def surface_scratch(V, F, P, n, device):
     """the scratch of :func:`surface_distance` for n poses of V vertices and F faces against P points (one per stream in use; it need not be zeroed)"""
-    need = int(lib().deodr_hip_surface_distance_scratch_bytes(int(V), int(F), int(P), int(n)))
-    if need == 0:
-        raise ValueError(f"surface_scratch: V = {V}, F = {F}, P = {P}, n = {n} is outside the limits of include/deodr_hip_surface.h")
-    with torch.cuda.device(device):
-        return torch.empty(need, dtype=torch.uint8, device=device)
+    need = lib().deodr_hip_surface_distance_scratch_bytes(int(V), int(F), int(P), int(n))
+    return _byte_scratch("surface_scratch", f"V = {V}, F = {F}, P = {P}, n = {n}", need, "deodr_hip_surface.h", device)
 
 
 def surface_distance(vertices, faces, corner_offsets, corners, points, params, point_weights=None, vertex_weights=None, directions=3, terms=None,
@@ -1784,50 +1765,10 @@ def surface_distance(vertices, faces, corner_offsets, corners, points, params, p
     1 points -> mesh, bit 2 mesh -> points.  The nearest_* and barycentric arrays are written when a tensor is given or ``want_nearest``, for the
     directions that are on.  The values and the tables are trusted (:mod:`deodr_amd.surface` checks its own on the host).  Deterministic;
     asynchronous on the current stream.  ``scratch``: a :func:`surface_scratch` of the caller's; None: one per device and stream."""
-    what = "surface_distance"
-    _rocm_tensor(what, "vertices", vertices)
-    if vertices.dim() != 3 or vertices.shape[0] < 1 or vertices.shape[1] < 1 or vertices.shape[2] != 3:
-        raise ValueError(f"{what}: vertices must have shape [n >= 1, V >= 1, 3], not {list(vertices.shape)}")
-    n, V = int(vertices.shape[0]), int(vertices.shape[1])
-    if not torch.is_tensor(faces) or faces.dim() != 2 or faces.shape[0] < 1 or faces.shape[1] != 3:
-        raise ValueError(f"{what}: faces must have shape [F >= 1, 3], not {list(getattr(faces, 'shape', ()))}")
-    if not torch.is_tensor(points) or points.dim() != 3 or int(points.shape[0]) != n or points.shape[1] < 1 or points.shape[2] != 3:
-        raise ValueError(f"{what}: points must have shape [{n}, P >= 1, 3], not {list(getattr(points, 'shape', ()))}")
-    F, P, directions = int(faces.shape[0]), int(points.shape[1]), int(directions)
-    if not 1 <= directions <= 3:
-        raise ValueError(f"{what}: directions must be in 1 .. 3, not {directions}")
-    rows = [("vertices", vertices, _F64_ONLY, None), ("faces", faces, (torch.int32,), (F, 3)), ("corner_offsets", corner_offsets, (torch.int32,), (V + 1,)),
-            ("corners", corners, (torch.int32,), (3 * F,)), ("points", points, _F64_ONLY, (n, P, 3)), ("params", params, _F64_ONLY, (3,))]  # fmt: skip
-    optional = (("point_weights", point_weights, _F64_ONLY, (n, P)), ("vertex_weights", vertex_weights, _F64_ONLY, (V,)),
-                ("terms", terms, _F64_ONLY, (n, 2)), ("loss", loss, _F64_ONLY, (n,)), ("vertices_b", vertices_b, _F64_ONLY, (n, V, 3)),
-                ("nearest_face", nearest_face, _INDICES, (n, P)), ("barycentric", barycentric, _F64_ONLY, (n, P, 3)),
-                ("nearest_point", nearest_point, _INDICES, (n, V)), ("scratch", scratch, (torch.uint8,), (None,)))  # fmt: skip
-    rows += [row for row in optional if row[1] is not None]
-    _check_tensors(what, "vertices", vertices.device, rows)
-    dev = vertices.device
-    need = int(lib().deodr_hip_surface_distance_scratch_bytes(V, F, P, n))
-    if need == 0 or not lib().deodr_hip_surface_distance_launches(V, F, P, n, directions):
-        raise ValueError(f"{what}: V = {V}, F = {F}, P = {P}, n = {n} is outside the limits of include/deodr_hip_surface.h (F * P <= {SURFACE_MAX_PAIRS}, "
-                         f"V * P <= {CHAMFER_MAX_PAIRS} with mesh -> points, n <= 65535)")  # fmt: skip
-    with torch.cuda.device(dev):
-        terms = torch.empty((n, 2), dtype=torch.float64, device=dev) if terms is None else terms
-        loss = torch.empty(n, dtype=torch.float64, device=dev) if loss is None else loss
-        vertices_b = torch.empty_like(vertices) if vertices_b is None else vertices_b
-        if want_nearest and directions & CHAMFER_POINTS_TO_MESH:
-            nearest_face = torch.empty((n, P), dtype=torch.int32, device=dev) if nearest_face is None else nearest_face
-            barycentric = torch.empty((n, P, 3), dtype=torch.float64, device=dev) if barycentric is None else barycentric
-        if want_nearest and nearest_point is None and directions & CHAMFER_MESH_TO_POINTS:
-            nearest_point = torch.empty((n, V), dtype=torch.int32, device=dev)
-        if scratch is None:
-            scratch = _cached_scratch("surface", dev, need, lambda: surface_scratch(V, F, P, n, dev),
-                                      f"{what}: pass scratch= (surface_scratch) when capturing a graph: none of this size exists for this stream yet")  # fmt: skip
-    _launch(lib().deodr_hip_surface_distance, dev, _ptr(vertices), V, _ptr(faces), F, _ptr(corner_offsets), _ptr(corners), _ptr(points), P,
-            _ptr(point_weights), _ptr(vertex_weights), _ptr(params), n, directions, _ptr(terms), _ptr(loss), _ptr(vertices_b), _ptr(nearest_face),
-            _ptr(barycentric), _ptr(nearest_point), _ptr(scratch), scratch.numel())  # fmt: skip
-    for t in (terms, loss, vertices_b, nearest_face, barycentric, nearest_point):
-        if t is not None:
-            _touched(t)
-    return terms, loss, vertices_b, nearest_face, barycentric, nearest_point
+    found = [("nearest_face", nearest_face, _INDICES, ()), ("barycentric", barycentric, _F64_ONLY, (3,))]
+    return _closest_point("surface_distance", "deodr_hip_surface.h", f"F * P <= {SURFACE_MAX_PAIRS}, V * P <= {CHAMFER_MAX_PAIRS} with mesh -> points, n <= 65535",
+                          surface_scratch, vertices, points, params, point_weights, vertex_weights, directions, terms, loss, vertices_b, found, nearest_point, scratch,
+                          want_nearest, mesh=(faces, corner_offsets, corners))  # fmt: skip
 
 
 # ---------------------------------------------------------------------------------------------------------------------

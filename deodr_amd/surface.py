@@ -17,7 +17,7 @@ points -- what runs on tensors the kernels do not take and what the kernels are 
 import numpy as np
 import torch
 
-from .chamfer import CHUNK_BYTES, PointCloudTerm, _array, _nearest
+from .chamfer import CHUNK_BYTES, PointCloudTerm, _array, _mesh_to_points
 
 LIVE_ARRAYS = 24  # [n, chunk, F] arrays alive at once in closest_point_torch, roughly: what a chunk is sized by
 
@@ -112,7 +112,7 @@ def surface_distance_torch(vertices, faces, points, params, point_weights=None, 
     are ``index_add_``'s, not in the kernels' order.  No autograd: see :class:`deodr_amd.fronthalf.SurfaceDistanceFunc`."""
     with torch.no_grad():
         v, p = vertices, points.to(vertices.dtype)
-        n, V, P = int(v.shape[0]), int(v.shape[1]), int(p.shape[1])
+        n, P = int(v.shape[0]), int(p.shape[1])
         faces = torch.as_tensor(faces, device=v.device).long()
         params = params.to(v.dtype)
         mix0, mix1, tau2 = params[0], params[1], params[2] * params[2]
@@ -130,11 +130,7 @@ def surface_distance_torch(vertices, faces, points, params, point_weights=None, 
             for b in range(n):
                 g[b].index_add_(0, corners[b].reshape(-1), mix0 * pull[b].reshape(-1, 3))
         if directions & 2:
-            u = torch.ones(V, dtype=v.dtype, device=v.device) if vertex_weights is None else vertex_weights.to(v.dtype)
-            d2, nearest_point = _nearest(v, p, chunk_bytes)
-            near = d2 <= tau2
-            terms[:, 1] = (u[None] * torch.where(near, d2, tau2)).sum(dim=1)
-            g += mix1 * ((2 * u[None] * near)[..., None] * (v - torch.gather(p, 1, nearest_point[..., None].expand(-1, -1, 3))))
+            nearest_point = _mesh_to_points(v, p, vertex_weights, mix1, tau2, terms, g, chunk_bytes)
         loss = (mix0 * terms[:, 0] if directions & 1 else 0) + (mix1 * terms[:, 1] if directions & 2 else 0)
         return terms, loss, g, nearest_face, barycentric, nearest_point
 
@@ -161,31 +157,17 @@ class PointSurfaceTerm(PointCloudTerm):
             raise ValueError(f"PointSurfaceTerm: the faces are those of {self.nb_vertices} vertices, not of {int(vertices.shape[1])}")
         return vertices
 
-    def evaluate_no_grad(self, vertices, want_nearest=False):
-        """(terms [n,2], loss [n], vertices_b [n,V,3], nearest_face [n,P] | None, barycentric [n,P,3] | None, nearest_point [n,V] | None) without
-        autograd: ``deodr_hip_surface_distance`` on float64 ROCm tensors, :func:`surface_distance_torch` elsewhere (the indices int64 either way)"""
-        v = self._posed(vertices).detach().contiguous()
-        V = int(v.shape[1])
-        u = self._vertex_weights(V)
-        if not self.uses_kernel(v):
-            to = lambda t: None if t is None else t.to(v.device)
-            out = surface_distance_torch(v, to(self.faces), to(self.points), to(self.params), to(self.point_weights), to(u), self.directions)
-            return out if want_nearest else out[:3] + (None, None, None)
-        from . import hip_renderer as hr
+    # :meth:`evaluate_no_grad` is PointCloudTerm's with these two: -> (terms [n,2], loss [n], vertices_b [n,V,3], nearest_face [n,P] | None, barycentric
+    # [n,P,3] | None, nearest_point [n,V] | None), ``deodr_hip_surface_distance`` on float64 ROCm tensors, :func:`surface_distance_torch` elsewhere (the
+    # indices int64 either way); :meth:`evaluate` is PointCloudTerm's as it stands (the adjoint of the loss is the ``vertices_b`` of the same call)
+    def _torch(self, v, u, want_nearest):
+        to = lambda t: None if t is None else t.to(v.device)
+        out = surface_distance_torch(v, to(self.faces), to(self.points), to(self.params), to(self.point_weights), to(u), self.directions)
+        return out if want_nearest else out[:3] + (None, None, None)
 
-        if (self.n, V) not in self._scratch:
-            self._scratch[(self.n, V)] = hr.surface_scratch(V, self.nb_faces, self.nb_points, self.n, v.device)
-        terms, loss, g, nf, bary, npt = hr.surface_distance(v, self.faces, self.corner_offsets, self.corners, self.points, self.params, self.point_weights, u,
-                                                            self.directions, scratch=self._scratch[(self.n, V)], want_nearest=want_nearest)  # fmt: skip
-        return terms, loss, g, (None if nf is None else nf.long()), bary, (None if npt is None else npt.long())  # (F, P < 2^31: the bit patterns are the values)
-
-    def evaluate(self, vertices):
-        """-> (loss [n], terms [n,2]) of ``vertices`` [n,V,3] (or [V,3]: the same mesh against every cloud).  The loss is differentiable in the
-        vertices (its adjoint is the ``vertices_b`` the same call produced); the terms are marked non-differentiable, as
-        :meth:`PointCloudTerm.evaluate`'s are.  Calls of one shape must not run on two streams at once (they share a scratch)."""
-        from . import fronthalf
-
-        return fronthalf.SurfaceDistanceFunc.apply(self._posed(vertices), self)
+    def _kernel(self, hr, V):
+        mesh = (self.faces, self.corner_offsets, self.corners)
+        return hr.surface_scratch, (V, self.nb_faces, self.nb_points, self.n), hr.surface_distance, mesh + (self.points, self.params)
 
     def correspondences(self, vertices):
         """-> (nearest_face [n,P] | None, barycentric [n,P,3] | None, nearest_point [n,V] | None): the closest face of every point and the

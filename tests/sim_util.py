@@ -58,7 +58,8 @@ def host_lib():
         ("host_elem_bytes", C.c_size_t, [C.c_int]), ("host_ranges_overlap", C.c_int, [C.c_size_t] * 4),
         ("host_capped_blocks", C.c_uint, [C.c_size_t, C.c_size_t, C.c_uint]), ("host_scratch_need", C.c_size_t, [C.c_size_t]),
         ("host_scratch_holds", C.c_int, [C.c_size_t] * 3), ("host_scratch_counter", C.c_size_t, [C.c_void_p, C.c_int]),
-        ("host_scratch_doubles", C.c_size_t, [C.c_void_p]),
+        ("host_scratch_doubles", C.c_size_t, [C.c_void_p]), ("host_any_pair_overlaps", C.c_int, [C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_int]),
+        ("host_carve", None, [C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t)]),
     ):  # fmt: skip
         getattr(L, name).restype, getattr(L, name).argtypes = restype, argtypes
     return L

@@ -269,3 +269,39 @@ def test_fit_eager_graphed_and_against_the_cpu():
 def test_zz_report_the_largest_errors():
     """(runs last in the file: what DESIGN.md 4m quotes)"""
     print(f"largest errors of this run: terms {WORST['terms']:.2e} (allowed {cr.GPU_TOL_TERMS:.1e}), gradient {WORST['gradient']:.2e} (allowed {cr.GPU_TOL_GRADIENT:.1e})")
+
+
+@pytest.mark.parametrize("operator", ["chamfer", "chamfer_grid", "surface_distance"])
+def test_a_scratch_serves_the_next_call_whatever_directions_the_last_one_had(operator):
+    """Which kernel clears the arrival tickets depends on ``directions`` (the first launch of the call does).  V = 65, P = 257 (F = 130), n = 2: two
+    workgroups of points, two tiles of points; one scratch, every byte 0xFF at first (NaN as doubles, no ticket and no index as words), serves calls
+    with directions 3, 2, 1, 3, and every result of each has the bits of the same call on a scratch filled afresh"""
+    from deodr_amd import hip_renderer as hr
+
+    V, P, F, n = 65, 257, 130, 2
+    rs = np.random.RandomState(7)
+    dev = lambda a: torch.as_tensor(a, device=DEV)
+    v, p, pw, uw = dev(rs.rand(n, V, 3)), dev(rs.rand(n, P, 3)), dev(0.5 + rs.rand(n, P)), dev(0.5 + rs.rand(V))
+    params = dev(np.array([0.7, 1.3, 0.25]))  # (a finite max_distance: some pairs are beyond it)
+    if operator == "surface_distance":
+        from deodr_amd.surface import corner_table
+
+        faces = np.stack([rs.permutation(V)[:3] for _ in range(F)]).astype(np.int32)
+        offsets, corners = corner_table(faces, V)
+        fresh = lambda: hr.surface_scratch(V, F, P, n, DEV).fill_(0xFF)
+        call = lambda d, scratch: hr.surface_distance(v, dev(faces), dev(offsets), dev(corners), p, params, pw, uw, d, scratch=scratch, want_nearest=True)
+    elif operator == "chamfer_grid":
+        fresh = lambda: hr.chamfer_grid_scratch(V, P, n, DEV).fill_(0xFF)
+        call = lambda d, scratch: hr.chamfer_grid(v, p, params, 0.1, pw, uw, d, scratch=scratch, want_nearest=True)
+    else:
+        fresh = lambda: hr.chamfer_scratch(V, P, n, DEV).fill_(0xFF)
+        call = lambda d, scratch: hr.chamfer(v, p, params, pw, uw, d, scratch=scratch, want_nearest=True)
+    shared = fresh()
+    for step, directions in enumerate((3, 2, 1, 3)):
+        got, want = call(directions, shared), call(directions, fresh())
+        assert len(got) == len(want) == (6 if operator == "surface_distance" else 5)
+        for a, b in zip(got, want):
+            assert (a is None) == (b is None), (step, directions)
+            assert a is None or torch.equal(a.contiguous().view(torch.uint8), b.contiguous().view(torch.uint8)), (step, directions)
+        # (the nearest_* arrays of the directions that are on were among them)
+        assert all((t is None) == (not directions & 1) for t in got[3:-1]) and (got[-1] is None) == (not directions & 2)
