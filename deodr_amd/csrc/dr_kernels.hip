@@ -1794,6 +1794,37 @@ int deodr_hip_pyramid_abi_version(void) { return DEODR_HIP_PYRAMID_ABI_VERSION; 
 
 namespace
 {
+const char *image_term_size(int n, int H, int W, int C) { return (double)n * H * W * C >= 1099511627776.0 ? "n H W C must be below 2^40" : NULL; }
+
+// What deodr_hip_pyramid_l2 and deodr_hip_ssim_l2 (below) check alike, in the order their messages are documented in: the arrays that must be given
+// (`param`: level_weights / mix, `param_bytes` long), `dims` and then `own` (the operator's own refusals, NULL: none), the dtype tag, the alignment,
+// the scratch against `need` (`need_fn` states it), the outputs against the inputs and each other.  -> 1 with the message set, or 0.
+int image_term_refused(const char *what, const void *image, const void *obs, const void *weights, const void *image_b, const double *param,
+					   const char *param_name, size_t param_bytes, const double *terms, size_t terms_bytes, const double *loss, void *scratch,
+					   size_t scratch_bytes, size_t need, const char *need_fn, const char *dims, const char *own, int n, int H, int W, int C, int pixel_dtype)
+{
+	char why[96];
+	if (!image || !obs || !param || !terms || !scratch)
+		return snprintf(why, sizeof why, "image, obs, %s, terms or scratch == NULL", param_name), fail(what, why);
+	if (dims || own)
+		return fail(what, dims ? dims : own);
+	const size_t elem = elem_bytes(pixel_dtype);
+	if (!elem)
+		return fail(what, "pixel_dtype must be DEODR_HIP_F32 or DEODR_HIP_F64");
+	const void *const pixels[] = {image, obs, weights, image_b};
+	const void *const doubles[] = {param, terms, loss, scratch};
+	if (any_misaligned(pixels, elem) || any_misaligned(doubles, 8))
+		return fail(what, "misaligned pointer");
+	if (!Scratch{scratch, scratch_bytes}.holds(need))
+		return snprintf(why, sizeof why, "scratch too small (%s)", need_fn), fail(what, why);
+	const size_t frame = (size_t)n * H * W * elem;
+	const Range outputs[] = {{terms, terms_bytes}, {loss, 8}, {image_b, frame * C}, {scratch, scratch_bytes}};
+	const Range inputs[] = {{image, frame * C}, {obs, frame * C}, {weights, frame}, {param, param_bytes}};
+	if (any_overlap(outputs, inputs) || any_overlap(outputs))
+		return fail(what, "an output must not overlap an input, the scratch or another output");
+	return 0;
+}
+
 struct PyramidLayout
 { // the scratch after its counter words, in doubles
 	size_t tiles, regions, partials_tile, partials_coarse, tile_w, tile_q, gamma, doubles;
@@ -1807,9 +1838,7 @@ const char *pyramid_dims(int n, int H, int W, int C, int levels)
 		return "C must be >= 1";
 	if (n < 1 || H < 1 || W < 1)
 		return "n, H and W must be >= 1";
-	if ((double)n * H * W * C >= 1099511627776.0)
-		return "n H W C must be below 2^40";
-	return NULL;
+	return image_term_size(n, H, W, C);
 }
 PyramidLayout pyramid_layout(int n, int H, int W, int C, int levels)
 {
@@ -1836,26 +1865,12 @@ size_t deodr_hip_pyramid_scratch_bytes(int n, int H, int W, int C, int levels)
 int deodr_hip_pyramid_l2(const void *image, const void *obs, const void *weights, int n, int H, int W, int C, int pixel_dtype, int levels,
 						 const double *level_weights, double *terms, double *loss, void *image_b, void *scratch, size_t scratch_bytes, void *stream)
 {
-	const char *what = "pyramid_l2";
-	if (!image || !obs || !level_weights || !terms || !scratch)
-		return fail(what, "image, obs, level_weights, terms or scratch == NULL");
-	if (const char *why = pyramid_dims(n, H, W, C, levels))
-		return fail(what, why);
-	const size_t elem = elem_bytes(pixel_dtype);
-	if (!elem)
-		return fail(what, "pixel_dtype must be DEODR_HIP_F32 or DEODR_HIP_F64");
-	const void *const pixels[] = {image, obs, weights, image_b};
-	const void *const doubles[] = {level_weights, terms, loss, scratch};
-	if (any_misaligned(pixels, elem) || any_misaligned(doubles, 8))
-		return fail(what, "misaligned pointer");
+	const size_t lam = 8 * ((size_t)levels + 1);
+	if (image_term_refused("pyramid_l2", image, obs, weights, image_b, level_weights, "level_weights", lam, terms, lam, loss, scratch, scratch_bytes,
+						   deodr_hip_pyramid_scratch_bytes(n, H, W, C, levels), "deodr_hip_pyramid_scratch_bytes", pyramid_dims(n, H, W, C, levels), NULL, n, H, W,
+						   C, pixel_dtype))
+		return 1;
 	const Scratch sc = {scratch, scratch_bytes};
-	if (!sc.holds(deodr_hip_pyramid_scratch_bytes(n, H, W, C, levels)))
-		return fail(what, "scratch too small (deodr_hip_pyramid_scratch_bytes)");
-	const size_t frame = (size_t)n * H * W * elem, lam = 8 * ((size_t)levels + 1);
-	const Range outputs[] = {{terms, lam}, {loss, 8}, {image_b, frame * C}, {scratch, scratch_bytes}};
-	const Range inputs[] = {{image, frame * C}, {obs, frame * C}, {weights, frame}, {level_weights, lam}};
-	if (any_overlap(outputs, inputs) || any_overlap(outputs))
-		return fail(what, "an output must not overlap an input, the scratch or another output");
 	const PyramidLayout l = pyramid_layout(n, H, W, C, levels);
 	double *const d = sc.doubles();
 	const PyramidArgs a = {image, obs, weights, image_b, level_weights, terms, loss, d + l.partials_tile, d + l.partials_coarse, d + l.tile_w,
@@ -1890,9 +1905,7 @@ const char *ssim_dims(int n, int H, int W, int C)
 { // -> NULL, or which limit of the header the dimensions break
 	if (n < 1 || H < 1 || W < 1 || C < 1)
 		return "n, H, W and C must be >= 1";
-	if ((double)n * H * W * C >= 1099511627776.0)
-		return "n H W C must be below 2^40";
-	return NULL;
+	return image_term_size(n, H, W, C);
 }
 } // namespace
 
@@ -1904,28 +1917,11 @@ size_t deodr_hip_ssim_scratch_bytes(int n, int H, int W, int C)
 int deodr_hip_ssim_l2(const void *image, const void *obs, const void *weights, int n, int H, int W, int C, int pixel_dtype, double data_range,
 					  const double *mix, double *terms, double *loss, void *image_b, void *scratch, size_t scratch_bytes, void *stream)
 {
-	const char *what = "ssim_l2";
-	if (!image || !obs || !mix || !terms || !scratch)
-		return fail(what, "image, obs, mix, terms or scratch == NULL");
-	if (const char *why = ssim_dims(n, H, W, C))
-		return fail(what, why);
-	if (!(data_range > 0) || !__builtin_isfinite(data_range))
-		return fail(what, "data_range must be finite and > 0");
-	const size_t elem = elem_bytes(pixel_dtype);
-	if (!elem)
-		return fail(what, "pixel_dtype must be DEODR_HIP_F32 or DEODR_HIP_F64");
-	const void *const pixels[] = {image, obs, weights, image_b};
-	const void *const doubles[] = {mix, terms, loss, scratch};
-	if (any_misaligned(pixels, elem) || any_misaligned(doubles, 8))
-		return fail(what, "misaligned pointer");
+	const char *const range = data_range > 0 && __builtin_isfinite(data_range) ? NULL : "data_range must be finite and > 0";
+	if (image_term_refused("ssim_l2", image, obs, weights, image_b, mix, "mix", 16, terms, 16, loss, scratch, scratch_bytes, deodr_hip_ssim_scratch_bytes(n, H, W, C),
+						   "deodr_hip_ssim_scratch_bytes", ssim_dims(n, H, W, C), range, n, H, W, C, pixel_dtype))
+		return 1;
 	const Scratch sc = {scratch, scratch_bytes};
-	if (!sc.holds(deodr_hip_ssim_scratch_bytes(n, H, W, C)))
-		return fail(what, "scratch too small (deodr_hip_ssim_scratch_bytes)");
-	const size_t frame = (size_t)n * H * W * elem;
-	const Range outputs[] = {{terms, 16}, {loss, 8}, {image_b, frame * C}, {scratch, scratch_bytes}};
-	const Range inputs[] = {{image, frame * C}, {obs, frame * C}, {weights, frame}, {mix, 16}};
-	if (any_overlap(outputs, inputs) || any_overlap(outputs))
-		return fail(what, "an output must not overlap an input, the scratch or another output");
 	double *const d = sc.doubles();
 	const int TY = (H + SSIM_TH - 1) / SSIM_TH, TX = (W + SSIM_TW - 1) / SSIM_TW;
 	const double c1 = 0.01 * data_range, c2 = 0.03 * data_range;

@@ -439,25 +439,22 @@ class SkinFunc(torch.autograd.Function):
         return v_b, q_b, c_b, None
 
 
-_pyramid_scratches = {}  # (device, n, H, W, C, levels) -> the scratch of PyramidL2Func (the kernels of one stream run one after the other)
+_image_term_scratches = {}  # (operator, device, n, H, W, C[, levels]) -> the scratch of the two classes below (the kernels of one stream run one after the other)
 
 
-def _pyramid_scratch(image, levels):
-    key = (image.device, *(int(v) for v in image.shape), levels)
-    if key not in _pyramid_scratches:
-        _pyramid_scratches[key] = hr.pyramid_scratch(*key[1:], image.device)
-    return _pyramid_scratches[key]
+class _ImageTermFunc(torch.autograd.Function):
+    """What the image data terms below share: (image [n,H,W,C]; obs, weights [n,H,W] | None, the term's float64 array on the device, its number:
+    constants) -> the loss, a float64 scalar.  The forward call computes d loss / d image as well and keeps it; the backward multiplies it by the
+    incoming scalar.  A term states ``operator(image, obs, weights, array, number, **how)``, its ``scratch`` maker and whether the number is one of
+    that maker's dimensions (``sized_by_number``)."""
 
-
-class PyramidL2Func(torch.autograd.Function):
-    """(image [n,H,W,C]; obs, weights [n,H,W] | None, level_weights [levels+1] float64 on the device, levels: constants) -> the multi-scale L2 loss
-    (``deodr_amd/pyramid.py`` has the formulas), a float64 scalar.  The forward call computes d loss / d image as well and keeps it; the backward
-    multiplies it by the incoming scalar."""
-
-    @staticmethod
-    def forward(ctx, image, obs, weights, level_weights, levels):
+    @classmethod
+    def forward(cls, ctx, image, obs, weights, array, number):
+        key = (cls.operator, image.device, *(int(v) for v in image.shape), *((number,) if cls.sized_by_number else ()))
+        if key not in _image_term_scratches:
+            _image_term_scratches[key] = cls.scratch(*key[2:], image.device)
         want = ctx.needs_input_grad[0]
-        _terms, loss, image_b = hr.pyramid_l2(image, obs, weights, levels, level_weights, scratch=_pyramid_scratch(image, levels), want_gradient=want)
+        _terms, loss, image_b = cls.operator(image, obs, weights, array, number, scratch=_image_term_scratches[key], want_gradient=want)
         if want:
             ctx.save_for_backward(image_b)
         return loss.reshape(())
@@ -468,33 +465,18 @@ class PyramidL2Func(torch.autograd.Function):
         return image_b * loss_b.to(image_b.dtype), None, None, None, None
 
 
-_ssim_scratches = {}  # (device, n, H, W, C) -> the scratch of SSIML2Func (the kernels of one stream run one after the other)
+class PyramidL2Func(_ImageTermFunc):
+    """``apply(image, obs, weights, level_weights [levels+1], levels)`` -> the multi-scale L2 loss (``deodr_amd/pyramid.py`` has the formulas)"""
+
+    scratch, sized_by_number = staticmethod(hr.pyramid_scratch), True
+    operator = staticmethod(lambda image, obs, weights, level_weights, levels, **how: hr.pyramid_l2(image, obs, weights, levels, level_weights, **how))
 
 
-def _ssim_scratch(image):
-    key = (image.device, *(int(v) for v in image.shape))
-    if key not in _ssim_scratches:
-        _ssim_scratches[key] = hr.ssim_scratch(*key[1:], image.device)
-    return _ssim_scratches[key]
+class SSIML2Func(_ImageTermFunc):
+    """``apply(image, obs, weights, mix [2], data_range)`` -> the mix of the pixel term and the structural term (``deodr_amd/ssim.py`` has the formulas)"""
 
-
-class SSIML2Func(torch.autograd.Function):
-    """(image [n,H,W,C]; obs, weights [n,H,W] | None, mix [2] float64 on the device, data_range: constants) -> the mix of the pixel term and the
-    structural term (``deodr_amd/ssim.py`` has the formulas), a float64 scalar.  The forward call computes d loss / d image as well and keeps it; the
-    backward multiplies it by the incoming scalar."""
-
-    @staticmethod
-    def forward(ctx, image, obs, weights, mix, data_range):
-        want = ctx.needs_input_grad[0]
-        _terms, loss, image_b = hr.ssim_l2(image, obs, weights, mix, data_range, scratch=_ssim_scratch(image), want_gradient=want)
-        if want:
-            ctx.save_for_backward(image_b)
-        return loss.reshape(())
-
-    @staticmethod
-    def backward(ctx, loss_b):
-        (image_b,) = ctx.saved_tensors
-        return image_b * loss_b.to(image_b.dtype), None, None, None, None
+    scratch, sized_by_number = staticmethod(hr.ssim_scratch), False
+    operator = staticmethod(hr.ssim_l2)
 
 
 class SpdSolveFunc(torch.autograd.Function):

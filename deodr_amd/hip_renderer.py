@@ -217,16 +217,29 @@ def _check_tensors(what, anchor, device, rows):
 _scratch_cache = {}  # (whose, device, stream) -> a zero-filled scratch of the library, grown to the largest request
 
 
-def _cached_scratch(whose, device, need, make, when_capturing):
-    """the scratch ``whose`` kernels use on the current stream of ``device``, at least ``need`` bytes: made (``make()``) or grown at the call, which a
-    stream that is being captured into a graph cannot do -- RuntimeError(``when_capturing``)"""
+def _own_or_cached_scratch(what, scratch, whose, device, need, make, *dims):
+    """``scratch`` where the caller of ``what`` gave one.  None: the scratch the kernels of the family ``whose`` use on the current stream of
+    ``device``, at least ``need`` bytes (a number, or the library's ``*_scratch_bytes`` to ask for ``dims``): made (``make(*dims, device)``) or
+    grown at the call, which a stream that is being captured into a graph cannot do -- RuntimeError"""
+    if scratch is not None:
+        return scratch
+    need = int(need(*dims)) if callable(need) else need
     key = (whose, device, torch.cuda.current_stream(device).cuda_stream)
     scratch = _scratch_cache.get(key)
     if scratch is None or scratch.numel() < need:
         if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError(when_capturing)
-        scratch = _scratch_cache[key] = make()
+            sized = " of this size" if dims else ""  # (a scratch without dimensions has one size)
+            raise RuntimeError(f"{what}: pass scratch= ({make.__name__}) when capturing a graph: none{sized} exists for this stream yet")
+        scratch = _scratch_cache[key] = make(*dims, device)
     return scratch
+
+
+def _byte_scratch(what, dims, need, header, device, zeroed=False):
+    """``need`` bytes (what the library's ``*_scratch_bytes`` gave for ``dims``; 0: refused) of scratch on ``device``, uninitialised or ``zeroed``"""
+    if need == 0:
+        raise ValueError(f"{what}: {dims} is outside the limits of include/{header}")
+    with torch.cuda.device(device):
+        return (torch.zeros if zeroed else torch.empty)(int(need), dtype=torch.uint8, device=device)
 
 
 # ---- texture estimation (include/deodr_hip_texture.h) ---------------------------------------------------------------------------------
@@ -247,8 +260,8 @@ def _texture_args(what, texture, others):
 
 def texture_scratch(device):
     """the scratch of :func:`texture_smoothness`, zero-filled as the library wants it once; for a caller that keeps its own (one per stream in use)"""
-    with torch.cuda.device(device):
-        return torch.zeros(int(lib().deodr_hip_texture_scratch_bytes(2, 2, 1)), dtype=torch.uint8, device=device)  # (the size does not depend on the texture)
+    need = lib().deodr_hip_texture_scratch_bytes(2, 2, 1)  # (the size does not depend on the texture)
+    return _byte_scratch("texture_scratch", "", need, "deodr_hip_texture.h", device, zeroed=True)
 
 
 def texture_smoothness(texture, gradient, weight, energy_out=None, scratch=None):
@@ -264,11 +277,9 @@ def texture_smoothness(texture, gradient, weight, energy_out=None, scratch=None)
             energy_out = torch.empty(1, dtype=torch.float64, device=dev)
         if energy_out.dtype != torch.float64 or energy_out.device != dev or energy_out.numel() != 1:
             raise ValueError(f"{what}: energy_out must be a float64 tensor of one element on the texture's device")
-        if scratch is None:
-            scratch = _cached_scratch("texture", dev, 0, lambda: texture_scratch(dev),
-                                      f"{what}: pass scratch= (texture_scratch) when capturing a graph: none exists for this stream yet")  # fmt: skip
-        elif scratch.device != dev or scratch.dtype != torch.uint8 or not scratch.is_contiguous():
+        if scratch is not None and (scratch.device != dev or scratch.dtype != torch.uint8 or not scratch.is_contiguous()):
             raise ValueError(f"{what}: scratch must be a texture_scratch() of the texture's device")
+        scratch = _own_or_cached_scratch(what, scratch, "texture", dev, 0, texture_scratch)
     _launch(lib().deodr_hip_texture_smoothness, dev, _ptr(texture), *dims, float(weight), _ptr(gradient), _ptr(energy_out), _ptr(scratch), scratch.numel())
     return energy_out
 
@@ -374,11 +385,8 @@ def basis_segments(K, N):
 def basis_scratch(K, N, batch, device):
     """the scratch of :func:`basis_apply_b` for a [K, N] basis and ``batch`` gradient vectors, zero-filled as the library wants it once; for a
     caller that keeps its own (one per stream in use; a fitter whose step is captured in a graph)"""
-    need = int(lib().deodr_hip_basis_scratch_bytes(int(K), int(N), int(batch)))
-    if need == 0:
-        raise ValueError(f"basis_scratch: K = {K}, N = {N}, batch = {batch} is outside the limits of include/deodr_hip_basis.h")
-    with torch.cuda.device(device):
-        return torch.zeros(need, dtype=torch.uint8, device=device)
+    need = lib().deodr_hip_basis_scratch_bytes(int(K), int(N), int(batch))
+    return _byte_scratch("basis_scratch", f"K = {K}, N = {N}, batch = {batch}", need, "deodr_hip_basis.h", device, zeroed=True)
 
 
 def basis_apply(basis, mean, coeffs, out=None, out_dtype=None):
@@ -435,9 +443,7 @@ def basis_apply_b(basis, g, out=None, accumulate=False, scratch=None):
     with torch.cuda.device(dev):
         if out is None:
             out = torch.empty((batch, K), dtype=torch.float64, device=dev)
-        if scratch is None:
-            scratch = _cached_scratch("basis", dev, int(lib().deodr_hip_basis_scratch_bytes(K, N, batch)), lambda: basis_scratch(K, N, batch, dev),
-                                      f"{what}: pass scratch= (basis_scratch) when capturing a graph: none of this size exists for this stream yet")  # fmt: skip
+        scratch = _own_or_cached_scratch(what, scratch, "basis", dev, lib().deodr_hip_basis_scratch_bytes, basis_scratch, K, N, batch)
     _launch(lib().deodr_hip_basis_apply_b, dev, _ptr(basis), _ptr(g), _dtype_tag(g), K, N, batch, _dtype_tag(basis), _ptr(out), int(bool(accumulate)),
             _ptr(scratch), scratch.numel())  # fmt: skip
     _touched(out)
@@ -465,11 +471,8 @@ def camera_blocks(V, n):
 
 def camera_scratch(V, n, device):
     """the scratch of :func:`camera_project_b` for V vertices and n views, zero-filled as the library wants it once (one per stream in use)"""
-    need = int(lib().deodr_hip_camera_scratch_bytes(int(V), int(n)))
-    if need == 0:
-        raise ValueError(f"camera_scratch: V = {V}, n = {n} is outside the limits of include/deodr_hip_camera.h")
-    with torch.cuda.device(device):
-        return torch.zeros(need, dtype=torch.uint8, device=device)
+    need = lib().deodr_hip_camera_scratch_bytes(int(V), int(n))
+    return _byte_scratch("camera_scratch", f"V = {V}, n = {n}", need, "deodr_hip_camera.h", device, zeroed=True)
 
 
 def camera_project_b(points, extrinsic, intrinsic, distortion, ij_b, depths_b=None, points_b=None, extrinsic_b=None, intrinsic_b=None,
@@ -506,9 +509,7 @@ def camera_project_b(points, extrinsic, intrinsic, distortion, ij_b, depths_b=No
             intrinsic_b = torch.empty((n, 3, 3), dtype=torch.float64, device=dev)
         if distortion is not None and distortion_b is None:
             distortion_b = torch.empty((n, 5), dtype=torch.float64, device=dev)
-        if scratch is None:
-            scratch = _cached_scratch("camera", dev, int(lib().deodr_hip_camera_scratch_bytes(V, n)), lambda: camera_scratch(V, n, dev),
-                                      f"{what}: pass scratch= (camera_scratch) when capturing a graph: none of this size exists for this stream yet")  # fmt: skip
+        scratch = _own_or_cached_scratch(what, scratch, "camera", dev, lib().deodr_hip_camera_scratch_bytes, camera_scratch, V, n)
     _launch(lib().deodr_hip_camera_project_b, dev, _ptr(points), _ptr(extrinsic), _ptr(intrinsic), _ptr(distortion), _ptr(ij_b), _ptr(depths_b),
             _ptr(points_b), _ptr(extrinsic_b), _ptr(intrinsic_b), _ptr(distortion_b), V, n, int(bool(accumulate)), _ptr(scratch), scratch.numel())  # fmt: skip
     for t in (points_b, extrinsic_b, intrinsic_b, distortion_b):
@@ -1126,11 +1127,8 @@ def sh_blocks(V, n):
 
 def sh_scratch(V, n, C, device):
     """the scratch of :func:`sh_shade_b` for V vertices, n views and C channels, zero-filled as the library wants it once (one per stream in use)"""
-    need = int(lib().deodr_hip_sh_scratch_bytes(int(V), int(n), int(C)))
-    if need == 0:
-        raise ValueError(f"sh_scratch: V = {V}, n = {n}, C = {C} is outside the limits of include/deodr_hip_lighting.h")
-    with torch.cuda.device(device):
-        return torch.zeros(need, dtype=torch.uint8, device=device)
+    need = lib().deodr_hip_sh_scratch_bytes(int(V), int(n), int(C))
+    return _byte_scratch("sh_scratch", f"V = {V}, n = {n}, C = {C}", need, "deodr_hip_lighting.h", device, zeroed=True)
 
 
 def sh_products(scratch, V, n, C):
@@ -1217,9 +1215,7 @@ def sh_shade_b(posed, faces, vf_offsets, vf_corners, sh, albedo=None, luminosity
             sh_b = torch.empty_like(sh)
         if albedo_b is None and want_albedo and albedo is not None:
             albedo_b = torch.empty_like(albedo)
-        if scratch is None:
-            scratch = _cached_scratch("sh", dev, int(lib().deodr_hip_sh_scratch_bytes(V, n, C)), lambda: sh_scratch(V, n, C, dev),
-                                      f"{what}: pass scratch= (sh_scratch) when capturing a graph: none of this size exists for this stream yet")  # fmt: skip
+        scratch = _own_or_cached_scratch(what, scratch, "sh", dev, lib().deodr_hip_sh_scratch_bytes, sh_scratch, V, n, C)
     _launch(lib().deodr_hip_sh_shade_b, dev, _ptr(posed), _ptr(faces), _ptr(vf_offsets), _ptr(vf_corners), _ptr(sh), S, _ptr(albedo), int(per_vertex), C,
             _ptr(luminosity_b), _ptr(colors_b), _ptr(posed_b), _ptr(sh_b), _ptr(albedo_b), int(bool(accumulate)), _ptr(scratch), scratch.numel(), V, n,
             int(bool(clockwise)))  # fmt: skip
@@ -1236,11 +1232,8 @@ SKIN_MAX_VIEWS, SKIN_MAX_JOINTS, SKIN_MAX_INFLUENCES, SKIN_MAX_VERTICES = 64, 25
 
 def skin_scratch(V, J, K, n, device):
     """the scratch of :func:`skin_apply_b` for V vertices, J joints, K influences per vertex and n poses (one per stream in use)"""
-    need = int(lib().deodr_hip_skin_scratch_bytes(int(V), int(J), int(K), int(n)))
-    if need == 0:
-        raise ValueError(f"skin_scratch: V = {V}, J = {J}, K = {K}, n = {n} is outside the limits of include/deodr_hip_skinning.h")
-    with torch.cuda.device(device):
-        return torch.zeros(need, dtype=torch.uint8, device=device)
+    need = lib().deodr_hip_skin_scratch_bytes(int(V), int(J), int(K), int(n))
+    return _byte_scratch("skin_scratch", f"V = {V}, J = {J}, K = {K}, n = {n}", need, "deodr_hip_skinning.h", device, zeroed=True)
 
 
 def _skin_args(what, vertices, joints, parents, quaternions, indices, weights):
@@ -1304,9 +1297,7 @@ def skin_apply_b(vertices, joints, parents, quaternions, indices, weights, world
     with torch.cuda.device(dev):
         vertices_b, quaternions_b, joints_b = (torch.empty(shape, dtype=torch.float64, device=dev) if t is None and w else t
                                                for w, (_, t, shape) in zip(want, optional))  # fmt: skip
-        if scratch is None:
-            scratch = _cached_scratch("skin", dev, int(lib().deodr_hip_skin_scratch_bytes(V, J, K, n)), lambda: skin_scratch(V, J, K, n, dev),
-                                      f"{what}: pass scratch= (skin_scratch) when capturing a graph: none of this size exists for this stream yet")  # fmt: skip
+        scratch = _own_or_cached_scratch(what, scratch, "skin", dev, lib().deodr_hip_skin_scratch_bytes, skin_scratch, V, J, K, n)
     # (a table without entries: torch gives an empty tensor no address, the library wants one it never reads)
     slots = joint_slots if nnz else joint_offsets
     _launch(lib().deodr_hip_skin_apply_b, dev, _ptr(vertices), _ptr(joints), _ptr(parents), _ptr(quaternions), _ptr(indices), _ptr(weights), _ptr(world),
@@ -1318,6 +1309,43 @@ def skin_apply_b(vertices, joints, parents, quaternions, indices, weights, world
     return vertices_b, quaternions_b, joints_b
 
 
+# ---- the image data terms: multi-scale L2 (include/deodr_hip_pyramid.h) and structural (include/deodr_hip_ssim.h) ------------------------------
+
+
+def _image_term(what, header, make_scratch, image, obs, weights, array_name, array, scalar, terms, loss, image_b, scratch, want_gradient):
+    """What :func:`pyramid_l2` and :func:`ssim_l2` share: the checks of their tensors, the results and the scratch where none were given, the call
+    ``deodr_hip_<what>``.  ``array``: the term's float64 parameters on the device, called ``array_name``; ``scalar(what)`` checks the term's number
+    -> (the number as the library takes it, the length of ``array`` and of ``terms``, what it adds to (n, H, W, C) for the scratch).  -> (terms,
+    loss, image_b)"""
+    _rocm_tensor(what, "image", image)
+    if image.dim() != 4 or min(image.shape) < 1:
+        raise ValueError(f"{what}: image must have shape [n >= 1, H >= 1, W >= 1, C >= 1], not {list(image.shape)}")
+    n, H, W, Cn = (int(v) for v in image.shape)
+    number, length, extra = scalar(what)
+    pix = (image.dtype,)
+    rows = [("image", image, _FLOATS, None), ("obs", obs, pix, (n, H, W, Cn)), (array_name, array, _F64_ONLY, (length,))]
+    optional = (("weights", weights, pix, (n, H, W)), ("terms", terms, _F64_ONLY, (length,)), ("loss", loss, _F64_ONLY, (1,)),
+                ("image_b", image_b, pix, (n, H, W, Cn)), ("scratch", scratch, (torch.uint8,), (None,)))  # fmt: skip
+    rows += [row for row in optional if row[1] is not None]
+    _check_tensors(what, "image", image.device, rows)
+    dev, family = image.device, make_scratch.__name__[: -len("_scratch")]
+    need = int(getattr(lib(), f"deodr_hip_{family}_scratch_bytes")(n, H, W, Cn, *extra))
+    if need == 0:
+        raise ValueError(f"{what}: image of shape {list(image.shape)} is outside the limits of include/{header}")
+    with torch.cuda.device(dev):
+        terms = torch.empty(length, dtype=torch.float64, device=dev) if terms is None else terms
+        loss = torch.empty(1, dtype=torch.float64, device=dev) if loss is None else loss
+        if image_b is None and want_gradient:
+            image_b = torch.empty_like(image)
+        scratch = _own_or_cached_scratch(what, scratch, family, dev, need, make_scratch, n, H, W, Cn, *extra)
+    _launch(getattr(lib(), f"deodr_hip_{what}"), dev, _ptr(image), _ptr(obs), _ptr(weights), n, H, W, Cn, _dtype_tag(image), number, _ptr(array),
+            _ptr(terms), _ptr(loss), _ptr(image_b), _ptr(scratch), scratch.numel())  # fmt: skip
+    for t in (terms, loss, image_b):
+        if t is not None:
+            _touched(t)
+    return terms, loss, image_b
+
+
 # ---- the multi-scale L2 data term (include/deodr_hip_pyramid.h) ---------------------------------------------------------------------------
 
 PYRAMID_MAX_LEVELS = _abi.PYRAMID_HEADER.defines["DEODR_HIP_PYRAMID_MAX_LEVELS"]
@@ -1325,11 +1353,8 @@ PYRAMID_MAX_LEVELS = _abi.PYRAMID_HEADER.defines["DEODR_HIP_PYRAMID_MAX_LEVELS"]
 
 def pyramid_scratch(n, H, W, C, levels, device):
     """the scratch of :func:`pyramid_l2` for n frames of H x W x C and ``levels`` coarse levels (one per stream in use; it need not be zeroed)"""
-    need = int(lib().deodr_hip_pyramid_scratch_bytes(int(n), int(H), int(W), int(C), int(levels)))
-    if need == 0:
-        raise ValueError(f"pyramid_scratch: n = {n}, H = {H}, W = {W}, C = {C}, levels = {levels} is outside the limits of include/deodr_hip_pyramid.h")
-    with torch.cuda.device(device):
-        return torch.empty(need, dtype=torch.uint8, device=device)
+    need = lib().deodr_hip_pyramid_scratch_bytes(int(n), int(H), int(W), int(C), int(levels))
+    return _byte_scratch("pyramid_scratch", f"n = {n}, H = {H}, W = {W}, C = {C}, levels = {levels}", need, "deodr_hip_pyramid.h", device)
 
 
 def pyramid_l2(image, obs, weights, levels, level_weights, terms=None, loss=None, image_b=None, scratch=None, want_gradient=True):
@@ -1338,38 +1363,14 @@ def pyramid_l2(image, obs, weights, levels, level_weights, terms=None, loss=None
     [n,H,W,C] float32 / float64 contiguous ROCm tensors, ``weights`` [n,H,W] of the same dtype or None, ``level_weights`` [levels+1] float64 ON THE
     DEVICE (read when the kernels run).  ``image_b`` is allocated when None and ``want_gradient``.  Deterministic; asynchronous on the current
     stream.  ``scratch``: a :func:`pyramid_scratch` of the caller's; None: one per device and stream."""
-    what = "pyramid_l2"
-    _rocm_tensor(what, "image", image)
-    if image.dim() != 4 or min(image.shape) < 1:
-        raise ValueError(f"{what}: image must have shape [n >= 1, H >= 1, W >= 1, C >= 1], not {list(image.shape)}")
-    n, H, W, Cn = (int(v) for v in image.shape)
-    levels = int(levels)
-    if not 1 <= levels <= PYRAMID_MAX_LEVELS:
-        raise ValueError(f"{what}: levels must be in 1 .. {PYRAMID_MAX_LEVELS}, not {levels}")
-    pix = (image.dtype,)
-    rows = [("image", image, _FLOATS, None), ("obs", obs, pix, (n, H, W, Cn)), ("level_weights", level_weights, _F64_ONLY, (levels + 1,))]
-    optional = (("weights", weights, pix, (n, H, W)), ("terms", terms, _F64_ONLY, (levels + 1,)), ("loss", loss, _F64_ONLY, (1,)),
-                ("image_b", image_b, pix, (n, H, W, Cn)), ("scratch", scratch, (torch.uint8,), (None,)))  # fmt: skip
-    rows += [row for row in optional if row[1] is not None]
-    _check_tensors(what, "image", image.device, rows)
-    dev = image.device
-    need = int(lib().deodr_hip_pyramid_scratch_bytes(n, H, W, Cn, levels))
-    if need == 0:
-        raise ValueError(f"{what}: image of shape {list(image.shape)} is outside the limits of include/deodr_hip_pyramid.h")
-    with torch.cuda.device(dev):
-        terms = torch.empty(levels + 1, dtype=torch.float64, device=dev) if terms is None else terms
-        loss = torch.empty(1, dtype=torch.float64, device=dev) if loss is None else loss
-        if image_b is None and want_gradient:
-            image_b = torch.empty_like(image)
-        if scratch is None:
-            scratch = _cached_scratch("pyramid", dev, need, lambda: pyramid_scratch(n, H, W, Cn, levels, dev),
-                                      f"{what}: pass scratch= (pyramid_scratch) when capturing a graph: none of this size exists for this stream yet")  # fmt: skip
-    _launch(lib().deodr_hip_pyramid_l2, dev, _ptr(image), _ptr(obs), _ptr(weights), n, H, W, Cn, _dtype_tag(image), levels, _ptr(level_weights),
-            _ptr(terms), _ptr(loss), _ptr(image_b), _ptr(scratch), scratch.numel())  # fmt: skip
-    for t in (terms, loss, image_b):
-        if t is not None:
-            _touched(t)
-    return terms, loss, image_b
+    def checked_levels(what):
+        count = int(levels)
+        if not 1 <= count <= PYRAMID_MAX_LEVELS:
+            raise ValueError(f"{what}: levels must be in 1 .. {PYRAMID_MAX_LEVELS}, not {count}")
+        return count, count + 1, (count,)
+
+    return _image_term("pyramid_l2", "deodr_hip_pyramid.h", pyramid_scratch, image, obs, weights, "level_weights", level_weights, checked_levels, terms, loss,
+                       image_b, scratch, want_gradient)  # fmt: skip
 
 
 # ---- the structural (SSIM) data term (include/deodr_hip_ssim.h) ----------------------------------------------------------------------------
@@ -1379,11 +1380,8 @@ SSIM_WINDOW = _abi.SSIM_HEADER.defines["DEODR_HIP_SSIM_WINDOW"]
 
 def ssim_scratch(n, H, W, C, device):
     """the scratch of :func:`ssim_l2` for n frames of H x W x C (one per stream in use; it need not be zeroed)"""
-    need = int(lib().deodr_hip_ssim_scratch_bytes(int(n), int(H), int(W), int(C)))
-    if need == 0:
-        raise ValueError(f"ssim_scratch: n = {n}, H = {H}, W = {W}, C = {C} is outside the limits of include/deodr_hip_ssim.h")
-    with torch.cuda.device(device):
-        return torch.empty(need, dtype=torch.uint8, device=device)
+    need = lib().deodr_hip_ssim_scratch_bytes(int(n), int(H), int(W), int(C))
+    return _byte_scratch("ssim_scratch", f"n = {n}, H = {H}, W = {W}, C = {C}", need, "deodr_hip_ssim.h", device)
 
 
 def ssim_l2(image, obs, weights, mix, data_range=1.0, terms=None, loss=None, image_b=None, scratch=None, want_gradient=True):
@@ -1393,38 +1391,13 @@ def ssim_l2(image, obs, weights, mix, data_range=1.0, terms=None, loss=None, ima
     not enter the windows, so ``image_b`` is in general not 0 where a weight is --, ``mix`` [2] float64 ON THE DEVICE (read when the kernels run).
     ``image_b`` is allocated when None and ``want_gradient``.  Deterministic; asynchronous on the current stream.  ``scratch``: a
     :func:`ssim_scratch` of the caller's; None: one per device and stream."""
-    what = "ssim_l2"
-    _rocm_tensor(what, "image", image)
-    if image.dim() != 4 or min(image.shape) < 1:
-        raise ValueError(f"{what}: image must have shape [n >= 1, H >= 1, W >= 1, C >= 1], not {list(image.shape)}")
-    n, H, W, Cn = (int(v) for v in image.shape)
-    data_range = float(data_range)
-    if not (data_range > 0 and data_range < float("inf")):
-        raise ValueError(f"{what}: data_range must be finite and > 0, not {data_range}")
-    pix = (image.dtype,)
-    rows = [("image", image, _FLOATS, None), ("obs", obs, pix, (n, H, W, Cn)), ("mix", mix, _F64_ONLY, (2,))]
-    optional = (("weights", weights, pix, (n, H, W)), ("terms", terms, _F64_ONLY, (2,)), ("loss", loss, _F64_ONLY, (1,)),
-                ("image_b", image_b, pix, (n, H, W, Cn)), ("scratch", scratch, (torch.uint8,), (None,)))  # fmt: skip
-    rows += [row for row in optional if row[1] is not None]
-    _check_tensors(what, "image", image.device, rows)
-    dev = image.device
-    need = int(lib().deodr_hip_ssim_scratch_bytes(n, H, W, Cn))
-    if need == 0:
-        raise ValueError(f"{what}: image of shape {list(image.shape)} is outside the limits of include/deodr_hip_ssim.h")
-    with torch.cuda.device(dev):
-        terms = torch.empty(2, dtype=torch.float64, device=dev) if terms is None else terms
-        loss = torch.empty(1, dtype=torch.float64, device=dev) if loss is None else loss
-        if image_b is None and want_gradient:
-            image_b = torch.empty_like(image)
-        if scratch is None:
-            scratch = _cached_scratch("ssim", dev, need, lambda: ssim_scratch(n, H, W, Cn, dev),
-                                      f"{what}: pass scratch= (ssim_scratch) when capturing a graph: none of this size exists for this stream yet")  # fmt: skip
-    _launch(lib().deodr_hip_ssim_l2, dev, _ptr(image), _ptr(obs), _ptr(weights), n, H, W, Cn, _dtype_tag(image), data_range, _ptr(mix),
-            _ptr(terms), _ptr(loss), _ptr(image_b), _ptr(scratch), scratch.numel())  # fmt: skip
-    for t in (terms, loss, image_b):
-        if t is not None:
-            _touched(t)
-    return terms, loss, image_b
+    def checked_range(what):
+        span = float(data_range)
+        if not (span > 0 and span < float("inf")):
+            raise ValueError(f"{what}: data_range must be finite and > 0, not {span}")
+        return span, 2, ()
+
+    return _image_term("ssim_l2", "deodr_hip_ssim.h", ssim_scratch, image, obs, weights, "mix", mix, checked_range, terms, loss, image_b, scratch, want_gradient)
 
 
 # ---- sparse symmetric positive definite solve (include/deodr_hip_solve.h) -----------------------------------------------------------------
@@ -1440,11 +1413,8 @@ def spd_launches(n, nnz, D, iterations):
 
 def spd_scratch(n, D, device):
     """the scratch of :func:`spd_solve` for a system of n rows and D columns (one per stream in use; it need not be zeroed)"""
-    need = int(lib().deodr_hip_spd_solve_scratch_bytes(int(n), int(D)))
-    if need == 0:
-        raise ValueError(f"spd_scratch: n = {n}, D = {D} is outside the limits of include/deodr_hip_solve.h")
-    with torch.cuda.device(device):
-        return torch.empty(need, dtype=torch.uint8, device=device)
+    need = lib().deodr_hip_spd_solve_scratch_bytes(int(n), int(D))
+    return _byte_scratch("spd_scratch", f"n = {n}, D = {D}", need, "deodr_hip_solve.h", device)
 
 
 def spd_solve(offsets, cols, vals, b, iterations, rel_tol=0.0, x=None, residual=None, scratch=None):
@@ -1478,10 +1448,7 @@ def spd_solve(offsets, cols, vals, b, iterations, rel_tol=0.0, x=None, residual=
     with torch.cuda.device(dev):
         x = torch.empty_like(b) if x is None else x
         residual = torch.empty(D, dtype=torch.float64, device=dev) if residual is None else residual
-        if scratch is None:
-            need = int(lib().deodr_hip_spd_solve_scratch_bytes(n, D))
-            scratch = _cached_scratch("solve", dev, need, lambda: spd_scratch(n, D, dev),
-                                      f"{what}: pass scratch= (spd_scratch) when capturing a graph: none of this size exists for this stream yet")  # fmt: skip
+        scratch = _own_or_cached_scratch(what, scratch, "solve", dev, lib().deodr_hip_spd_solve_scratch_bytes, spd_scratch, n, D)
     _launch(lib().deodr_hip_spd_solve, dev, _ptr(offsets), _ptr(cols), _ptr(vals), n, nnz, _ptr(b), _ptr(x), D, iterations, rel_tol, _ptr(residual),
             _ptr(scratch), scratch.numel())  # fmt: skip
     _touched(x), _touched(residual)
@@ -1505,11 +1472,8 @@ def arap_blocks(V):
 
 def arap_scratch(V, n, device):
     """the scratch of :func:`arap_energy` for n poses of V vertices (one per stream in use; it need not be zeroed)"""
-    need = int(lib().deodr_hip_arap_scratch_bytes(int(V), int(n)))
-    if need == 0:
-        raise ValueError(f"arap_scratch: V = {V}, n = {n} is outside the limits of include/deodr_hip_arap.h")
-    with torch.cuda.device(device):
-        return torch.empty(need, dtype=torch.uint8, device=device)
+    need = lib().deodr_hip_arap_scratch_bytes(int(V), int(n))
+    return _byte_scratch("arap_scratch", f"V = {V}, n = {n}", need, "deodr_hip_arap.h", device)
 
 
 def arap_energy(offsets, cols, weights, vertices_ref, vertices, cregu, energy=None, gradient=None, rotations=None, scratch=None, want_rotations=False):
@@ -1543,10 +1507,7 @@ def arap_energy(offsets, cols, weights, vertices_ref, vertices, cregu, energy=No
         gradient = torch.empty_like(vertices) if gradient is None else gradient
         if rotations is None and want_rotations:
             rotations = torch.empty((n, V, 4), dtype=torch.float64, device=dev)
-        if scratch is None:
-            need = int(lib().deodr_hip_arap_scratch_bytes(V, n))
-            scratch = _cached_scratch("arap", dev, need, lambda: arap_scratch(V, n, dev),
-                                      f"{what}: pass scratch= (arap_scratch) when capturing a graph: none of this size exists for this stream yet")  # fmt: skip
+        scratch = _own_or_cached_scratch(what, scratch, "arap", dev, lib().deodr_hip_arap_scratch_bytes, arap_scratch, V, n)
     _launch(lib().deodr_hip_arap_energy, dev, _ptr(offsets), _ptr(cols), _ptr(weights), V, nnz, _ptr(vertices_ref), _ptr(vertices), n, cregu,
             _ptr(energy), _ptr(gradient), _ptr(rotations), _ptr(scratch), scratch.numel())  # fmt: skip
     _touched(energy), _touched(gradient)
@@ -1571,14 +1532,6 @@ def chamfer_launches(V, P, n, directions=3):
 def chamfer_segments(queries, references):
     """``deodr_hip_chamfer_segments``: into how many contiguous parts the references of a search are cut (the second dimension of its grid)"""
     return int(lib().deodr_hip_chamfer_segments(int(queries), int(references)))
-
-
-def _byte_scratch(what, dims, need, header, device):
-    """``need`` bytes (what the library's ``*_scratch_bytes`` gave for ``dims``; 0: refused) of uninitialised scratch on ``device``"""
-    if need == 0:
-        raise ValueError(f"{what}: {dims} is outside the limits of include/{header}")
-    with torch.cuda.device(device):
-        return torch.empty(int(need), dtype=torch.uint8, device=device)
 
 
 def chamfer_scratch(V, P, n, device):
@@ -1632,9 +1585,7 @@ def _closest_point(what, header, limits, make_scratch, vertices, points, params,
                        for _, t, dtypes, tail in found]  # fmt: skip
         if want_nearest and nearest_point is None and directions & CHAMFER_MESH_TO_POINTS:
             nearest_point = torch.empty((n, V), dtype=torch.int32, device=dev)
-        if scratch is None:
-            scratch = _cached_scratch(make_scratch.__name__[: -len("_scratch")], dev, need, lambda: make_scratch(*dims, dev),
-                                      f"{what}: pass scratch= ({make_scratch.__name__}) when capturing a graph: none of this size exists for this stream yet")  # fmt: skip
+        scratch = _own_or_cached_scratch(what, scratch, make_scratch.__name__[: -len("_scratch")], dev, need, make_scratch, *dims)
     out = (terms, loss, vertices_b, *results, nearest_point)
     of_mesh = () if mesh is None else (_ptr(mesh[0]), dims[1], _ptr(mesh[1]), _ptr(mesh[2]))
     _launch(getattr(lib(), f"deodr_hip_{what}"), dev, _ptr(vertices), V, *of_mesh, _ptr(points), P, _ptr(point_weights), _ptr(vertex_weights), _ptr(params),
@@ -1701,9 +1652,7 @@ def sort_keys(keys, bits=32, sorted_keys=None, order=None, scratch=None, want_so
         if want_sorted and sorted_keys is None:
             sorted_keys = torch.empty_like(keys)
         order = torch.empty((n, N), dtype=torch.int32, device=dev) if order is None else order
-        if scratch is None:
-            scratch = _cached_scratch("sort_keys", dev, need, lambda: sort_keys_scratch(N, n, bits, dev),
-                                      f"{what}: pass scratch= (sort_keys_scratch) when capturing a graph: none of this size exists for this stream yet")  # fmt: skip
+        scratch = _own_or_cached_scratch(what, scratch, "sort_keys", dev, need, sort_keys_scratch, N, n, bits)
     _launch(lib().deodr_hip_sort_keys, dev, _ptr(keys), N, n, bits, _ptr(sorted_keys), _ptr(order), _ptr(scratch), scratch.numel())
     for t in (sorted_keys, order):
         if t is not None:

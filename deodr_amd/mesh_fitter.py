@@ -52,37 +52,49 @@ def _pixel_weights(weights, shape, device, pixel_dtype):
     return None if w is None else torch.as_tensor(w, device=device).to(pixel_dtype).contiguous()
 
 
-def _pyramid_schedule(levels, weights, device):
-    """the ``pyramid_levels=`` / ``pyramid_weights=`` keywords of the colour and camera fitters -> (levels, the level weights as a float64 tensor
-    [levels+1] on ``device`` -- all ones when ``weights`` is None --, or None when ``levels`` is 0: the data term is the plain L2 of the fit step)"""
+def _image_term_keywords(fitter, pyramid_levels, pyramid_weights, ssim_weight, ssim_data_range, device):
+    """the ``pyramid_levels=`` / ``pyramid_weights=`` and ``ssim_weight=`` / ``ssim_data_range=`` keywords of the colour and camera fitters -> the
+    fitter's ``pyramid_levels``, ``pyramid_weights`` (a float64 tensor [levels+1] on ``device`` -- all ones when the keyword is None --, or None when
+    the levels are 0), ``ssim_mix`` (the float64 tensor [1 - weight, weight] on ``device``, or None when the weight is 0) and ``ssim_data_range``
+    (a float).  With both terms off the data term is the plain L2 of the fit step."""
     from . import pyramid
 
+    levels, weight, real = pyramid_levels, ssim_weight, (int, float, np.integer, np.floating)
     if isinstance(levels, bool) or int(levels) != levels or not 0 <= int(levels) <= pyramid.MAX_LEVELS:
         raise ValueError(f"pyramid_levels must be an integer in 0 .. {pyramid.MAX_LEVELS}, not {levels!r}")
     levels = int(levels)
-    if levels == 0:
-        if weights is not None:
-            raise ValueError("pyramid_weights needs pyramid_levels > 0")
-        return 0, None
-    w = np.ones(levels + 1) if weights is None else np.array(weights, dtype=np.float64)
+    if levels == 0 and pyramid_weights is not None:
+        raise ValueError("pyramid_weights needs pyramid_levels > 0")
+    w = np.ones(levels + 1) if pyramid_weights is None else np.array(pyramid_weights, dtype=np.float64)
     if w.shape != (levels + 1,):
         raise ValueError(f"pyramid_weights must have pyramid_levels + 1 = {levels + 1} entries, not shape {list(w.shape)}")
     if not np.all(w >= 0):  # (a NaN is refused as well)
         raise ValueError("pyramid_weights must be >= 0")
-    return levels, torch.as_tensor(w, device=device)
-
-
-def _ssim_mix(weight, data_range, pyramid_levels, device):
-    """the ``ssim_weight=`` / ``ssim_data_range=`` keywords of the colour and camera fitters -> (the float64 tensor [1 - weight, weight] on ``device``,
-    or None when ``weight`` is 0: the data term is the plain L2 of the fit step; the data range as a float)"""
-    if isinstance(weight, bool) or not isinstance(weight, (int, float, np.integer, np.floating)) or not 0 <= float(weight) <= 1:  # (a NaN is refused as well)
+    if isinstance(weight, bool) or not isinstance(weight, real) or not 0 <= float(weight) <= 1:  # (a NaN is refused as well)
         raise ValueError(f"ssim_weight must be a real number in 0 .. 1, not {weight!r}")
-    if isinstance(data_range, bool) or not isinstance(data_range, (int, float, np.integer, np.floating)) or not 0 < float(data_range) < np.inf:
-        raise ValueError(f"ssim_data_range must be a finite real number > 0, not {data_range!r}")
+    if isinstance(ssim_data_range, bool) or not isinstance(ssim_data_range, real) or not 0 < float(ssim_data_range) < np.inf:
+        raise ValueError(f"ssim_data_range must be a finite real number > 0, not {ssim_data_range!r}")
     weight = float(weight)
-    if weight > 0 and pyramid_levels:
+    if weight > 0 and levels:
         raise ValueError("ssim_weight > 0 and pyramid_levels > 0 cannot be combined: composing the two data terms is not supported")
-    return (torch.as_tensor([1.0 - weight, weight], dtype=torch.float64, device=device) if weight > 0 else None), float(data_range)
+    fitter.pyramid_levels, fitter.pyramid_weights = levels, torch.as_tensor(w, device=device) if levels else None
+    fitter.ssim_mix = torch.as_tensor([1.0 - weight, weight], dtype=torch.float64, device=device) if weight > 0 else None
+    fitter.ssim_data_range = float(ssim_data_range)
+
+
+def _neighbourhood_term(fitter):
+    """whether the multi-scale or the structural data term is on: they are not the fit step's (the gradient of a pixel depends on its neighbours), so
+    the iteration is render, the term's image_b, render_backward under autograd"""
+    return bool(fitter.pyramid_levels) or fitter.ssim_mix is not None
+
+
+def _render_data_term(fitter, camera, obs, weights):
+    """-> (the data term that is switched on -- multi-scale, structural or the plain L2 -- of ``fitter.scene`` under ``camera``, the image)"""
+    if fitter.pyramid_levels:
+        return fitter.scene.render_pyramid_l2(camera, obs, fitter.pyramid_levels, weights=weights, level_weights=fitter.pyramid_weights)
+    if fitter.ssim_mix is not None:
+        return fitter.scene.render_ssim_l2(camera, obs, weights=weights, mix=fitter.ssim_mix, data_range=fitter.ssim_data_range)
+    return fitter.scene.render_l2(camera, obs, weights=weights)
 
 
 def _smoothing_keywords(smoothing, iterations):
@@ -578,7 +590,7 @@ class _PoseFitter:
 
         if self.subdivisions or self.shape_basis is not None or self.skin is not None:  # (with a basis or a skin the rendered vertex array is not the parameter either)
             return None
-        if self.pyramid_levels or self.ssim_mix is not None:  # (the multi-scale and the structural data term are not the fit step's: render, the term's image_b, render_backward under autograd)
+        if _neighbourhood_term(self):
             return None
         if self.smoothing_system is not None:  # (the solve sits between the gradients and the momentum update, which the fixed sequence fuses with the energy)
             return None
@@ -917,8 +929,7 @@ class MeshRGBFitterWithPose(_PoseFitter):
                  subdivisions=0, shape_basis=None, coefficient_regu=0.0, sigmas=None, light_sh_init=None, vertex_albedo=False, albedo_regu=0.0,
                  skin=None, joint_quaternions_init=None, joint_regu=0.0, pyramid_levels=0, pyramid_weights=None, ssim_weight=0.0,
                  ssim_data_range=1.0, smoothing=0.0, smoothing_iterations=None, rigidity="laplacian", arap_weights="uniform"):  # fmt: skip
-        self.pyramid_levels, self.pyramid_weights = _pyramid_schedule(pyramid_levels, pyramid_weights, torch.device(device))
-        self.ssim_mix, self.ssim_data_range = _ssim_mix(ssim_weight, ssim_data_range, self.pyramid_levels, torch.device(device))
+        _image_term_keywords(self, pyramid_levels, pyramid_weights, ssim_weight, ssim_data_range, torch.device(device))
         self.default_color = np.asarray(default_color, dtype=np.float64)
         self._init_lighting(light_sh_init, vertex_albedo, albedo_regu)
         self.default_light_directional = np.asarray(default_light_directional, dtype=np.float64)
@@ -1008,15 +1019,7 @@ class MeshRGBFitterWithPose(_PoseFitter):
         """-> (data energy, image [n,H,W,C]).  The data term of the colour fitters is exactly sum (image - obs)^2
         (mesh_fitter.py:296-318): rendered AND back-propagated by the one-call fit step (Scene3DDevice.render_l2)."""
         self._pose_scene()
-        if self.pyramid_levels:
-            loss, image = self.scene.render_pyramid_l2(self.camera, self._observation(), self.pyramid_levels, weights=self._fit_weights(),
-                                                       level_weights=self.pyramid_weights)  # fmt: skip
-            return self.data_weight * loss, image
-        if self.ssim_mix is not None:
-            loss, image = self.scene.render_ssim_l2(self.camera, self._observation(), weights=self._fit_weights(), mix=self.ssim_mix,
-                                                    data_range=self.ssim_data_range)  # fmt: skip
-            return self.data_weight * loss, image
-        loss, image = self.scene.render_l2(self.camera, self._observation(), weights=self._fit_weights())
+        loss, image = _render_data_term(self, self.camera, self._observation(), self._fit_weights())
         return self.data_weight * loss, image
 
     def diff_image(self, image):
@@ -1482,8 +1485,7 @@ class CameraFitterMultiFrame:
                  faces_uv=None, texture=None, light_directional=None, light_ambient=1.0, update=GROUPS, shared_intrinsics=True, sigmas=None, sigma=1.0,
                  inertia=0.9, damping=0.05, step_scale=None, clockwise=False, device="cuda", pixel_dtype=torch.float64, pyramid_levels=0,
                  pyramid_weights=None, ssim_weight=0.0, ssim_data_range=1.0):  # fmt: skip
-        self.pyramid_levels, self.pyramid_weights = _pyramid_schedule(pyramid_levels, pyramid_weights, torch.device(device))
-        self.ssim_mix, self.ssim_data_range = _ssim_mix(ssim_weight, ssim_data_range, self.pyramid_levels, torch.device(device))
+        _image_term_keywords(self, pyramid_levels, pyramid_weights, ssim_weight, ssim_data_range, torch.device(device))
         unknown = [g for g in update if g not in self.GROUPS]
         if unknown:
             raise ValueError(f"CameraFitterMultiFrame: update may list {self.GROUPS}, not {unknown}")
@@ -1577,8 +1579,8 @@ class CameraFitterMultiFrame:
         self._direct = None
         topo = mesh.topology
         params = [p[2] for p in self._parameters()]
-        if (self.direct and not self.pyramid_levels and self.ssim_mix is None and fronthalf.usable(mesh.vertices, *params) and topo._edge_faces is not None
-                and n <= hip_renderer.CAMERA_MAX_VIEWS):  # (the multi-scale and the structural data term are not the fit step's: through autograd)
+        if (self.direct and not _neighbourhood_term(self) and fronthalf.usable(mesh.vertices, *params) and topo._edge_faces is not None
+                and n <= hip_renderer.CAMERA_MAX_VIEWS):  # fmt: skip
             self._direct = self._direct_buffers(n, height, width, nb_colors)
         self.iter = 0
 
@@ -1644,12 +1646,7 @@ class CameraFitterMultiFrame:
         leaves = {name: x.detach().requires_grad_(group in self.update) for name, group, x, *_ in rows}
         camera = DeviceCamera.from_pose(leaves["quaternions"], leaves["translations"], leaves["focal"], leaves["center"], self.height, self.width,
                                         leaves.get("distortion"), shared_intrinsics=self.shared_intrinsics, device=self.device)  # fmt: skip
-        if self.pyramid_levels:
-            loss, image = self.scene.render_pyramid_l2(camera, self._obs, self.pyramid_levels, weights=self.weights, level_weights=self.pyramid_weights)
-        elif self.ssim_mix is not None:
-            loss, image = self.scene.render_ssim_l2(camera, self._obs, weights=self.weights, mix=self.ssim_mix, data_range=self.ssim_data_range)
-        else:
-            loss, image = self.scene.render_l2(camera, self._obs, weights=self.weights)
+        loss, image = _render_data_term(self, camera, self._obs, self.weights)
         wanted = [name for name, group, *_ in rows if group in self.update]
         grads = dict(zip(wanted, torch.autograd.grad(loss, [leaves[k] for k in wanted]))) if wanted else {}
         self.e_data.copy_(loss.detach().reshape(1))

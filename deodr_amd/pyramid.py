@@ -9,6 +9,8 @@ torch ops on CPU tensors and on whatever the kernels do not take.  All arithmeti
 
 import torch
 
+from .image_terms import check_frames, device_array, uses_kernel
+
 MAX_LEVELS = 8  # DEODR_HIP_PYRAMID_MAX_LEVELS of include/deodr_hip_pyramid.h
 
 
@@ -32,9 +34,7 @@ def pyramid_terms_torch(image, obs, weights, levels):
     """-> [levels+1] float64: term_l of the formulas above as torch ops, differentiable in ``image``.  ``image``, ``obs`` [n,H,W,C], ``weights``
     [n,H,W] (>= 0) or None"""
     levels = check_levels(levels, "pyramid_terms")
-    if image.dim() != 4 or image.shape != obs.shape or (weights is not None and tuple(weights.shape) != tuple(image.shape[:3])):
-        raise ValueError(f"pyramid_terms: expected image and obs [n,H,W,C] and weights [n,H,W], not {list(image.shape)}, {list(obs.shape)}"
-                         + (f" and {list(weights.shape)}" if weights is not None else ""))  # fmt: skip
+    check_frames("pyramid_terms", image, obs, weights)
     w = torch.ones(image.shape[:3], dtype=torch.float64, device=image.device) if weights is None else weights.detach().to(torch.float64)
     q = w[..., None] * (image.to(torch.float64) - obs.detach().to(torch.float64))
     terms = []
@@ -51,24 +51,13 @@ def _level_weights(level_weights, levels, device, what="pyramid_l2"):
     updated in place stays the caller's tensor)"""
     if level_weights is None:
         return torch.ones(levels + 1, dtype=torch.float64, device=device)
-    lw = level_weights if torch.is_tensor(level_weights) else torch.as_tensor(level_weights, dtype=torch.float64)
-    if lw.dim() != 1 or lw.numel() != levels + 1:
-        raise ValueError(f"{what}: level_weights must have {levels + 1} entries (levels + 1), not shape {list(lw.shape)}")
-    return lw.detach().to(device=device, dtype=torch.float64)
+    return device_array(level_weights, levels + 1, device, f"{what}: level_weights must have {levels + 1} entries (levels + 1)")
 
 
 def pyramid_l2_torch(image, obs, weights, levels, level_weights):
     """-> the loss (a float64 scalar tensor) as torch ops, differentiable in ``image``"""
     levels = check_levels(levels)
     return (_level_weights(level_weights, levels, image.device) * pyramid_terms_torch(image, obs, weights, levels)).sum()
-
-
-def uses_kernel(image, obs, weights, level_weights):
-    """whether :func:`pyramid_l2` runs the kernels on these tensors: contiguous ROCm tensors of one float32 / float64 dtype on one device"""
-    frames = [image, obs] + ([] if weights is None else [weights])
-    return (all(torch.is_tensor(t) and t.is_cuda and t.is_contiguous() and t.device == image.device for t in frames + [level_weights])
-            and image.dtype in (torch.float32, torch.float64) and all(t.dtype == image.dtype for t in frames) and level_weights.dtype == torch.float64
-            and image.dim() == 4 and image.numel() > 0)  # fmt: skip
 
 
 def pyramid_terms(image, obs, weights=None, levels=3):
@@ -88,9 +77,7 @@ def pyramid_l2(image, obs, weights=None, levels=3, level_weights=None):
     constants).  ``level_weights`` None: all ones; a float64 tensor on the device of ``image`` is read by the kernels when they run, so a captured
     graph sees what was copied into it since."""
     levels = check_levels(levels)
-    if image.dim() != 4 or image.shape != obs.shape or (weights is not None and tuple(weights.shape) != tuple(image.shape[:3])):
-        raise ValueError(f"pyramid_l2: expected image and obs [n,H,W,C] and weights [n,H,W], not {list(image.shape)}, {list(obs.shape)}"
-                         + (f" and {list(weights.shape)}" if weights is not None else ""))  # fmt: skip
+    check_frames("pyramid_l2", image, obs, weights)
     lw = _level_weights(level_weights, levels, image.device)
     if uses_kernel(image, obs, weights, lw):
         from . import fronthalf

@@ -430,6 +430,18 @@ class Scene3DDevice:
         extra.update(self._differentiated_shared())  # (the same convention)
         return self._rasterize_l2(camera, ij, depths, colors, shade, textured, backface_culling, obs.expand(n, -1, -1, -1).contiguous(), **extra)
 
+    def _rendered_frames(self, camera, obs, weights, backface_culling):
+        """-> (``render(camera)`` [n,H,W,C], ``obs`` and ``weights`` (or None) as contiguous tensors of its views, dtype and device): what the image
+        data terms below take"""
+        image = self.render(camera, backface_culling=backface_culling)
+        n = image.shape[0]
+        obs = obs.to(device=image.device, dtype=image.dtype).expand(n, -1, -1, -1).contiguous()
+        if weights is not None:
+            if tuple(weights.shape) not in ((n, camera.height, camera.width), (camera.height, camera.width)):
+                raise ValueError(f"weights must have shape [{n}, {camera.height}, {camera.width}] or [{camera.height}, {camera.width}], not {list(weights.shape)}")
+            weights = weights.to(device=image.device, dtype=image.dtype).expand(n, -1, -1).contiguous()
+        return image, obs, weights
+
     def render_pyramid_l2(self, camera, obs, levels, weights=None, level_weights=None, backface_culling=True):
         """-> (the multi-scale L2 loss of ``render(camera)`` against ``obs`` as a differentiable scalar, the rendered images [n,H,W,C]):
         :meth:`render` followed by :func:`deodr_amd.pyramid.pyramid_l2` (``levels`` coarse levels, ``level_weights`` [levels+1], None: ones), so the
@@ -438,13 +450,7 @@ class Scene3DDevice:
         a pixel depends on the residuals of its neighbours."""
         from . import pyramid
 
-        image = self.render(camera, backface_culling=backface_culling)
-        n = image.shape[0]
-        obs = obs.to(device=image.device, dtype=image.dtype).expand(n, -1, -1, -1).contiguous()
-        if weights is not None:
-            if tuple(weights.shape) not in ((n, camera.height, camera.width), (camera.height, camera.width)):
-                raise ValueError(f"weights must have shape [{n}, {camera.height}, {camera.width}] or [{camera.height}, {camera.width}], not {list(weights.shape)}")
-            weights = weights.to(device=image.device, dtype=image.dtype).expand(n, -1, -1).contiguous()
+        image, obs, weights = self._rendered_frames(camera, obs, weights, backface_culling)
         return pyramid.pyramid_l2(image, obs, weights, levels, level_weights), image
 
     def render_ssim_l2(self, camera, obs, weights=None, mix=None, data_range=1.0, backface_culling=True):
@@ -456,13 +462,7 @@ class Scene3DDevice:
         neighbourhood."""
         from . import ssim
 
-        image = self.render(camera, backface_culling=backface_culling)
-        n = image.shape[0]
-        obs = obs.to(device=image.device, dtype=image.dtype).expand(n, -1, -1, -1).contiguous()
-        if weights is not None:
-            if tuple(weights.shape) not in ((n, camera.height, camera.width), (camera.height, camera.width)):
-                raise ValueError(f"weights must have shape [{n}, {camera.height}, {camera.width}] or [{camera.height}, {camera.width}], not {list(weights.shape)}")
-            weights = weights.to(device=image.device, dtype=image.dtype).expand(n, -1, -1).contiguous()
+        image, obs, weights = self._rendered_frames(camera, obs, weights, backface_culling)
         return ssim.ssim_l2(image, obs, weights, mix, data_range), image
 
     def _differentiated_shared(self):

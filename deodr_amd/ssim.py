@@ -17,6 +17,8 @@ import math
 import torch
 import torch.nn.functional as F
 
+from .image_terms import check_frames, device_array, uses_kernel
+
 WINDOW = 11  # DEODR_HIP_SSIM_WINDOW of include/deodr_hip_ssim.h
 SIGMA = 1.5
 
@@ -26,12 +28,6 @@ def gaussian_window():
     e = [math.exp(-(k * k) / (2 * SIGMA * SIGMA)) for k in range(-(WINDOW // 2), WINDOW // 2 + 1)]
     total = sum(e)
     return [v / total for v in e]
-
-
-def _check_frames(what, image, obs, weights):
-    if image.dim() != 4 or image.shape != obs.shape or (weights is not None and tuple(weights.shape) != tuple(image.shape[:3])):
-        raise ValueError(f"{what}: expected image and obs [n,H,W,C] and weights [n,H,W], not {list(image.shape)}, {list(obs.shape)}"
-                         + (f" and {list(weights.shape)}" if weights is not None else ""))  # fmt: skip
 
 
 def check_data_range(data_range, what="ssim_l2"):
@@ -68,7 +64,7 @@ def ssim_map_torch(image, obs, data_range=1.0):
 def ssim_terms_torch(image, obs, weights=None, data_range=1.0):
     """-> [2] float64: (sum w (image - obs)^2, sum w (1 - SSIM)) as torch ops, differentiable in ``image``.  ``image``, ``obs`` [n,H,W,C], ``weights``
     [n,H,W] (>= 0) or None"""
-    _check_frames("ssim_terms", image, obs, weights)
+    check_frames("ssim_terms", image, obs, weights)
     w = torch.ones(image.shape[:3], dtype=torch.float64, device=image.device) if weights is None else weights.detach().to(torch.float64)
     d = image.to(torch.float64) - obs.detach().to(torch.float64)
     return torch.stack(((w[..., None] * d * d).sum(), (w[..., None] * (1 - ssim_map_torch(image, obs, data_range))).sum()))
@@ -79,10 +75,7 @@ def _mix(mix, device, what="ssim_l2"):
     stays the caller's tensor)"""
     if mix is None:
         return torch.tensor([0.0, 1.0], dtype=torch.float64, device=device)
-    m = mix if torch.is_tensor(mix) else torch.as_tensor(mix, dtype=torch.float64)
-    if m.dim() != 1 or m.numel() != 2:
-        raise ValueError(f"{what}: mix must have 2 entries (alpha, beta), not shape {list(m.shape)}")
-    return m.detach().to(device=device, dtype=torch.float64)
+    return device_array(mix, 2, device, f"{what}: mix must have 2 entries (alpha, beta)")
 
 
 def ssim_l2_torch(image, obs, weights=None, mix=None, data_range=1.0):
@@ -90,17 +83,9 @@ def ssim_l2_torch(image, obs, weights=None, mix=None, data_range=1.0):
     return (_mix(mix, image.device) * ssim_terms_torch(image, obs, weights, data_range)).sum()
 
 
-def uses_kernel(image, obs, weights, mix):
-    """whether :func:`ssim_l2` runs the kernels on these tensors: contiguous ROCm tensors of one float32 / float64 dtype on one device"""
-    frames = [image, obs] + ([] if weights is None else [weights])
-    return (all(torch.is_tensor(t) and t.is_cuda and t.is_contiguous() and t.device == image.device for t in frames + [mix])
-            and image.dtype in (torch.float32, torch.float64) and all(t.dtype == image.dtype for t in frames) and mix.dtype == torch.float64
-            and image.dim() == 4 and image.numel() > 0)  # fmt: skip
-
-
 def ssim_terms(image, obs, weights=None, data_range=1.0):
     """-> [2] float64, the unweighted (term_0, term_1), for display (no gradient)"""
-    _check_frames("ssim_terms", image, obs, weights)
+    check_frames("ssim_terms", image, obs, weights)
     data_range = check_data_range(data_range, "ssim_terms")
     m = _mix(None, image.device, "ssim_terms")
     if uses_kernel(image, obs, weights, m):
@@ -115,7 +100,7 @@ def ssim_l2(image, obs, weights=None, mix=None, data_range=1.0):
     """-> ``mix[0] term_0 + mix[1] term_1`` as a float64 scalar tensor, differentiable in ``image`` only (``obs``, ``weights``, ``mix`` are constants).
     ``mix`` None: (0, 1); a float64 tensor [2] on the device of ``image`` passes through untouched and is read by the kernels when they run, so a
     captured graph sees what was copied into it since.  The weights multiply the SSIM map and do not enter the windows (the module's docstring)."""
-    _check_frames("ssim_l2", image, obs, weights)
+    check_frames("ssim_l2", image, obs, weights)
     data_range = check_data_range(data_range)
     m = _mix(mix, image.device)
     if uses_kernel(image, obs, weights, m):

@@ -124,6 +124,12 @@ def test_bad_arguments_are_refused_before_any_launch():
             if other != out:
                 for at in (base[other], base[other] + sizes[other] - 8, base[other] - sizes[out] + 8):
                     assert call(**{out: at}) == refusal, (out, other, hex(at))
+    # two things wrong at once: the checks run in the order above, and the first one speaks
+    assert call(image=None, n=0) == (1, what + ": image, obs, level_weights, terms or scratch == NULL")
+    assert call(n=0, dtype=7) == (1, what + ": n, H and W must be >= 1")
+    assert call(dtype=7, image=base["image"] + 4) == (1, what + ": pixel_dtype must be DEODR_HIP_F32 or DEODR_HIP_F64")
+    assert call(image=base["image"] + 4, scratch_bytes=need - 1) == (1, what + ": misaligned pointer")
+    assert call(scratch_bytes=need - 1, terms=base["image"]) == (1, what + ": scratch too small (deodr_hip_pyramid_scratch_bytes)")
 
 
 def test_host_wrapper_checks_its_tensors_before_the_library(monkeypatch):

@@ -92,6 +92,28 @@ def test_kernels_against_long_double(name, variant, dtype):
     assert float(terms[0]) > 0 or name == "1x1x1x1_L3"
 
 
+def test_results_and_scratch_where_none_are_given():
+    """the smallest ragged two-tile frame of the three-launch path with nothing but the inputs: the wrapper allocates the results, ``want_gradient=False``
+    leaves ``image_b`` None with the same ``terms`` and ``loss``, and the scratch is the one per stream that a larger frame made before"""
+    from deodr_amd import hip_renderer as hr
+
+    case = pr.make_case("1x9x8x4_L4", "holes", np.float64)
+    image, obs, weights, lam = (torch.as_tensor(case[k], device=DEV) for k in ("image", "obs", "weights", "lam"))
+    larger = torch.rand((2, 20, 24, 4), dtype=torch.float64, device=DEV)
+    hr.pyramid_l2(larger, larger.flip(0), None, 5, torch.ones(6, dtype=torch.float64, device=DEV))
+    key = ("pyramid", image.device, torch.cuda.current_stream(image.device).cuda_stream)
+    cached = hr._scratch_cache[key]
+    assert cached.numel() >= int(hr.lib().deodr_hip_pyramid_scratch_bytes(2, 20, 24, 4, 5)) > int(hr.lib().deodr_hip_pyramid_scratch_bytes(1, 9, 8, 4, 4))
+    terms, loss, image_b = hr.pyramid_l2(image, obs, weights, case["levels"], lam)
+    terms2, loss2, none = hr.pyramid_l2(image, obs, weights, case["levels"], lam, want_gradient=False)
+    assert hr._scratch_cache[key] is cached  # (neither call made another)
+    own = hr.pyramid_l2(image, obs, weights, case["levels"], lam, scratch=hr.pyramid_scratch(1, 9, 8, 4, 4, DEV))
+    assert none is None and image_b.shape == image.shape and image_b.dtype == image.dtype and terms.shape == (5,) and loss.shape == (1,)
+    assert torch.equal(terms2, terms) and torch.equal(loss2, loss)
+    assert torch.equal(own[0], terms) and torch.equal(own[1], loss) and torch.equal(own[2], image_b)
+    assert bool((cached[:8] == 0).all())  # the counter is left at zero
+
+
 def test_op_against_the_torch_formulas_on_the_same_tensors():
     from deodr_amd.pyramid import pyramid_l2, pyramid_l2_torch, pyramid_terms, uses_kernel
 

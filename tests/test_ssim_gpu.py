@@ -86,6 +86,29 @@ def test_kernels_against_long_double(combo):
         assert float(terms[0]) > 0 and float(terms[1]) > 0
 
 
+def test_results_and_scratch_where_none_are_given():
+    """the ragged 2 x 2 tiles with nothing but the inputs: the wrapper allocates the results, ``want_gradient=False`` leaves ``image_b`` None with the
+    same ``terms`` and ``loss``, and the scratch is the one per stream that a larger frame made before"""
+    from deodr_amd import hip_renderer as hr
+
+    case = sr.make_case("2x2 tiles ragged 1x29x53x5", "holes255", np.float64)
+    image, obs, weights = (torch.as_tensor(case[k], device=DEV) for k in ("image", "obs", "weights"))
+    mix = torch.as_tensor(case["mix"], dtype=torch.float64, device=DEV)
+    larger = torch.rand((2, 40, 70, 5), dtype=torch.float64, device=DEV)
+    hr.ssim_l2(larger, larger.flip(0), None, mix)
+    key = ("ssim", image.device, torch.cuda.current_stream(image.device).cuda_stream)
+    cached = hr._scratch_cache[key]
+    assert cached.numel() >= int(hr.lib().deodr_hip_ssim_scratch_bytes(2, 40, 70, 5)) > int(hr.lib().deodr_hip_ssim_scratch_bytes(1, 29, 53, 5))
+    terms, loss, image_b = hr.ssim_l2(image, obs, weights, mix, case["data_range"])
+    terms2, loss2, none = hr.ssim_l2(image, obs, weights, mix, case["data_range"], want_gradient=False)
+    assert hr._scratch_cache[key] is cached  # (neither call made another)
+    own = hr.ssim_l2(image, obs, weights, mix, case["data_range"], scratch=hr.ssim_scratch(1, 29, 53, 5, DEV))
+    assert none is None and image_b.shape == image.shape and image_b.dtype == image.dtype and terms.shape == (2,) and loss.shape == (1,)
+    assert torch.equal(terms2, terms) and torch.equal(loss2, loss)
+    assert torch.equal(own[0], terms) and torch.equal(own[1], loss) and torch.equal(own[2], image_b)
+    assert bool((cached[:8] == 0).all())  # the counter is left at zero
+
+
 def test_op_against_the_torch_formulas_on_the_same_tensors():
     from deodr_amd.ssim import ssim_l2, ssim_l2_torch, ssim_terms, uses_kernel
 

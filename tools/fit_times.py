@@ -5,6 +5,7 @@ share (hipEvent times of the library's kernels inside the step) and, with `--cou
     depth    MeshDepthFitter, 200 x 200 depth image of the hand (the reference's tests/test_depth_image_hand_fitting.py workload)
     rgb      MeshRGBFitterWithPose, 1024 x 1024 colour image of the hand mesh (configs[1]-like, untextured colour fit)
     multi8   MeshRGBFitterWithPoseMultiFrame, 8 views of 1024 x 1024 (configs[3]), one batched launch per step
+`--pyramid-levels L` / `--ssim-weight W`: the colour fitters with that data term (the autograd iteration; no rasterizer share is reported to compare).
 """
 import ctypes, os, sys, time
 import numpy as np, torch
@@ -13,6 +14,8 @@ from deodr_amd import hip_renderer as hr, scenes
 from deodr_amd.mesh_fitter import MeshDepthFitter, MeshRGBFitterWithPose, MeshRGBFitterWithPoseMultiFrame
 
 GOLD = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
+option = lambda name, kind: {name.strip("-").replace("-", "_"): kind(sys.argv.pop(sys.argv.index(name) + 1))} if name in sys.argv else {}
+term = {**option("--pyramid-levels", int), **option("--ssim-weight", float)}  # (keywords of the colour fitters)
 which = [a for a in sys.argv[1:] if not a.startswith("--")] or ["depth", "rgb", "multi8"]
 steps = 30
 hand = np.load(os.path.join(GOLD, "hand_mesh.npz"))
@@ -43,10 +46,10 @@ def build(name):
 
     def make(euler, color):
         if name == "rgb":
-            f = MeshRGBFitterWithPose(v0, faces, euler[0], np.zeros(3), color, light, ambient, cregu=1000, pixel_dtype=pixel_dtype)
+            f = MeshRGBFitterWithPose(v0, faces, euler[0], np.zeros(3), color, light, ambient, cregu=1000, pixel_dtype=pixel_dtype, **term)
             f.set_image(np.zeros((1024, 1024, 3)))
         else:
-            f = MeshRGBFitterWithPoseMultiFrame(v0, faces, euler, np.zeros((8, 3)), color, light, ambient, cregu=2000, pixel_dtype=pixel_dtype)
+            f = MeshRGBFitterWithPoseMultiFrame(v0, faces, euler, np.zeros((8, 3)), color, light, ambient, cregu=2000, pixel_dtype=pixel_dtype, **term)
             f.set_images([np.zeros((1024, 1024, 3))] * 8)
         f.set_background_color(bg)
         return f

@@ -135,6 +135,10 @@ CONFIGURATIONS = [
     ("rgb sh[9] shape_basis", lambda: rgb(light_sh_init=sh((9,)), **shape_basis())),
     ("rgb directional update_lights=False", lambda: rgb(update_lights=False)),
     ("multi 3 views", lambda: rgb(views=3)),
+    ("rgb pyramid_levels=3", lambda: rgb(pyramid_levels=3, pyramid_weights=[1.0, 0.5, 2.0, 0.25])),
+    ("rgb ssim_weight=0.5", lambda: rgb(ssim_weight=0.5)),
+    ("multi 3 views pyramid_levels=3", lambda: rgb(views=3, pyramid_levels=3)),
+    ("multi 3 views ssim_weight=0.5", lambda: rgb(views=3, ssim_weight=0.5, ssim_data_range=2.0)),
     ("multi 3 views sh[9,3] vertex_albedo albedo_regu", lambda: rgb(views=3, light_sh_init=sh((9, 3)), vertex_albedo=True, albedo_regu=1.0)),
     ("texture", lambda: texture()),
     ("texture basis coefficient_regu", lambda: texture(basis=True)),
@@ -145,6 +149,8 @@ CONFIGURATIONS = [
     ("camera per-view intrinsics", lambda: camera(shared_intrinsics=False)),
     ("camera sigmas", lambda: camera(sigmas={"focal": 0.5, "translations": np.array([0.1, 0.1, 0.3]), "distortion": 0.01})),
     ("camera update=(extrinsic, focal)", lambda: camera(update=("extrinsic", "focal"))),
+    ("camera pyramid_levels=2", lambda: camera(pyramid_levels=2)),
+    ("camera ssim_weight=0.5", lambda: camera(ssim_weight=0.5)),
 ]  # fmt: skip
 
 
