@@ -4,6 +4,7 @@
 A few regular expressions over a header the project owns, not a C parser: it takes the declarations that header contains (``typedef
 struct``, prototypes, integer ``#define``s) and raises ``ImportError``, quoting the declaration, on anything else."""
 
+import collections
 import ctypes as C
 import os
 import re
@@ -11,23 +12,25 @@ import types
 
 _INCLUDE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
 HEADER_PATH = os.path.join(_INCLUDE, "deodr_hip.h")
-# The companion headers, each versioned on its own and bound onto the same library: (the parsed header's name here -- its path is that name + _PATH --,
-# the file, whether its prototypes may point to the structs of deodr_hip.h)
-_COMPANIONS = (
-    ("TEXTURE_HEADER", "deodr_hip_texture.h", False),  # texture estimation
-    ("SUBDIV_HEADER", "deodr_hip_subdiv.h", False),  # Loop subdivision
-    ("RETAINED_HEADER", "deodr_hip_retained.h", True),  # fit step into retained frames
-    ("BASIS_HEADER", "deodr_hip_basis.h", False),  # linear bases: morphable models
-    ("CAMERA_HEADER", "deodr_hip_camera.h", False),  # camera calibration
-    ("LIGHTING_HEADER", "deodr_hip_lighting.h", False),  # spherical-harmonic lighting, per-vertex albedo
-    ("SKINNING_HEADER", "deodr_hip_skinning.h", False),  # linear blend skinning
-    ("PYRAMID_HEADER", "deodr_hip_pyramid.h", False),  # multi-scale L2 data term
-    ("SSIM_HEADER", "deodr_hip_ssim.h", False),  # structural (SSIM) data term
-    ("SOLVE_HEADER", "deodr_hip_solve.h", False),  # sparse SPD solve: smoothed vertex steps
-    ("ARAP_HEADER", "deodr_hip_arap.h", False),  # as-rigid-as-possible energy
-    ("CHAMFER_HEADER", "deodr_hip_chamfer.h", False),  # closest-point (Chamfer) data term
-    ("SURFACE_HEADER", "deodr_hip_surface.h", False),  # point-to-surface distance
-    ("CHAMFER_GRID_HEADER", "deodr_hip_chamfer_grid.h", False),  # closest-point term over a uniform grid, stable sort by key
+# The companion headers, each versioned on its own and bound onto the same library; the only list of them.  Everything else follows from `key`: the
+# file include/deodr_hip_{key}.h, the parsed header {KEY}_HEADER here and its path {KEY}_HEADER_PATH, DEODR_HIP_{KEY}_ABI_VERSION and
+# deodr_hip_{key}_abi_version().  sees_structs: whether its prototypes may point to the structs of deodr_hip.h; words: what a version mismatch is called
+Companion = collections.namedtuple("Companion", "key sees_structs words")
+COMPANIONS = (
+    Companion("texture", False, "texture"),  # texture estimation
+    Companion("subdiv", False, "subdivision"),  # Loop subdivision
+    Companion("retained", True, "retained-frames"),  # fit step into retained frames
+    Companion("basis", False, "linear-basis"),  # linear bases: morphable models
+    Companion("camera", False, "camera"),  # camera calibration
+    Companion("lighting", False, "lighting"),  # spherical-harmonic lighting, per-vertex albedo
+    Companion("skinning", False, "skinning"),  # linear blend skinning
+    Companion("pyramid", False, "pyramid-loss"),  # multi-scale L2 data term
+    Companion("ssim", False, "ssim-loss"),  # structural (SSIM) data term
+    Companion("solve", False, "sparse-solve"),  # sparse SPD solve: smoothed vertex steps
+    Companion("arap", False, "arap-energy"),  # as-rigid-as-possible energy
+    Companion("chamfer", False, "chamfer-term"),  # closest-point (Chamfer) data term
+    Companion("surface", False, "surface-distance"),  # point-to-surface distance
+    Companion("chamfer_grid", False, "chamfer-grid"),  # closest-point term over a uniform grid, stable sort by key
 )
 
 # C type (without `const`, without spaces around the stars) -> ctypes.  Data pointers are c_void_p: callers pass device addresses (Python
@@ -62,7 +65,8 @@ def _typed_name(text, ctypes_of, declaration):
 
 
 def parse(text, name="include/deodr_hip.h", structs=None):
-    """-> namespace(name, defines {name: int}, structs {name: ctypes.Structure}, functions {name: (restype, [argtypes])}) of a header text;
+    """-> namespace(name, defines {name: int}, structs {name: ctypes.Structure}, functions {name: (restype, [argtypes])}, parameters {name: [names]})
+    of a header text;
     ``name``: what the header is called in error texts; ``structs``: those of a header this one includes, which its prototypes may point to"""
     global _parsing
     _parsing = name
@@ -70,7 +74,7 @@ def parse(text, name="include/deodr_hip.h", structs=None):
     text = re.sub(r"#ifdef __cplusplus.*?#endif", " ", text, flags=re.S)  # (the extern "C" braces)
     defines = {name: int(value) for name, value in re.findall(r"^[ \t]*#define[ \t]+(\w+)[ \t]+(-?\d+)[ \t]*$", text, flags=re.M)}
     text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
-    ctypes_of, included, structs, functions = dict(_CTYPES), structs or {}, {}, {}
+    ctypes_of, included, structs, functions, parameters = dict(_CTYPES), structs or {}, {}, {}, {}
     ctypes_of.update({n + "*": C.POINTER(s) for n, s in included.items()})
 
     def struct(m):
@@ -92,8 +96,9 @@ def parse(text, name="include/deodr_hip.h", structs=None):
             _refuse("cannot parse", decl)
         restype = None if m.group(1).split() == ["void"] else _ctype(m.group(1), ctypes_of, decl)
         params = [] if m.group(3).split() == ["void"] else m.group(3).split(",")
-        functions[m.group(2)] = (restype, [_typed_name(p, ctypes_of, decl)[0] for p in params])
-    return types.SimpleNamespace(name=name, defines=defines, structs=structs, functions=functions)
+        typed = [_typed_name(p, ctypes_of, decl) for p in params]
+        functions[m.group(2)], parameters[m.group(2)] = (restype, [c_type for c_type, _ in typed]), [name for _, name in typed]
+    return types.SimpleNamespace(name=name, defines=defines, structs=structs, functions=functions, parameters=parameters)
 
 
 def bind(library, header=None):
@@ -113,6 +118,12 @@ def _parse_file(path, structs=None):
 
 
 HEADER = _parse_file(HEADER_PATH)
-for _name, _file, _sees_structs in _COMPANIONS:
-    globals()[_name + "_PATH"] = os.path.join(_INCLUDE, _file)
-    globals()[_name] = _parse_file(globals()[_name + "_PATH"], HEADER.structs if _sees_structs else None)
+for _c in COMPANIONS:
+    _path = os.path.join(_INCLUDE, f"deodr_hip_{_c.key}.h")
+    globals()[_c.key.upper() + "_HEADER_PATH"], globals()[_c.key.upper() + "_HEADER"] = _path, _parse_file(_path, HEADER.structs if _c.sees_structs else None)
+
+
+def companion(c):
+    """-> (parsed header, its DEODR_HIP_{KEY}_ABI_VERSION) of a row of COMPANIONS"""
+    header = globals()[c.key.upper() + "_HEADER"]
+    return header, header.defines[f"DEODR_HIP_{c.key.upper()}_ABI_VERSION"]

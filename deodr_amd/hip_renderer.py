@@ -27,27 +27,8 @@ _H = _abi.HEADER  # the structs, the constants and (in lib()) the signatures are
 _SceneC, _FitOptionsC, ABI_VERSION = _H.structs["DeodrHipScene"], _H.structs["DeodrHipFitOptions"], _H.defines["DEODR_HIP_ABI_VERSION"]
 ERR_FACES, ERR_FACES_UV, ERR_NO_TEXTURE, ERR_INTERNAL, ERR_DET_RANGE = (_H.defines["DEODR_HIP_ERR_" + n] for n in "FACES FACES_UV NO_TEXTURE INTERNAL DET_RANGE".split())
 MAX_COLORS, _F32, _F64 = (_H.defines["DEODR_HIP_" + n] for n in ("MAX_COLORS", "F32", "F64"))
-# The companion headers, bound onto the same library and versioned each on its own: (header, KEY of deodr_hip_KEY_abi_version() and of
-# DEODR_HIP_KEY_ABI_VERSION, what a version mismatch is called)
-_COMPANIONS = (
-    (_abi.TEXTURE_HEADER, "texture", "texture"),  # texture estimation
-    (_abi.SUBDIV_HEADER, "subdiv", "subdivision"),  # Loop subdivision
-    (_abi.RETAINED_HEADER, "retained", "retained-frames"),  # fit step into retained frames
-    (_abi.BASIS_HEADER, "basis", "linear-basis"),  # linear bases: morphable models
-    (_abi.CAMERA_HEADER, "camera", "camera"),  # camera calibration
-    (_abi.LIGHTING_HEADER, "lighting", "lighting"),  # spherical-harmonic lighting, per-vertex albedo
-    (_abi.SKINNING_HEADER, "skinning", "skinning"),  # linear blend skinning
-    (_abi.PYRAMID_HEADER, "pyramid", "pyramid-loss"),  # multi-scale L2 data term
-    (_abi.SSIM_HEADER, "ssim", "ssim-loss"),  # structural (SSIM) data term
-    (_abi.SOLVE_HEADER, "solve", "sparse-solve"),  # sparse SPD solve: smoothed vertex steps
-    (_abi.ARAP_HEADER, "arap", "arap-energy"),  # as-rigid-as-possible energy
-    (_abi.CHAMFER_HEADER, "chamfer", "chamfer-term"),  # closest-point (Chamfer) data term
-    (_abi.SURFACE_HEADER, "surface", "surface-distance"),  # point-to-surface distance
-    (_abi.CHAMFER_GRID_HEADER, "chamfer_grid", "chamfer-grid"),  # closest-point term over a uniform grid, stable sort by key
-)
-TEXTURE_ABI_VERSION, SUBDIV_ABI_VERSION, RETAINED_ABI_VERSION, BASIS_ABI_VERSION, CAMERA_ABI_VERSION, LIGHTING_ABI_VERSION, SKINNING_ABI_VERSION, PYRAMID_ABI_VERSION, SSIM_ABI_VERSION, SOLVE_ABI_VERSION, ARAP_ABI_VERSION, CHAMFER_ABI_VERSION, SURFACE_ABI_VERSION, CHAMFER_GRID_ABI_VERSION = (
-    h.defines[f"DEODR_HIP_{key.upper()}_ABI_VERSION"] for h, key, _ in _COMPANIONS
-)
+for _c in _abi.COMPANIONS:  # TEXTURE_ABI_VERSION, SUBDIV_ABI_VERSION, ...: of the companion headers, each versioned on its own
+    globals()[_c.key.upper() + "_ABI_VERSION"] = _abi.companion(_c)[1]
 # words of the 64-byte status block at the start of the workspace
 _STATUS_NEEDED, _STATUS_ERRORS = _H.defines["DEODR_HIP_STATUS_WORD_NEEDED_PAIRS"], _H.defines["DEODR_HIP_STATUS_WORD_SCENE_ERRORS"]
 
@@ -66,10 +47,11 @@ def lib():
         L = C.CDLL(LIB_PATH)
         if L.deodr_hip_abi_version() != ABI_VERSION:
             raise ImportError("libdeodr_hip.so ABI version mismatch; rebuild it")
-        for header, key, words in _COMPANIONS:
+        for c in _abi.COMPANIONS:  # bound onto the same library
+            header, version = _abi.companion(c)
             _abi.bind(L, header)  # (a library that lacks one of its symbols is refused by name)
-            if getattr(L, f"deodr_hip_{key}_abi_version")() != header.defines[f"DEODR_HIP_{key.upper()}_ABI_VERSION"]:
-                raise ImportError(f"libdeodr_hip.so {words} ABI version mismatch ({header.name}); rebuild it")
+            if getattr(L, f"deodr_hip_{c.key}_abi_version")() != version:
+                raise ImportError(f"libdeodr_hip.so {c.words} ABI version mismatch ({header.name}); rebuild it")
         _lib = _abi.bind(L)
     return _lib
 

@@ -1,62 +1,19 @@
-"""CPU checks of the companion header include/deodr_hip_arap.h (the as-rigid-as-possible energy): it parses with the parser of deodr_hip.h and shares
-no name with the other eleven headers, its prototypes are type by type what the header documents, every name it declares is exported by the
-cross-compiled library and bound with the declared types, its version is 1 on both sides, the constants of deodr_amd/csrc/dr_arap.h are the ones the
-case tables are built for, every bad argument of the launching entry point is refused through its error code with a message before any launch (fake
-pointers, no GPU), the scratch size is 0 outside the limits, monotone inside them and the documented formula, the launch rule is pinned at its
-boundaries, and the host wrapper refuses CPU tensors, wrong dtypes and wrong shapes without reaching the library."""
+"""CPU checks of the as-rigid-as-possible energy at the C ABI (include/deodr_hip_arap.h; the header itself: tests/test_companion_headers.py): the
+constants of deodr_amd/csrc/dr_arap.h are the ones the case tables are built for, every bad argument of the launching entry point is refused
+through its error code with a message before any launch (fake pointers, no GPU), the scratch size is 0 outside the limits, monotone inside them
+and the documented formula, the launch rule is pinned at its boundaries, and the host wrapper refuses CPU tensors, wrong dtypes and wrong shapes
+without reaching the library."""
 
-import ctypes as C
 import os
 import re
 
 import pytest
 
-ARAP_FUNCTIONS = ["deodr_hip_arap_energy", "deodr_hip_arap_scratch_bytes", "deodr_hip_arap_launches", "deodr_hip_arap_blocks", "deodr_hip_arap_abi_version"]
 
-
-def test_companion_header_parses_and_is_versioned_on_its_own():
-    from deodr_amd import _abi
-
-    h = _abi.ARAP_HEADER
-    assert sorted(h.functions) == sorted(ARAP_FUNCTIONS)
-    assert h.defines == {"DEODR_HIP_ARAP_ABI_VERSION": 1, "DEODR_HIP_ARAP_SWEEPS": 5, "DEODR_HIP_ARAP_BLOCK": 256, "DEODR_HIP_ARAP_MAX_BLOCKS": 512}
-    assert h.structs == {} and h.name == "include/deodr_hip_arap.h"
-    others = (_abi.HEADER, _abi.TEXTURE_HEADER, _abi.SUBDIV_HEADER, _abi.RETAINED_HEADER, _abi.BASIS_HEADER, _abi.CAMERA_HEADER, _abi.LIGHTING_HEADER,
-              _abi.SKINNING_HEADER, _abi.PYRAMID_HEADER, _abi.SSIM_HEADER, _abi.SOLVE_HEADER)  # fmt: skip
-    assert len(others) == 11
-    for other in others:
-        assert not set(h.functions) & set(other.functions) and not set(h.defines) & set(other.defines)
-    assert re.search(r"#define\s+DEODR_HIP_ARAP_ABI_VERSION\s+1\b", open(_abi.ARAP_HEADER_PATH).read())
-    p, i, z, d, u = C.c_void_p, C.c_int, C.c_size_t, C.c_double, C.c_uint32
-    assert h.functions["deodr_hip_arap_energy"] == (i, [p, p, p, i, u, p, p, i, d, p, p, p, p, z, p])  # 15 parameters
-    assert h.functions["deodr_hip_arap_scratch_bytes"] == (z, [i, i])
-    assert h.functions["deodr_hip_arap_launches"] == (i, [i, u, i])
-    assert h.functions["deodr_hip_arap_blocks"] == (i, [i])
-    assert h.functions["deodr_hip_arap_abi_version"] == (i, [])
-
-
-def test_library_exports_and_binds_every_name_of_the_companion_header():
-    import __graft_entry__ as g
-    from deodr_amd import _abi
+def test_the_constants_are_the_header_s():
     from deodr_amd import hip_renderer as hr
 
-    raw = C.CDLL(g.build_hip())
-    for name in ARAP_FUNCTIONS:
-        assert hasattr(raw, name), name
-    assert raw.deodr_hip_arap_abi_version() == 1 == hr.ARAP_ABI_VERSION
     assert (hr.ARAP_SWEEPS, hr.ARAP_BLOCK, hr.ARAP_MAX_BLOCKS) == (5, 256, 512)
-    L = hr.lib()  # binds every header
-    for name, (restype, argtypes) in _abi.ARAP_HEADER.functions.items():
-        f = getattr(L, name)
-        assert f.restype is restype and list(f.argtypes) == argtypes, name
-
-
-def test_the_header_is_on_the_list_that_decides_whether_the_library_is_stale():
-    import inspect
-
-    import __graft_entry__ as g
-
-    assert '"deodr_hip_arap.h"' in inspect.getsource(g.build_hip)
 
 
 def test_the_constants_of_the_kernels_are_the_case_table_s():
@@ -104,6 +61,8 @@ def test_the_launch_rule_at_its_boundaries():
 
 def test_bad_arguments_are_refused_before_any_launch():
     """every pointer below is fake and never dereferenced: a refusal happens before any HIP call"""
+    from abi_cases import entry, misaligned, nulls, overlap_placements
+    from deodr_amd import _abi
     from deodr_amd import hip_renderer as hr
 
     L = hr.lib()
@@ -111,28 +70,23 @@ def test_bad_arguments_are_refused_before_any_launch():
     base = dict(offsets=0x10000000, cols=0x11000000, weights=0x12000000, vertices_ref=0x13000000, vertices=0x14000000, energy=0x15000000,
                 gradient=0x16000000, rotations=0x17000000, scratch=0x18000000)  # fmt: skip
 
-    def call(V=V, nnz=nnz, n=n, cregu=1.0, scratch_bytes=None, **changed):
-        a = dict(base, **changed)
-        need = L.deodr_hip_arap_scratch_bytes(V, n)
-        rc = L.deodr_hip_arap_energy(a["offsets"], a["cols"], a["weights"], V, nnz, a["vertices_ref"], a["vertices"], n, cregu, a["energy"], a["gradient"],
-                                     a["rotations"], a["scratch"], need if scratch_bytes is None else scratch_bytes, None)  # fmt: skip
-        return rc, L.deodr_hip_last_error().decode()
-
+    call = entry(L, _abi.ARAP_HEADER, "deodr_hip_arap_energy", base, V=V, nnz=nnz, n=n, cregu=1.0,
+                 scratch_bytes=lambda a: L.deodr_hip_arap_scratch_bytes(a["V"], a["n"]))  # fmt: skip
     what = "arap_energy"
-    for p in base:  # a NULL pointer (rotations may be NULL: the call then gets past every check of this test only with real memory, not tried here)
-        if p != "rotations":
-            rc, msg = call(**{p: None})
-            assert rc == 1 and msg.startswith(what + ":") and "== NULL" in msg, (p, msg)
+    # a NULL pointer (rotations may be NULL: the call then gets past every check of this test only with real memory, not tried here)
+    for bad in nulls(p for p in base if p != "rotations"):
+        rc, msg = call(**bad)
+        assert rc == 1 and msg.startswith(what + ":") and "== NULL" in msg, (bad, msg)
     for bad in (0, -1, -(2**31)):
         assert call(V=bad, scratch_bytes=1 << 20) == (1, what + ": V must be positive"), bad
     for bad in (0, -1, 65536):
         assert call(n=bad, scratch_bytes=1 << 20) == (1, what + ": n must be in 1 .. 65535"), bad
     for bad in (-1e-300, -1.0, float("-inf"), float("nan")):
         assert call(cregu=bad) == (1, what + ": cregu must be >= 0"), bad
-    for p in ("offsets", "cols"):
-        assert call(**{p: base[p] + 2}) == (1, what + ": misaligned pointer"), p
-    for p in ("weights", "vertices_ref", "vertices", "energy", "gradient", "rotations", "scratch"):
-        assert call(**{p: base[p] + 4}) == (1, what + ": misaligned pointer"), p
+    for bad in misaligned(base, ("offsets", "cols"), 2):
+        assert call(**bad) == (1, what + ": misaligned pointer"), bad
+    for bad in misaligned(base, ("weights", "vertices_ref", "vertices", "energy", "gradient", "rotations", "scratch"), 4):
+        assert call(**bad) == (1, what + ": misaligned pointer"), bad
     need = L.deodr_hip_arap_scratch_bytes(V, n)
     for short in (0, 64, need - 1):
         assert call(scratch_bytes=short) == (1, what + ": scratch too small (deodr_hip_arap_scratch_bytes)"), short
@@ -143,17 +97,16 @@ def test_bad_arguments_are_refused_before_any_launch():
     for out in ("energy", "gradient", "rotations", "scratch"):
         for other in sizes:
             if other != out:
-                for at in (base[other], base[other] + sizes[other] - 8, base[other] - sizes[out] + 8):
+                for at in overlap_placements(base, sizes, out, other):
                     assert call(**{out: at}) == refusal, (out, other, hex(at))
 
 
 def test_host_wrapper_checks_its_tensors_before_the_library(monkeypatch):
     import torch
 
+    from abi_cases import no_library
+    from abi_cases import on_device as dev
     from deodr_amd import hip_renderer as hr
-
-    def no_library():
-        raise AssertionError("the library was reached")
 
     monkeypatch.setattr(hr, "lib", no_library)
     f64 = lambda *shape: torch.zeros(*shape, dtype=torch.float64)
@@ -161,11 +114,6 @@ def test_host_wrapper_checks_its_tensors_before_the_library(monkeypatch):
     with pytest.raises(ValueError, match="vertices must be a ROCm tensor"):
         hr.arap_energy(i32(6), i32(9), f64(9), f64(5, 3), f64(2, 5, 3), 1.0)
 
-    class OnDevice(torch.Tensor):
-        is_cuda = property(lambda self: True)
-        device = property(lambda self: torch.device("cuda", 0))
-
-    dev = lambda x: x.as_subclass(OnDevice)
     O, Cc, W, Q, P = dev(i32(6)), dev(i32(9)), dev(f64(9)), dev(f64(5, 3)), dev(f64(2, 5, 3))
     for bad in (dev(f64(5, 3)), dev(f64(2, 5, 4)), dev(f64(0, 5, 3)), dev(f64(2, 0, 3)), dev(f64(2, 5, 3, 1))):
         with pytest.raises(ValueError, match=r"vertices must have shape \[n >= 1, V >= 1, 3\]"):

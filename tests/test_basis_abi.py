@@ -1,62 +1,22 @@
-"""CPU checks of the companion header include/deodr_hip_basis.h (linear bases): it parses with the parser of deodr_hip.h and shares no name with the
-other headers, every name it declares is exported by the cross-compiled library and bound with the declared types, its version is 1 on both sides,
-every bad argument of the two entry points is refused with a message before any launch (fake pointers, no GPU), the segment rule and the scratch
-size behave as the header says, and the host wrappers refuse CPU tensors, wrong dtypes and wrong shapes without reaching the library."""
+"""CPU checks of the linear bases at the C ABI (include/deodr_hip_basis.h; the header itself: tests/test_companion_headers.py): a library that lacks
+a declared symbol is refused by name, every bad argument of the two entry points is refused with a message before any launch (fake pointers, no
+GPU), the segment rule and the scratch size behave as the header says, and the host wrappers refuse CPU tensors, wrong dtypes and wrong shapes
+without reaching the library."""
 
 import ctypes as C
-import re
 
 import pytest
 
-BASIS_FUNCTIONS = ["deodr_hip_basis_apply", "deodr_hip_basis_apply_b", "deodr_hip_basis_scratch_bytes", "deodr_hip_basis_segments",
-                   "deodr_hip_basis_abi_version"]  # fmt: skip
 
-
-def test_companion_header_parses_and_is_versioned_on_its_own():
-    from deodr_amd import _abi
-
-    h = _abi.BASIS_HEADER
-    assert sorted(h.functions) == sorted(BASIS_FUNCTIONS)
-    assert h.defines == {"DEODR_HIP_BASIS_ABI_VERSION": 1} and h.structs == {}
-    assert h.name == "include/deodr_hip_basis.h"
-    for other in (_abi.HEADER, _abi.TEXTURE_HEADER, _abi.SUBDIV_HEADER, _abi.RETAINED_HEADER):  # disjoint from the other headers
-        assert not set(h.functions) & set(other.functions) and not set(h.defines) & set(other.defines)
-    text = open(_abi.BASIS_HEADER_PATH).read()
-    assert re.search(r"#define\s+DEODR_HIP_BASIS_ABI_VERSION\s+1\b", text)
-    p, i = C.c_void_p, C.c_int
-    assert h.functions["deodr_hip_basis_apply"] == (i, [p, p, p, i, i, i, i, p, i, p])
-    assert h.functions["deodr_hip_basis_apply_b"] == (i, [p, p, i, i, i, i, i, p, i, p, C.c_size_t, p])
-    assert h.functions["deodr_hip_basis_scratch_bytes"] == (C.c_size_t, [i, i, i])
-    assert h.functions["deodr_hip_basis_segments"] == (i, [i, i])
-    assert h.functions["deodr_hip_basis_abi_version"] == (i, [])
-
-
-def test_library_exports_and_binds_every_name_of_the_companion_header():
+def test_a_library_that_lacks_a_declared_symbol_is_refused_by_name():
     import __graft_entry__ as g
     from deodr_amd import _abi
-    from deodr_amd import hip_renderer as hr
 
-    raw = C.CDLL(g.build_hip())
-    for name in BASIS_FUNCTIONS:
-        assert hasattr(raw, name), name
-    assert raw.deodr_hip_basis_abi_version() == 1 == hr.BASIS_ABI_VERSION
-    L = hr.lib()  # binds every header
-    for name, (restype, argtypes) in _abi.BASIS_HEADER.functions.items():
-        f = getattr(L, name)
-        assert f.restype is restype and list(f.argtypes) == argtypes, name
     more = _abi.parse(open(_abi.BASIS_HEADER_PATH).read().replace("int deodr_hip_basis_abi_version(void);",
                                                                   "int deodr_hip_basis_abi_version(void);\nint deodr_hip_basis_not_there(int on);"),
                       "include/deodr_hip_basis.h")  # fmt: skip
     with pytest.raises(ImportError, match=r"deodr_hip_basis_not_there, which include/deodr_hip_basis\.h declares"):
         _abi.bind(C.CDLL(g.build_hip()), more)
-
-
-def test_the_header_is_on_the_list_that_decides_whether_the_library_is_stale():
-    import inspect
-
-    import __graft_entry__ as g
-
-    assert '"deodr_hip_basis.h"' in inspect.getsource(g.build_hip)
 
 
 INVALID = [(0, 10), (-1, 10), (1025, 10), (4, 0), (4, -5), (4, 2**30 + 1), (1024, 2**21), (3, 2**30)]  # (K, N): a range, or K N > 2^31 - 1
@@ -88,26 +48,22 @@ def test_segments_and_scratch_follow_the_header():
 
 def test_bad_arguments_are_refused_before_any_launch():
     """every pointer below is fake and never dereferenced: a refusal happens before any HIP call"""
+    from abi_cases import entry, nulls
     from deodr_amd import _abi
     from deodr_amd import hip_renderer as hr
 
     L = hr.lib()
     F32, F64 = _abi.HEADER.defines["DEODR_HIP_F32"], _abi.HEADER.defines["DEODR_HIP_F64"]
     basis, mean, coeffs, y, g, c_b, scratch = 0x10000000, 0x20000000, 0x30000000, 0x40000000, 0x50000000, 0x60000000, 0x70000000
+    base = dict(basis=basis, mean=mean, coeffs=coeffs, y=y, g=g, coeffs_b=c_b, scratch=scratch)
+    apply = entry(L, _abi.BASIS_HEADER, "deodr_hip_basis_apply", base, K=4, N=100, batch=2, basis_dtype=F32, y_dtype=F64)
+    apply_b = entry(L, _abi.BASIS_HEADER, "deodr_hip_basis_apply_b", base, g_dtype=F32, K=4, N=100, batch=2, basis_dtype=F32, accumulate=0,
+                    scratch_bytes=lambda a: L.deodr_hip_basis_scratch_bytes(a["K"], a["N"], a["batch"]))  # fmt: skip
 
-    def apply(basis=basis, mean=mean, coeffs=coeffs, K=4, N=100, batch=2, basis_dtype=F32, y=y, y_dtype=F64):
-        rc = L.deodr_hip_basis_apply(basis, mean, coeffs, K, N, batch, basis_dtype, y, y_dtype, None)
-        return rc, L.deodr_hip_last_error().decode()
-
-    def apply_b(basis=basis, g=g, g_dtype=F32, K=4, N=100, batch=2, basis_dtype=F32, c_b=c_b, accumulate=0, scratch=scratch, scratch_bytes=None):
-        need = L.deodr_hip_basis_scratch_bytes(K, N, batch)
-        rc = L.deodr_hip_basis_apply_b(basis, g, g_dtype, K, N, batch, basis_dtype, c_b, accumulate, scratch, need if scratch_bytes is None else scratch_bytes, None)
-        return rc, L.deodr_hip_last_error().decode()
-
-    for call, what, required in ((apply, "basis_apply", ("basis", "coeffs", "y")), (apply_b, "basis_apply_b", ("basis", "g", "c_b", "scratch"))):
-        for p in required:
-            rc, msg = call(**{p: None})
-            assert rc == 1 and msg.startswith(what + ":") and "== NULL" in msg, (p, msg)
+    for call, what, required in ((apply, "basis_apply", ("basis", "coeffs", "y")), (apply_b, "basis_apply_b", ("basis", "g", "coeffs_b", "scratch"))):
+        for bad in nulls(required):
+            rc, msg = call(**bad)
+            assert rc == 1 and msg.startswith(what + ":") and "== NULL" in msg, (bad, msg)
         for bad in (dict(K=0), dict(K=-1), dict(K=1025)):
             assert call(**bad) == (1, what + ": K must be in 1 .. 1024"), bad
         for bad in (dict(batch=0), dict(batch=-1), dict(batch=65)):
@@ -125,14 +81,14 @@ def test_bad_arguments_are_refused_before_any_launch():
     for bad in (dict(basis=basis + 2), dict(basis=basis + 4, basis_dtype=F64), dict(mean=mean + 1), dict(mean=mean + 4, basis_dtype=F64), dict(coeffs=coeffs + 4),
                 dict(y=y + 4), dict(y=y + 2, y_dtype=F32)):  # fmt: skip
         assert apply(**bad) == (1, "basis_apply: misaligned pointer"), bad
-    for bad in (dict(basis=basis + 2), dict(basis=basis + 4, basis_dtype=F64), dict(g=g + 3), dict(g=g + 4, g_dtype=F64), dict(c_b=c_b + 4), dict(scratch=scratch + 4)):
+    for bad in (dict(basis=basis + 2), dict(basis=basis + 4, basis_dtype=F64), dict(g=g + 3), dict(g=g + 4, g_dtype=F64), dict(coeffs_b=c_b + 4), dict(scratch=scratch + 4)):
         assert apply_b(**bad) == (1, "basis_apply_b: misaligned pointer"), bad
     # y [2, 100] float64 = 1600 bytes against basis [4, 100] float32 = 1600 bytes, mean 400 bytes, coeffs [2, 4] = 64 bytes
     for y_at in (basis, basis + 1600 - 8, basis - 1600 + 8, mean, mean + 400 - 8, mean - 1600 + 8, coeffs, coeffs + 64 - 8, coeffs - 1600 + 8):
         assert apply(y=y_at) == (1, "basis_apply: y must not overlap basis, mean or coeffs"), hex(y_at)
     # coeffs_b [2, 4] = 64 bytes against basis 1600 bytes and g [2, 100] float32 = 800 bytes
     for at in (basis, basis + 1600 - 8, basis - 64 + 8, g, g + 800 - 8, g - 64 + 8):
-        assert apply_b(c_b=at) == (1, "basis_apply_b: coeffs_b must not overlap basis or g"), hex(at)
+        assert apply_b(coeffs_b=at) == (1, "basis_apply_b: coeffs_b must not overlap basis or g"), hex(at)
     need = L.deodr_hip_basis_scratch_bytes(4, 100, 2)
     for short in (0, 8, need - 1):
         assert apply_b(scratch_bytes=short) == (1, "basis_apply_b: scratch too small (deodr_hip_basis_scratch_bytes)"), short
@@ -141,10 +97,9 @@ def test_bad_arguments_are_refused_before_any_launch():
 def test_host_wrappers_check_their_tensors_before_the_library(monkeypatch):
     import torch
 
+    from abi_cases import no_library
+    from abi_cases import on_device as dev
     from deodr_amd import hip_renderer as hr
-
-    def no_library():
-        raise AssertionError("the library was reached")
 
     monkeypatch.setattr(hr, "lib", no_library)
     basis, mean, coeffs, g = torch.zeros(4, 10), torch.zeros(10), torch.zeros(2, 4, dtype=torch.float64), torch.zeros(2, 10)
@@ -157,12 +112,6 @@ def test_host_wrappers_check_their_tensors_before_the_library(monkeypatch):
     with pytest.raises(ValueError, match="ROCm tensor"):
         hr.basis_apply(basis.numpy(), None, coeffs)
 
-    # the checks behind the device check, on tensors that only claim to be on the device
-    class OnDevice(torch.Tensor):
-        is_cuda = property(lambda self: True)
-        device = property(lambda self: torch.device("cuda", 0))
-
-    dev = lambda t: t.as_subclass(OnDevice)
     B, m, c, gd = dev(basis), dev(mean), dev(coeffs), dev(g)
     with pytest.raises(ValueError, match="basis must be float32 or float64"):
         hr.basis_apply(dev(basis.to(torch.float16)), None, c)

@@ -1,65 +1,20 @@
-"""CPU checks of the companion header include/deodr_hip_chamfer.h (the closest-point energy): it parses with the parser of deodr_hip.h and shares no
-name with the other twelve headers, its prototypes are type by type what the header documents, every name it declares is exported by the
-cross-compiled library and bound with the declared types, its version is 1 on both sides, the constants of deodr_amd/csrc/dr_chamfer.h are the ones
-the case tables are built for, every bad argument of the launching entry point is refused through its error code with a message before any launch
-(fake pointers, no GPU), the scratch size is 0 outside the limits and the documented formula inside, the split rule is swept for monotonicity and
-bounds, and the host wrapper refuses CPU tensors, wrong dtypes and wrong shapes without reaching the library."""
+"""CPU checks of the closest-point energy at the C ABI (include/deodr_hip_chamfer.h; the header itself: tests/test_companion_headers.py): the
+constants of deodr_amd/csrc/dr_chamfer.h are the ones the case tables are built for, every bad argument of the launching entry point is refused
+through its error code with a message before any launch (fake pointers, no GPU), the scratch size is 0 outside the limits and the documented
+formula inside, the split rule is swept for monotonicity and bounds, and the host wrapper refuses CPU tensors, wrong dtypes and wrong shapes
+without reaching the library."""
 
-import ctypes as C
 import os
 import re
 
 import pytest
 
-CHAMFER_FUNCTIONS = ["deodr_hip_chamfer", "deodr_hip_chamfer_scratch_bytes", "deodr_hip_chamfer_launches", "deodr_hip_chamfer_segments", "deodr_hip_chamfer_abi_version"]
-DEFINES = {"ABI_VERSION": 1, "POINTS_TO_MESH": 1, "MESH_TO_POINTS": 2, "BLOCK": 256, "TILE": 256, "MAX_BLOCKS": 512, "TARGET_BLOCKS": 1024, "MAX_SEGMENTS": 64,
-           "MAX_PAIRS": 2**36}  # fmt: skip
 
-
-def test_companion_header_parses_and_is_versioned_on_its_own():
-    from deodr_amd import _abi
-
-    h = _abi.CHAMFER_HEADER
-    assert sorted(h.functions) == sorted(CHAMFER_FUNCTIONS)
-    assert h.defines == {"DEODR_HIP_CHAMFER_" + k: v for k, v in DEFINES.items()}
-    assert h.structs == {} and h.name == "include/deodr_hip_chamfer.h"
-    others = (_abi.HEADER, _abi.TEXTURE_HEADER, _abi.SUBDIV_HEADER, _abi.RETAINED_HEADER, _abi.BASIS_HEADER, _abi.CAMERA_HEADER, _abi.LIGHTING_HEADER,
-              _abi.SKINNING_HEADER, _abi.PYRAMID_HEADER, _abi.SSIM_HEADER, _abi.SOLVE_HEADER, _abi.ARAP_HEADER)  # fmt: skip
-    assert len(others) == 12
-    for other in others:
-        assert not set(h.functions) & set(other.functions) and not set(h.defines) & set(other.defines)
-    assert re.search(r"#define\s+DEODR_HIP_CHAMFER_ABI_VERSION\s+1\b", open(_abi.CHAMFER_HEADER_PATH).read())
-    p, i, z = C.c_void_p, C.c_int, C.c_size_t
-    assert h.functions["deodr_hip_chamfer"] == (i, [p, i, p, i, p, p, p, i, i, p, p, p, p, p, p, z, p])  # 17 parameters
-    assert h.functions["deodr_hip_chamfer_scratch_bytes"] == (z, [i, i, i])
-    assert h.functions["deodr_hip_chamfer_launches"] == (i, [i, i, i, i])
-    assert h.functions["deodr_hip_chamfer_segments"] == (i, [i, i])
-    assert h.functions["deodr_hip_chamfer_abi_version"] == (i, [])
-
-
-def test_library_exports_and_binds_every_name_of_the_companion_header():
-    import __graft_entry__ as g
-    from deodr_amd import _abi
+def test_the_host_side_has_the_operator_s_names():
     from deodr_amd import hip_renderer as hr
 
-    raw = C.CDLL(g.build_hip())
-    for name in CHAMFER_FUNCTIONS:
-        assert hasattr(raw, name), name
-    assert raw.deodr_hip_chamfer_abi_version() == 1 == hr.CHAMFER_ABI_VERSION
-    L = hr.lib()  # binds every header
-    for name, (restype, argtypes) in _abi.CHAMFER_HEADER.functions.items():
-        f = getattr(L, name)
-        assert f.restype is restype and list(f.argtypes) == argtypes, name
     for name in ("chamfer", "chamfer_scratch", "chamfer_launches", "chamfer_segments", "CHAMFER_ABI_VERSION"):
         assert hasattr(hr, name), name
-
-
-def test_the_header_is_on_the_list_that_decides_whether_the_library_is_stale():
-    import inspect
-
-    import __graft_entry__ as g
-
-    assert '"deodr_hip_chamfer.h"' in inspect.getsource(g.build_hip)
 
 
 def test_the_constants_of_the_kernels_are_the_case_table_s():
@@ -120,6 +75,8 @@ def test_the_split_rule_is_monotone_and_bounded():
 
 def test_bad_arguments_are_refused_before_any_launch():
     """every pointer below is fake and never dereferenced: a refusal happens before any HIP call"""
+    from abi_cases import entry, misaligned, nulls, overlap_placements
+    from deodr_amd import _abi
     from deodr_amd import hip_renderer as hr
 
     L = hr.lib()
@@ -128,18 +85,13 @@ def test_bad_arguments_are_refused_before_any_launch():
                 loss=0x16000000, vertices_b=0x17000000, nearest_vertex=0x18000000, nearest_point=0x19000000, scratch=0x1A000000)  # fmt: skip
     optional = ("point_weights", "vertex_weights", "nearest_vertex", "nearest_point")
 
-    def call(V=V, P=P, n=n, directions=3, scratch_bytes=None, **changed):
-        a = dict(base, **changed)
-        need = L.deodr_hip_chamfer_scratch_bytes(V, P, n)
-        rc = L.deodr_hip_chamfer(a["vertices"], V, a["points"], P, a["point_weights"], a["vertex_weights"], a["params"], n, directions, a["terms"], a["loss"],
-                                 a["vertices_b"], a["nearest_vertex"], a["nearest_point"], a["scratch"], need if scratch_bytes is None else scratch_bytes, None)  # fmt: skip
-        return rc, L.deodr_hip_last_error().decode()
-
+    call = entry(L, _abi.CHAMFER_HEADER, "deodr_hip_chamfer", base, V=V, P=P, n=n, directions=3,
+                 scratch_bytes=lambda a: L.deodr_hip_chamfer_scratch_bytes(a["V"], a["P"], a["n"]))  # fmt: skip
     what = "chamfer"
-    for p in base:  # a NULL required pointer (the optional ones may be NULL: such a call gets past every check only with real memory, not tried here)
-        if p not in optional:
-            rc, msg = call(**{p: None})
-            assert rc == 1 and msg.startswith(what + ":") and "== NULL" in msg, (p, msg)
+    # a NULL required pointer (the optional ones may be NULL: such a call gets past every check only with real memory, not tried here)
+    for bad in nulls(p for p in base if p not in optional):
+        rc, msg = call(**bad)
+        assert rc == 1 and msg.startswith(what + ":") and "== NULL" in msg, (bad, msg)
     for bad in (0, -1, -(2**31)):
         assert call(V=bad, scratch_bytes=1 << 20) == (1, what + ": V must be positive"), bad
         assert call(P=bad, scratch_bytes=1 << 20) == (1, what + ": P must be positive"), bad
@@ -149,11 +101,10 @@ def test_bad_arguments_are_refused_before_any_launch():
         assert call(directions=bad) == (1, what + ": directions must be in 1 .. 3"), bad
     assert call(V=2**18, P=2**18 + 1, n=1, scratch_bytes=1 << 40) == (1, what + ": V * P is above DEODR_HIP_CHAMFER_MAX_PAIRS (the search is brute force)")
     assert call(V=2**31 - 1, P=2**31 - 1, n=1, scratch_bytes=1 << 40)[1].endswith("(the search is brute force)")
-    for p in ("nearest_vertex", "nearest_point"):
-        assert call(**{p: base[p] + 2}) == (1, what + ": misaligned pointer"), p
-    for p in base:
-        if p not in ("nearest_vertex", "nearest_point"):
-            assert call(**{p: base[p] + 4}) == (1, what + ": misaligned pointer"), p
+    for bad in misaligned(base, ("nearest_vertex", "nearest_point"), 2):
+        assert call(**bad) == (1, what + ": misaligned pointer"), bad
+    for bad in misaligned(base, (p for p in base if p not in ("nearest_vertex", "nearest_point")), 4):
+        assert call(**bad) == (1, what + ": misaligned pointer"), bad
     need = L.deodr_hip_chamfer_scratch_bytes(V, P, n)
     for short in (0, 64, need - 1):
         assert call(scratch_bytes=short) == (1, what + ": scratch too small (deodr_hip_chamfer_scratch_bytes)"), short
@@ -163,17 +114,16 @@ def test_bad_arguments_are_refused_before_any_launch():
     for out in ("terms", "loss", "vertices_b", "nearest_vertex", "nearest_point", "scratch"):
         for other in sizes:
             if other != out:
-                for at in (base[other], base[other] + sizes[other] - 8, base[other] - sizes[out] + 8):
+                for at in overlap_placements(base, sizes, out, other):
                     assert call(**{out: at}) == refusal, (out, other, hex(at))
 
 
 def test_host_wrapper_checks_its_tensors_before_the_library(monkeypatch):
     import torch
 
+    from abi_cases import no_library
+    from abi_cases import on_device as dev
     from deodr_amd import hip_renderer as hr
-
-    def no_library():
-        raise AssertionError("the library was reached")
 
     monkeypatch.setattr(hr, "lib", no_library)
     f64 = lambda *shape: torch.zeros(*shape, dtype=torch.float64)
@@ -181,11 +131,6 @@ def test_host_wrapper_checks_its_tensors_before_the_library(monkeypatch):
     with pytest.raises(ValueError, match="vertices must be a ROCm tensor"):
         hr.chamfer(f64(2, 5, 3), f64(2, 9, 3), f64(3))
 
-    class OnDevice(torch.Tensor):
-        is_cuda = property(lambda self: True)
-        device = property(lambda self: torch.device("cuda", 0))
-
-    dev = lambda x: x.as_subclass(OnDevice)
     Vt, Pt, Prm = dev(f64(2, 5, 3)), dev(f64(2, 9, 3)), dev(f64(3))
     for bad in (dev(f64(5, 3)), dev(f64(2, 5, 4)), dev(f64(0, 5, 3)), dev(f64(2, 0, 3)), dev(f64(2, 5, 3, 1))):
         with pytest.raises(ValueError, match=r"vertices must have shape \[n >= 1, V >= 1, 3\]"):

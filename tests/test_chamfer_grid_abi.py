@@ -1,11 +1,9 @@
-"""CPU checks of the companion header include/deodr_hip_chamfer_grid.h (the stable sort by key and the closest-point energy over a uniform grid):
-it parses with the parser of deodr_hip.h and shares no name with the other headers, its prototypes are type by type what the header documents,
-every name it declares is exported by the cross-compiled library and bound with the declared types, its version is 1 on both sides, its constants
-are the restatement's, every bad argument of the two launching entry points is refused through its error code with a message before any launch
-(fake pointers, no GPU), ``scratch_bytes`` / ``launches`` / ``table_bits`` are the restatement's at and around their change points and 0 for
-refused arguments, and the host wrappers refuse CPU tensors, wrong dtypes and wrong shapes without reaching the library."""
+"""CPU checks of the stable sort by key and the closest-point energy over a uniform grid at the C ABI (include/deodr_hip_chamfer_grid.h; the
+header itself: tests/test_companion_headers.py): its constants are the restatement's and the kernels', every bad argument of the two launching
+entry points is refused through its error code with a message before any launch (fake pointers, no GPU), ``scratch_bytes`` / ``launches`` /
+``table_bits`` are the restatement's at and around their change points and 0 for refused arguments, and the host wrappers refuse CPU tensors,
+wrong dtypes and wrong shapes without reaching the library."""
 
-import ctypes as C
 import os
 import re
 
@@ -13,56 +11,15 @@ import pytest
 
 import chamfer_grid_reference as gr
 
-FUNCTIONS = ["deodr_hip_sort_keys", "deodr_hip_sort_keys_scratch_bytes", "deodr_hip_sort_keys_launches", "deodr_hip_chamfer_grid",
-             "deodr_hip_chamfer_grid_scratch_bytes", "deodr_hip_chamfer_grid_launches", "deodr_hip_chamfer_grid_table_bits", "deodr_hip_chamfer_grid_abi_version"]  # fmt: skip
-DEFINES = {"DEODR_HIP_SORT_DIGIT_BITS": gr.DIGIT_BITS, "DEODR_HIP_SORT_BLOCK": gr.SORT_BLOCK, "DEODR_HIP_SORT_ITEMS": gr.SORT_ITEMS,
-           "DEODR_HIP_SORT_MAX_ITEMS": gr.SORT_MAX_ITEMS, "DEODR_HIP_CHAMFER_GRID_NONE": 0xFFFFFFFF, "DEODR_HIP_CHAMFER_GRID_RINGS": gr.RINGS, "DEODR_HIP_CHAMFER_GRID_TABLE_LOAD": gr.TABLE_LOAD,
-           "DEODR_HIP_CHAMFER_GRID_CELL_LIMIT": gr.CELL_LIMIT, "DEODR_HIP_CHAMFER_GRID_MAX_ITEMS": gr.MAX_ITEMS, "DEODR_HIP_CHAMFER_GRID_MIN_TABLE_BITS": gr.MIN_TABLE_BITS,
-           "DEODR_HIP_CHAMFER_GRID_MAX_TABLE_BITS": gr.MAX_TABLE_BITS, "DEODR_HIP_CHAMFER_GRID_GATHER_VERTICES": gr.GATHER_VERTICES,
-           "DEODR_HIP_CHAMFER_GRID_ABI_VERSION": 1}  # fmt: skip
 
-
-def test_companion_header_parses_and_is_versioned_on_its_own():
-    from deodr_amd import _abi
-
-    h = _abi.CHAMFER_GRID_HEADER
-    assert sorted(h.functions) == sorted(FUNCTIONS) and h.defines == DEFINES
-    assert h.structs == {} and h.name == "include/deodr_hip_chamfer_grid.h"
-    others = [_abi.HEADER] + [getattr(_abi, name) for name, _file, _structs in _abi._COMPANIONS if name != "CHAMFER_GRID_HEADER"]
-    assert len(others) == 14
-    for other in others:
-        assert not set(h.functions) & set(other.functions) and not set(h.defines) & set(other.defines)
-    assert re.search(r"#define\s+DEODR_HIP_CHAMFER_GRID_ABI_VERSION\s+1\b", open(_abi.CHAMFER_GRID_HEADER_PATH).read())
-    p, i, z, d = C.c_void_p, C.c_int, C.c_size_t, C.c_double
-    assert h.functions["deodr_hip_sort_keys"] == (i, [p, i, i, i, p, p, p, z, p])
-    assert h.functions["deodr_hip_sort_keys_scratch_bytes"] == (z, [i, i, i]) and h.functions["deodr_hip_sort_keys_launches"] == (i, [i, i, i])
-    assert h.functions["deodr_hip_chamfer_grid"] == (i, [p, i, p, i, p, p, p, d, i, i, p, p, p, p, p, p, z, p])  # deodr_hip_chamfer's and cell_size
-    assert h.functions["deodr_hip_chamfer_grid_scratch_bytes"] == (z, [i, i, i]) and h.functions["deodr_hip_chamfer_grid_launches"] == (i, [i, i, i, i])
-    assert h.functions["deodr_hip_chamfer_grid_table_bits"] == (i, [i]) and h.functions["deodr_hip_chamfer_grid_abi_version"] == (i, [])
-    assert gr.SORT_ITEMS % gr.SORT_BLOCK == 0 and 1 << gr.DIGIT_BITS == gr.SORT_BLOCK and 2 * gr.MAX_ITEMS == 1 << gr.MAX_TABLE_BITS
-
-
-def test_library_exports_and_binds_every_name_and_the_header_is_registered():
-    import inspect
-
-    import __graft_entry__ as g
-    from deodr_amd import _abi
+def test_the_constants_are_the_restatement_s_and_the_host_side_has_the_operators_names():
     from deodr_amd import hip_renderer as hr
 
-    raw = C.CDLL(g.build_hip())
-    for name in FUNCTIONS:
-        assert hasattr(raw, name), name
-    assert raw.deodr_hip_chamfer_grid_abi_version() == 1 == hr.CHAMFER_GRID_ABI_VERSION
-    L = hr.lib()  # binds every header
-    for name, (restype, argtypes) in _abi.CHAMFER_GRID_HEADER.functions.items():
-        f = getattr(L, name)
-        assert f.restype is restype and list(f.argtypes) == argtypes, name
+    assert gr.SORT_ITEMS % gr.SORT_BLOCK == 0 and 1 << gr.DIGIT_BITS == gr.SORT_BLOCK and 2 * gr.MAX_ITEMS == 1 << gr.MAX_TABLE_BITS
     for name in ("chamfer_grid", "chamfer_grid_scratch", "chamfer_grid_launches", "chamfer_grid_table_bits", "sort_keys", "sort_keys_scratch", "sort_keys_launches",
                  "CHAMFER_GRID_ABI_VERSION", "CHAMFER_GRID_NONE"):  # fmt: skip
         assert hasattr(hr, name), name
     assert hr.CHAMFER_GRID_NONE == gr.NONE and (hr.SORT_DIGIT_BITS, hr.SORT_ITEMS, hr.CHAMFER_GRID_RINGS) == (gr.DIGIT_BITS, gr.SORT_ITEMS, gr.RINGS)
-    assert '"deodr_hip_chamfer_grid.h"' in inspect.getsource(g.build_hip)
-    assert ("CHAMFER_GRID_HEADER", "deodr_hip_chamfer_grid.h", False) in _abi._COMPANIONS
 
 
 def test_the_kernels_use_the_header_s_constants_and_no_atomics_on_values():
@@ -112,6 +69,8 @@ def test_sizes_at_and_around_their_change_points_and_zero_for_refused_arguments(
 
 def test_bad_arguments_of_the_sort_are_refused_before_any_launch():
     """every pointer below is fake and never dereferenced: a refusal happens before any HIP call"""
+    from abi_cases import entry, misaligned, nulls, overlap_placements
+    from deodr_amd import _abi
     from deodr_amd import hip_renderer as hr
 
     L = hr.lib()
@@ -119,35 +78,33 @@ def test_bad_arguments_of_the_sort_are_refused_before_any_launch():
     base = dict(keys=0x10000000, sorted_keys=0x11000000, order=0x12000000, scratch=0x13000000)
     need = L.deodr_hip_sort_keys_scratch_bytes(N, n, bits)
 
-    def call(N=N, n=n, bits=bits, scratch_bytes=need, **changed):
-        a = dict(base, **changed)
-        rc = L.deodr_hip_sort_keys(a["keys"], N, n, bits, a["sorted_keys"], a["order"], a["scratch"], scratch_bytes, None)
-        return rc, L.deodr_hip_last_error().decode()
-
+    call = entry(L, _abi.CHAMFER_GRID_HEADER, "deodr_hip_sort_keys", base, N=N, n=n, bits=bits, scratch_bytes=need)
     what = "sort_keys"
-    for p in ("keys", "order", "scratch"):
-        rc, msg = call(**{p: None})
-        assert rc == 1 and msg.startswith(what + ":") and "== NULL" in msg, (p, msg)
+    for bad in nulls(("keys", "order", "scratch")):
+        rc, msg = call(**bad)
+        assert rc == 1 and msg.startswith(what + ":") and "== NULL" in msg, (bad, msg)
     for bad in (0, -1, gr.SORT_MAX_ITEMS + 1):
         assert call(N=bad, scratch_bytes=1 << 40) == (1, what + ": N must be in 1 .. DEODR_HIP_SORT_MAX_ITEMS"), bad
     for bad in (0, -1, 65536):
         assert call(n=bad, scratch_bytes=1 << 40) == (1, what + ": n must be in 1 .. 65535"), bad
     for bad in (0, -1, 33):
         assert call(bits=bad) == (1, what + ": bits must be in 1 .. 32"), bad
-    for p in base:
-        assert call(**{p: base[p] + 2}) == (1, what + ": misaligned pointer"), p
+    for bad in misaligned(base, base, 2):
+        assert call(**bad) == (1, what + ": misaligned pointer"), bad
     for short in (0, 64, need - 1):
         assert call(scratch_bytes=short) == (1, what + ": scratch too small (deodr_hip_sort_keys_scratch_bytes)"), short
     sizes = dict(keys=4 * n * N, sorted_keys=4 * n * N, order=4 * n * N, scratch=need)
     for a in base:
         for b in base:
             if a != b:
-                for at in (base[b], base[b] + sizes[b] - 4, base[b] - sizes[a] + 4):
+                for at in overlap_placements(base, sizes, a, b, unit=4):
                     assert call(**{a: at}) == (1, what + ": keys, sorted_keys, order and scratch must not overlap"), (a, b, hex(at))
 
 
 def test_bad_arguments_of_the_operator_are_refused_before_any_launch():
     """every pointer below is fake and never dereferenced: a refusal happens before any HIP call"""
+    from abi_cases import entry, misaligned, nulls, overlap_placements
+    from deodr_amd import _abi
     from deodr_amd import hip_renderer as hr
 
     L = hr.lib()
@@ -156,18 +113,13 @@ def test_bad_arguments_of_the_operator_are_refused_before_any_launch():
                 loss=0x16000000, vertices_b=0x17000000, nearest_vertex=0x18000000, nearest_point=0x19000000, scratch=0x1A000000)  # fmt: skip
     optional = ("point_weights", "vertex_weights", "nearest_vertex", "nearest_point")
 
-    def call(V=V, P=P, n=n, directions=3, cell_size=0.1, scratch_bytes=None, **changed):
-        a = dict(base, **changed)
-        need = L.deodr_hip_chamfer_grid_scratch_bytes(V, P, n)
-        rc = L.deodr_hip_chamfer_grid(a["vertices"], V, a["points"], P, a["point_weights"], a["vertex_weights"], a["params"], cell_size, n, directions, a["terms"],
-                                      a["loss"], a["vertices_b"], a["nearest_vertex"], a["nearest_point"], a["scratch"], need if scratch_bytes is None else scratch_bytes, None)  # fmt: skip
-        return rc, L.deodr_hip_last_error().decode()
-
+    call = entry(L, _abi.CHAMFER_GRID_HEADER, "deodr_hip_chamfer_grid", base, V=V, P=P, n=n, directions=3, cell_size=0.1,
+                 scratch_bytes=lambda a: L.deodr_hip_chamfer_grid_scratch_bytes(a["V"], a["P"], a["n"]))  # fmt: skip
     what = "chamfer_grid"
-    for p in base:  # a NULL required pointer (the optional ones may be NULL: such a call gets past every check only with real memory, not tried here)
-        if p not in optional:
-            rc, msg = call(**{p: None})
-            assert rc == 1 and msg.startswith(what + ":") and "== NULL" in msg, (p, msg)
+    # a NULL required pointer (the optional ones may be NULL: such a call gets past every check only with real memory, not tried here)
+    for bad in nulls(p for p in base if p not in optional):
+        rc, msg = call(**bad)
+        assert rc == 1 and msg.startswith(what + ":") and "== NULL" in msg, (bad, msg)
     for bad in (0, -1, -(2**31), gr.MAX_ITEMS + 1):
         assert call(V=bad, scratch_bytes=1 << 40) == (1, what + ": V must be in 1 .. DEODR_HIP_CHAMFER_GRID_MAX_ITEMS"), bad
         assert call(P=bad, scratch_bytes=1 << 40) == (1, what + ": P must be in 1 .. DEODR_HIP_CHAMFER_GRID_MAX_ITEMS"), bad
@@ -177,11 +129,10 @@ def test_bad_arguments_of_the_operator_are_refused_before_any_launch():
         assert call(directions=bad) == (1, what + ": directions must be in 1 .. 3"), bad
     for bad in (0.0, -0.1, float("inf"), float("-inf"), float("nan")):
         assert call(cell_size=bad) == (1, what + ": cell_size must be finite and > 0"), bad
-    for p in ("nearest_vertex", "nearest_point"):
-        assert call(**{p: base[p] + 2}) == (1, what + ": misaligned pointer"), p
-    for p in base:
-        if p not in ("nearest_vertex", "nearest_point"):
-            assert call(**{p: base[p] + 4}) == (1, what + ": misaligned pointer"), p
+    for bad in misaligned(base, ("nearest_vertex", "nearest_point"), 2):
+        assert call(**bad) == (1, what + ": misaligned pointer"), bad
+    for bad in misaligned(base, (p for p in base if p not in ("nearest_vertex", "nearest_point")), 4):
+        assert call(**bad) == (1, what + ": misaligned pointer"), bad
     need = L.deodr_hip_chamfer_grid_scratch_bytes(V, P, n)
     for short in (0, 64, need - 1):
         assert call(scratch_bytes=short) == (1, what + ": scratch too small (deodr_hip_chamfer_grid_scratch_bytes)"), short
@@ -191,17 +142,16 @@ def test_bad_arguments_of_the_operator_are_refused_before_any_launch():
     for out in ("terms", "loss", "vertices_b", "nearest_vertex", "nearest_point", "scratch"):
         for other in sizes:
             if other != out:
-                for at in (base[other], base[other] + sizes[other] - 8, base[other] - sizes[out] + 8):
+                for at in overlap_placements(base, sizes, out, other):
                     assert call(**{out: at}) == refusal, (out, other, hex(at))
 
 
 def test_host_wrappers_check_their_tensors_before_the_library(monkeypatch):
     import torch
 
+    from abi_cases import no_library
+    from abi_cases import on_device as dev
     from deodr_amd import hip_renderer as hr
-
-    def no_library():
-        raise AssertionError("the library was reached")
 
     monkeypatch.setattr(hr, "lib", no_library)
     f64 = lambda *shape: torch.zeros(*shape, dtype=torch.float64)
@@ -211,11 +161,6 @@ def test_host_wrappers_check_their_tensors_before_the_library(monkeypatch):
     with pytest.raises(ValueError, match="keys must be a ROCm tensor"):
         hr.sort_keys(i32(2, 9))
 
-    class OnDevice(torch.Tensor):
-        is_cuda = property(lambda self: True)
-        device = property(lambda self: torch.device("cuda", 0))
-
-    dev = lambda x: x.as_subclass(OnDevice)
     Vt, Pt, Prm = dev(f64(2, 5, 3)), dev(f64(2, 9, 3)), dev(f64(3))
     for bad in (dev(f64(5, 3)), dev(f64(2, 5, 4)), dev(f64(0, 5, 3)), dev(f64(2, 0, 3))):
         with pytest.raises(ValueError, match=r"vertices must have shape \[n >= 1, V >= 1, 3\]"):

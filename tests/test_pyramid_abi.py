@@ -1,57 +1,16 @@
-"""CPU checks of the companion header include/deodr_hip_pyramid.h (the multi-scale L2 data term): it parses with the parser of deodr_hip.h and shares no
-name with the other headers, its prototypes are type by type what the header documents, every name it declares is exported by the cross-compiled
-library and bound with the declared types, its version is 1 on both sides, every bad argument of the launching entry point is refused through its
-error code with a message before any launch (fake pointers, no GPU), the scratch size is 0 outside the limits and monotone inside them, and the host
-wrapper refuses CPU tensors, wrong dtypes and wrong shapes without reaching the library."""
-
-import ctypes as C
-import re
+"""CPU checks of the multi-scale L2 data term at the C ABI (include/deodr_hip_pyramid.h; the header itself: tests/test_companion_headers.py):
+every bad argument of the launching entry point is refused through its error code with a message before any launch (fake pointers, no GPU), the
+scratch size is 0 outside the limits and monotone inside them, and the host wrapper refuses CPU tensors, wrong dtypes and wrong shapes without
+reaching the library."""
 
 import pytest
 
-PYRAMID_FUNCTIONS = ["deodr_hip_pyramid_l2", "deodr_hip_pyramid_scratch_bytes", "deodr_hip_pyramid_abi_version"]
 
-
-def test_companion_header_parses_and_is_versioned_on_its_own():
-    from deodr_amd import _abi
-
-    h = _abi.PYRAMID_HEADER
-    assert sorted(h.functions) == sorted(PYRAMID_FUNCTIONS)
-    assert h.defines == {"DEODR_HIP_PYRAMID_ABI_VERSION": 1, "DEODR_HIP_PYRAMID_MAX_LEVELS": 8} and h.structs == {}
-    assert h.name == "include/deodr_hip_pyramid.h"
-    for other in (_abi.HEADER, _abi.TEXTURE_HEADER, _abi.SUBDIV_HEADER, _abi.RETAINED_HEADER, _abi.BASIS_HEADER, _abi.CAMERA_HEADER, _abi.LIGHTING_HEADER,
-                  _abi.SKINNING_HEADER):  # fmt: skip
-        assert not set(h.functions) & set(other.functions) and not set(h.defines) & set(other.defines)
-    assert re.search(r"#define\s+DEODR_HIP_PYRAMID_ABI_VERSION\s+1\b", open(_abi.PYRAMID_HEADER_PATH).read())
-    p, i, z = C.c_void_p, C.c_int, C.c_size_t
-    assert h.functions["deodr_hip_pyramid_l2"] == (i, [p, p, p, i, i, i, i, i, i, p, p, p, p, p, z, p])  # 16 parameters
-    assert h.functions["deodr_hip_pyramid_scratch_bytes"] == (z, [i, i, i, i, i])
-    assert h.functions["deodr_hip_pyramid_abi_version"] == (i, [])
-
-
-def test_library_exports_and_binds_every_name_of_the_companion_header():
-    import __graft_entry__ as g
-    from deodr_amd import _abi
+def test_the_level_limit_is_the_header_s():
     from deodr_amd import hip_renderer as hr
     from deodr_amd import pyramid
 
-    raw = C.CDLL(g.build_hip())
-    for name in PYRAMID_FUNCTIONS:
-        assert hasattr(raw, name), name
-    assert raw.deodr_hip_pyramid_abi_version() == 1 == hr.PYRAMID_ABI_VERSION
     assert hr.PYRAMID_MAX_LEVELS == pyramid.MAX_LEVELS == 8
-    L = hr.lib()  # binds every header
-    for name, (restype, argtypes) in _abi.PYRAMID_HEADER.functions.items():
-        f = getattr(L, name)
-        assert f.restype is restype and list(f.argtypes) == argtypes, name
-
-
-def test_the_header_is_on_the_list_that_decides_whether_the_library_is_stale():
-    import inspect
-
-    import __graft_entry__ as g
-
-    assert '"deodr_hip_pyramid.h"' in inspect.getsource(g.build_hip)
 
 
 def test_scratch_is_zero_outside_the_limits_and_monotone_inside():
@@ -81,6 +40,8 @@ def test_scratch_is_zero_outside_the_limits_and_monotone_inside():
 
 def test_bad_arguments_are_refused_before_any_launch():
     """every pointer below is fake and never dereferenced: a refusal happens before any HIP call"""
+    from abi_cases import entry, misaligned, nulls, overlap_placements
+    from deodr_amd import _abi
     from deodr_amd import hip_renderer as hr
 
     L = hr.lib()
@@ -88,31 +49,26 @@ def test_bad_arguments_are_refused_before_any_launch():
     base = dict(image=0x10000000, obs=0x11000000, weights=0x12000000, level_weights=0x13000000, terms=0x14000000, loss=0x15000000, image_b=0x16000000,
                 scratch=0x17000000)  # fmt: skip
 
-    def call(n=n, H=H, W=W, Cn=Cn, levels=levels, dtype=hr._F64, scratch_bytes=None, **changed):
-        a = dict(base, **changed)
-        need = L.deodr_hip_pyramid_scratch_bytes(n, H, W, Cn, levels)
-        rc = L.deodr_hip_pyramid_l2(a["image"], a["obs"], a["weights"], n, H, W, Cn, dtype, levels, a["level_weights"], a["terms"], a["loss"], a["image_b"],
-                                    a["scratch"], need if scratch_bytes is None else scratch_bytes, None)  # fmt: skip
-        return rc, L.deodr_hip_last_error().decode()
-
+    call = entry(L, _abi.PYRAMID_HEADER, "deodr_hip_pyramid_l2", base, n=n, H=H, W=W, C=Cn, pixel_dtype=hr._F64, levels=levels,
+                 scratch_bytes=lambda a: L.deodr_hip_pyramid_scratch_bytes(a["n"], a["H"], a["W"], a["C"], a["levels"]))  # fmt: skip
     what = "pyramid_l2"
-    for p in ("image", "obs", "level_weights", "terms", "scratch"):  # a NULL that is not allowed
-        rc, msg = call(**{p: None})
-        assert rc == 1 and msg.startswith(what + ":") and "== NULL" in msg, (p, msg)
+    for bad in nulls(("image", "obs", "level_weights", "terms", "scratch")):  # a NULL that is not allowed
+        rc, msg = call(**bad)
+        assert rc == 1 and msg.startswith(what + ":") and "== NULL" in msg, (bad, msg)
     for bad in (0, -1, 9, 100):
         assert call(levels=bad) == (1, what + ": levels must be in 1 .. 8"), bad
     for bad in (0, -3):
-        assert call(Cn=bad) == (1, what + ": C must be >= 1"), bad
+        assert call(C=bad) == (1, what + ": C must be >= 1"), bad
     for bad in (dict(n=0), dict(H=0), dict(W=-1)):
         assert call(**bad) == (1, what + ": n, H and W must be >= 1"), bad
-    assert call(n=64, H=2**15, W=2**15, Cn=16) == (1, what + ": n H W C must be below 2^40")
+    assert call(n=64, H=2**15, W=2**15, C=16) == (1, what + ": n H W C must be below 2^40")
     for bad in (2, -1, 7):
-        assert call(dtype=bad) == (1, what + ": pixel_dtype must be DEODR_HIP_F32 or DEODR_HIP_F64"), bad
+        assert call(pixel_dtype=bad) == (1, what + ": pixel_dtype must be DEODR_HIP_F32 or DEODR_HIP_F64"), bad
     for p in ("image", "obs", "weights", "image_b"):  # aligned to their element
         assert call(**{p: base[p] + 4}) == (1, what + ": misaligned pointer"), p
-        assert call(dtype=hr._F32, **{p: base[p] + 2}) == (1, what + ": misaligned pointer"), p
-    for p in ("level_weights", "terms", "loss", "scratch"):
-        assert call(**{p: base[p] + 4}) == (1, what + ": misaligned pointer"), p
+        assert call(pixel_dtype=hr._F32, **{p: base[p] + 2}) == (1, what + ": misaligned pointer"), p
+    for bad in misaligned(base, ("level_weights", "terms", "loss", "scratch"), 4):
+        assert call(**bad) == (1, what + ": misaligned pointer"), bad
     need = L.deodr_hip_pyramid_scratch_bytes(n, H, W, Cn, levels)
     for short in (0, 64, need - 1):
         assert call(scratch_bytes=short) == (1, what + ": scratch too small (deodr_hip_pyramid_scratch_bytes)"), short
@@ -122,12 +78,12 @@ def test_bad_arguments_are_refused_before_any_launch():
     for out in ("terms", "loss", "image_b", "scratch"):
         for other in sizes:
             if other != out:
-                for at in (base[other], base[other] + sizes[other] - 8, base[other] - sizes[out] + 8):
+                for at in overlap_placements(base, sizes, out, other):
                     assert call(**{out: at}) == refusal, (out, other, hex(at))
     # two things wrong at once: the checks run in the order above, and the first one speaks
     assert call(image=None, n=0) == (1, what + ": image, obs, level_weights, terms or scratch == NULL")
-    assert call(n=0, dtype=7) == (1, what + ": n, H and W must be >= 1")
-    assert call(dtype=7, image=base["image"] + 4) == (1, what + ": pixel_dtype must be DEODR_HIP_F32 or DEODR_HIP_F64")
+    assert call(n=0, pixel_dtype=7) == (1, what + ": n, H and W must be >= 1")
+    assert call(pixel_dtype=7, image=base["image"] + 4) == (1, what + ": pixel_dtype must be DEODR_HIP_F32 or DEODR_HIP_F64")
     assert call(image=base["image"] + 4, scratch_bytes=need - 1) == (1, what + ": misaligned pointer")
     assert call(scratch_bytes=need - 1, terms=base["image"]) == (1, what + ": scratch too small (deodr_hip_pyramid_scratch_bytes)")
 
@@ -135,10 +91,9 @@ def test_bad_arguments_are_refused_before_any_launch():
 def test_host_wrapper_checks_its_tensors_before_the_library(monkeypatch):
     import torch
 
+    from abi_cases import no_library
+    from abi_cases import on_device as dev
     from deodr_amd import hip_renderer as hr
-
-    def no_library():
-        raise AssertionError("the library was reached")
 
     monkeypatch.setattr(hr, "lib", no_library)
     f64 = lambda *shape: torch.zeros(*shape, dtype=torch.float64)
@@ -146,11 +101,6 @@ def test_host_wrapper_checks_its_tensors_before_the_library(monkeypatch):
     with pytest.raises(ValueError, match="image must be a ROCm tensor"):
         hr.pyramid_l2(image, image, None, 3, lam)
 
-    class OnDevice(torch.Tensor):
-        is_cuda = property(lambda self: True)
-        device = property(lambda self: torch.device("cuda", 0))
-
-    dev = lambda x: x.as_subclass(OnDevice)
     I, O, Lw = dev(image), dev(f64(2, 5, 6, 3)), dev(lam)
     with pytest.raises(ValueError, match=r"image must have shape \[n >= 1, H >= 1, W >= 1, C >= 1\]"):
         hr.pyramid_l2(dev(f64(5, 6, 3)), O, None, 3, Lw)

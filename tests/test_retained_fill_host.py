@@ -1,9 +1,9 @@
-"""CPU checks of the retained background fill: the companion header include/deodr_hip_retained.h (layout, version, binding), and -- with
+"""CPU checks of the retained background fill: what only include/deodr_hip_retained.h says at the C ABI (the header itself:
+tests/test_companion_headers.py), and -- with
 tests/fake_hip.py standing in for the library -- WHEN HipRasterizer.render_fit tells the library that the buffers still hold the previous frame.
 The fake renders every frame in full whatever it is told: what is under test is the claim, call by call."""
 
 import ctypes as C
-import re
 import types
 
 import pytest
@@ -13,45 +13,25 @@ import fake_hip
 from deodr_amd import scenes
 
 ENTRY = "deodr_hip_render_scene_fit_retained"
-RETAINED_FUNCTIONS = [ENTRY, "deodr_hip_retained_abi_version"]
 
 
-def test_companion_header_parses_and_is_versioned_on_its_own():
+def test_the_entry_is_fit_ex_with_the_claim_and_points_to_the_main_header_s_structs():
     from deodr_amd import _abi
 
     h = _abi.RETAINED_HEADER
-    assert sorted(h.functions) == sorted(RETAINED_FUNCTIONS)
-    assert h.defines == {"DEODR_HIP_RETAINED_ABI_VERSION": 1} and h.structs == {}
-    assert h.name == "include/deodr_hip_retained.h"
-    # nothing of it leaks into the main header's binding, which stays what the existing tests pin
-    assert not set(h.functions) & set(_abi.HEADER.functions) and "DEODR_HIP_RETAINED_ABI_VERSION" not in _abi.HEADER.defines
     assert _abi.HEADER.defines["DEODR_HIP_ABI_VERSION"] == 13
-    text = open(_abi.RETAINED_HEADER_PATH).read()
-    assert re.search(r"#define\s+DEODR_HIP_RETAINED_ABI_VERSION\s+1\b", text)
     # deodr_hip_render_scene_fit_ex's arguments with `retained` between the options and the workspace; the structs are the main header's
-    scene, options = C.POINTER(_abi.HEADER.structs["DeodrHipScene"]), C.POINTER(_abi.HEADER.structs["DeodrHipFitOptions"])
-    assert h.functions[ENTRY] == (C.c_int, [scene, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int, options, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p])
     ex = _abi.HEADER.functions["deodr_hip_render_scene_fit_ex"][1]
     assert h.functions[ENTRY][1] == ex[:7] + [C.c_int] + ex[7:]
-    assert h.functions["deodr_hip_retained_abi_version"] == (C.c_int, [])
     with pytest.raises(ImportError, match=r"include/deodr_hip_retained\.h: no ctypes type for `const DeodrHipScene \*`"):
-        _abi.parse(text, "include/deodr_hip_retained.h")  # (without the main header's structs)
+        _abi.parse(open(_abi.RETAINED_HEADER_PATH).read(), "include/deodr_hip_retained.h")  # (without the main header's structs)
 
 
-def test_library_exports_and_binds_every_name_of_the_companion_header():
-    import __graft_entry__ as g
-    from deodr_amd import _abi
+def test_the_workspace_holds_one_more_tile_bitmap_per_view():
     from deodr_amd import hip_renderer as hr
 
-    raw = C.CDLL(g.build_hip())
-    for name in RETAINED_FUNCTIONS:
-        assert hasattr(raw, name), name
-    assert raw.deodr_hip_retained_abi_version() == 1 == hr.RETAINED_ABI_VERSION
+    # one more tile bitmap per view than one bitmap's worth: 64 x 64 pixels are 64 tiles, two words
     L = hr.lib()
-    for name, (restype, argtypes) in _abi.RETAINED_HEADER.functions.items():
-        f = getattr(L, name)
-        assert f.restype is restype and list(f.argtypes) == argtypes, name
-    # the workspace holds one more tile bitmap per view than one bitmap's worth: 64 x 64 pixels are 64 tiles, two words
     assert L.deodr_hip_workspace_bytes(10, 64, 64, 3, 2, 0) == 2 * L.deodr_hip_workspace_bytes(10, 64, 64, 3, 1, 0) > 0
 
 

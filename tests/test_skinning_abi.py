@@ -1,58 +1,19 @@
-"""CPU checks of the companion header include/deodr_hip_skinning.h (linear blend skinning): it parses with the parser of deodr_hip.h and shares no
-name with the other headers, its prototypes are type by type what the header documents, every name it declares is exported by the cross-compiled
-library and bound with the declared types, its version is 1 on both sides, every bad argument of the two launching entry points is refused with a
-message before any launch (fake pointers, no GPU), the scratch size is what the header says and 0 outside the limits, the host wrappers refuse CPU
-tensors, wrong dtypes and wrong shapes without reaching the library, and ``Skin`` refuses every table the header's model does not allow."""
+"""CPU checks of linear blend skinning at the C ABI (include/deodr_hip_skinning.h; the header itself: tests/test_companion_headers.py): its tables
+are device arrays, every bad argument of the two launching entry points is refused with a message before any launch (fake pointers, no GPU), the
+scratch size is what the header says and 0 outside the limits, the host wrappers refuse CPU tensors, wrong dtypes and wrong shapes without
+reaching the library, and ``Skin`` refuses every table the header's model does not allow."""
 
-import ctypes as C
 import re
 
 import numpy as np
 import pytest
 
-SKINNING_FUNCTIONS = ["deodr_hip_skin_apply", "deodr_hip_skin_apply_b", "deodr_hip_skin_scratch_bytes", "deodr_hip_skinning_abi_version"]
 
-
-def test_companion_header_parses_and_is_versioned_on_its_own():
+def test_the_tables_are_device_arrays():
     from deodr_amd import _abi
 
-    h = _abi.SKINNING_HEADER
-    assert sorted(h.functions) == sorted(SKINNING_FUNCTIONS)
-    assert h.defines == {"DEODR_HIP_SKINNING_ABI_VERSION": 1} and h.structs == {}
-    assert h.name == "include/deodr_hip_skinning.h"
-    for other in (_abi.HEADER, _abi.TEXTURE_HEADER, _abi.SUBDIV_HEADER, _abi.RETAINED_HEADER, _abi.BASIS_HEADER, _abi.CAMERA_HEADER, _abi.LIGHTING_HEADER):
-        assert not set(h.functions) & set(other.functions) and not set(h.defines) & set(other.defines)
     text = open(_abi.SKINNING_HEADER_PATH).read()
-    assert re.search(r"#define\s+DEODR_HIP_SKINNING_ABI_VERSION\s+1\b", text)
     assert not re.search(r"\bint\s*\*", re.sub(r"/\*.*?\*/", " ", text, flags=re.S))  # the tables are device arrays: uint32_t *, never int * (host memory to _abi)
-    p, i, z = C.c_void_p, C.c_int, C.c_size_t
-    assert h.functions["deodr_hip_skin_apply"] == (i, [p, p, p, p, p, p, p, p, i, i, i, i, p])  # 13 parameters
-    assert h.functions["deodr_hip_skin_apply_b"] == (i, [p, p, p, p, p, p, p, p, p, p, i, p, p, p, p, z, i, i, i, i, p])  # 21 parameters
-    assert h.functions["deodr_hip_skin_scratch_bytes"] == (z, [i, i, i, i])
-    assert h.functions["deodr_hip_skinning_abi_version"] == (i, [])
-
-
-def test_library_exports_and_binds_every_name_of_the_companion_header():
-    import __graft_entry__ as g
-    from deodr_amd import _abi
-    from deodr_amd import hip_renderer as hr
-
-    raw = C.CDLL(g.build_hip())
-    for name in SKINNING_FUNCTIONS:
-        assert hasattr(raw, name), name
-    assert raw.deodr_hip_skinning_abi_version() == 1 == hr.SKINNING_ABI_VERSION
-    L = hr.lib()  # binds every header
-    for name, (restype, argtypes) in _abi.SKINNING_HEADER.functions.items():
-        f = getattr(L, name)
-        assert f.restype is restype and list(f.argtypes) == argtypes, name
-
-
-def test_the_header_is_on_the_list_that_decides_whether_the_library_is_stale():
-    import inspect
-
-    import __graft_entry__ as g
-
-    assert '"deodr_hip_skinning.h"' in inspect.getsource(g.build_hip)
 
 
 def test_scratch_follows_the_header_and_is_zero_outside_the_limits():
@@ -69,33 +30,25 @@ def test_scratch_follows_the_header_and_is_zero_outside_the_limits():
 
 def test_bad_arguments_are_refused_before_any_launch():
     """every pointer below is fake and never dereferenced: a refusal happens before any HIP call"""
+    from abi_cases import entry, misaligned, nulls
+    from deodr_amd import _abi
     from deodr_amd import hip_renderer as hr
 
     L = hr.lib()
     V, J, K, n, nnz = 100, 4, 2, 2, 150
     base = dict(vertices=0x10000000, joints=0x11000000, parents=0x12000000, quaternions=0x13000000, indices=0x14000000, weights=0x15000000,
-                world=0x16000000, posed=0x17000000, joint_offsets=0x18000000, joint_slots=0x19000000, vertices_b=0x1A000000, quaternions_b=0x1B000000,
-                joints_b=0x1C000000, scratch=0x1D000000)  # fmt: skip
-
-    def apply(V=V, J=J, K=K, n=n, **changed):
-        a = dict(base, **changed)
-        rc = L.deodr_hip_skin_apply(a["vertices"], a["joints"], a["parents"], a["quaternions"], a["indices"], a["weights"], a["world"], a["posed"], V, J, K, n, None)
-        return rc, L.deodr_hip_last_error().decode()
-
-    def apply_b(V=V, J=J, K=K, n=n, nnz=nnz, scratch_bytes=None, **changed):
-        a = dict(base, **changed)  # (posed stands for posed_b)
-        need = L.deodr_hip_skin_scratch_bytes(V, J, K, n)
-        rc = L.deodr_hip_skin_apply_b(a["vertices"], a["joints"], a["parents"], a["quaternions"], a["indices"], a["weights"], a["world"], a["posed"],
-                                      a["joint_offsets"], a["joint_slots"], nnz, a["vertices_b"], a["quaternions_b"], a["joints_b"], a["scratch"],
-                                      need if scratch_bytes is None else scratch_bytes, V, J, K, n, None)  # fmt: skip
-        return rc, L.deodr_hip_last_error().decode()
+                world=0x16000000, posed=0x17000000, posed_b=0x17000000, joint_offsets=0x18000000, joint_slots=0x19000000, vertices_b=0x1A000000,
+                quaternions_b=0x1B000000, joints_b=0x1C000000, scratch=0x1D000000)  # fmt: skip
+    apply = entry(L, _abi.SKINNING_HEADER, "deodr_hip_skin_apply", base, V=V, J=J, K=K, n=n)
+    apply_b = entry(L, _abi.SKINNING_HEADER, "deodr_hip_skin_apply_b", base, V=V, J=J, K=K, n=n, nnz=nnz,
+                    scratch_bytes=lambda a: L.deodr_hip_skin_scratch_bytes(a["V"], a["J"], a["K"], a["n"]))  # fmt: skip
 
     inputs = ("vertices", "joints", "parents", "quaternions", "indices", "weights")
     for call, what, required in ((apply, "skin_apply", inputs + ("world", "posed")),
-                                 (apply_b, "skin_apply_b", inputs + ("world", "posed", "joint_offsets", "joint_slots", "scratch"))):  # fmt: skip
-        for p in required:  # a NULL among the required pointers
-            rc, msg = call(**{p: None})
-            assert rc == 1 and msg.startswith(what + ":") and "== NULL" in msg, (p, msg)
+                                 (apply_b, "skin_apply_b", inputs + ("world", "posed_b", "joint_offsets", "joint_slots", "scratch"))):  # fmt: skip
+        for bad in nulls(required):  # a NULL among the required pointers
+            rc, msg = call(**bad)
+            assert rc == 1 and msg.startswith(what + ":") and "== NULL" in msg, (bad, msg)
         for bad in (dict(n=0), dict(n=-1), dict(n=65)):
             assert call(**bad) == (1, what + ": n must be in 1 .. 64"), bad
         for bad in (dict(J=0), dict(J=-3), dict(J=257)):
@@ -104,14 +57,14 @@ def test_bad_arguments_are_refused_before_any_launch():
             assert call(**bad) == (1, what + ": K must be in 1 .. 8"), bad
         for bad in (dict(V=0), dict(V=-7), dict(V=2**24 + 1)):
             assert call(**bad) == (1, what + ": V must be in 1 .. 2^24"), bad
-        doubles = ("vertices", "joints", "quaternions", "weights", "world", "posed") + (("vertices_b", "quaternions_b", "joints_b", "scratch") if call is apply_b else ())
-        for p in doubles:
-            assert call(**{p: base[p] + 4}) == (1, what + ": misaligned pointer"), p
-        for p in ("parents", "indices") + (("joint_offsets", "joint_slots") if call is apply_b else ()):  # 4-byte aligned
-            assert call(**{p: base[p] + 2}) == (1, what + ": misaligned pointer"), p
+        doubles = ("vertices", "joints", "quaternions", "weights", "world") + (("posed_b", "vertices_b", "quaternions_b", "joints_b", "scratch") if call is apply_b else ("posed",))
+        for bad in misaligned(base, doubles, 4):
+            assert call(**bad) == (1, what + ": misaligned pointer"), bad
+        for bad in misaligned(base, ("parents", "indices") + (("joint_offsets", "joint_slots") if call is apply_b else ()), 2):  # 4-byte aligned
+            assert call(**bad) == (1, what + ": misaligned pointer"), bad
     # bytes: vertices(_b) 2400, joints(_b) 96, parents 16, quaternions(_b) 256, indices 800, weights 1600, world 448, posed(_b) 4800, offsets 20, slots 600
-    sizes = dict(vertices=2400, joints=96, parents=16, quaternions=256, indices=800, weights=1600, world=448, posed=4800, joint_offsets=20, joint_slots=600,
-                 vertices_b=2400, quaternions_b=256, joints_b=96)  # fmt: skip
+    sizes = dict(vertices=2400, joints=96, parents=16, quaternions=256, indices=800, weights=1600, world=448, posed=4800, posed_b=4800, joint_offsets=20,
+                 joint_slots=600, vertices_b=2400, quaternions_b=256, joints_b=96)  # fmt: skip
     refusal = (1, "skin_apply: an output must not overlap an input or the other output")
     for out in ("world", "posed"):
         for inp in inputs:
@@ -131,7 +84,7 @@ def test_bad_arguments_are_refused_before_any_launch():
         assert apply_b(scratch_bytes=short) == (1, what + ": scratch too small (deodr_hip_skin_scratch_bytes)"), short
     refusal = (1, what + ": an output must not overlap an input, the scratch or another output")
     for out in ("vertices_b", "quaternions_b", "joints_b"):
-        for inp in inputs + ("world", "posed", "joint_offsets", "joint_slots"):
+        for inp in inputs + ("world", "posed_b", "joint_offsets", "joint_slots"):
             for at in (base[inp], base[inp] + (sizes[inp] - 4) // 8 * 8, base[inp] - sizes[out] + 8):
                 assert apply_b(**{out: at}) == refusal, (out, inp, hex(at))
         assert apply_b(**{out: base["scratch"] + 64}) == refusal and apply_b(**{out: base["scratch"] + need - 8}) == refusal, out
@@ -142,10 +95,9 @@ def test_bad_arguments_are_refused_before_any_launch():
 def test_host_wrappers_check_their_tensors_before_the_library(monkeypatch):
     import torch
 
+    from abi_cases import no_library
+    from abi_cases import on_device as dev
     from deodr_amd import hip_renderer as hr
-
-    def no_library():
-        raise AssertionError("the library was reached")
 
     monkeypatch.setattr(hr, "lib", no_library)
     f64 = lambda *shape: torch.zeros(*shape, dtype=torch.float64)
@@ -157,11 +109,6 @@ def test_host_wrappers_check_their_tensors_before_the_library(monkeypatch):
     with pytest.raises(ValueError, match="ROCm tensor"):
         hr.skin_apply_b(v, c, par, q, idx, w, f64(n, J, 7), f64(n, V, 3), i32(J + 1), i32(5))
 
-    class OnDevice(torch.Tensor):
-        is_cuda = property(lambda self: True)
-        device = property(lambda self: torch.device("cuda", 0))
-
-    dev = lambda x: x.as_subclass(OnDevice)
     Vt, Ct, P, Q, I, W = (dev(t) for t in (v, c, par, q, idx, w))
     with pytest.raises(ValueError, match=r"vertices must have shape \[1 <= V <= 2\^24, 3\]"):
         hr.skin_apply(dev(f64(V, 2)), Ct, P, Q, I, W)

@@ -1,61 +1,19 @@
-"""CPU checks of the companion header include/deodr_hip_solve.h (the sparse symmetric positive definite solve): it parses with the parser of deodr_hip.h
-and shares no name with the other ten headers, its prototypes are type by type what the header documents, every name it declares is exported by the
-cross-compiled library and bound with the declared types, its version is 1 on both sides, the constants of deodr_amd/csrc/dr_solve.h are the ones the
-case table is built for, every bad argument of the launching entry point is refused through its error code with a message before any launch (fake
-pointers, no GPU), the scratch size is 0 outside the limits, monotone inside them and the documented formula, the launch rule is the documented one
-either side of N_SMALL, and the host wrapper refuses CPU tensors, wrong dtypes and wrong shapes without reaching the library."""
+"""CPU checks of the sparse symmetric positive definite solve at the C ABI (include/deodr_hip_solve.h; the header itself:
+tests/test_companion_headers.py): the constants of deodr_amd/csrc/dr_solve.h are the ones the case table is built for, every bad argument of the
+launching entry point is refused through its error code with a message before any launch (fake pointers, no GPU), the scratch size is 0 outside
+the limits, monotone inside them and the documented formula, the launch rule is the documented one either side of N_SMALL, and the host wrapper
+refuses CPU tensors, wrong dtypes and wrong shapes without reaching the library."""
 
-import ctypes as C
 import os
 import re
 
 import pytest
 
-SOLVE_FUNCTIONS = ["deodr_hip_spd_solve", "deodr_hip_spd_solve_scratch_bytes", "deodr_hip_spd_solve_launches", "deodr_hip_solve_abi_version"]
 
-
-def test_companion_header_parses_and_is_versioned_on_its_own():
-    from deodr_amd import _abi
-
-    h = _abi.SOLVE_HEADER
-    assert sorted(h.functions) == sorted(SOLVE_FUNCTIONS)
-    assert h.defines == {"DEODR_HIP_SOLVE_ABI_VERSION": 1, "DEODR_HIP_SOLVE_N_SMALL": 1024} and h.structs == {}
-    assert h.name == "include/deodr_hip_solve.h"
-    others = (_abi.HEADER, _abi.TEXTURE_HEADER, _abi.SUBDIV_HEADER, _abi.RETAINED_HEADER, _abi.BASIS_HEADER, _abi.CAMERA_HEADER, _abi.LIGHTING_HEADER,
-              _abi.SKINNING_HEADER, _abi.PYRAMID_HEADER, _abi.SSIM_HEADER)  # fmt: skip
-    assert len(others) == 10
-    for other in others:
-        assert not set(h.functions) & set(other.functions) and not set(h.defines) & set(other.defines)
-    assert re.search(r"#define\s+DEODR_HIP_SOLVE_ABI_VERSION\s+1\b", open(_abi.SOLVE_HEADER_PATH).read())
-    p, i, z, d, u = C.c_void_p, C.c_int, C.c_size_t, C.c_double, C.c_uint32
-    assert h.functions["deodr_hip_spd_solve"] == (i, [p, p, p, i, u, p, p, i, i, d, p, p, z, p])  # 14 parameters
-    assert h.functions["deodr_hip_spd_solve_scratch_bytes"] == (z, [i, i])
-    assert h.functions["deodr_hip_spd_solve_launches"] == (i, [i, u, i, i])
-    assert h.functions["deodr_hip_solve_abi_version"] == (i, [])
-
-
-def test_library_exports_and_binds_every_name_of_the_companion_header():
-    import __graft_entry__ as g
-    from deodr_amd import _abi
+def test_the_limits_are_the_header_s():
     from deodr_amd import hip_renderer as hr
 
-    raw = C.CDLL(g.build_hip())
-    for name in SOLVE_FUNCTIONS:
-        assert hasattr(raw, name), name
-    assert raw.deodr_hip_solve_abi_version() == 1 == hr.SOLVE_ABI_VERSION
     assert hr.SOLVE_N_SMALL == 1024 and hr.SOLVE_MAX_D == 4
-    L = hr.lib()  # binds every header
-    for name, (restype, argtypes) in _abi.SOLVE_HEADER.functions.items():
-        f = getattr(L, name)
-        assert f.restype is restype and list(f.argtypes) == argtypes, name
-
-
-def test_the_header_is_on_the_list_that_decides_whether_the_library_is_stale():
-    import inspect
-
-    import __graft_entry__ as g
-
-    assert '"deodr_hip_solve.h"' in inspect.getsource(g.build_hip)
 
 
 def test_the_constants_of_the_kernels_are_the_case_table_s():
@@ -105,23 +63,20 @@ def test_the_launch_rule_either_side_of_n_small():
 
 def test_bad_arguments_are_refused_before_any_launch():
     """every pointer below is fake and never dereferenced: a refusal happens before any HIP call"""
+    from abi_cases import entry, misaligned, nulls, overlap_placements
+    from deodr_amd import _abi
     from deodr_amd import hip_renderer as hr
 
     L = hr.lib()
     n, nnz, D = 41, 250, 3  # (4 (n + 1) and 4 nnz multiples of 8: the overlaps below stay aligned)
     base = dict(offsets=0x10000000, cols=0x11000000, vals=0x12000000, b=0x13000000, x=0x14000000, residual=0x15000000, scratch=0x16000000)
 
-    def call(n=n, nnz=nnz, D=D, iterations=8, rel_tol=0.0, scratch_bytes=None, **changed):
-        a = dict(base, **changed)
-        need = L.deodr_hip_spd_solve_scratch_bytes(n, D)
-        rc = L.deodr_hip_spd_solve(a["offsets"], a["cols"], a["vals"], n, nnz, a["b"], a["x"], D, iterations, rel_tol, a["residual"], a["scratch"],
-                                   need if scratch_bytes is None else scratch_bytes, None)  # fmt: skip
-        return rc, L.deodr_hip_last_error().decode()
-
+    call = entry(L, _abi.SOLVE_HEADER, "deodr_hip_spd_solve", base, n=n, nnz=nnz, D=D, iterations=8, rel_tol=0.0,
+                 scratch_bytes=lambda a: L.deodr_hip_spd_solve_scratch_bytes(a["n"], a["D"]))  # fmt: skip
     what = "spd_solve"
-    for p in base:  # a NULL pointer
-        rc, msg = call(**{p: None})
-        assert rc == 1 and msg.startswith(what + ":") and "== NULL" in msg, (p, msg)
+    for bad in nulls(base):  # a NULL pointer
+        rc, msg = call(**bad)
+        assert rc == 1 and msg.startswith(what + ":") and "== NULL" in msg, (bad, msg)
     for bad in (0, -1, -(2**31)):
         assert call(n=bad, scratch_bytes=1 << 20) == (1, what + ": n must be positive"), bad
     assert call(nnz=n - 1) == (1, what + ": nnz must be >= n (the diagonal is stored)")
@@ -131,10 +86,10 @@ def test_bad_arguments_are_refused_before_any_launch():
         assert call(iterations=bad) == (1, what + ": iterations must be >= 1"), bad
     for bad in (-1e-300, -1.0, float("-inf"), float("nan")):
         assert call(rel_tol=bad) == (1, what + ": rel_tol must be >= 0"), bad
-    for p in ("offsets", "cols"):
-        assert call(**{p: base[p] + 2}) == (1, what + ": misaligned pointer"), p
-    for p in ("vals", "b", "x", "residual", "scratch"):
-        assert call(**{p: base[p] + 4}) == (1, what + ": misaligned pointer"), p
+    for bad in misaligned(base, ("offsets", "cols"), 2):
+        assert call(**bad) == (1, what + ": misaligned pointer"), bad
+    for bad in misaligned(base, ("vals", "b", "x", "residual", "scratch"), 4):
+        assert call(**bad) == (1, what + ": misaligned pointer"), bad
     need = L.deodr_hip_spd_solve_scratch_bytes(n, D)
     for short in (0, 64, need - 1):
         assert call(scratch_bytes=short) == (1, what + ": scratch too small (deodr_hip_spd_solve_scratch_bytes)"), short
@@ -146,17 +101,16 @@ def test_bad_arguments_are_refused_before_any_launch():
     for out in ("x", "residual", "scratch"):
         for other in sizes:
             if other != out and (out, other) != ("x", "b"):
-                for at in (base[other], base[other] + sizes[other] - 8, base[other] - sizes[out] + 8):
+                for at in overlap_placements(base, sizes, out, other):
                     assert call(**{out: at}) == refusal, (out, other, hex(at))
 
 
 def test_host_wrapper_checks_its_tensors_before_the_library(monkeypatch):
     import torch
 
+    from abi_cases import no_library
+    from abi_cases import on_device as dev
     from deodr_amd import hip_renderer as hr
-
-    def no_library():
-        raise AssertionError("the library was reached")
 
     monkeypatch.setattr(hr, "lib", no_library)
     f64 = lambda *shape: torch.zeros(*shape, dtype=torch.float64)
@@ -164,11 +118,6 @@ def test_host_wrapper_checks_its_tensors_before_the_library(monkeypatch):
     with pytest.raises(ValueError, match="b must be a ROCm tensor"):
         hr.spd_solve(i32(6), i32(9), f64(9), f64(5, 3), 4)
 
-    class OnDevice(torch.Tensor):
-        is_cuda = property(lambda self: True)
-        device = property(lambda self: torch.device("cuda", 0))
-
-    dev = lambda x: x.as_subclass(OnDevice)
     O, Cc, V, B = dev(i32(6)), dev(i32(9)), dev(f64(9)), dev(f64(5, 3))
     for bad in (dev(f64(5)), dev(f64(5, 5)), dev(f64(0, 3)), dev(f64(5, 3, 1))):
         with pytest.raises(ValueError, match=r"b must have shape \[n >= 1, 1 <= D <= 4\]"):

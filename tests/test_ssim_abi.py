@@ -1,61 +1,19 @@
-"""CPU checks of the companion header include/deodr_hip_ssim.h (the structural data term): it parses with the parser of deodr_hip.h and shares no name
-with the other nine headers, its prototypes are type by type what the header documents, every name it declares is exported by the cross-compiled
-library and bound with the declared types, its version is 1 on both sides, the taps and the tiling in deodr_amd/csrc/dr_ssim.h are the ones the Python
-side and the case table use, every bad argument of the launching entry point is refused through its error code with a message before any launch
-(fake pointers, no GPU), the scratch size is 0 outside the limits, monotone inside them and the documented formula, and the host wrapper refuses CPU
-tensors, wrong dtypes and wrong shapes without reaching the library."""
+"""CPU checks of the structural data term at the C ABI (include/deodr_hip_ssim.h; the header itself: tests/test_companion_headers.py): the taps and
+the tiling in deodr_amd/csrc/dr_ssim.h are the ones the Python side and the case table use, every bad argument of the launching entry point is
+refused through its error code with a message before any launch (fake pointers, no GPU), the scratch size is 0 outside the limits, monotone inside
+them and the documented formula, and the host wrapper refuses CPU tensors, wrong dtypes and wrong shapes without reaching the library."""
 
-import ctypes as C
 import os
 import re
 
 import pytest
 
-SSIM_FUNCTIONS = ["deodr_hip_ssim_l2", "deodr_hip_ssim_scratch_bytes", "deodr_hip_ssim_abi_version"]
 
-
-def test_companion_header_parses_and_is_versioned_on_its_own():
-    from deodr_amd import _abi
-
-    h = _abi.SSIM_HEADER
-    assert sorted(h.functions) == sorted(SSIM_FUNCTIONS)
-    assert h.defines == {"DEODR_HIP_SSIM_ABI_VERSION": 1, "DEODR_HIP_SSIM_WINDOW": 11} and h.structs == {}
-    assert h.name == "include/deodr_hip_ssim.h"
-    others = (_abi.HEADER, _abi.TEXTURE_HEADER, _abi.SUBDIV_HEADER, _abi.RETAINED_HEADER, _abi.BASIS_HEADER, _abi.CAMERA_HEADER, _abi.LIGHTING_HEADER,
-              _abi.SKINNING_HEADER, _abi.PYRAMID_HEADER)  # fmt: skip
-    assert len(others) == 9
-    for other in others:
-        assert not set(h.functions) & set(other.functions) and not set(h.defines) & set(other.defines)
-    assert re.search(r"#define\s+DEODR_HIP_SSIM_ABI_VERSION\s+1\b", open(_abi.SSIM_HEADER_PATH).read())
-    p, i, z, d = C.c_void_p, C.c_int, C.c_size_t, C.c_double
-    assert h.functions["deodr_hip_ssim_l2"] == (i, [p, p, p, i, i, i, i, i, d, p, p, p, p, p, z, p])  # 16 parameters
-    assert h.functions["deodr_hip_ssim_scratch_bytes"] == (z, [i, i, i, i])
-    assert h.functions["deodr_hip_ssim_abi_version"] == (i, [])
-
-
-def test_library_exports_and_binds_every_name_of_the_companion_header():
-    import __graft_entry__ as g
-    from deodr_amd import _abi
+def test_the_window_is_the_header_s():
     from deodr_amd import hip_renderer as hr
     from deodr_amd import ssim
 
-    raw = C.CDLL(g.build_hip())
-    for name in SSIM_FUNCTIONS:
-        assert hasattr(raw, name), name
-    assert raw.deodr_hip_ssim_abi_version() == 1 == hr.SSIM_ABI_VERSION
     assert hr.SSIM_WINDOW == ssim.WINDOW == 11
-    L = hr.lib()  # binds every header
-    for name, (restype, argtypes) in _abi.SSIM_HEADER.functions.items():
-        f = getattr(L, name)
-        assert f.restype is restype and list(f.argtypes) == argtypes, name
-
-
-def test_the_header_is_on_the_list_that_decides_whether_the_library_is_stale():
-    import inspect
-
-    import __graft_entry__ as g
-
-    assert '"deodr_hip_ssim.h"' in inspect.getsource(g.build_hip)
 
 
 def test_the_taps_and_the_tiling_of_the_kernels_are_the_python_side_s():
@@ -94,6 +52,8 @@ def test_scratch_is_zero_outside_the_limits_monotone_inside_and_the_documented_f
 
 def test_bad_arguments_are_refused_before_any_launch():
     """every pointer below is fake and never dereferenced: a refusal happens before any HIP call"""
+    from abi_cases import entry, misaligned, nulls, overlap_placements
+    from deodr_amd import _abi
     from deodr_amd import hip_renderer as hr
 
     L = hr.lib()
@@ -101,29 +61,24 @@ def test_bad_arguments_are_refused_before_any_launch():
     base = dict(image=0x10000000, obs=0x11000000, weights=0x12000000, mix=0x13000000, terms=0x14000000, loss=0x15000000, image_b=0x16000000,
                 scratch=0x17000000)  # fmt: skip
 
-    def call(n=n, H=H, W=W, Cn=Cn, dtype=hr._F64, data_range=1.0, scratch_bytes=None, **changed):
-        a = dict(base, **changed)
-        need = L.deodr_hip_ssim_scratch_bytes(n, H, W, Cn)
-        rc = L.deodr_hip_ssim_l2(a["image"], a["obs"], a["weights"], n, H, W, Cn, dtype, data_range, a["mix"], a["terms"], a["loss"], a["image_b"],
-                                 a["scratch"], need if scratch_bytes is None else scratch_bytes, None)  # fmt: skip
-        return rc, L.deodr_hip_last_error().decode()
-
+    call = entry(L, _abi.SSIM_HEADER, "deodr_hip_ssim_l2", base, n=n, H=H, W=W, C=Cn, pixel_dtype=hr._F64, data_range=1.0,
+                 scratch_bytes=lambda a: L.deodr_hip_ssim_scratch_bytes(a["n"], a["H"], a["W"], a["C"]))  # fmt: skip
     what = "ssim_l2"
-    for p in ("image", "obs", "mix", "terms", "scratch"):  # a NULL that is not allowed
-        rc, msg = call(**{p: None})
-        assert rc == 1 and msg.startswith(what + ":") and "== NULL" in msg, (p, msg)
-    for bad in (dict(n=0), dict(H=0), dict(W=-1), dict(Cn=0), dict(Cn=-3)):
+    for bad in nulls(("image", "obs", "mix", "terms", "scratch")):  # a NULL that is not allowed
+        rc, msg = call(**bad)
+        assert rc == 1 and msg.startswith(what + ":") and "== NULL" in msg, (bad, msg)
+    for bad in (dict(n=0), dict(H=0), dict(W=-1), dict(C=0), dict(C=-3)):
         assert call(**bad) == (1, what + ": n, H, W and C must be >= 1"), bad
-    assert call(n=64, H=2**15, W=2**15, Cn=16) == (1, what + ": n H W C must be below 2^40")
+    assert call(n=64, H=2**15, W=2**15, C=16) == (1, what + ": n H W C must be below 2^40")
     for bad in (0.0, -1.0, float("inf"), float("-inf"), float("nan")):
         assert call(data_range=bad) == (1, what + ": data_range must be finite and > 0"), bad
     for bad in (2, -1, 7):
-        assert call(dtype=bad) == (1, what + ": pixel_dtype must be DEODR_HIP_F32 or DEODR_HIP_F64"), bad
+        assert call(pixel_dtype=bad) == (1, what + ": pixel_dtype must be DEODR_HIP_F32 or DEODR_HIP_F64"), bad
     for p in ("image", "obs", "weights", "image_b"):  # aligned to their element
         assert call(**{p: base[p] + 4}) == (1, what + ": misaligned pointer"), p
-        assert call(dtype=hr._F32, **{p: base[p] + 2}) == (1, what + ": misaligned pointer"), p
-    for p in ("mix", "terms", "loss", "scratch"):
-        assert call(**{p: base[p] + 4}) == (1, what + ": misaligned pointer"), p
+        assert call(pixel_dtype=hr._F32, **{p: base[p] + 2}) == (1, what + ": misaligned pointer"), p
+    for bad in misaligned(base, ("mix", "terms", "loss", "scratch"), 4):
+        assert call(**bad) == (1, what + ": misaligned pointer"), bad
     need = L.deodr_hip_ssim_scratch_bytes(n, H, W, Cn)
     for short in (0, 64, need - 1):
         assert call(scratch_bytes=short) == (1, what + ": scratch too small (deodr_hip_ssim_scratch_bytes)"), short
@@ -133,13 +88,13 @@ def test_bad_arguments_are_refused_before_any_launch():
     for out in ("terms", "loss", "image_b", "scratch"):
         for other in sizes:
             if other != out:
-                for at in (base[other], base[other] + sizes[other] - 8, base[other] - sizes[out] + 8):
+                for at in overlap_placements(base, sizes, out, other):
                     assert call(**{out: at}) == refusal, (out, other, hex(at))
     # two things wrong at once: the checks run in the order above, and the first one speaks
     assert call(image=None, n=0) == (1, what + ": image, obs, mix, terms or scratch == NULL")
-    assert call(n=0, dtype=7) == (1, what + ": n, H, W and C must be >= 1")
-    assert call(data_range=0.0, dtype=7) == (1, what + ": data_range must be finite and > 0")
-    assert call(dtype=7, image=base["image"] + 4) == (1, what + ": pixel_dtype must be DEODR_HIP_F32 or DEODR_HIP_F64")
+    assert call(n=0, pixel_dtype=7) == (1, what + ": n, H, W and C must be >= 1")
+    assert call(data_range=0.0, pixel_dtype=7) == (1, what + ": data_range must be finite and > 0")
+    assert call(pixel_dtype=7, image=base["image"] + 4) == (1, what + ": pixel_dtype must be DEODR_HIP_F32 or DEODR_HIP_F64")
     assert call(image=base["image"] + 4, scratch_bytes=need - 1) == (1, what + ": misaligned pointer")
     assert call(scratch_bytes=need - 1, terms=base["image"]) == (1, what + ": scratch too small (deodr_hip_ssim_scratch_bytes)")
 
@@ -147,10 +102,9 @@ def test_bad_arguments_are_refused_before_any_launch():
 def test_host_wrapper_checks_its_tensors_before_the_library(monkeypatch):
     import torch
 
+    from abi_cases import no_library
+    from abi_cases import on_device as dev
     from deodr_amd import hip_renderer as hr
-
-    def no_library():
-        raise AssertionError("the library was reached")
 
     monkeypatch.setattr(hr, "lib", no_library)
     f64 = lambda *shape: torch.zeros(*shape, dtype=torch.float64)
@@ -158,11 +112,6 @@ def test_host_wrapper_checks_its_tensors_before_the_library(monkeypatch):
     with pytest.raises(ValueError, match="image must be a ROCm tensor"):
         hr.ssim_l2(image, image, None, mix)
 
-    class OnDevice(torch.Tensor):
-        is_cuda = property(lambda self: True)
-        device = property(lambda self: torch.device("cuda", 0))
-
-    dev = lambda x: x.as_subclass(OnDevice)
     I, O, M = dev(image), dev(f64(2, 5, 6, 3)), dev(mix)
     with pytest.raises(ValueError, match=r"image must have shape \[n >= 1, H >= 1, W >= 1, C >= 1\]"):
         hr.ssim_l2(dev(f64(5, 6, 3)), O, None, M)

@@ -1,47 +1,16 @@
-"""CPU checks of the companion header include/deodr_hip_subdiv.h (Loop subdivision): it parses with the parser of deodr_hip.h and shares no name
-with the other two headers, every name it declares is exported by the cross-compiled library and bound with the declared types, its version is 1 on
-both sides, every bad argument of deodr_hip_subdiv_apply is refused with a message before any launch (fake pointers, no GPU), and the host
-wrapper refuses CPU tensors without reaching the library."""
+"""CPU checks of Loop subdivision at the C ABI (include/deodr_hip_subdiv.h; the header itself: tests/test_companion_headers.py): a library that
+lacks a declared symbol is refused by name, the instance rule, every bad argument of deodr_hip_subdiv_apply is refused with a message before any
+launch (fake pointers, no GPU), and the host wrapper refuses CPU tensors without reaching the library."""
 
 import ctypes as C
-import re
 
 import pytest
 
-SUBDIV_FUNCTIONS = ["deodr_hip_subdiv_apply", "deodr_hip_subdiv_lanes", "deodr_hip_subdiv_abi_version"]
 
-
-def test_companion_header_parses_and_is_versioned_on_its_own():
-    from deodr_amd import _abi
-
-    h = _abi.SUBDIV_HEADER
-    assert sorted(h.functions) == sorted(SUBDIV_FUNCTIONS)
-    assert h.defines == {"DEODR_HIP_SUBDIV_ABI_VERSION": 1} and h.structs == {}
-    assert h.name == "include/deodr_hip_subdiv.h"
-    for other in (_abi.HEADER, _abi.TEXTURE_HEADER):  # disjoint from the other two headers
-        assert not set(h.functions) & set(other.functions) and not set(h.defines) & set(other.defines)
-    text = open(_abi.SUBDIV_HEADER_PATH).read()
-    assert re.search(r"#define\s+DEODR_HIP_SUBDIV_ABI_VERSION\s+1\b", text)
-    restype, argtypes = h.functions["deodr_hip_subdiv_apply"]
-    assert restype is C.c_int
-    assert argtypes == [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]
-    assert h.functions["deodr_hip_subdiv_lanes"] == (C.c_int, [C.c_int, C.c_uint32])
-    assert h.functions["deodr_hip_subdiv_abi_version"] == (C.c_int, [])
-
-
-def test_library_exports_and_binds_every_name_of_the_companion_header():
+def test_a_library_that_lacks_a_declared_symbol_is_refused_by_name():
     import __graft_entry__ as g
     from deodr_amd import _abi
-    from deodr_amd import hip_renderer as hr
 
-    raw = C.CDLL(g.build_hip())
-    for name in SUBDIV_FUNCTIONS:
-        assert hasattr(raw, name), name
-    assert raw.deodr_hip_subdiv_abi_version() == 1 == hr.SUBDIV_ABI_VERSION
-    L = hr.lib()  # binds the three headers
-    for name, (restype, argtypes) in _abi.SUBDIV_HEADER.functions.items():
-        f = getattr(L, name)
-        assert f.restype is restype and list(f.argtypes) == argtypes, name
     more = _abi.parse(open(_abi.SUBDIV_HEADER_PATH).read().replace("int deodr_hip_subdiv_abi_version(void);",
                                                                    "int deodr_hip_subdiv_abi_version(void);\nint deodr_hip_subdiv_not_there(int on);"),
                       "include/deodr_hip_subdiv.h")  # fmt: skip
@@ -62,6 +31,7 @@ def test_instance_rule():
 
 def test_subdiv_apply_rejects_bad_arguments_before_any_launch():
     """every pointer below is fake and never dereferenced: a refusal happens before any HIP call"""
+    from abi_cases import entry, nulls
     from deodr_amd import _abi
     from deodr_amd import hip_renderer as hr
 
@@ -69,13 +39,12 @@ def test_subdiv_apply_rejects_bad_arguments_before_any_launch():
     F32, F64, MAXC = _abi.HEADER.defines["DEODR_HIP_F32"], _abi.HEADER.defines["DEODR_HIP_F64"], _abi.HEADER.defines["DEODR_HIP_MAX_COLORS"]
     offsets, cols, vals, x, y = 0x100000, 0x200000, 0x300000, 0x400000, 0x500000
 
-    def apply(offsets=offsets, cols=cols, vals=vals, n_rows=100, n_cols=50, nnz=400, x=x, y=y, batch=2, D=3, dtype=F64, accumulate=0):
-        rc = L.deodr_hip_subdiv_apply(offsets, cols, vals, n_rows, n_cols, nnz, x, y, batch, D, dtype, accumulate, None)
-        return rc, L.deodr_hip_last_error().decode()
+    base = dict(offsets=offsets, cols=cols, vals=vals, x=x, y=y)
+    apply = entry(L, _abi.SUBDIV_HEADER, "deodr_hip_subdiv_apply", base, n_rows=100, n_cols=50, nnz=400, batch=2, D=3, dtype=F64, accumulate=0)
 
-    for p in ("offsets", "cols", "vals", "x", "y"):
-        rc, msg = apply(**{p: None})
-        assert rc == 1 and "== NULL" in msg, (p, msg)
+    for bad in nulls(base):
+        rc, msg = apply(**bad)
+        assert rc == 1 and "== NULL" in msg, (bad, msg)
     for bad in (dict(n_rows=0), dict(n_rows=-3), dict(n_cols=0), dict(n_cols=-1), dict(nnz=0)):
         assert apply(**bad) == (1, "subdiv_apply: n_rows, n_cols and nnz must be positive"), bad
     for bad in (dict(batch=0), dict(batch=-1), dict(batch=65536)):
@@ -96,10 +65,8 @@ def test_subdiv_apply_rejects_bad_arguments_before_any_launch():
 def test_host_wrapper_checks_its_tensors_before_the_library(monkeypatch):
     import torch
 
+    from abi_cases import no_library
     from deodr_amd import hip_renderer as hr
-
-    def no_library():
-        raise AssertionError("the library was reached")
 
     monkeypatch.setattr(hr, "lib", no_library)
     offsets, cols = torch.tensor([0, 1, 2], dtype=torch.int32), torch.tensor([0, 1], dtype=torch.int32)

@@ -1,69 +1,31 @@
-"""CPU checks of the companion header include/deodr_hip_surface.h (the point-to-surface distance): it parses with the parser of deodr_hip.h and
-shares no name with the other thirteen headers, its prototypes are type by type what the header documents, every name it declares is exported by
-the cross-compiled library and bound with the declared types, its version is 1 on both sides, it is on the list that decides whether the library is
-stale, every bad argument of the launching entry point is refused through its error code with a message before any launch (fake pointers, no GPU),
-the scratch size is 0 outside the limits and the documented formula inside, the launch counts, the host wrapper refuses CPU tensors, wrong dtypes
-and wrong shapes without reaching the library, and ``corner_table`` is checked and a wrong table refused on the host."""
+"""CPU checks of the point-to-surface distance at the C ABI (include/deodr_hip_surface.h; the header itself: tests/test_companion_headers.py): the
+header states the rule it uses and why, its kernels add no value with an atomic and reuse the one vertex search, every bad argument of the
+launching entry point is refused through its error code with a message before any launch (fake pointers, no GPU), the scratch size is 0 outside
+the limits and the documented formula inside, the launch counts, the host wrapper refuses CPU tensors, wrong dtypes and wrong shapes without
+reaching the library, and ``corner_table`` is checked and a wrong table refused on the host."""
 
-import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
 
-SURFACE_FUNCTIONS = ["deodr_hip_surface_distance", "deodr_hip_surface_distance_scratch_bytes", "deodr_hip_surface_distance_launches", "deodr_hip_surface_abi_version"]
 MAX_PAIRS = 2**32
 
 
-def test_companion_header_parses_and_is_versioned_on_its_own():
-    from deodr_amd import _abi
-
-    h = _abi.SURFACE_HEADER
-    assert sorted(h.functions) == sorted(SURFACE_FUNCTIONS)
-    assert h.defines == {"DEODR_HIP_SURFACE_ABI_VERSION": 1, "DEODR_HIP_SURFACE_MAX_PAIRS": MAX_PAIRS}
-    assert h.structs == {} and h.name == "include/deodr_hip_surface.h"
-    others = (_abi.HEADER, _abi.TEXTURE_HEADER, _abi.SUBDIV_HEADER, _abi.RETAINED_HEADER, _abi.BASIS_HEADER, _abi.CAMERA_HEADER, _abi.LIGHTING_HEADER,
-              _abi.SKINNING_HEADER, _abi.PYRAMID_HEADER, _abi.SSIM_HEADER, _abi.SOLVE_HEADER, _abi.ARAP_HEADER, _abi.CHAMFER_HEADER)  # fmt: skip
-    assert len(others) == 13
-    for other in others:
-        assert not set(h.functions) & set(other.functions) and not set(h.defines) & set(other.defines)
-    text = open(_abi.SURFACE_HEADER_PATH).read()
-    assert re.search(r"#define\s+DEODR_HIP_SURFACE_ABI_VERSION\s+1\b", text)
-    assert "deodr_hip_chamfer_segments" in text and "LOWEST face index" in text and "TIES ARE THE GENERIC CASE" in text  # the rule it uses, and why
-    p, i, z = C.c_void_p, C.c_int, C.c_size_t
-    assert h.functions["deodr_hip_surface_distance"] == (i, [p, i, p, i, p, p, p, i, p, p, p, i, i, p, p, p, p, p, p, p, z, p])  # 22 parameters
-    assert h.functions["deodr_hip_surface_distance_scratch_bytes"] == (z, [i, i, i, i])
-    assert h.functions["deodr_hip_surface_distance_launches"] == (i, [i, i, i, i, i])
-    assert h.functions["deodr_hip_surface_abi_version"] == (i, [])
-
-
-def test_library_exports_and_binds_every_name_of_the_companion_header():
-    import __graft_entry__ as g
+def test_the_header_states_its_rule_and_the_host_side_has_the_operator_s_names():
     from deodr_amd import _abi
     from deodr_amd import hip_renderer as hr
 
-    raw = C.CDLL(g.build_hip())
-    for name in SURFACE_FUNCTIONS:
-        assert hasattr(raw, name), name
-    assert raw.deodr_hip_surface_abi_version() == 1 == hr.SURFACE_ABI_VERSION
-    L = hr.lib()  # binds every header
-    for name, (restype, argtypes) in _abi.SURFACE_HEADER.functions.items():
-        f = getattr(L, name)
-        assert f.restype is restype and list(f.argtypes) == argtypes, name
+    text = open(_abi.SURFACE_HEADER_PATH).read()
+    assert "deodr_hip_chamfer_segments" in text and "LOWEST face index" in text and "TIES ARE THE GENERIC CASE" in text  # the rule it uses, and why
     for name in ("surface_distance", "surface_scratch", "surface_launches", "SURFACE_ABI_VERSION", "SURFACE_MAX_PAIRS"):
         assert hasattr(hr, name), name
     assert hr.SURFACE_MAX_PAIRS == MAX_PAIRS
 
 
-def test_the_header_is_on_the_list_that_decides_whether_the_library_is_stale():
-    import inspect
-
+def test_the_kernels_add_no_value_atomically_and_reuse_the_vertex_search():
     import __graft_entry__ as g
-    from deodr_amd import _abi
 
-    assert '"deodr_hip_surface.h"' in inspect.getsource(g.build_hip)
-    assert ("SURFACE_HEADER", "deodr_hip_surface.h", False) in _abi._COMPANIONS
     source = open(os.path.join(g.CSRC, "dr_surface.h")).read()
     assert "atomicAdd" not in source and "atomic_add" not in source  # no atomics on values (the tickets are grid_sum's, in dr_fronthalf.h)
     assert source.count("chamfer_walk_kernel") == 1 and "chamfer_walk_kernel<true, false>" in source  # (named in the overview alone: no second copy of that search)
@@ -100,6 +62,8 @@ def test_launch_counts():
 
 def test_bad_arguments_are_refused_before_any_launch():
     """every pointer below is fake and never dereferenced: a refusal happens before any HIP call"""
+    from abi_cases import entry, misaligned, nulls, overlap_placements
+    from deodr_amd import _abi
     from deodr_amd import hip_renderer as hr
 
     L = hr.lib()
@@ -110,19 +74,13 @@ def test_bad_arguments_are_refused_before_any_launch():
     optional = ("point_weights", "vertex_weights", "nearest_face", "barycentric", "nearest_point")
     words = ("faces", "corner_offsets", "corners", "nearest_face", "nearest_point")
 
-    def call(V=V, F=F, P=P, n=n, directions=3, scratch_bytes=None, **changed):
-        a = dict(base, **changed)
-        need = L.deodr_hip_surface_distance_scratch_bytes(V, F, P, n)
-        rc = L.deodr_hip_surface_distance(a["vertices"], V, a["faces"], F, a["corner_offsets"], a["corners"], a["points"], P, a["point_weights"],
-                                          a["vertex_weights"], a["params"], n, directions, a["terms"], a["loss"], a["vertices_b"], a["nearest_face"],
-                                          a["barycentric"], a["nearest_point"], a["scratch"], need if scratch_bytes is None else scratch_bytes, None)  # fmt: skip
-        return rc, L.deodr_hip_last_error().decode()
-
+    call = entry(L, _abi.SURFACE_HEADER, "deodr_hip_surface_distance", base, V=V, F=F, P=P, n=n, directions=3,
+                 scratch_bytes=lambda a: L.deodr_hip_surface_distance_scratch_bytes(a["V"], a["F"], a["P"], a["n"]))  # fmt: skip
     what = "surface_distance"
-    for p in base:  # a NULL required pointer (the optional ones may be NULL: such a call gets past every check only with real memory, not tried here)
-        if p not in optional:
-            rc, msg = call(**{p: None})
-            assert rc == 1 and msg.startswith(what + ":") and "== NULL" in msg, (p, msg)
+    # a NULL required pointer (the optional ones may be NULL: such a call gets past every check only with real memory, not tried here)
+    for bad in nulls(p for p in base if p not in optional):
+        rc, msg = call(**bad)
+        assert rc == 1 and msg.startswith(what + ":") and "== NULL" in msg, (bad, msg)
     for bad in (0, -1, -(2**31)):
         assert call(V=bad, scratch_bytes=1 << 20) == (1, what + ": V must be positive"), bad
         assert call(F=bad, scratch_bytes=1 << 20) == (1, what + ": F must be in 1 .. 715827882"), bad
@@ -138,11 +96,10 @@ def test_bad_arguments_are_refused_before_any_launch():
         assert call(V=2**20, F=2, P=2**17, n=1, directions=d, scratch_bytes=1 << 40) == (
             1, what + ": V * P is above DEODR_HIP_CHAMFER_MAX_PAIRS with mesh -> points on (the search is brute force)")  # fmt: skip
     assert L.deodr_hip_surface_distance_launches(2**20, 2, 2**17, 1, 1) == 5
-    for p in words:
-        assert call(**{p: base[p] + 2}) == (1, what + ": misaligned pointer"), p
-    for p in base:
-        if p not in words:
-            assert call(**{p: base[p] + 4}) == (1, what + ": misaligned pointer"), p
+    for bad in misaligned(base, words, 2):
+        assert call(**bad) == (1, what + ": misaligned pointer"), bad
+    for bad in misaligned(base, (p for p in base if p not in words), 4):
+        assert call(**bad) == (1, what + ": misaligned pointer"), bad
     need = L.deodr_hip_surface_distance_scratch_bytes(V, F, P, n)
     for short in (0, 64, need - 1):
         assert call(scratch_bytes=short) == (1, what + ": scratch too small (deodr_hip_surface_distance_scratch_bytes)"), short
@@ -153,17 +110,16 @@ def test_bad_arguments_are_refused_before_any_launch():
     for out in ("terms", "loss", "vertices_b", "nearest_face", "barycentric", "nearest_point", "scratch"):
         for other in sizes:
             if other != out:
-                for at in (base[other], base[other] + sizes[other] - 8, base[other] - sizes[out] + 8):
+                for at in overlap_placements(base, sizes, out, other):
                     assert call(**{out: at}) == refusal, (out, other, hex(at))
 
 
 def test_host_wrapper_checks_its_tensors_before_the_library(monkeypatch):
     import torch
 
+    from abi_cases import no_library
+    from abi_cases import on_device as dev
     from deodr_amd import hip_renderer as hr
-
-    def no_library():
-        raise AssertionError("the library was reached")
 
     monkeypatch.setattr(hr, "lib", no_library)
     f64 = lambda *shape: torch.zeros(*shape, dtype=torch.float64)
@@ -171,11 +127,6 @@ def test_host_wrapper_checks_its_tensors_before_the_library(monkeypatch):
     with pytest.raises(ValueError, match="vertices must be a ROCm tensor"):
         hr.surface_distance(f64(2, 5, 3), i32(4, 3), i32(6), i32(12), f64(2, 9, 3), f64(3))
 
-    class OnDevice(torch.Tensor):
-        is_cuda = property(lambda self: True)
-        device = property(lambda self: torch.device("cuda", 0))
-
-    dev = lambda x: x.as_subclass(OnDevice)
     Vt, Ft, Ot, Ct, Pt, Prm = dev(f64(2, 5, 3)), dev(i32(4, 3)), dev(i32(6)), dev(i32(12)), dev(f64(2, 9, 3)), dev(f64(3))
     call = lambda **kw: hr.surface_distance(**dict(dict(vertices=Vt, faces=Ft, corner_offsets=Ot, corners=Ct, points=Pt, params=Prm), **kw))
     for bad in (dev(f64(5, 3)), dev(f64(2, 5, 4)), dev(f64(0, 5, 3)), dev(f64(2, 0, 3))):
