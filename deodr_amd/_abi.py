@@ -10,7 +10,8 @@ import os
 import re
 import types
 
-_INCLUDE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
+_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+_INCLUDE, _INCLUDE_STAGED = os.path.join(_ROOT, "include"), os.path.join(_ROOT, "include_staged")
 HEADER_PATH = os.path.join(_INCLUDE, "deodr_hip.h")
 # The companion headers, each versioned on its own and bound onto the same library; the only list of them.  Everything else follows from `key`: the
 # file include/deodr_hip_{key}.h, the parsed header {KEY}_HEADER here and its path {KEY}_HEADER_PATH, DEODR_HIP_{KEY}_ABI_VERSION and
@@ -31,6 +32,12 @@ COMPANIONS = (
     Companion("chamfer", False, "chamfer-term"),  # closest-point (Chamfer) data term
     Companion("surface", False, "surface-distance"),  # point-to-surface distance
     Companion("chamfer_grid", False, "chamfer-grid"),  # closest-point term over a uniform grid, stable sort by key
+)
+# The STAGED companions: the same rows, the same derived names, bound and version-checked by hip_renderer.lib() like the others, but their headers
+# live in include_staged/.  A family waits here while the table above cannot change; the next change of that table moves the header into include/
+# and the row into COMPANIONS ("Adding an operator family").
+STAGED = (
+    Companion("surface_grid", False, "surface-grid"),  # point-to-surface distance over a uniform grid of triangles
 )
 
 # C type (without `const`, without spaces around the stars) -> ctypes.  Data pointers are c_void_p: callers pass device addresses (Python
@@ -114,16 +121,16 @@ def bind(library, header=None):
 
 def _parse_file(path, structs=None):
     with open(path) as f:
-        return parse(f.read(), "include/" + os.path.basename(path), structs)
+        return parse(f.read(), os.path.basename(os.path.dirname(path)) + "/" + os.path.basename(path), structs)
 
 
 HEADER = _parse_file(HEADER_PATH)
-for _c in COMPANIONS:
-    _path = os.path.join(_INCLUDE, f"deodr_hip_{_c.key}.h")
+for _c in COMPANIONS + STAGED:
+    _path = os.path.join(_INCLUDE if _c in COMPANIONS else _INCLUDE_STAGED, f"deodr_hip_{_c.key}.h")
     globals()[_c.key.upper() + "_HEADER_PATH"], globals()[_c.key.upper() + "_HEADER"] = _path, _parse_file(_path, HEADER.structs if _c.sees_structs else None)
 
 
 def companion(c):
-    """-> (parsed header, its DEODR_HIP_{KEY}_ABI_VERSION) of a row of COMPANIONS"""
+    """-> (parsed header, its DEODR_HIP_{KEY}_ABI_VERSION) of a row of COMPANIONS or STAGED"""
     header = globals()[c.key.upper() + "_HEADER"]
     return header, header.defines[f"DEODR_HIP_{c.key.upper()}_ABI_VERSION"]

@@ -73,6 +73,7 @@
 #include "../../include/deodr_hip_chamfer.h"
 #include "../../include/deodr_hip_surface.h"
 #include "../../include/deodr_hip_chamfer_grid.h"
+#include "../../include_staged/deodr_hip_surface_grid.h"
 #include "dr_fititer.h" // <- dr_finalize.h <- dr_backward.h <- dr_backward_generic.h <- dr_forward.h <- dr_forward_generic.h <- dr_setup.h <- dr_workspace.h <- dr_prims.h
 #include "dr_texfit.h"  // texture smoothness + step (include/deodr_hip_texture.h); uses grid_sum of dr_fronthalf.h
 #include "dr_subdiv.h"  // rows of a sparse matrix applied to [batch, n, D] blocks (include/deodr_hip_subdiv.h): Loop subdivision and its adjoint
@@ -88,6 +89,7 @@
 #include "dr_surface.h" // point-to-surface distance: the closest point of the closest triangle by a brute-force tiled search over face records, on the machinery of dr_chamfer.h (include/deodr_hip_surface.h)
 #include "dr_sort.h"	// a stable LSD radix sort by key: histograms, a scan over (digit, workgroup), a scatter ranked by ballots (include/deodr_hip_chamfer_grid.h)
 #include "dr_chamfer_grid.h" // the closest-point energy over a uniform grid of hashed cells: keys, sort, build, ring search, gather; the combine steps of dr_chamfer.h (include/deodr_hip_chamfer_grid.h)
+#include "dr_surface_grid.h" // point-to-surface distance over a uniform grid of triangles: one record per face keyed by its box's minimum corner, shell search, gather (include_staged/deodr_hip_surface_grid.h)
 
 using namespace dr;
 using namespace dr::dispatch;
@@ -2359,6 +2361,103 @@ int deodr_hip_chamfer_grid(const double *vertices, int V, const double *points, 
 		hipLaunchKernelGGL(chamfer_grid_search_kernel, dim3(((unsigned)V - 1) / CHAMFER_BLOCK + 1, (unsigned)n), block, 0, st, g, 0, (int)to_mesh);
 	hipLaunchKernelGGL(chamfer_vertices_kernel, dim3(chamfer_blocks(V), (unsigned)n), block, 0, st, a);
 	return check_hip(hipGetLastError(), "chamfer_grid launch");
+}
+
+// ---- point-to-surface distance over a uniform grid of triangles (include_staged/deodr_hip_surface_grid.h, kernels in dr_surface_grid.h)
+
+int deodr_hip_surface_grid_abi_version(void) { return DEODR_HIP_SURFACE_GRID_ABI_VERSION; }
+
+namespace
+{
+const char *surface_grid_dims(int V, int F, int P, int n)
+{ // -> NULL, or which limit of the header the arguments break
+	if (V <= 0 || V > CG_MAX_ITEMS)
+		return "V must be in 1 .. DEODR_HIP_CHAMFER_GRID_MAX_ITEMS";
+	if (F <= 0 || F > CG_MAX_ITEMS)
+		return "F must be in 1 .. DEODR_HIP_CHAMFER_GRID_MAX_ITEMS";
+	if (P <= 0 || P > CG_MAX_ITEMS)
+		return "P must be in 1 .. DEODR_HIP_CHAMFER_GRID_MAX_ITEMS";
+	return chamfer_poses(n);
+}
+} // namespace
+
+size_t deodr_hip_surface_grid_scratch_bytes(int V, int F, int P, int n)
+{
+	SurfaceGridCall c;
+	return surface_grid_dims(V, F, P, n) ? 0 : surface_grid_carve(c, V, F, P, n, NULL);
+}
+
+int deodr_hip_surface_grid_launches(int V, int F, int P, int n, int directions)
+{
+	if (surface_grid_dims(V, F, P, n) || !chamfer_directions(directions))
+		return 0;
+	int launches = 1; // the vertices' combine step
+	if (directions & DEODR_HIP_CHAMFER_POINTS_TO_MESH) // prep, keys, sort, build of the faces; search, combine, sort of the assignment, gather
+		launches += 3 + 3 * sort_passes(chamfer_grid_table_bits(F)) + 3 + 3 * sort_passes(chamfer_grid_assign_bits(F));
+	if (directions & DEODR_HIP_CHAMFER_MESH_TO_POINTS) // keys, sort, build of the points; search of the vertices
+		launches += 2 + 3 * sort_passes(chamfer_grid_table_bits(P)) + 1;
+	return launches;
+}
+
+int deodr_hip_surface_grid(const double *vertices, int V, const int32_t *faces, int F, const int32_t *corner_offsets, const int32_t *corners,
+						   const double *points, int P, const double *point_weights, const double *vertex_weights, const double *params, double cell_size,
+						   int n, int directions, double *terms, double *loss, double *vertices_b, uint32_t *nearest_face, double *barycentric,
+						   uint32_t *nearest_point, void *scratch, size_t scratch_bytes, void *stream)
+{
+	const char *what = "surface_grid";
+	if (!vertices || !faces || !corner_offsets || !corners || !points || !params || !terms || !loss || !vertices_b || !scratch)
+		return fail(what, "vertices, faces, corner_offsets, corners, points, params, terms, loss, vertices_b or scratch == NULL");
+	if (const char *why = surface_grid_dims(V, F, P, n))
+		return fail(what, why);
+	const void *const words[] = {faces, corner_offsets, corners, nearest_face, nearest_point};
+	const void *const doubles[] = {vertices, points, point_weights, vertex_weights, params, terms, loss, vertices_b, barycentric, scratch};
+	const size_t N = (size_t)n, nv = N * (size_t)V, np = N * (size_t)P;
+	const Range outputs[] = {{terms, 16 * N}, {loss, 8 * N}, {vertices_b, 24 * nv}, {nearest_face, 4 * np}, {barycentric, 24 * np}, {nearest_point, 4 * nv}, {scratch, scratch_bytes}};
+	const Range inputs[] = {{vertices, 24 * nv}, {faces, 12 * (size_t)F}, {corner_offsets, 4 * ((size_t)V + 1)}, {corners, 12 * (size_t)F}, {points, 24 * np},
+							{point_weights, 8 * np}, {vertex_weights, 8 * (size_t)V}, {params, 24}};
+	SurfaceGridCall call = {{vertices, faces, corner_offsets, corners, points, point_weights, vertex_weights, params, terms, loss, vertices_b, nearest_face, barycentric, nearest_point}};
+	if (closest_point_refused(what, directions, cell_size > 0 && cell_size < __builtin_inf() ? NULL : "cell_size must be finite and > 0", any_misaligned(words, 4) || any_misaligned(doubles, 8), scratch,
+							  scratch_bytes, surface_grid_carve(call, V, F, P, n, NULL), "scratch too small (deodr_hip_surface_grid_scratch_bytes)", any_overlap(outputs, inputs) || any_overlap(outputs)))
+		return 1;
+	surface_grid_carve(call, V, F, P, n, scratch);
+	const bool to_mesh = directions & DEODR_HIP_CHAMFER_POINTS_TO_MESH, to_points = directions & DEODR_HIP_CHAMFER_MESH_TO_POINTS;
+	SurfaceArgs &a = call.a; // the records, surface_closest() and the combine steps of dr_surface.h, with one segment per search and gather
+	a.directions = directions;
+	SurfaceGridArgs &f = call.f; // the face grid
+	f.points = points, f.params = params, f.cell_size = cell_size;
+	ChamferGridArgs &g = call.g; // the points' grid and the search of the vertices over it (dr_chamfer_grid.h)
+	g.set[0].coords = vertices, g.set[1].coords = points, g.params = params, g.point_weights = point_weights, g.cell_size = cell_size, g.clear_tickets = !to_mesh;
+	f.point_order = to_points ? g.set[1].order : nullptr;
+	uint32_t *const sort_words = call.sort_words;
+	const hipStream_t st = (hipStream_t)stream;
+	const dim3 block(CHAMFER_BLOCK);
+	if (to_mesh)
+	{
+		const size_t T = (size_t)1 << f.table_bits;
+		hipLaunchKernelGGL(surface_grid_prep_kernel, dim3(chamfer_blocks(F), (unsigned)n), block, 0, st, a, f);
+		hipLaunchKernelGGL(surface_grid_keys_kernel, dim3(chamfer_blocks(T > (size_t)F ? (int)T : F), (unsigned)n), block, 0, st, a, f);
+		sort_launch(f.keys, F, n, f.table_bits, f.sorted_keys, f.order, sort_words, st);
+		hipLaunchKernelGGL(surface_grid_build_kernel, dim3(chamfer_blocks(F), (unsigned)n), block, 0, st, a, f);
+	}
+	if (to_points)
+	{
+		const ChamferGridSet &s = g.set[1];
+		const size_t T = (size_t)1 << s.table_bits;
+		hipLaunchKernelGGL(chamfer_grid_keys_kernel, dim3(chamfer_blocks(T > (size_t)P ? (int)T : P), (unsigned)n), block, 0, st, g, 1);
+		sort_launch(s.keys, P, n, s.table_bits, s.sorted_keys, s.order, sort_words, st);
+		hipLaunchKernelGGL(chamfer_grid_build_kernel, dim3(chamfer_blocks(P), (unsigned)n), block, 0, st, g, 1);
+	}
+	if (to_mesh)
+	{
+		hipLaunchKernelGGL(surface_grid_search_kernel, dim3(((unsigned)P - 1) / CHAMFER_BLOCK + 1, (unsigned)n), block, 0, st, a, f);
+		hipLaunchKernelGGL(surface_points_kernel, dim3(chamfer_blocks(P), (unsigned)n), block, 0, st, a);
+		sort_launch(a.assign, P, n, chamfer_grid_assign_bits(F), f.sorted_assign, f.assign_order, sort_words, st);
+		hipLaunchKernelGGL(surface_grid_gather_kernel, dim3(((unsigned)F - 1) / SG_GATHER_FACES + 1, (unsigned)n), block, 0, st, a, f);
+	}
+	if (to_points)
+		hipLaunchKernelGGL(chamfer_grid_search_kernel, dim3(((unsigned)V - 1) / CHAMFER_BLOCK + 1, (unsigned)n), block, 0, st, g, 0, 0);
+	hipLaunchKernelGGL(surface_vertices_kernel, dim3(chamfer_blocks(V), (unsigned)n), block, 0, st, a);
+	return check_hip(hipGetLastError(), "surface_grid launch");
 }
 
 #ifdef DR_WAVE_TRACE

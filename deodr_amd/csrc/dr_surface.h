@@ -11,7 +11,9 @@
 //                        would diverge); strict < keeps the lowest face; the partial (d2, face) of (segment, point) -> scratch.
 // surface_points_kernel  a thread per (pose, point): the minimum over the segments in order, surface_closest() once more on the winner (the same
 //                        text, so the same bits) -> nearest_face, barycentric, assign (the face, or CHAMFER_NONE beyond tau2), the pull
-//                        ((2 w) bary_0, (2 w) bary_1, (2 w) bary_2, e) of the point, term_0 through grid_sum.
+//                        ((2 w) bary_0, (2 w) bary_1, (2 w) bary_2, e) of the point, term_0 through grid_sum.  A winner CHAMFER_NONE (the search
+//                        over the face grid of dr_surface_grid.h found no face within tau2; this file's search never reports it) is passed on:
+//                        barycentric (0, 0, 0), the constant w tau2, no gradient.
 // surface_gather_kernel  a thread per face, grid (ceil(F / BLOCK), Sg, n): the compare-and-fetch walk of dr_chamfer.h over the staged assign words of
 //                        a segment of the points; where assign[k] == f the pull is fetched and its nine products added, in increasing k -> scratch.
 // chamfer_walk_kernel<true, false>   mesh -> points: the vertex-major search of dr_chamfer.h, unchanged.
@@ -180,18 +182,19 @@ __global__ __launch_bounds__(CHAMFER_BLOCK) void surface_points_kernel(SurfaceAr
 		uint32_t arg;
 		chamfer_combine(a.pd2, a.pidx, pose, a.Sp, P, k, best, arg);
 		const double *const p = a.points + 3 * (pose * P + k);
+		const bool found = arg != CHAMFER_NONE; // (always, after the brute-force search; the search over the face grid reports no face beyond tau2)
 		SurfaceRec r;
-		surface_copy((double *)&r, rec + (size_t)SURFACE_REC * arg);
+		surface_copy((double *)&r, rec + (size_t)SURFACE_REC * (found ? arg : 0u));
 		const SurfaceHit h = surface_closest(r, p[0], p[1], p[2]); // (h.d2 == best: the same text on the same values)
 		const double b0 = (1.0 - h.v) - h.w;
-		const bool near = best <= tau2;
+		const bool near = found && best <= tau2;
 		a.assign[pose * P + k] = near ? arg : CHAMFER_NONE;
 		if (a.nearest_face)
 			a.nearest_face[pose * P + k] = arg;
 		if (a.barycentric)
 		{
 			double *const out = a.barycentric + 3 * (pose * P + k);
-			out[0] = b0, out[1] = h.v, out[2] = h.w;
+			out[0] = found ? b0 : 0.0, out[1] = found ? h.v : 0.0, out[2] = found ? h.w : 0.0;
 		}
 		const double w = a.point_weights ? a.point_weights[pose * P + k] : 1.0, w2 = 2 * w;
 		double *const pull = a.pull + 6 * (pose * P + k);

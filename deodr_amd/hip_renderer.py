@@ -27,7 +27,7 @@ _H = _abi.HEADER  # the structs, the constants and (in lib()) the signatures are
 _SceneC, _FitOptionsC, ABI_VERSION = _H.structs["DeodrHipScene"], _H.structs["DeodrHipFitOptions"], _H.defines["DEODR_HIP_ABI_VERSION"]
 ERR_FACES, ERR_FACES_UV, ERR_NO_TEXTURE, ERR_INTERNAL, ERR_DET_RANGE = (_H.defines["DEODR_HIP_ERR_" + n] for n in "FACES FACES_UV NO_TEXTURE INTERNAL DET_RANGE".split())
 MAX_COLORS, _F32, _F64 = (_H.defines["DEODR_HIP_" + n] for n in ("MAX_COLORS", "F32", "F64"))
-for _c in _abi.COMPANIONS:  # TEXTURE_ABI_VERSION, SUBDIV_ABI_VERSION, ...: of the companion headers, each versioned on its own
+for _c in _abi.COMPANIONS + _abi.STAGED:  # TEXTURE_ABI_VERSION, SUBDIV_ABI_VERSION, ...: of the companion headers, each versioned on its own
     globals()[_c.key.upper() + "_ABI_VERSION"] = _abi.companion(_c)[1]
 # words of the 64-byte status block at the start of the workspace
 _STATUS_NEEDED, _STATUS_ERRORS = _H.defines["DEODR_HIP_STATUS_WORD_NEEDED_PAIRS"], _H.defines["DEODR_HIP_STATUS_WORD_SCENE_ERRORS"]
@@ -47,7 +47,7 @@ def lib():
         L = C.CDLL(LIB_PATH)
         if L.deodr_hip_abi_version() != ABI_VERSION:
             raise ImportError("libdeodr_hip.so ABI version mismatch; rebuild it")
-        for c in _abi.COMPANIONS:  # bound onto the same library
+        for c in _abi.COMPANIONS + _abi.STAGED:  # bound onto the same library
             header, version = _abi.companion(c)
             _abi.bind(L, header)  # (a library that lacks one of its symbols is refused by name)
             if getattr(L, f"deodr_hip_{c.key}_abi_version")() != version:
@@ -216,10 +216,15 @@ def _own_or_cached_scratch(what, scratch, whose, device, need, make, *dims):
     return scratch
 
 
+def _include(header):
+    """the path in the repository of a header of the C ABI, for error texts: a staged companion is in include_staged/"""
+    return ("include_staged/" if any(header == f"deodr_hip_{c.key}.h" for c in _abi.STAGED) else "include/") + header
+
+
 def _byte_scratch(what, dims, need, header, device, zeroed=False):
     """``need`` bytes (what the library's ``*_scratch_bytes`` gave for ``dims``; 0: refused) of scratch on ``device``, uninitialised or ``zeroed``"""
     if need == 0:
-        raise ValueError(f"{what}: {dims} is outside the limits of include/{header}")
+        raise ValueError(f"{what}: {dims} is outside the limits of {_include(header)}")
     with torch.cuda.device(device):
         return (torch.zeros if zeroed else torch.empty)(int(need), dtype=torch.uint8, device=device)
 
@@ -1556,7 +1561,7 @@ def _closest_point(what, header, limits, make_scratch, vertices, points, params,
     dev = vertices.device
     need = int(getattr(lib(), f"deodr_hip_{what}_scratch_bytes")(*dims))
     if need == 0 or not getattr(lib(), f"deodr_hip_{what}_launches")(*dims, directions):  # (the launches: a limit that depends on the directions)
-        raise ValueError(f"{what}: {said} is outside the limits of include/{header} ({limits})")
+        raise ValueError(f"{what}: {said} is outside the limits of {_include(header)} ({limits})")
     results = [t for _, t, _, _ in found]
     with torch.cuda.device(dev):
         terms = torch.empty((n, 2), dtype=torch.float64, device=dev) if terms is None else terms
@@ -1700,6 +1705,35 @@ def surface_distance(vertices, faces, corner_offsets, corners, points, params, p
     return _closest_point("surface_distance", "deodr_hip_surface.h", f"F * P <= {SURFACE_MAX_PAIRS}, V * P <= {CHAMFER_MAX_PAIRS} with mesh -> points, n <= 65535",
                           surface_scratch, vertices, points, params, point_weights, vertex_weights, directions, terms, loss, vertices_b, found, nearest_point, scratch,
                           want_nearest, mesh=(faces, corner_offsets, corners))  # fmt: skip
+
+
+# ---- point-to-surface distance over a uniform grid of triangles (include_staged/deodr_hip_surface_grid.h) -----------------------------------
+
+SURFACE_GRID_NONE, SURFACE_GRID_GATHER_FACES = (_abi.SURFACE_GRID_HEADER.defines["DEODR_HIP_SURFACE_GRID_" + n] for n in ("NONE", "GATHER_FACES"))
+
+
+def surface_grid_launches(V, F, P, n, directions=3):
+    """``deodr_hip_surface_grid_launches``: the kernel launches of a :func:`surface_grid` call (0 for arguments the call refuses)"""
+    return int(lib().deodr_hip_surface_grid_launches(int(V), int(F), int(P), int(n), int(directions)))
+
+
+def surface_grid_scratch(V, F, P, n, device):
+    """the scratch of :func:`surface_grid` for n poses of V vertices and F faces against P points (one per stream in use; it need not be zeroed)"""
+    need = lib().deodr_hip_surface_grid_scratch_bytes(int(V), int(F), int(P), int(n))
+    return _byte_scratch("surface_grid_scratch", f"V = {V}, F = {F}, P = {P}, n = {n}", need, "deodr_hip_surface_grid.h", device)
+
+
+def surface_grid(vertices, faces, corner_offsets, corners, points, params, cell_size, point_weights=None, vertex_weights=None, directions=3, terms=None,
+                 loss=None, vertices_b=None, nearest_face=None, barycentric=None, nearest_point=None, scratch=None, want_nearest=False):  # fmt: skip
+    """``deodr_hip_surface_grid``: :func:`surface_distance` with the closest face found over a uniform grid of triangles, one record per face, the
+    cell edge ``max(cell_size, max_distance / CHAMFER_GRID_RINGS, the longest side of a face's box)`` -- the same arguments and results, the same
+    faces and barycentric coordinates; a point with no face (a vertex with no point) within ``max_distance`` (``params[2]``, which must be FINITE:
+    trusted here, :mod:`deodr_amd.surface` checks its own) reports ``SURFACE_GRID_NONE`` and barycentric coordinates (0, 0, 0).  No cap on F * P
+    or V * P.  ``scratch``: a :func:`surface_grid_scratch` of the caller's; None: one per device and stream."""
+    found = [("nearest_face", nearest_face, _INDICES, ()), ("barycentric", barycentric, _F64_ONLY, (3,))]
+    return _closest_point("surface_grid", "deodr_hip_surface_grid.h", f"V, F, P <= {CHAMFER_GRID_MAX_ITEMS}, n <= 65535", surface_grid_scratch, vertices, points, params,
+                          point_weights, vertex_weights, directions, terms, loss, vertices_b, found, nearest_point, scratch, want_nearest,
+                          mesh=(faces, corner_offsets, corners), cell_size=(cell_size,))  # fmt: skip
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -770,7 +770,12 @@ class MeshPointCloudFitter(_PoseFitter):
 
     ``search``: "brute" (the default) or "grid", ``cell_size``: the term's (``PointCloudTerm(search="grid")``, include/deodr_hip_chamfer_grid.h):
     the same neighbours found over a uniform grid, for clouds of 10^5 points and more; it needs a finite ``max_distance``, composes with every
-    keyword the brute search composes with, and is refused together with ``metric="surface"``.
+    keyword the brute search composes with, and is refused together with ``metric="surface"``, whose own keyword is ``surface_search``.
+
+    ``surface_search``: "brute" (the default) or "grid", only with ``metric="surface"``: the closest faces found over a uniform grid of the
+    triangles and mesh -> points over the points' grid (``PointSurfaceTerm(search="grid")``, include_staged/deodr_hip_surface_grid.h), for the
+    dense scans the surface metric is for -- a VGA depth frame against a mesh of 10^4 faces is beyond the brute-force operator's cap on F * P.
+    It needs a finite ``max_distance``, takes ``cell_size``, and composes with every keyword the surface metric composes with.
 
     The step factors are this fitter's own, chosen on examples/point_cloud_hand_fitting.py with ``normalise=True`` (both terms are then mean squared
     distances, so the translation gradient is of the order of the offset whatever V and P are, and a vertex gradient of the order of offset / V):
@@ -788,16 +793,20 @@ class MeshPointCloudFitter(_PoseFitter):
     def __init__(self, vertices, faces, euler_init, translation_init, cregu=0.002, inertia=0.9, damping=0.05, device="cuda", n_poses=1,
                  directions="both", max_distance=float("inf"), mix=(1.0, 1.0), normalise=True, subdivisions=0, shape_basis=None, coefficient_regu=0.0,
                  sigmas=None, skin=None, joint_quaternions_init=None, joint_regu=0.0, smoothing=0.0, smoothing_iterations=None, rigidity="laplacian",
-                 arap_weights="uniform", metric="vertex", search="brute", cell_size=None):  # fmt: skip
+                 arap_weights="uniform", metric="vertex", search="brute", cell_size=None, surface_search="brute"):  # fmt: skip
         if metric not in ("vertex", "surface"):
             raise ValueError(f'metric must be "vertex" or "surface", not {metric!r}')
         if search not in ("brute", "grid"):
             raise ValueError(f'search must be "brute" or "grid", not {search!r}')
+        if surface_search not in ("brute", "grid"):
+            raise ValueError(f'surface_search must be "brute" or "grid", not {surface_search!r}')
         if search == "grid" and metric == "surface":
-            raise ValueError('search="grid" finds nearest VERTICES: it does not go with metric="surface" (a grid over the triangles does not exist yet)')
-        if cell_size is not None and search != "grid":
-            raise ValueError('cell_size belongs to search="grid"')
-        self.metric, self.search = metric, search
+            raise ValueError('search="grid" finds nearest VERTICES: it does not go with metric="surface" (the grid over the triangles is surface_search="grid")')
+        if surface_search != "brute" and metric != "surface":
+            raise ValueError(f'surface_search="{surface_search}" belongs to metric="surface"')
+        if cell_size is not None and search != "grid" and surface_search != "grid":
+            raise ValueError('cell_size belongs to surface_search="grid"' if metric == "surface" else 'cell_size belongs to search="grid"')
+        self.metric, self.search, self.surface_search = metric, search, surface_search
         super().__init__(vertices, faces, euler_init, translation_init, cregu, inertia, damping, device, n_poses=n_poses, subdivisions=subdivisions,
                          shape_basis=shape_basis, coefficient_regu=coefficient_regu, sigmas=sigmas, skin=skin,
                          joint_quaternions_init=joint_quaternions_init, joint_regu=joint_regu, smoothing=smoothing,
@@ -807,6 +816,8 @@ class MeshPointCloudFitter(_PoseFitter):
         self._term_keywords = dict(directions=directions, max_distance=max_distance, mix=mix, normalise=normalise)
         if search == "grid":  # (its own refusals -- an infinite max_distance, a bad cell_size -- come from the term, in set_point_clouds)
             self._term_keywords.update(search=search, cell_size=cell_size)
+        if surface_search == "grid":
+            self._term_keywords.update(search=surface_search, cell_size=cell_size)
         self.term = None
 
     def set_point_clouds(self, points, weights=None, vertex_weights=None):

@@ -12,12 +12,16 @@ records, a face-major gather, no lists, no floating-point atomics, a fixed numbe
 :class:`PointSurfaceTerm` is a :class:`deodr_amd.chamfer.PointCloudTerm` (the same clouds, padding, weights and device-resident ``params``) that
 also holds the faces and their transposed corner table; :func:`surface_distance_torch` is the same definition as torch ops, chunked over the
 points -- what runs on tensors the kernels do not take and what the kernels are timed against; :func:`corner_table` builds the table.
-``deodr_amd.pytorch.MeshPointCloudFitter(metric="surface")`` fits with it."""
+``deodr_amd.pytorch.MeshPointCloudFitter(metric="surface")`` fits with it.
+
+``PointSurfaceTerm(search="grid")`` finds the same faces over a uniform grid of hashed cells holding the triangles, one record per face
+(``include_staged/deodr_hip_surface_grid.h``, ``deodr_amd/csrc/dr_surface_grid.h``): the cost grows with F + P instead of F * P and there is no cap
+on F * P or V * P; it needs a finite ``max_distance``, and a point with no face within it has no correspondence (-1, barycentric zeros)."""
 
 import numpy as np
 import torch
 
-from .chamfer import CHUNK_BYTES, PointCloudTerm, _array, _mesh_to_points
+from .chamfer import CHUNK_BYTES, PointCloudTerm, _array, _mesh_to_points, mask_beyond
 
 LIVE_ARRAYS = 24  # [n, chunk, F] arrays alive at once in closest_point_torch, roughly: what a chunk is sized by
 
@@ -141,11 +145,19 @@ class PointSurfaceTerm(PointCloudTerm):
     ``faces``: integers in ``[0, nb_vertices)``, checked here; the transposed corner table the kernels need is built here too
     (:func:`corner_table`).  Everything else -- ``points``, the padding of clouds of unequal length (copies of the first point at weight 0),
     ``point_weights``, ``vertex_weights`` (of mesh -> points), ``directions``, ``max_distance``, ``mix``, ``normalise``, the device tensors
-    ``self.params``, ``self.points`` and the weights that may be ``copy_``-ed into between calls and replays -- is :class:`PointCloudTerm`'s."""
+    ``self.params``, ``self.points`` and the weights that may be ``copy_``-ed into between calls and replays -- is :class:`PointCloudTerm`'s.
+
+    ``search``: "brute" (the default: every (point, face) pair is visited, F * P is capped) or "grid": the same faces over a uniform grid of
+    triangles (``deodr_hip_surface_grid``) and the nearest points of mesh -> points over the points' grid; the same barycentric coordinates, loss
+    and terms, the gradient up to the order of its sums (on CPU tensors: the same bits), no cap on F * P or V * P.  The rules and messages are
+    :class:`PointCloudTerm`'s: a finite ``max_distance`` -- refused here otherwise, and at a call when it was ``copy_``-ed into ``params`` where the
+    host can see it --, ``cell_size`` finite and > 0 and only with the grid (None: :func:`deodr_amd.chamfer.default_cell_size` of the clouds; the
+    kernels never use a cell below ``max_distance / 4`` or below the longest side of a face's bounding box), and :meth:`correspondences` gives -1
+    and zero barycentric coordinates where there is no face within ``max_distance``."""
 
     def __init__(self, faces, nb_vertices, points, point_weights=None, vertex_weights=None, directions="both", max_distance=float("inf"), mix=(1.0, 1.0),
-                 normalise=True, device="cuda"):  # fmt: skip
-        super().__init__(points, point_weights, vertex_weights, directions, max_distance, mix, normalise, device)
+                 normalise=True, device="cuda", search="brute", cell_size=None):  # fmt: skip
+        super().__init__(points, point_weights, vertex_weights, directions, max_distance, mix, normalise, device, search=search, cell_size=cell_size)
         offsets, corners = corner_table(faces, nb_vertices)
         self.nb_vertices, self.nb_faces = int(nb_vertices), int(len(corners) // 3)
         self.faces = torch.as_tensor(np.ascontiguousarray(np.asarray(_array(faces)), dtype=np.int32), device=self.device)
@@ -162,11 +174,25 @@ class PointSurfaceTerm(PointCloudTerm):
     # indices int64 either way); :meth:`evaluate` is PointCloudTerm's as it stands (the adjoint of the loss is the ``vertices_b`` of the same call)
     def _torch(self, v, u, want_nearest):
         to = lambda t: None if t is None else t.to(v.device)
-        out = surface_distance_torch(v, to(self.faces), to(self.points), to(self.params), to(self.point_weights), to(u), self.directions)
-        return out if want_nearest else out[:3] + (None, None, None)
+        faces, points, params = to(self.faces), to(self.points), to(self.params)
+        out = surface_distance_torch(v, faces, points, params, to(self.point_weights), to(u), self.directions)
+        if not want_nearest:
+            return out[:3] + (None, None, None)
+        if self.search == "grid":  # the same values; the correspondences beyond max_distance are none
+            p, face, bary, nearest_point = points.to(v.dtype), out[3], out[4], out[5]
+            if face is not None:
+                a, b, c = (torch.gather(v, 1, faces.long()[face][..., k, None].expand(-1, -1, 3)) for k in range(3))
+                e = ((a + bary[..., 1:2] * (b - a)) + bary[..., 2:3] * (c - a)) - p  # the header's closest point, operation by operation
+                tau2 = params[2].to(v.dtype) * params[2].to(v.dtype)
+                near = (e[..., 0] * e[..., 0] + e[..., 1] * e[..., 1]) + e[..., 2] * e[..., 2] <= tau2
+                face, bary = torch.where(near, face, torch.full_like(face, -1)), torch.where(near[..., None], bary, torch.zeros_like(bary))
+            out = out[:3] + (face, bary, None if nearest_point is None else mask_beyond(v, p, nearest_point, params))
+        return out
 
     def _kernel(self, hr, V):
         mesh = (self.faces, self.corner_offsets, self.corners)
+        if self.search == "grid":
+            return hr.surface_grid_scratch, (V, self.nb_faces, self.nb_points, self.n), hr.surface_grid, mesh + (self.points, self.params, self.cell_size)
         return hr.surface_scratch, (V, self.nb_faces, self.nb_points, self.n), hr.surface_distance, mesh + (self.points, self.params)
 
     def correspondences(self, vertices):

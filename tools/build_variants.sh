@@ -38,13 +38,17 @@ ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 OUT=$ROOT/tools/variants
 mkdir -p $OUT
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -ffp-contract=off -munsafe-fp-atomics"
+copy_sources() { # the kernels and every header of the C ABI (include/ and the staged ones) -> a scratch tree $1 of the same layout
+  mkdir -p $1/deodr_amd/csrc $1/include $1/include_staged
+  cp $ROOT/deodr_amd/csrc/*.h $ROOT/deodr_amd/csrc/*.hip $1/deodr_amd/csrc/
+  cp $ROOT/include/*.h $1/include/
+  cp $ROOT/include_staged/*.h $1/include_staged/
+}
 PATCHED=""
 patched_sources() { # a scratch copy of the sources with the instrumentation applied (once per invocation)
   if [ -z "$PATCHED" ]; then
     PATCHED=$(mktemp -d /tmp/deodr_instr.XXXXXX)
-    mkdir -p $PATCHED/deodr_amd/csrc $PATCHED/include
-    cp $ROOT/deodr_amd/csrc/*.h $ROOT/deodr_amd/csrc/*.hip $PATCHED/deodr_amd/csrc/
-    cp $ROOT/include/*.h $PATCHED/include/
+    copy_sources $PATCHED
     (cd $PATCHED/deodr_amd/csrc && patch -p1 --no-backup-if-mismatch < $OUT/instrumentation.patch) || { echo "instrumentation.patch no longer fits the sources"; exit 1; }
   fi
 }
@@ -56,13 +60,11 @@ for v in ${@:-fwdtrace wavetrace tiletrace fwd4 fwd6}; do
     abl*) patched_sources; build $PATCHED/deodr_amd/csrc $v "-DDR_ABLATE=${v#abl}" ;;
     mfma) patched_sources; build $PATCHED/deodr_amd/csrc $v -DDR_OWNER_MFMA=1 ;;
     fininfwd)
-      FIF=$(mktemp -d /tmp/deodr_fif.XXXXXX); mkdir -p $FIF/deodr_amd/csrc $FIF/include
-      cp $ROOT/deodr_amd/csrc/*.h $ROOT/deodr_amd/csrc/*.hip $FIF/deodr_amd/csrc/; cp $ROOT/include/*.h $FIF/include/
+      FIF=$(mktemp -d /tmp/deodr_fif.XXXXXX); copy_sources $FIF
       (cd $FIF/deodr_amd/csrc && patch -p1 --no-backup-if-mismatch < $OUT/finalize_in_forward.patch) || { echo "finalize_in_forward.patch no longer fits the sources"; exit 1; }
       build $FIF/deodr_amd/csrc $v "-DDR_FIN_IN_FWD=1 -DDR_SPLIT_EDGES=0" ;; # (its block counters count one walker per tile: no split tiles)
     classtrace)
-      CT=$(mktemp -d /tmp/deodr_ct.XXXXXX); mkdir -p $CT/deodr_amd/csrc $CT/include
-      cp $ROOT/deodr_amd/csrc/*.h $ROOT/deodr_amd/csrc/*.hip $CT/deodr_amd/csrc/; cp $ROOT/include/*.h $CT/include/
+      CT=$(mktemp -d /tmp/deodr_ct.XXXXXX); copy_sources $CT
       (cd $CT/deodr_amd/csrc && patch -p1 --no-backup-if-mismatch < $OUT/forward_class_timeline.patch) || { echo "forward_class_timeline.patch no longer fits the sources"; exit 1; }
       build $CT/deodr_amd/csrc $v "" ;;
     wavetrace) build $ROOT/deodr_amd/csrc $v -DDR_WAVE_TRACE ;;
